@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py -- forward throughput of the MI355X hot path, one JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload all|c2|c3|c4|c5|mixer|da|...] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload all|c2|c3|c4|c5|mixer|da|...] [--dump-outputs DIR] [--full [--no-cpu]]
+
+A plain run sets up, warms up, times exactly K steps, writes the last timed step's outputs when --dump-outputs is given, and prints
+the line: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, plus the run's `config` (workload, precision,
+ranks).  Everything else described below -- box calibration, the two drift windows, per-block timing and the roofline, the strict
+passes, the model passes, the dominant-kernel tally and the CPU baseline -- runs only with `--full`.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...`
@@ -56,6 +61,12 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="all")
     ap.add_argument("--batch", type=int, default=256, help="images per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: box calibration, drift windows, per-block timing + roofline, strict "
+                         "and model passes, dominant-kernel tally, CPU baseline (the --no-* switches below apply to these)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write each block's output of the last timed step to DIR/<key>.npy (float32; outputs above "
+                         "the size cap as a fixed, seeded sample of their elements)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-strict", action="store_true", help="skip the per-block strict-mode (fp32-class) timing passes")
     ap.add_argument("--cpu-sample", type=int, default=None, help="override the per-block CPU-baseline sample size (images)")
@@ -356,20 +367,26 @@ def main(argv=None):
             dist.barrier()
         torch.cuda.synchronize()
 
-    def window():
-        """K steps bracketed by barrier + synchronize on both sides; seconds on this rank."""
+    last = {}
+
+    def window(keep=False):
+        """K steps bracketed by barrier + synchronize on both sides; seconds on this rank.  keep: hold on to the LAST step's outputs
+        (only that step's: the steps before it free theirs as they always did)."""
         barrier()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
+        for i in range(args.steps):
+            if keep and i == args.steps - 1:
+                last["outs"] = step()
+            else:
+                step()
         barrier()
         return time.perf_counter() - t0
 
     # ---- box calibration BEFORE the timed region (rank 0 measures, every rank waits): yardsticks + telemetry -------------------------
-    card = tele.find_card(tele.pci_address(dev_index))       # the sysfs directory of THIS GPU (a host may list eight cards)
     calib = {}
-    want_calib = rank == 0 and not args.only and not args.no_calib
+    want_calib = args.full and rank == 0 and not args.only and not args.no_calib
     if want_calib:
+        card = tele.find_card(tele.pci_address(dev_index))   # the sysfs directory of THIS GPU (a host may list eight cards)
         calib["idle"] = tele.snapshot(card)
         src = blocks[0]["x"].reshape(-1) if blocks[0]["x"].dtype == torch.float32 else None
         calib["before"] = yardsticks(dev, src)
@@ -377,12 +394,15 @@ def main(argv=None):
     for _ in range(args.warmup):
         step()
     # THE timed region of the contract: W warm-up steps, then exactly K steps between barrier + synchronize pairs, max over ranks
-    elapsed = local_elapsed = window()
+    elapsed = local_elapsed = window(keep=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(blocks, last.get("outs", []), args.dump_outputs)
+    last.clear()
     # two more windows of K steps right behind it (same bracket): drift of a cold / power-managed box shows as a trend across the three
     sampler = tele.LoadSampler(card) if want_calib else None
     if sampler is not None:
         sampler.start()
-    extra = [window() for _ in range(0 if args.only else 2)]
+    extra = [window() for _ in range(2 if args.full and not args.only else 0)]
     if sampler is not None:
         calib["load"] = sampler.stop()
 
@@ -395,6 +415,8 @@ def main(argv=None):
 
     elapsed = max_over_ranks(elapsed)
     extra = [max_over_ranks(e) for e in extra]
+    if not args.full:
+        return plain_line(args, rank, world, dist, shared_gpu, dev_index, local_elapsed, elapsed, wl, wname, gather_kind, comm, comm_ok)
 
     # per-block durations with HIP events on the launch stream (un-timed extra passes)
     pmc, pmc_note = load_pmc_traffic()
@@ -525,6 +547,100 @@ def main(argv=None):
         dist.destroy_process_group()
 
 
+DUMP_BYTES = 60 << 20           # --dump-outputs: all arrays together stay under 64 MB
+DUMP_ELEMS = 1 << 20            # per output: a larger one is written as a seeded sample of this many elements (fewer when outputs are many)
+DUMP_SEED = 4321
+
+
+def dump_outputs(blocks, outs, dirname):
+    """Write every block's output of the last timed step to DIR/<key>.npy (float32, float64 stays float64).  An output with more
+    elements than the per-output cap is written as the elements at a fixed, seeded, sorted set of flat indices (torch.Generator seeded
+    with DUMP_SEED, drawn on the CPU: the same indices on every run and every build for the same shape)."""
+    import re
+    import numpy as np
+    import torch
+    arrays = []
+    for b, y in zip(blocks, outs):
+        ys = list(y) if isinstance(y, (list, tuple)) else [y]
+        for i, t in enumerate(ys):
+            if torch.is_tensor(t):
+                arrays.append((b["key"] if len(ys) == 1 else "%s_%d" % (b["key"], i), t))
+    cap = max(1, min(DUMP_ELEMS, DUMP_BYTES // 8 // max(1, len(arrays))))
+    os.makedirs(dirname, exist_ok=True)
+    seen = set()
+    for key, t in arrays:
+        name = re.sub(r"[^A-Za-z0-9_.-]", "_", key)
+        while name in seen:
+            name += "_"
+        seen.add(name)
+        flat = t.detach().reshape(-1)
+        if flat.numel() > cap:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.randint(0, flat.numel(), (cap,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        a = flat.cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+
+
+def plain_line(args, rank, world, dist, shared_gpu, dev_index, local_elapsed, elapsed, wl, wname, gather_kind, comm, comm_ok):
+    """The line of a plain run (no --full): the headline keys, meaning what they mean in the --full line, plus the run's config."""
+    import torch
+    import mi355attn
+    rank_ms = [round(local_elapsed / args.steps * 1e3, 4)]
+    ranks_seen, rank_devs = [rank], [dev_index]
+    if dist is not None:
+        ms_all = [None] * world
+        dist.all_gather_object(ms_all, (rank, rank_ms[0], torch.cuda.current_device()))
+        ranks_seen = sorted(r for r, _, _ in ms_all)
+        rank_ms = [m for _, m, _ in sorted(ms_all)]
+        rank_devs = [d for _, _, d in sorted(ms_all)]
+    if comm is not None:
+        comm.close()
+    if rank == 0:
+        distinct = len(set(rank_devs)) if shared_gpu else world
+        out = headline(dict(batch=args.batch, steps=args.steps, warmup=args.warmup, world=world, distinct_gpus=distinct,
+                            value=world * args.batch * args.steps / elapsed, ms_per_step=elapsed / args.steps * 1e3,
+                            dtype=wl.get("dtype", "f32"), precision=mi355attn.default_precision()))
+        out["config"] = {"workload": wname, "precision": PRECISION_NAMES[mi355attn.default_precision()], "ranks_seen": len(ranks_seen),
+                         "gather": gather_kind, "batch_per_gpu": args.batch, "parallelism": "batch-shard x%d" % world,
+                         "dist_backend": "none" if world == 1 else args.dist_backend,
+                         "rccl_self_test": ("passed on every rank" if comm_ok else ("not run (single rank)" if world == 1 else
+                                            ("not run (gloo backend)" if shared_gpu else "FAILED or skipped: see gather"))),
+                         "distinct_gpus": distinct, "full": "off: --full adds calibration, roofline, per-block and CPU-baseline figures"}
+        out["ms_per_step_by_rank"] = rank_ms
+        line = json.dumps(out, separators=(",", ":"))
+        if args.detail:
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(args.detail)), exist_ok=True)
+                with open(args.detail, "w") as f:
+                    json.dump({"line": out, "detail": {"ms_per_step_by_rank": rank_ms, "ranks": ranks_seen, "rank_devices": rank_devs}}, f,
+                              indent=1)
+            except OSError as e:
+                sys.stderr.write("[bench] --detail %s not written: %s\n" % (args.detail, e))
+        print(line)
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+PRECISION_NAMES = {0: "strict(bf16x3)", 1: "fp16-mfma", 2: "bf16-mfma"}
+
+
+def headline(m):
+    """The top-level keys of the line, shared by the plain and the --full run."""
+    shared = m["distinct_gpus"] != m["world"]
+    return {
+        "metric": "forward images/sec through one step (+ ms/block), B=%d per GPU, 224x224-derived shapes" % m["batch"],
+        "value": round(m["value"], 1), "unit": "images/s",
+        # ranks that SHARE a GPU (--dist-backend gloo on a one-GPU box) are not an N-GPU result: n_gpus counts distinct devices then
+        "n_gpus": m["distinct_gpus"] if shared else m["world"], "steps": m["steps"], "warmup": m["warmup"],
+        "ms_per_step": round(m["ms_per_step"], 4), "higher_is_better": True,
+        "scaling": "none (%d ranks share %d GPU: launch-path run, not a scaling point)" % (m["world"], m["distinct_gpus"]) if shared else "weak",
+        "vs_baseline": None,
+        "dtype": m["dtype"] if m["dtype"] in ("f32", "f32/f16") else {0: "bf16x3", 1: "f16", 2: "bf16"}[m["precision"]],
+        "data": "synthetic (torch.randn seed 4321; module-default init seed 1234)",
+    }
+
+
 DRIVER_KEYS_PER_DICT = 24       # the driver's BENCH record keeps the first 24 keys of every dict of the line (scalar leaves only)
 
 
@@ -547,7 +663,7 @@ def assemble_line(m):
     per_block, calib = m["per_block"], m["calib"]
     bef, aft, load, idle = calib.get("before", {}), calib.get("after", {}), calib.get("load", {}), calib.get("idle", {})
     cfg = {"workload": m["workload"],
-           "precision": {0: "strict(bf16x3)", 1: "fp16-mfma", 2: "bf16-mfma"}[m["precision"]],
+           "precision": PRECISION_NAMES[m["precision"]],
            "ranks_seen": m["ranks_seen"], "gather": m["gather"],
            "stream_copy_GBps": bef.get("stream_copy_GBps"), "mfma_16x16x32_TFLOPs": bef.get("mfma_16x16x32_TFLOPs"),
            "mfma_32x32x16_TFLOPs": bef.get("mfma_32x32x16_TFLOPs"),
@@ -587,22 +703,11 @@ def assemble_line(m):
             roof["kernel_" + k] = dominant[k]
     roof["legend"] = ("fracs: block time on its graded roof (2.5 PFLOP/s or 8 TB/s); hbm_fracs: algorithmic activation bytes / PMC counter "
                       "bytes over the block time, of 8 TB/s; traffic_x: counter bytes over algorithmic bytes")
-    shared = m["distinct_gpus"] != m["world"]
-    out = {
-        "metric": "forward images/sec through one step (+ ms/block), B=%d per GPU, 224x224-derived shapes" % m["batch"],
-        "value": round(m["value"], 1), "unit": "images/s",
-        # ranks that SHARE a GPU (--dist-backend gloo on a one-GPU box) are not an N-GPU result: n_gpus counts distinct devices then
-        "n_gpus": m["distinct_gpus"] if shared else m["world"], "steps": m["steps"], "warmup": m["warmup"],
-        "ms_per_step": round(m["ms_per_step"], 4), "higher_is_better": True,
-        "scaling": "none (%d ranks share %d GPU: launch-path run, not a scaling point)" % (m["world"], m["distinct_gpus"]) if shared else "weak",
-        "vs_baseline": None,
-        "dtype": m["dtype"] if m["dtype"] in ("f32", "f32/f16") else {0: "bf16x3", 1: "f16", 2: "bf16"}[m["precision"]],
-        "data": "synthetic (torch.randn seed 4321; module-default init seed 1234)",
-        "config": cfg,
-        # `roofline` grades the slowest BLOCK of the step (a block is many launches: `block` names it, achieved / frac are the block's);
-        # `kernel` names the one kernel that takes the largest share of that block, its own figures are the kernel_* keys
-        "roofline": roof,
-    }
+    out = headline(m)
+    out["config"] = cfg
+    # `roofline` grades the slowest BLOCK of the step (a block is many launches: `block` names it, achieved / frac are the block's);
+    # `kernel` names the one kernel that takes the largest share of that block, its own figures are the kernel_* keys
+    out["roofline"] = roof
     return out
 
 

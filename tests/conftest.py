@@ -12,8 +12,6 @@ for p in (ROOT, PKG, os.path.join(ROOT, "tests", "golden")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-REFERENCE = os.environ.get("MI355_REFERENCE", "/root/reference")
-
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
@@ -62,10 +60,6 @@ def assert_parity(y, r, tol=1e-3, what=""):
     rf, ma = rel_fro(y, r), max_abs_ratio(y, r)
     assert rf <= tol and ma <= tol, f"{what}: rel_fro={rf:.3e} max_abs_ratio={ma:.3e} (tol {tol:g})"
     return rf, ma
-
-
-def have_reference():
-    return os.path.isdir(os.path.join(REFERENCE, "attention_mechanisms"))
 
 
 class no_range_fallback:

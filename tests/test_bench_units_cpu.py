@@ -166,3 +166,38 @@ def test_new_flags_parse():
     a = bench.parse_args(["--gpus", "2", "--dist-backend", "gloo", "--detail", "/tmp/x.json", "--no-calib"])
     assert a.dist_backend == "gloo" and a.detail == "/tmp/x.json" and a.no_calib and a.gpus == 2
     assert bench.parse_args([]).dist_backend == "nccl"
+
+
+def test_full_is_off_by_default_and_dump_outputs_parses():
+    a = bench.parse_args([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out/dump"])
+    assert a.full and a.dump_outputs == "out/dump"
+
+
+def test_dump_outputs_writes_float32_and_a_fixed_sample(tmp_path):
+    import numpy as np
+    torch.manual_seed(0)
+    small = torch.randn(3, 5, dtype=torch.float16)
+    big = torch.randn(bench.DUMP_ELEMS + 1000)
+    blocks = [dict(key="Small"), dict(key="Big"), dict(key="Pair")]
+    outs = [small, big, (torch.ones(4, dtype=torch.float64), torch.zeros(2))]
+    for d in ("a", "b"):
+        bench.dump_outputs(blocks, outs, str(tmp_path / d))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["Big.npy", "Pair_0.npy", "Pair_1.npy", "Small.npy"]
+    s = np.load(tmp_path / "a" / "Small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.float().reshape(-1).numpy())
+    assert np.load(tmp_path / "a" / "Pair_0.npy").dtype == np.float64
+    b1, b2 = np.load(tmp_path / "a" / "Big.npy"), np.load(tmp_path / "b" / "Big.npy")
+    assert b1.dtype == np.float32 and b1.size == bench.DUMP_ELEMS and np.array_equal(b1, b2)
+    assert np.isin(b1, big.numpy()).all()
+    total = sum(os.path.getsize(tmp_path / "a" / n) for n in names)
+    assert total < 64 << 20
+
+
+def test_dump_outputs_stays_under_64_mb_with_many_outputs(tmp_path):
+    blocks = [dict(key="B%d" % i) for i in range(40)]
+    outs = [torch.zeros(bench.DUMP_ELEMS + 1) for _ in blocks]
+    bench.dump_outputs(blocks, outs, str(tmp_path))
+    assert sum(os.path.getsize(tmp_path / n) for n in os.listdir(tmp_path)) < 64 << 20

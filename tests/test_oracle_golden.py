@@ -6,19 +6,18 @@
    modules' constructors (no reference checkout needed).
 2. The drop-in modules reproduce the reference's state_dict layout and init stream (per-parameter shapes and
    fp64 checksums match the golden record).
-3. When the reference checkout is present (build container only) the oracle is additionally compared with
-   the live reference on shapes outside the golden table (ragged HW, odd channel counts, batch 1).
+3. The oracle is additionally compared with outputs of the real reference on shapes outside the golden table
+   (ragged HW, odd channel counts, batch 1), recorded in tests/golden/live/.
 """
 import importlib
 import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 from cases import BY_ID, CASES, build_case, flat_out, sample_index
-from conftest import REFERENCE, ROOT, have_reference, rel_fro
+from conftest import ROOT, rel_fro
 
 
 def _build(c):
@@ -101,51 +100,31 @@ def test_window_index_is_a_permutation_and_bit_exact():
         assert sorted(tab.reshape(-1).tolist()) == list(range(reso * reso))
 
 
-# ---- live cross-checks against the real reference (build container only) ----------------------------------
-needs_ref = pytest.mark.skipif(not have_reference(), reason="reference checkout not present")
+# ---- cross-checks against the real reference on shapes outside the golden table ------------------------------------
+# (inputs, the reference modules' weights and their outputs recorded by tests/golden/make_live_reference.py)
+def _live(name):
+    return np.load(os.path.join(ROOT, "tests", "golden", "live", name + ".npz"))
 
 
-def _ref_cls(mod, cls):
-    sys.dont_write_bytecode = True
-    saved = {k: sys.modules.pop(k) for k in list(sys.modules)
-             if k.split(".")[0] in ("attention_mechanisms", "vision_transformers", "mlps")}
-    sys.path.insert(0, REFERENCE)
-    try:
-        return getattr(importlib.import_module(mod), cls)
-    finally:
-        sys.path.remove(REFERENCE)
-        for k in list(sys.modules):
-            if k.split(".")[0] in ("attention_mechanisms", "vision_transformers", "mlps"):
-                del sys.modules[k]
-        sys.modules.update(saved)
-
-
-@needs_ref
 @pytest.mark.parametrize("shape,C,red", [((1, 48, 7, 9), 48, 16), ((3, 32, 5, 5), 32, 4), ((2, 80, 13, 1), 80, 16)])
 def test_oracle_vs_live_reference_ragged_channel_attention(shape, C, red):
     import oracle as O
-    torch.manual_seed(7)
-    x = torch.randn(*shape)
-    se = _ref_cls("attention_mechanisms.se_module", "SELayer")(C, red).eval()
-    cb = _ref_cls("attention_mechanisms.cbam", "CBAM")(C, red, 3).eval()
-    ec = _ref_cls("attention_mechanisms.eca", "ECALayer")(C).eval()
-    with torch.no_grad():
-        assert rel_fro(O.se_forward(x, se.fc[0].weight, se.fc[2].weight), se(x)) <= 1e-6
-        assert rel_fro(O.cbam_forward(x, cb.ca.fc[0].weight, cb.ca.fc[2].weight, cb.sa.conv.weight), cb(x)) <= 1e-6
-        assert rel_fro(O.eca_forward(x, ec.conv.weight), ec(x)) <= 1e-6
+    i = [(1, 48, 7, 9), (3, 32, 5, 5), (2, 80, 13, 1)].index(shape)
+    r = {k.split("__", 1)[1]: torch.from_numpy(v) for k, v in _live("chan").items() if k.startswith("chan%d__" % i)}
+    x = r["x"]
+    assert tuple(x.shape) == shape and tuple(r["se_w1"].shape[:2]) == tuple(r["cbam_w1"].shape[:2]) == (C // red, C)
+    assert rel_fro(O.se_forward(x, r["se_w1"], r["se_w2"]), r["se_y"]) <= 1e-6
+    assert rel_fro(O.cbam_forward(x, r["cbam_w1"], r["cbam_w2"], r["cbam_ws"]), r["cbam_y"]) <= 1e-6
+    assert rel_fro(O.eca_forward(x, r["eca_w"]), r["eca_y"]) <= 1e-6
 
 
-@needs_ref
 def test_oracle_vs_live_reference_lepe_all_modes():
     import oracle as O
-    Lepe = _ref_cls("vision_transformers.cswin", "LePEAttention")
-    torch.manual_seed(3)
-    for reso, idx, split, dim, heads in ((8, 0, 2, 32, 2), (8, 1, 4, 32, 1), (6, -1, 6, 64, 4)):
-        m = Lepe(dim, reso, idx, split_size=split, num_heads=heads).eval()
-        qkv = torch.randn(3, 2, reso * reso, dim)
-        with torch.no_grad():
-            ref = m(qkv)
-        got = O.lepe_attention_forward(qkv, m.get_v.weight, m.get_v.bias, reso, idx, split, heads)
+    rec = _live("lepe")
+    for i, (reso, idx, split, dim, heads) in enumerate(((8, 0, 2, 32, 2), (8, 1, 4, 32, 1), (6, -1, 6, 64, 4))):
+        qkv, w, b, ref = (torch.from_numpy(rec["lepe%d__%s" % (i, k)]) for k in ("qkv", "w", "b", "y"))
+        assert tuple(qkv.shape) == (3, 2, reso * reso, dim)
+        got = O.lepe_attention_forward(qkv, w, b, reso, idx, split, heads)
         assert rel_fro(got, ref) <= 1e-6
 
 

@@ -160,7 +160,7 @@ def test_bench_two_ranks_share_one_gpu_on_gloo(workload, first_key):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "4"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--workload", workload, "--batch", "16",
-           "--steps", "2", "--warmup", "1", "--no-cpu", "--no-strict", "--no-calib"]
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-strict", "--no-calib"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -407,3 +407,28 @@ def test_one_wave_per_simd_gemm_under_graph_capture_and_on_a_side_stream():
     side.synchronize()
     assert torch.equal(y_side, y_ref)
     _drain_range()
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_outputs(tmp_path):
+    """A plain bench.py run (no --full): the headline keys only, exactly --steps timed steps, and --dump-outputs writes the last timed
+    step's outputs, the same values on a second run with the same arguments."""
+    import numpy as np
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    lines = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "c2", "--batch", "4", "--steps", "3",
+               "--warmup", "1", "--dump-outputs", str(tmp_path / d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+    line = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert "roofline" not in line and "cpu_baseline" not in line
+    assert sorted(os.listdir(tmp_path / "a")) == ["CBAM.npy", "ECA.npy", "SE.npy"]
+    for n in ("SE", "CBAM", "ECA"):
+        a, b = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert a.dtype == np.float32 and a.size == min(4 * 256 * 56 * 56, bench.DUMP_ELEMS) and np.isfinite(a).all()
+        assert np.allclose(a, b, rtol=1e-5, atol=1e-6), n

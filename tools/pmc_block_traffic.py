@@ -1,11 +1,11 @@
 #!/usr/bin/env python
 """Fabric traffic per forward of ONE bench block from the two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE; separate runs) of
-`bench.py --workload all --only <block>`:
+`bench.py --full --workload all --only <block>`:
 
     python tools/pmc_block_traffic.py <block name> <fetch.db> <write.db> <forwards>  ->  one JSON line {block, bytes, kernels}
 
 Every kernel of the run except torch's own (RNG fill, copies) and the stream-copy yardstick belongs to the block; `forwards` is the
-number of forward calls of the run (warmup + steps + 1 + steps of bench.py).  Units/corrections as in tools/pmc_traffic.py
+number of forward calls of the run (warmup + steps + 1 + steps of bench.py --full).  Units/corrections as in tools/pmc_traffic.py
 (MI355X_MICROARCH.md section HBM): KiB counters, FETCH_SIZE doubled (gfx950 reports half of a wide coalesced stream);
 Infinity-Cache hits are included -- traffic below L2, not DRAM-only.
 """

@@ -66,6 +66,6 @@ def main(fetch_db, write_db, forwards_per_block):
 
 
 if __name__ == "__main__":
-    # bench.py --no-cpu --steps 3 --warmup 1: each block runs warmup + steps + 1 + steps forwards
+    # bench.py --full --no-cpu --steps 3 --warmup 1: each block runs warmup + steps + 1 + steps forwards
     fw = int(sys.argv[3]) if len(sys.argv) > 3 else (1 + 3 + 1 + 3)
     main(sys.argv[1], sys.argv[2], fw)
