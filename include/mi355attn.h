@@ -188,9 +188,18 @@ int         mi355_workspace_forget(const void* ws, size_t ws_bytes);
  * Launches also refuse shapes whose per-image workgroup set cannot be resident at once (they take the multi-pass kernels). */
 int         mi355_sync_status(void);
 /* fp16 range guard.  The default operand format (precision 1) is IEEE half: a finite fp32 value of magnitude >= 65520 becomes inf where
- * the fp32 reference stays finite.  The producers of fp16 operand tensors -- mi355_cast16_fwd, mi355_layernorm16_fwd and every GEMM
- * epilogue with a 16-bit output (mi355_linear16*_fwd, mi355_mhsa_fwd's qkv, the patch embedding) -- watch the magnitudes they convert
- * and, on the first saturation, store a code into a pinned host word.  mi355_range_status() reads that word WITHOUT a device
+ * the fp32 reference stays finite.  Every kernel that converts an fp32 value to an fp16 operand watches the magnitudes it converts and, on
+ * the first saturation, stores a code into a pinned host word (the code names the producer family in mi355_last_error):
+ *   1 mi355_cast16_fwd (and the input cast inside mi355_linear16_x32_fwd)     2 mi355_layernorm16_fwd, the 16-bit LayerNorm-in-GEMM operands
+ *   3 every GEMM epilogue with a 16-bit output (mi355_linear16*_fwd, mi355_mhsa_fwd's qkv, the patch embedding's 16-bit path)
+ *   4 the fused block kernels (mi355_mlp_fused_fwd / mi355_proj_mlp_fused_fwd / mi355_cswin_stripe_attn_fwd / mi355_mixer_token_fwd ...)
+ *   5 the LayerNorm-folding GEMM epilogue (mi355_linear16_lnc_fwd / mi355_ln_center16_fwd)
+ *   6 the fp16 operand staging of the fp32-input GEMMs (mi355_linear_fwd incl. its small-output kernel, mi355_token_mix_fwd,
+ *     mi355_conv2d_tokens_fwd, mi355_patch_embed_fwd and the im2col pass of mi355_patch_embed_ws_fwd)
+ *   7 the fp16 q / k / v staging of the fp32-I/O attention cores (mi355_sdpa_fwd, mi355_sdpa_general_fwd with io16 = 0,
+ *     mi355_cswin_lepe_attn_fwd); their probabilities are in [0, 1] and need no check
+ *   8 the DoubleAttention kernels (mi355_double_attn_fwd: x, the A product, G, M' and the weights; the softmax factors are bounded)
+ * Not yet reporting: XCA on an fp32 qkv input (mi355_xca16_fwd with qkv_is16 = 0).  mi355_range_status() reads that word WITHOUT a device
  * synchronisation: MI355_OK = nothing pending; MI355_ERANGE = some launch that has already executed produced inf from finite values
  * (cleared by the report).  A host that wants certainty for a forward synchronises the stream first.  Remedy: run the module in
  * precision 0 (strict: bf16 hi/lo split, fp32 range) or precision 2 (bf16).  bf16 operands are never flagged. */
@@ -526,7 +535,9 @@ int mi355_cswin_stripe_attn_fwd(const float* x, const void* wqkv16, const float*
  * `layernorm` is a flag word: bit 0 = normalise x; bit 1 (round 6) = the caller has PROVEN from the folded weights that the one unbounded
  * 16-bit intermediate, gelu(W1' xn + b1'), stays below 65504 (|xn| <= sqrt(C - 1), so max_i (sum_j |W1'[i][j]| sqrt(C - 1) + |b1'[i]|) bounds
  * it): the kernel then does not report into the fp16 range word and the launch does not count as a producer for mi355_range_wait.  Without
- * bit 1 (and in precision 1) a saturating hidden activation is reported with code 4. */
+ * bit 1 (and in precision 1) a saturating hidden activation is reported with code 4.  Any other value of `layernorm` (outside 0..3) is
+ * MI355_EINVAL -- a caller of the old boolean form that passed, say, 2 gets an error instead of a silent "no LayerNorm, no report".
+ * mi355_proj_mlp_fused_fwd takes the same flag word. */
 int mi355_mlp_fused_fwd(const float* x, const void* w1_16, const float* b1, const void* w2_16, const float* b2, const float* gamma,
                         float* y, long M, int C, int hidden, int layernorm, float eps, int precision, mi355_stream_t stream);
 

@@ -289,9 +289,14 @@ int range_pending(const char* who) {
     static const char* const names[] = {"?", "mi355_cast16_fwd", "mi355_layernorm16_fwd", "a 16-bit-output GEMM epilogue (mi355_linear16_fwd family)",
                                         "a fused block kernel (mi355_mlp_fused_fwd / mi355_proj_mlp_fused_fwd / mi355_cswin_stripe_attn_fwd / "
                                         "mi355_ln_linear16_fwd / mi355_layernorm16_t_fwd / mi355_mixer_token_fwd)",
-                                        "the LayerNorm-folding GEMM epilogue (mi355_linear16_lnc_fwd / mi355_ln_center16_fwd)"};
+                                        "the LayerNorm-folding GEMM epilogue (mi355_linear16_lnc_fwd / mi355_ln_center16_fwd)",
+                                        "the fp16 operand staging of an fp32-input GEMM (mi355_linear_fwd / mi355_token_mix_fwd / mi355_conv2d_tokens_fwd / "
+                                        "mi355_patch_embed_fwd / mi355_patch_embed_ws_fwd)",
+                                        "the fp16 q / k / v staging of an fp32-I/O attention core (mi355_sdpa_fwd / mi355_sdpa_general_fwd / "
+                                        "mi355_cswin_lepe_attn_fwd)",
+                                        "a DoubleAttention kernel (mi355_double_attn_fwd: x, the A product, G, M' or the weights staged to fp16)"};
     return fail(MI355_ERANGE, "%s: an EARLIER launch of %s converted a finite value of magnitude >= 65520 to fp16: that tensor holds inf "
-                "where the fp32 reference is finite.  Run the module in precision 0 (strict) or 2 (bf16)", who, names[code < 6 ? code : 0]);
+                "where the fp32 reference is finite.  Run the module in precision 0 (strict) or 2 (bf16)", who, names[code < 9 ? code : 0]);
 }
 unsigned spin_limit() { return (unsigned)opt(O_SPIN_LIMIT); }
 int sync_pending(const char* who) {

@@ -44,6 +44,15 @@ struct AttnPair {
     AttnArgs a0, a1;
     int split;
 };
+// The fp32-I/O instantiations take the range word as well (q / k / v staged to fp16 report code 7; null unless fp16).  A separate type, so
+// that the kernel arguments -- and the code -- of the 16-bit-I/O instantiations stay exactly as they were.
+struct AttnPairRg : AttnPair {
+    unsigned* ovf;
+};
+template <bool IO16>
+using attn_kargs = typename std::conditional<IO16, AttnPair, AttnPairRg>::type;
+template <bool IO16>
+const attn_kargs<IO16>& attn_pick(const AttnPairRg& p) { return p; }
 
 // OCC: workgroups per CU the register allocation is asked to leave room for.  The window kernels are latency-bound (a workgroup does
 // one memory round trip, a few dozen MFMAs, one store), so resident workgroups per CU are the throughput lever.
@@ -55,7 +64,7 @@ struct AttnPair {
 #define MI355_ATTN_FMA_SM 1
 #endif
 template <int PREC, int D, int KT, bool LEPE, bool IO16, int NW, int OCC = 1, int TFULL = -1>
-__global__ __launch_bounds__(NW * 64, OCC) void win_attn_kernel(const AttnPair pr) {
+__global__ __launch_bounds__(NW * 64, OCC) void win_attn_kernel(const attn_kargs<IO16> pr) {
     constexpr bool FMA_SM = MI355_ATTN_FMA_SM != 0;
     // XCD-aware block order: hardware hands consecutive block ids to the 8 XCDs round-robin, but consecutive LOGICAL ids are the heads
     // of one window, whose q / k / v slices are adjacent 64-byte (d = 32) pieces of the same token rows -- neighbours that should
@@ -73,6 +82,11 @@ __global__ __launch_bounds__(NW * 64, OCC) void win_attn_kernel(const AttnPair p
     constexpr int TK = KT * 16;               // padded key count
     constexpr int KP = D + 8;                 // K row pitch (elements)
     constexpr int VP = TK + 4;                // V^T row pitch (elements, multiple of 4 -> 8-byte aligned reads)
+    // fp16 range guard of the fp32-I/O fp16 instantiations: running |max| of the fp32 q (after the pre-scale), k and v values converted to
+    // fp16 (common.h rg_absmax4), reported at the end.  The 16-bit-I/O instantiations read operands their producers already checked; the
+    // probabilities P are in [0, 1].
+    constexpr bool RG = !IO16 && PREC == 1;
+    float rgm = 0.f;
     constexpr int OP = IO16 ? D + 8 : D + 4;  // O slab pitch (elements: 16-bit when the output is 16-bit, else floats)
     constexpr int K_EL = TK * KP, V_EL = D * VP;
     using slab_t = typename std::conditional<IO16, unsigned short, float>::type;
@@ -171,6 +185,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void win_attn_kernel(const AttnPair p
         const int key = idx / D4, d4 = idx % D4;
         f4 v = {0.f, 0.f, 0.f, 0.f};
         if (key < T) v = *reinterpret_cast<const f4*>(base + (long)tok(key) * row3 + a.koff + d4 * 4);
+        if constexpr (RG) rgm = rg_absmax4(rgm, v);
         const v4 h = M_::cvt(v);
         *reinterpret_cast<v4*>(s_k + key * KP + d4 * 4) = h;
         if constexpr (NS == 2) *reinterpret_cast<v4*>(s_k + K_EL + key * KP + d4 * 4) = M_::cvt_lo(v, h);
@@ -183,6 +198,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void win_attn_kernel(const AttnPair p
             const int key = kg * 4 + j;
             r[j] = f4{0.f, 0.f, 0.f, 0.f};
             if (key < T) r[j] = *reinterpret_cast<const f4*>(base + (long)tok(key) * row3 + a.voff + d4 * 4);
+            if constexpr (RG) rgm = rg_absmax4(rgm, r[j]);
         }
         const f4 c[4] = {{r[0].x, r[1].x, r[2].x, r[3].x}, {r[0].y, r[1].y, r[2].y, r[3].y},
                          {r[0].z, r[1].z, r[2].z, r[3].z}, {r[0].w, r[1].w, r[2].w, r[3].w}};
@@ -232,6 +248,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void win_attn_kernel(const AttnPair p
                     hi4 = *reinterpret_cast<const f4*>(qrow + ks * 32 + g * 8 + 4);
                 }
                 if (a.pre_scale) { lo4 = lo4 * a.scale; hi4 = hi4 * a.scale; }
+                if constexpr (RG) rgm = rg_absmax4(rg_absmax4(rgm, lo4), hi4);
                 const v4 h0 = M_::cvt(lo4), h1 = M_::cvt(hi4);
                 qf[ks][0] = v8{h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
                 if constexpr (NS == 2) {
@@ -421,11 +438,12 @@ __global__ __launch_bounds__(NW * 64, OCC) void win_attn_kernel(const AttnPair p
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
+    if constexpr (RG) rg_report(rgm, pr.ovf, 7u);
 }
 
 template <int D, bool LEPE, bool IO16>
 int launch_attn(const AttnArgs& a, int B, int precision, hipStream_t st, const AttnArgs* other = nullptr) {
-    AttnPair pr{};
+    AttnPairRg pr{};
     pr.a0 = a;
     pr.split = B * a.nwin * a.heads;
     int grid = pr.split;
@@ -435,11 +453,12 @@ int launch_attn(const AttnArgs& a, int B, int precision, hipStream_t st, const A
     }
     if (IO16 && precision == MI355_PREC_STRICT)
         return mi355::fail(MI355_EINVAL, "16-bit activation I/O needs precision 1 (fp16) or 2 (bf16)");
+    if (!IO16 && precision == MI355_PREC_FP16) pr.ovf = mi355::range_word(st);       // fp32 q / k / v staged to fp16: a producer
     MI355_TRACE(st, "win_attn_kernel<d=%d%s%s> B=%d windows=%d heads=%d tokens=%d", D, LEPE ? ",lepe" : "", IO16 ? ",io16" : "", B, a.nwin, a.heads, a.T);
-#define GO(P, KT_, NW_) win_attn_kernel<P, D, KT_, LEPE, (IO16 && P != 0), NW_><<<grid, NW_ * 64, 0, st>>>(pr)
-#define GO_OCC(P, KT_, NW_, OCC_) win_attn_kernel<P, D, KT_, LEPE, (IO16 && P != 0), NW_, ((IO16 && P != 0 && D == 32) ? OCC_ : 1)><<<grid, NW_ * 64, 0, st>>>(pr)
+#define GO(P, KT_, NW_) win_attn_kernel<P, D, KT_, LEPE, (IO16 && P != 0), NW_><<<grid, NW_ * 64, 0, st>>>(attn_pick<(IO16 && P != 0)>(pr))
+#define GO_OCC(P, KT_, NW_, OCC_) win_attn_kernel<P, D, KT_, LEPE, (IO16 && P != 0), NW_, ((IO16 && P != 0 && D == 32) ? OCC_ : 1)><<<grid, NW_ * 64, 0, st>>>(attn_pick<(IO16 && P != 0)>(pr))
 #define GO_FULL(P, KT_, NW_, OCC_, TF_) \
-    win_attn_kernel<P, D, KT_, LEPE, (IO16 && P != 0), NW_, ((IO16 && P != 0 && D == 32) ? OCC_ : 1), TF_><<<grid, NW_ * 64, 0, st>>>(pr)
+    win_attn_kernel<P, D, KT_, LEPE, (IO16 && P != 0), NW_, ((IO16 && P != 0 && D == 32) ? OCC_ : 1), TF_><<<grid, NW_ * 64, 0, st>>>(attn_pick<(IO16 && P != 0)>(pr))
     const bool hot = IO16 && (!other || other->T == a.T);        // 16-bit I/O shapes of the models: compile-time count of full key tiles
 #define BYKT(P)                                          \
     do {                                                 \

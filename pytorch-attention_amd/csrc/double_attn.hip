@@ -113,16 +113,21 @@ inline size_t r16(size_t n) { return (n + 15) & ~(size_t)15; }
 // x (B, C, HW) fp32 -> xt (B, HW, C) in the 16-bit operand type: the token-major activation the fast GEMM engine wants as its row operand
 // (64 x 64 tiles through LDS: 256-byte runs in, 128-byte runs out).
 template <typename T>
-__global__ __launch_bounds__(256) void nchw_to_tokens16_kernel(const float* __restrict__ x, T* __restrict__ xt, int C, int HW) {
+__global__ __launch_bounds__(256) void nchw_to_tokens16_kernel(const float* __restrict__ x, T* __restrict__ xt, int C, int HW,
+                                                               unsigned* ovf) {
     __shared__ float tile[64][65];
     const int b = blockIdx.z, p0 = blockIdx.x * 64, c0 = blockIdx.y * 64, t = threadIdx.x;
     {
         const int tx = t & 63, ty = t >> 6;
+        float rgm = 0.f;                                            // fp16: every tile value becomes an operand (range code 8)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int cl = ty * 16 + r, c = c0 + cl, p = p0 + tx;
-            tile[cl][tx] = (c < C && p < HW) ? x[((long)b * C + c) * HW + p] : 0.f;
+            const float v = (c < C && p < HW) ? x[((long)b * C + c) * HW + p] : 0.f;
+            if constexpr (std::is_same<T, _Float16>::value) rgm = rg_max3abs(rgm, v, v);
+            tile[cl][tx] = v;
         }
+        if constexpr (std::is_same<T, _Float16>::value) rg_report_f(rgm, ovf, 8u);
     }
     __syncthreads();
     const int pl = t >> 2, cq = t & 3, p = p0 + pl;
@@ -201,8 +206,8 @@ int mi355_double_attn_fwd(const float* x, const float* wA, const float* bA, cons
         void* xt16 = q; q += r16((size_t)B * HW * C * 2);
         void* w16 = q;
         const dim3 tgrid(cdiv(HW, 64), cdiv(C, 64), B);
-        if (precision == MI355_PREC_FP16) nchw_to_tokens16_kernel<_Float16><<<tgrid, 256, 0, st>>>(x, static_cast<_Float16*>(xt16), C, HW);
-        else                              nchw_to_tokens16_kernel<__bf16><<<tgrid, 256, 0, st>>>(x, static_cast<__bf16*>(xt16), C, HW);
+        if (precision == MI355_PREC_FP16) nchw_to_tokens16_kernel<_Float16><<<tgrid, 256, 0, st>>>(x, static_cast<_Float16*>(xt16), C, HW, mi355::range_word(st));
+        else                              nchw_to_tokens16_kernel<__bf16><<<tgrid, 256, 0, st>>>(x, static_cast<__bf16*>(xt16), C, HW, nullptr);
         rc = mi355_cast16_fwd(Wcat, w16, (size_t)M3 * C, precision, stream);
         if (rc) return rc;
         rc = mi355_linear16_tr_fwd(xt16, w16, bcat, nullptr, ABV, B * HW, M3, C, C, HW, precision, stream);

@@ -67,6 +67,7 @@ struct DaArgs {
     const float* bp;           // (C)
     float* y;                  // (B, C, HW)
     int B, HW, S, tiles, tiles_per;
+    unsigned* ovf;             // fp16 range word (precision 1, else null): x, A, G, M' and the weights staged to fp16 report code 8
 };
 
 // ---- weights to the operand format (once per call; 130 K elements) ---------------------------------------------------------------
@@ -74,7 +75,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void da_prep_kernel(const float* __restrict__ wA, const float* __restrict__ wB, const float* __restrict__ wV,
                                                       const float* __restrict__ bA, const float* __restrict__ bB, const float* __restrict__ bV,
                                                       const float* __restrict__ wP, T* __restrict__ w16, float* __restrict__ bias,
-                                                      T* __restrict__ wp16, int C) {
+                                                      T* __restrict__ wp16, int C, unsigned* ovf) {
     constexpr float LOG2E = 1.4426950408889634f;
     const int i = blockIdx.x * 256 + threadIdx.x, n = CM * C;
     if (i < n) {
@@ -82,6 +83,8 @@ __global__ __launch_bounds__(256) void da_prep_kernel(const float* __restrict__ 
         w16[n + i] = (T)(wB[i] * LOG2E);
         w16[2 * n + i] = (T)(wV[i] * LOG2E);
         wp16[i] = (T)wP[i];                                         // (C, 128): the same element count
+        if constexpr (std::is_same<T, _Float16>::value)
+            rg_report_f(rg_max3abs(rg_max3abs(0.f, wA[i], wB[i] * LOG2E), wV[i] * LOG2E, wP[i]), ovf, 8u);
     }
     if (i < CM) {
         bias[i] = bA[i];
@@ -98,6 +101,9 @@ __global__ __launch_bounds__(512) void da_pass1_kernel(const DaArgs a) {
     using v4 = typename M_::v4;
     using el = typename M_::e;
     static_assert(Mma<PREC>::NSPLIT == 1, "16-bit operand modes only");
+    // fp16 range guard (common.h rg_max3abs, code 8): the unbounded values this kernel converts -- x, A = WA x + bA, and (S = 1) G and
+    // M' = WP G.  E = 2^(b - m) <= 2^8 (the reference maximum moves by more than 8) and the channel softmax of V are bounded.
+    float rgm = 0.f;
     constexpr int C = 32 * KS;
     constexpr int XP = C + 8;                  // pitch of X^T rows (elements): 16 rows x 16 bytes land on 64 distinct banks
     constexpr int EP = 40;                     // pitch of E rows (32 px + 8)
@@ -183,8 +189,11 @@ __global__ __launch_bounds__(512) void da_pass1_kernel(const DaArgs a) {
                              "ds_read_b128 %3, %4 offset:384\n\ts_waitcnt lgkmcnt(0)"
                              : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]) : "v"(ra) : "memory");
 #pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    *reinterpret_cast<v4*>(&s_xt[(4 * q + i) * XP + 4 * cg]) = M_::cvt(f4{r[0][i], r[1][i], r[2][i], r[3][i]});
+                for (int i = 0; i < 4; ++i) {
+                    const f4 xv = f4{r[0][i], r[1][i], r[2][i], r[3][i]};
+                    if constexpr (PREC == 1) rgm = rg_max3abs4(rgm, xv);
+                    *reinterpret_cast<v4*>(&s_xt[(4 * q + i) * XP + 4 * cg]) = M_::cvt(xv);
+                }
             }
         }
         DA_BAR();                                                   // B1: X^T complete; raw[buf] and s_v of the previous tile free to reuse / read
@@ -213,6 +222,7 @@ __global__ __launch_bounds__(512) void da_pass1_kernel(const DaArgs a) {
         const bool tail = px0 + PT > a.HW;                          // wave-uniform
         // A: operand of the product over pixels, k slot i <-> pixel 4g + i, slot 4 + i <-> pixel 16 + 4g + i
         v8 afrag;
+        if constexpr (PREC == 1) rgm = rg_max3abs4(rg_max3abs4(rgm, acc[0][0]), acc[1][0]);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             afrag[i] = M_::cvt1(acc[0][0][i]);
@@ -349,8 +359,11 @@ __global__ __launch_bounds__(512) void da_pass1_kernel(const DaArgs a) {
         if (g == 0) s_alpha[16 * w + l15] = 1.0f / lsum;
         __syncthreads();
 #pragma unroll
-        for (int j = 0; j < 8; ++j)
-            *reinterpret_cast<v4*>(&s_g[(16 * j + l15) * GP + 16 * w + 4 * g]) = M_::cvt(G[j] * s_alpha[16 * j + l15]);
+        for (int j = 0; j < 8; ++j) {
+            const f4 gv = G[j] * s_alpha[16 * j + l15];
+            if constexpr (PREC == 1) rgm = rg_max3abs4(rgm, gv);
+            *reinterpret_cast<v4*>(&s_g[(16 * j + l15) * GP + 16 * w + 4 * g]) = M_::cvt(gv);
+        }
         __syncthreads();
         const el* wp = static_cast<const el*>(a.wp16);
         el* m16 = static_cast<el*>(a.m16) + (long)b * C * CM;
@@ -364,9 +377,11 @@ __global__ __launch_bounds__(512) void da_pass1_kernel(const DaArgs a) {
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks)
                     acc = M_::mma(*reinterpret_cast<const v8*>(&s_g[(16 * rt + l15) * GP + 32 * ks + 8 * g]), bf[ks], acc);
+                if constexpr (PREC == 1) rgm = rg_max3abs4(rgm, acc);
                 *reinterpret_cast<v4*>(m16 + (long)(16 * ct + l15) * CM + 16 * rt + 4 * g) = M_::cvt(acc);
             }
         }
+        if constexpr (PREC == 1) rg_report_f(rgm, a.ovf, 8u);
         return;
     }
     // ---- the range's partial result ------------------------------------------------------------------------------------------------
@@ -378,6 +393,7 @@ __global__ __launch_bounds__(512) void da_pass1_kernel(const DaArgs a) {
         ml[16 * w + l15] = m_run;
         ml[CM + 16 * w + l15] = lsum;
     }
+    if constexpr (PREC == 1) rg_report_f(rgm, a.ovf, 8u);
 }
 
 // ---- combine: G = merge of the ranges (normalised), M'^T = G^T WP^T ----------------------------------------------------------------
@@ -391,6 +407,7 @@ __global__ __launch_bounds__(256) void da_combine_kernel(const DaArgs a, int C) 
     __shared__ float s_sc[MAXS][CM];
     __shared__ __attribute__((aligned(16))) unsigned short s_g[CM * GP];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, l15 = lane & 15, g = lane >> 4, b = blockIdx.x, S = a.S;
+    float rgm = 0.f;                                                // fp16 range guard (code 8): G and M' = WP G
     if (t < CM) {
         const float* ml = a.ml + (long)b * S * 2 * CM;
         float M = -INFINITY;
@@ -407,6 +424,7 @@ __global__ __launch_bounds__(256) void da_combine_kernel(const DaArgs a, int C) 
         const int idx = t + 256 * e, k = idx >> 5, mq = idx & 31;
         f4 sum = f4{0.f, 0.f, 0.f, 0.f};
         for (int s = 0; s < S; ++s) sum += *reinterpret_cast<const f4*>(gt + ((long)s * CM + k) * CM + 4 * mq) * s_sc[s][k];
+        if constexpr (PREC == 1) rgm = rg_max3abs4(rgm, sum);
         *reinterpret_cast<v4*>(&s_g[k * GP + 4 * mq]) = M_::cvt(sum);
     }
     __syncthreads();
@@ -423,9 +441,11 @@ __global__ __launch_bounds__(256) void da_combine_kernel(const DaArgs a, int C) 
             for (int ks = 0; ks < 4; ++ks)
                 acc = M_::mma(*reinterpret_cast<const v8*>(&s_g[(16 * rt + l15) * GP + 32 * ks + 8 * g]), bf[ks], acc);
             // lane: column o = 16 ct + l15, rows k' = 16 rt + 4g + [0,4)
+            if constexpr (PREC == 1) rgm = rg_max3abs4(rgm, acc);
             *reinterpret_cast<v4*>(m16 + (long)(16 * ct + l15) * CM + 16 * rt + 4 * g) = M_::cvt(acc);
         }
     }
+    if constexpr (PREC == 1) rg_report_f(rgm, a.ovf, 8u);
 }
 
 // ---- pass 2: y = M' V + bP -----------------------------------------------------------------------------------------------------------
@@ -560,17 +580,18 @@ int double_attn_fused(const float* x, const float* wA, const float* bA, const fl
     a.ml = reinterpret_cast<float*>(p);        p += r256((size_t)B * a.S * 2 * CM * 4);
     a.m16 = p;
     a.x = x; a.w16 = w16; a.bias = bias; a.wp16 = wp16; a.bp = bP; a.y = y;
+    a.ovf = precision == MI355_PREC_FP16 ? range_word(st) : nullptr;
     const int pgrid = cdiv((long)CM * C, 256);
     const int nsub = 2, groups = cdiv(HW, 64 * nsub);
     if (precision == MI355_PREC_FP16) {
-        da_prep_kernel<_Float16><<<pgrid, 256, 0, st>>>(wA, wB, wV, bA, bB, bV, wP, static_cast<_Float16*>(w16), bias, static_cast<_Float16*>(wp16), C);
+        da_prep_kernel<_Float16><<<pgrid, 256, 0, st>>>(wA, wB, wV, bA, bB, bV, wP, static_cast<_Float16*>(w16), bias, static_cast<_Float16*>(wp16), C, a.ovf);
         if (C == 256) da_pass1_kernel<1, 8><<<B * a.S, 512, 0, st>>>(a);
         else          da_pass1_kernel<1, 4><<<B * a.S, 512, 0, st>>>(a);
         if (a.S > 1) da_combine_kernel<1><<<B, 256, 0, st>>>(a, C);
         if (C == 256) da_pass2_kernel<1, 2><<<B * groups, 512, 0, st>>>(a, nsub, groups);
         else          da_pass2_kernel<1, 1><<<B * groups, 512, 0, st>>>(a, nsub, groups);
     } else {
-        da_prep_kernel<__bf16><<<pgrid, 256, 0, st>>>(wA, wB, wV, bA, bB, bV, wP, static_cast<__bf16*>(w16), bias, static_cast<__bf16*>(wp16), C);
+        da_prep_kernel<__bf16><<<pgrid, 256, 0, st>>>(wA, wB, wV, bA, bB, bV, wP, static_cast<__bf16*>(w16), bias, static_cast<__bf16*>(wp16), C, nullptr);
         if (C == 256) da_pass1_kernel<2, 8><<<B * a.S, 512, 0, st>>>(a);
         else          da_pass1_kernel<2, 4><<<B * a.S, 512, 0, st>>>(a);
         if (a.S > 1) da_combine_kernel<2><<<B, 256, 0, st>>>(a, C);

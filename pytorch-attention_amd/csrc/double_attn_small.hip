@@ -36,6 +36,7 @@ struct DsArgs {
     const float* x; float* y;
     const float* wA; const float* bA; const float* wB; const float* bB; const float* wV; const float* bV; const float* wP; const float* bP;
     int HW;
+    unsigned* ovf;                // fp16 range word (precision 1, else null): weights, x, A and M' staged to fp16 report code 8
 };
 
 template <int PREC, int C>
@@ -57,11 +58,15 @@ __global__ __launch_bounds__(512) void da_small_kernel(const DsArgs a) {
     const int b = blockIdx.x, HW = a.HW;
     const float* xb = a.x + (long)b * C * HW;
     unsigned char* xt = s_x + w * (DS_GPX * XP);
+    // fp16 range guard (common.h rg_max3abs, code 8): the unbounded values converted to fp16 -- the weights, x, A = WA x + bA and
+    // M' = WP G.  The softmax factors (2^(b - max) and the channel softmax of V) are in [0, 1].
+    float rgm = 0.f;
 
     // ---- weight fragments, kept in registers for the whole image.  B-operand form (column = out channel l15, k = 8 consecutive input
     //      channels) for WA / WB; the same lane -> (row, k) map as the A operand for WV.  log2 e folded into WB, WV and their biases.
     auto wfrag = [&](const float* wrow, float s) {
         const f4 lo = *reinterpret_cast<const f4*>(wrow) * s, hi = *reinterpret_cast<const f4*>(wrow + 4) * s;
+        if constexpr (PREC == 1) rgm = rg_max3abs4(rg_max3abs4(rgm, lo), hi);
         const v4 h0 = M_::cvt(lo), h1 = M_::cvt(hi);
         return v8{h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
     };
@@ -107,6 +112,7 @@ __global__ __launch_bounds__(512) void da_small_kernel(const DsArgs a) {
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             const int ch = 8 * i + chs;
+            if constexpr (PREC == 1) rgm = rg_max3abs4(rgm, xr[i]);
             const v4 h = M_::cvt(xr[i]);
 #pragma unroll
             for (int e = 0; e < 4; ++e) *reinterpret_cast<el*>(xt + (pq * 4 + e) * XP + ch * 2) = h[e];
@@ -177,6 +183,7 @@ __global__ __launch_bounds__(512) void da_small_kernel(const DsArgs a) {
         // G[i][j] += sum over the group's 32 pixels of A[i][p] E[j][p]: k enumerates (pixel tile, lane group, r) in both operands
 #pragma unroll
         for (int it = 0; it < 2; ++it) {
+            if constexpr (PREC == 1) rgm = rg_max3abs4(rg_max3abs4(rgm, accA[0][it]), accA[1][it]);
             const v4 a0 = M_::cvt(accA[0][it]), a1 = M_::cvt(accA[1][it]);
             const v8 af = v8{a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
 #pragma unroll
@@ -238,6 +245,7 @@ __global__ __launch_bounds__(512) void da_small_kernel(const DsArgs a) {
         float acc = 0.f;
 #pragma unroll 8
         for (int i = 0; i < 32; ++i) acc = __builtin_fmaf(wp[i], s_g[i * 32 + j], acc);
+        if constexpr (PREC == 1) rgm = rg_max3abs(rgm, acc, acc);
         *reinterpret_cast<el*>(s_m + q * 2) = M_::cvt1(acc);
     }
     __syncthreads();
@@ -262,6 +270,7 @@ __global__ __launch_bounds__(512) void da_small_kernel(const DsArgs a) {
             }
         }
     }
+    if constexpr (PREC == 1) rg_report_f(rgm, a.ovf, 8u);
 }
 
 }  // namespace
@@ -275,7 +284,7 @@ bool double_attn_small_ok(int B, int C, int cm, int cn, int HW, int precision) {
 
 int double_attn_small(const float* x, const float* wA, const float* bA, const float* wB, const float* bB, const float* wV, const float* bV,
                       const float* wP, const float* bP, float* y, int B, int C, int HW, int precision, hipStream_t st) {
-    DsArgs a{x, y, wA, bA, wB, bB, wV, bV, wP, bP, HW};
+    DsArgs a{x, y, wA, bA, wB, bB, wV, bV, wP, bP, HW, precision == MI355_PREC_FP16 ? range_word(st) : nullptr};
     // V tile + max(the eight X^T tiles, the merge area)
     const size_t xt = (size_t)8 * DS_GPX * (C * 2 + 16);
     const size_t merge = (size_t)(8 * 1024 + 8 * 32 * 2 + 1024) * 4 + (size_t)C * 64;

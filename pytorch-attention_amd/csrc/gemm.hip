@@ -35,6 +35,7 @@ struct GemmArgs {
     int Cin, H, W, ps, gw, P;
     int Pout;                                 // output rows per image (P + 1 when a cls row follows the patches, else P)
     int KH, KW, stride, pad, OW, Kreal;       // AMODE 2 / 3 (Kreal = Cin*KH*KW; K may be padded up to a multiple of 4)
+    unsigned* ovf;                            // fp16 range word (set by launch() for PREC 1): the staged operands report code 6
 };
 
 __device__ __forceinline__ f4 ld4_guard(const float* p, bool ok) {
@@ -42,9 +43,12 @@ __device__ __forceinline__ f4 ld4_guard(const float* p, bool ok) {
     return ok ? *reinterpret_cast<const f4*>(p) : z;
 }
 
+// The fp16 instantiation folds the staged values into the lane's running |max| (common.h rg_absmax4: an input inf is skipped, a finite
+// value >= 65520 is reported); the arithmetic is the same for every mode.
 template <int PREC>
-__device__ __forceinline__ void st_lds4(unsigned short* hi, unsigned short* lo, int off, f4 v) {
+__device__ __forceinline__ void st_lds4(unsigned short* hi, unsigned short* lo, int off, f4 v, float& rgm) {
     using M_ = Mma<PREC>;
+    if constexpr (PREC == 1) rgm = rg_absmax4(rgm, v);
     typename M_::v4 h = M_::cvt(v);
     *reinterpret_cast<typename M_::v4*>(hi + off) = h;
     if constexpr (M_::NSPLIT == 2) *reinterpret_cast<typename M_::v4*>(lo + off) = M_::cvt_lo(v, h);
@@ -121,6 +125,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs g) {
     }
 
     f4 ra[4], rb[4];
+    float rgm = 0.f;                                         // fp16 range guard: running |max| of the staged operands (PREC 1)
     auto load_tile = [&](int k0) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -170,19 +175,19 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs g) {
         unsigned short* hiB = hiA + BM * PITCH;
         unsigned short* loB = loA + BM * PITCH;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) st_lds4<PREC>(hiA, loA, (lr + 32 * i) * PITCH + lk, ra[i]);
+        for (int i = 0; i < 4; ++i) st_lds4<PREC>(hiA, loA, (lr + 32 * i) * PITCH + lk, ra[i], rgm);
         if constexpr (BMODE == 0) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) st_lds4<PREC>(hiB, loB, (lr + 32 * i) * PITCH + lk, rb[i]);
+            for (int i = 0; i < 4; ++i) st_lds4<PREC>(hiB, loB, (lr + 32 * i) * PITCH + lk, rb[i], rgm);
         } else {                                             // transpose the 4(k) x 4(n) micro-tile: rows n, 4 consecutive k
             const f4 c0 = {rb[0].x, rb[1].x, rb[2].x, rb[3].x};
             const f4 c1 = {rb[0].y, rb[1].y, rb[2].y, rb[3].y};
             const f4 c2 = {rb[0].z, rb[1].z, rb[2].z, rb[3].z};
             const f4 c3 = {rb[0].w, rb[1].w, rb[2].w, rb[3].w};
-            st_lds4<PREC>(hiB, loB, (bn4 + 0) * PITCH + bk, c0);
-            st_lds4<PREC>(hiB, loB, (bn4 + 1) * PITCH + bk, c1);
-            st_lds4<PREC>(hiB, loB, (bn4 + 2) * PITCH + bk, c2);
-            st_lds4<PREC>(hiB, loB, (bn4 + 3) * PITCH + bk, c3);
+            st_lds4<PREC>(hiB, loB, (bn4 + 0) * PITCH + bk, c0, rgm);
+            st_lds4<PREC>(hiB, loB, (bn4 + 1) * PITCH + bk, c1, rgm);
+            st_lds4<PREC>(hiB, loB, (bn4 + 2) * PITCH + bk, c2, rgm);
+            st_lds4<PREC>(hiB, loB, (bn4 + 3) * PITCH + bk, c3, rgm);
         }
     };
 
@@ -217,6 +222,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs g) {
         if (kt + 1 < nk) store_tile(buf ^ 1);
         __syncthreads();
     }
+    if constexpr (PREC == 1) rg_report(rgm, g.ovf, 6u);
 
     // ---- epilogue: 2 passes of 32 rows per wave through a private LDS slab ---------------------------------
     float* slab = reinterpret_cast<float*>(lds_raw) + wave * 32 * EPITCH;
@@ -281,13 +287,19 @@ __global__ void cls_row_kernel(const float* __restrict__ cls, const float* __res
 // With a cls row (ViT, cls LAST: row P of every image) that row of the operand is zero, so the product there is bias + table row P.
 template <typename T>
 __global__ __launch_bounds__(256) void im2col16_kernel(const float* __restrict__ img, T* __restrict__ a16, int Cin, int H, int W, int ps,
-                                                       int rows_per_img, int K) {
+                                                       int rows_per_img, int K, unsigned* ovf) {
     extern __shared__ __attribute__((aligned(16))) float s_band[];         // ps x W
     typedef T v8t __attribute__((ext_vector_type(8)));
     const int gw = W / ps, gh = H / ps;
     const int c = blockIdx.x % Cin, py = (blockIdx.x / Cin) % gh, b = blockIdx.x / (Cin * gh);
     const float* src = img + (((long)b * Cin + c) * H + (long)py * ps) * W;
-    for (int i = threadIdx.x; i < ps * W / 4; i += 256) reinterpret_cast<f4*>(s_band)[i] = reinterpret_cast<const f4*>(src)[i];
+    float rgm = 0.f;                                                         // fp16: every band value becomes an operand (range code 6)
+    for (int i = threadIdx.x; i < ps * W / 4; i += 256) {
+        const f4 v = reinterpret_cast<const f4*>(src)[i];
+        if constexpr (std::is_same<T, _Float16>::value) rgm = rg_absmax4(rgm, v);
+        reinterpret_cast<f4*>(s_band)[i] = v;
+    }
+    if constexpr (std::is_same<T, _Float16>::value) rg_report(rgm, ovf, 6u);
     __syncthreads();
     const int cpr = ps / 8, cpp = ps * cpr;                                  // 16-byte chunks per patch row / per patch
     for (int q = threadIdx.x; q < gw * cpp; q += 256) {
@@ -325,7 +337,12 @@ int launch(const GemmArgs& g, int batch, int precision, hipStream_t st) {
     MI355_TRACE(st, "gemm_kernel<prec %d,b%d,a%d> batch=%d M=%d N=%d K=%d", precision, BMODE, AMODE, batch, g.M, g.N, g.K);
     switch (precision) {
         case MI355_PREC_STRICT: gemm_kernel<0, BMODE, AMODE><<<grid, 256, 0, st>>>(g); break;
-        case MI355_PREC_FP16:   gemm_kernel<1, BMODE, AMODE><<<grid, 256, 0, st>>>(g); break;
+        case MI355_PREC_FP16: {                                // fp16 operands: a producer (fp32 values staged to fp16 report code 6)
+            GemmArgs gr = g;
+            gr.ovf = mi355::range_word(st);
+            gemm_kernel<1, BMODE, AMODE><<<grid, 256, 0, st>>>(gr);
+            break;
+        }
         case MI355_PREC_BF16:   gemm_kernel<2, BMODE, AMODE><<<grid, 256, 0, st>>>(g); break;
         default: return mi355::fail(MI355_EINVAL, "precision must be 0, 1 or 2 (got %d)", precision);
     }
@@ -464,8 +481,8 @@ int mi355_patch_embed_ws_fwd(const float* img, const float* Wp, const float* bp,
     const size_t shm = (size_t)ps * W * 4;
     {
         MI355_TRACE(st, "im2col16_kernel B=%d %dx%d ps=%d", B, H, W, ps);
-        if (precision == MI355_PREC_FP16) im2col16_kernel<_Float16><<<blocks, 256, shm, st>>>(img, static_cast<_Float16*>(a16), Cin, H, W, ps, P + 1, K);
-        else                              im2col16_kernel<__bf16><<<blocks, 256, shm, st>>>(img, static_cast<__bf16*>(a16), Cin, H, W, ps, P + 1, K);
+        if (precision == MI355_PREC_FP16) im2col16_kernel<_Float16><<<blocks, 256, shm, st>>>(img, static_cast<_Float16*>(a16), Cin, H, W, ps, P + 1, K, mi355::range_word(st));
+        else                              im2col16_kernel<__bf16><<<blocks, 256, shm, st>>>(img, static_cast<__bf16*>(a16), Cin, H, W, ps, P + 1, K, nullptr);
     }
     g16::G16Args g{};
     g.A = a16; g.B = w16; g.C = tokens; g.bias = bp; g.resid = table; g.resid_period = P + 1;

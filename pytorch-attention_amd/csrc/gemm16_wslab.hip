@@ -163,9 +163,11 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void gemm16_wslab_kernel(const G16
         __syncthreads();                              // next tile's rows complete in s_x[buf ^ 1]; everybody is done reading s_x[buf]
         buf ^= 1;
     }
+    // the input-cast report (code 1) goes first, the epilogue's (code 3) second: the order of the cast16 + linear16 sequence this entry
+    // replaces, so that a lane whose input and output both saturate leaves the same code
     if constexpr (std::is_same<T, _Float16>::value) {
-        rg_report_f(rgmax, g.ovf, 3u);
         if constexpr (A32) rg_report(rgin, g.ovf, 1u);
+        rg_report_f(rgmax, g.ovf, 3u);
     }
 }
 

@@ -16,6 +16,7 @@ namespace {
 struct SmallArgs {
     const float* A; const float* B; const float* bias; float* C;
     int M, N, K, lda, ldb, ldc, tiles_n;
+    unsigned* ovf;              // fp16 range word (PREC 1): the converted operands report code 6 like gemm_kernel's staging
 };
 
 template <int PREC, int CH>
@@ -38,7 +39,9 @@ __global__ __launch_bounds__(64) void gemm_small_kernel(const SmallArgs g) {
     }
     f4 acc[2] = {f4{0.f, 0.f, 0.f, 0.f}, f4{0.f, 0.f, 0.f, 0.f}};
 
-    auto pack = [](f4 lo4, f4 hi4, v8* out) {                      // 8 fp32 -> operand fragment (hi, and lo in strict mode)
+    float rgm = 0.f;                                               // fp16 range guard: running |max| of the converted values
+    auto pack = [&rgm](f4 lo4, f4 hi4, v8* out) {                  // 8 fp32 -> operand fragment (hi, and lo in strict mode)
+        if constexpr (PREC == 1) rgm = rg_absmax4(rg_absmax4(rgm, lo4), hi4);
         const v4 a = M_::cvt(lo4), b = M_::cvt(hi4);
         out[0] = v8{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
         if constexpr (NS == 2) {
@@ -84,6 +87,7 @@ __global__ __launch_bounds__(64) void gemm_small_kernel(const SmallArgs g) {
         if (k0 + 2 * KC < g.K) load(c0, k0 + 2 * KC);
         if (k0 + KC < g.K) compute(c1, k0 + KC);
     }
+    if constexpr (PREC == 1) rg_report(rgm, g.ovf, 6u);
     // C / D layout: lane holds column (lane & 15), rows (lane >> 4) * 4 + [0, 4) of each 16 x 16 tile
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -113,7 +117,8 @@ int gemm_small_nt(const float* A, const float* B, const float* bias, float* C, i
     // rejections sit in FRONT of MI355_TRACE (a refused launch must not leave an event pair under this kernel's tag: ADVICE round 5)
     if (precision != MI355_PREC_STRICT && precision != MI355_PREC_FP16 && precision != MI355_PREC_BF16)
         return fail(MI355_EINVAL, "precision must be 0, 1 or 2 (got %d)", precision);
-    SmallArgs g{A, B, bias, C, M, N, K, lda, ldb, ldc, cdiv(N, 32)};
+    SmallArgs g{A, B, bias, C, M, N, K, lda, ldb, ldc, cdiv(N, 32), nullptr};
+    if (precision == MI355_PREC_FP16) g.ovf = range_word(st);
     MI355_TRACE(st, "gemm_small_kernel<prec %d> M=%d N=%d K=%d", precision, M, N, K);
     switch (precision) {
         case MI355_PREC_STRICT: gemm_small_kernel<0, 2><<<(int)tiles, 64, 0, st>>>(g); break;

@@ -430,6 +430,7 @@ extern "C" int mi355_mlp_fused_fwd(const float* x, const void* w1_16, const floa
                                    float* y, long M, int C, int hidden, int layernorm, float eps, int precision, mi355_stream_t stream) {
     MI355_CHECK_ARG(x && w1_16 && b1 && w2_16 && y && M > 0);
     MI355_CHECK_ARG(precision == MI355_PREC_FP16 || precision == MI355_PREC_BF16);
+    MI355_CHECK_ARG(layernorm >= 0 && layernorm <= 3);                          // flag word: bit 0 LayerNorm, bit 1 range proven
     if (!aligned16(x) || !aligned16(y) || !aligned16(w1_16) || !aligned16(w2_16))
         return mi355::fail(MI355_EUNSUPPORTED, "mi355_mlp_fused_fwd: 16-byte aligned buffers required");
     if (mi355::mlp_wide_applicable(C, hidden) && mi355::opt_mlp_wide()) {        // C = 256 / 384: the weight-split kernel (mlp_wide.hip), W2 row-major
@@ -493,6 +494,7 @@ extern "C" int mi355_proj_mlp_fused_fwd(const float* x, const void* ctx16, const
                                         int layernorm, float eps, int precision, mi355_stream_t stream) {
     MI355_CHECK_ARG(x && ctx16 && wp16 && bp && w1_16 && b1 && w2_16 && y && M > 0);
     MI355_CHECK_ARG(precision == MI355_PREC_FP16 || precision == MI355_PREC_BF16);
+    MI355_CHECK_ARG(layernorm >= 0 && layernorm <= 3);                          // flag word: bit 0 LayerNorm, bit 1 range proven
     if (!((C == 64 && hidden == 256) || (C == 128 && hidden == 512)))
         return mi355::fail(MI355_EUNSUPPORTED, "mi355_proj_mlp_fused_fwd: built for C = 64, hidden = 256 and C = 128, hidden = 512 (got C = %d, hidden = %d)", C, hidden);
     if (!aligned16(x) || !aligned16(y) || !aligned16(w1_16) || !aligned16(w2_16) || !aligned16(ctx16) || !aligned16(wp16) || !aligned16(bp))

@@ -32,12 +32,19 @@ struct SdpaArgs {
     long ldq, ldk, ldv, ldo;         // row strides in elements
     float scale;
 };
+// The fp32-I/O instantiations take the range word as well (q / k / v staged to fp16 report code 7; null unless fp16).  A separate type, so
+// that the kernel arguments -- and the code -- of the 16-bit-I/O instantiations stay exactly as they were.
+struct SdpaArgsRg : SdpaArgs {
+    unsigned* ovf;
+};
+template <bool IO16>
+using sdpa_kargs = typename std::conditional<IO16, SdpaArgs, SdpaArgsRg>::type;
 
 constexpr int KTILE = 64;            // keys per streamed tile
 constexpr int NWV = 4;               // waves per workgroup
 
 template <int PREC, int D, int DV, bool IO16>
-__global__ __launch_bounds__(NWV * 64) void sdpa_stream_kernel(const SdpaArgs a) {
+__global__ __launch_bounds__(NWV * 64) void sdpa_stream_kernel(const sdpa_kargs<IO16> a) {
     constexpr int NTHR = NWV * 64;
     static_assert(!IO16 || PREC != 0, "16-bit I/O exists for the fp16 / bf16 operand modes only");
     using M_ = Mma<PREC>;
@@ -68,6 +75,10 @@ __global__ __launch_bounds__(NWV * 64) void sdpa_stream_kernel(const SdpaArgs a)
     const gel* vbase = static_cast<const gel*>(a.v) + (long)b * a.Nkv * a.ldv + head * a.hd + sl * DV;
     const float* bias = a.bias ? a.bias + (long)b * a.bias_bstride + (long)head * a.Nq * a.Nkv : nullptr;
     const float L2E = 1.44269504088896340736f;
+    // fp16 range guard of the fp32-I/O fp16 instantiation: running |max| of the q / k / v values converted to fp16 (common.h rg_absmax4),
+    // reported at the end.  The 16-bit-I/O instantiations read operands their producers already checked; the probabilities are in [0, 1].
+    constexpr bool RG = !IO16 && PREC == 1;
+    float rgm = 0.f;
 
     // ---- Q fragments of this wave's 16 queries (B operand of S^T = K . Q^T): column q = l15, k = d = ks*32 + g*8 + [0,8) ----
     const int q0 = qb * 64 + wave * 16;
@@ -85,6 +96,7 @@ __global__ __launch_bounds__(NWV * 64) void sdpa_stream_kernel(const SdpaArgs a)
                     lo4 = *reinterpret_cast<const f4*>(qrow + ks * 32 + g * 8);
                     hi4 = *reinterpret_cast<const f4*>(qrow + ks * 32 + g * 8 + 4);
                 }
+                if constexpr (RG) rgm = rg_absmax4(rg_absmax4(rgm, lo4), hi4);
                 const v4 h0 = M_::cvt(lo4), h1 = M_::cvt(hi4);
                 qf[ks][0] = v8{h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
                 if constexpr (NS == 2) {
@@ -130,6 +142,7 @@ __global__ __launch_bounds__(NWV * 64) void sdpa_stream_kernel(const SdpaArgs a)
                 if constexpr (IO16) {
                     *reinterpret_cast<v8*>(s_k + key * KP + dc * 8) = kreg[it];
                 } else {
+                    if constexpr (RG) rgm = rg_absmax4(rgm, kreg[it]);
                     const v4 h = M_::cvt(kreg[it]);
                     *reinterpret_cast<v4*>(s_k + key * KP + dc * 4) = h;
                     if constexpr (NS == 2) *reinterpret_cast<v4*>(s_k + K_EL + key * KP + dc * 4) = M_::cvt_lo(kreg[it], h);
@@ -145,6 +158,7 @@ __global__ __launch_bounds__(NWV * 64) void sdpa_stream_kernel(const SdpaArgs a)
                     for (int e = 0; e < 8; ++e)
                         *reinterpret_cast<v4*>(s_v + (dc * 8 + e) * VP + kg * 4) = v4{vreg[it][0][e], vreg[it][1][e], vreg[it][2][e], vreg[it][3][e]};
                 } else {
+                    if constexpr (RG) rgm = rg_absmax4(rg_absmax4(rg_absmax4(rg_absmax4(rgm, vreg[it][0]), vreg[it][1]), vreg[it][2]), vreg[it][3]);
                     const f4 c[4] = {{vreg[it][0].x, vreg[it][1].x, vreg[it][2].x, vreg[it][3].x},
                                      {vreg[it][0].y, vreg[it][1].y, vreg[it][2].y, vreg[it][3].y},
                                      {vreg[it][0].z, vreg[it][1].z, vreg[it][2].z, vreg[it][3].z},
@@ -289,6 +303,7 @@ __global__ __launch_bounds__(NWV * 64) void sdpa_stream_kernel(const SdpaArgs a)
         if (q0 + r < a.Nq)
             *reinterpret_cast<gv*>(obase + (long)(q0 + r) * a.ldo + cv) = *reinterpret_cast<const gv*>(slab + r * OP + cv);
     }
+    if constexpr (RG) rg_report(rgm, a.ovf, 7u);
 }
 
 template <int D, int DV, bool IO16>
@@ -297,11 +312,14 @@ int launch(SdpaArgs a, int B, int precision, hipStream_t st) {
     const long blocks = (long)B * a.heads * ((a.Nq + 63) / 64) * a.nsl;
     if (blocks > 0x7FFFFFFFL) return mi355::fail(MI355_EUNSUPPORTED, "mi355_sdpa_general_fwd: grid too large");
     const int grid = (int)blocks;
-    if (precision == 1) sdpa_stream_kernel<1, D, DV, IO16><<<grid, NWV * 64, 0, st>>>(a);
-    else if (precision == 2) sdpa_stream_kernel<2, D, DV, IO16><<<grid, NWV * 64, 0, st>>>(a);
+    sdpa_kargs<IO16> ka{};
+    static_cast<SdpaArgs&>(ka) = a;
+    if constexpr (!IO16) ka.ovf = precision == 1 ? mi355::range_word(st) : nullptr;    // fp32 q / k / v staged to fp16: a producer
+    if (precision == 1) sdpa_stream_kernel<1, D, DV, IO16><<<grid, NWV * 64, 0, st>>>(ka);
+    else if (precision == 2) sdpa_stream_kernel<2, D, DV, IO16><<<grid, NWV * 64, 0, st>>>(ka);
     else {
         if constexpr (IO16) return mi355::fail(MI355_EINVAL, "mi355_sdpa_general_fwd: 16-bit I/O needs precision 1 or 2");
-        else sdpa_stream_kernel<0, D, DV, false><<<grid, NWV * 64, 0, st>>>(a);
+        else sdpa_stream_kernel<0, D, DV, false><<<grid, NWV * 64, 0, st>>>(ka);
     }
     return MI355_OK;
 }

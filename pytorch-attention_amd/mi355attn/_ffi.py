@@ -185,6 +185,7 @@ def lib():
 
 
 MI355_EUNSUPPORTED = -2          # include/mi355attn.h: shape outside the kernel's envelope, nothing launched
+MI355_ERANGE = -5                # include/mi355attn.h: a finite value saturated to inf in an fp16 operand tensor
 
 
 def check(code, what):

@@ -111,11 +111,11 @@ class _forced_strict:
 def guarded_forward(module, *args, **kwargs):
     """Run `module(*args)` in the package's default precision; if fp16 operands overflowed, warn and run it again in strict mode
     (precision 0: bf16 hi / lo split, fp32 range and fp32-class accuracy at a third of the MFMA rate).  Two detectors:
-      * the range guard (mi355_range_status): cast16, the 16-bit LayerNorms and every 16-bit GEMM epilogue report a finite value that
-        saturates to inf;
-      * a non-finite OUTPUT for finite inputs: the fused block kernels (mlp_fused.hip, cswin_fused.hip, xcit.hip, the LayerNorm-in-GEMM
-        operand paths) keep their 16-bit intermediates in registers / LDS and do not track them -- a saturated intermediate there
-        always reaches the block's output as inf / NaN (GELU, the second product, the softmax all propagate it), so it is caught here.
+      * the range guard (mi355_range_status): cast16, the 16-bit LayerNorms, every 16-bit GEMM epilogue, the fused block kernels
+        (code 4) and the fp16 staging of the fp32-input GEMMs and attention cores (codes 6, 7) report a finite value that saturates to inf;
+      * a non-finite OUTPUT for finite inputs: XCA on an fp32 qkv (mi355_xca16_fwd with qkv_is16 = 0) does not report its fp16
+        context yet -- a saturated value there reaches the block's output as inf / NaN and is caught by THIS detector only.  module(x)
+        (range_fallback_forward) reads only the range word and returns such an output silently.
     The strict re-run overrides sub-modules built with an explicit 16-bit `precision=` as well.  Synchronises the device once per
     call -- a convenience for checkpoints with outlier activations, not the fast path."""
     import warnings
@@ -185,6 +185,8 @@ def range_fallback_forward(module, forward, args, kwargs):
                 pass
             if rc == 0:
                 return y
+            if rc != _ffi.MI355_ERANGE:                       # a HIP error of the wait itself is not an overflow: raise it, never re-run
+                check(rc, "mi355_range_wait")
             msg = lib().mi355_last_error()
             why = msg.decode() if msg else "fp16 range word set"
         except _ffi.Mi355RangeError as e:                     # a later launch of this very forward saw the report in its pre-launch check
@@ -675,14 +677,24 @@ def _derived_get(anchors, subkey, tag, build):
     is still THE SAME LIVE OBJECT (weak references: CPython recycles ids, the caching allocator recycles addresses, and a fresh
     parameter starts at version 0 again -- an id/address/version tag alone can resurrect the weights of a deleted model), and it is
     dropped as soon as one of them is collected, so the derived copies do not outlive their model.  `tag` captures in-place updates
-    (version counters) and moves (data pointers)."""
+    (version counters) and moves (data pointers).
+
+    A derived fp16 tensor that holds inf (a weight that saturates fp16: its cast16 reported once, when it was built) is remembered as
+    saturated, and every later use raises Mi355RangeError -- the cached copy would otherwise feed inf into every later forward with no
+    producer left to report it.  range_fallback_forward turns the error into a strict re-run, whose derived copies are not fp16.  One
+    host read per build (not under stream capture)."""
     key = tuple(id(a) for a in anchors) + (subkey,)
     hit = _derived.get(key)
     if hit is not None and hit[1] == tag and all(r() is a for r, a in zip(hit[0], anchors)):
+        if hit[3]:
+            raise _ffi.Mi355RangeError(f"fp16 range guard: a cached fp16 copy of a parameter ({subkey[0]}) holds inf -- the weight "
+                                       "saturates fp16.  Run the module in precision 0 (strict) or 2 (bf16)")
         return hit[2]
     val = build()
+    fp16 = [t for t in _tensors_of(val) if t.dtype == torch.float16 and t.is_cuda]
+    saturated = bool(fp16) and not _ffi._capturing() and bool(torch.stack([torch.isinf(t).any() for t in fp16]).any())
     refs = tuple(weakref.ref(a, lambda _r, k=key: _derived.pop(k, None)) for a in anchors)
-    _derived[key] = (refs, tag, val)
+    _derived[key] = (refs, tag, val, saturated)
     return val
 
 
