@@ -58,7 +58,8 @@ const char* mi355_last_error(void);         /* thread-local message of the last 
  * it launches on, so a host that drives several GPUs from one process can tune (or, in a test, sabotage) one of them without the
  * others seeing it.  A device whose key was never set follows the process default, which mi355_set_default_option changes (what a
  * binding uses for promises it makes for every device, e.g. "ws_persistent").  The failure word of mi355_sync_status and the range
- * word of mi355_range_status are per device as well: a time-out or an fp16 overflow on one GPU never fails another GPU's next call.
+ * word of mi355_range_status are per calling thread and device: a time-out or an fp16 overflow on one GPU never fails another GPU's
+ * next call, and one thread's never fails (or is cleared by) another thread's call on the same GPU.
  *   "chunk_images"  images per pool->scale chunk (0 = auto: ~200 MB of x per chunk so that a chunk's re-read is served
  *                   by the 256 MiB Infinity Cache -- default; a value >= B disables chunking);
  *   "nt"            bit0 = non-temporal loads, bit1 = non-temporal stores in the final streaming pass (default 3);
@@ -180,16 +181,21 @@ long        mi355_trace_end(char* report, size_t report_bytes);
 /* Drop what the library remembers about workspaces inside [ws, ws + ws_bytes) ("ws_persistent"): call before freeing or
  * repurposing such a buffer.  The next call that uses the memory zeroes its exchange area again. */
 int         mi355_workspace_forget(const void* ws, size_t ws_bytes);
-/* Failure report of the single-read exchange kernels (SE, CBAM, GCT / LCT gates).  Their inter-workgroup polls are bounded
- * (option "spin_limit", sweeps; default 1 << 22 ~ a second); a poll that runs out stores a code into a pinned host word that
- * the library reads WITHOUT a device synchronisation.  MI355_OK = nothing pending.  MI355_ESYNC = some launch that has already
- * executed produced invalid output (text in mi355_last_error); the condition is cleared by the report.  The same check runs at
- * the start of every later mi355_se_fwd / mi355_se_ex_fwd / mi355_cbam_fwd / gate call, which then fails instead of launching.
+/* Failure report of the single-read exchange kernels (SE, CBAM, GCT / LCT gates), per calling thread.  Their inter-workgroup polls
+ * are bounded (option "spin_limit", sweeps; default 1 << 22 ~ a second); a poll that runs out stores a code into a pinned host word
+ * of the thread that issued the launch, which the library reads WITHOUT a device synchronisation.  MI355_OK = nothing pending for
+ * this thread.  MI355_ESYNC = some launch of this thread that has already executed produced invalid output (text in
+ * mi355_last_error); the condition is cleared by the report.  The same check runs at the start of every later mi355_se_fwd /
+ * mi355_se_ex_fwd / mi355_cbam_fwd / gate call of this thread, which then fails instead of launching.
+ * Per thread: the library keeps 64 thread slots of report words (this word and the range word below); a thread takes one on its first
+ * call and returns it at exit.  Threads beyond 64 alive at once share one overflow slot and then see each other's reports.  A hipGraph
+ * captured on thread T reports into T's slot when it is replayed, whichever thread replays it.
  * Launches also refuse shapes whose per-image workgroup set cannot be resident at once (they take the multi-pass kernels). */
 int         mi355_sync_status(void);
-/* fp16 range guard.  The default operand format (precision 1) is IEEE half: a finite fp32 value of magnitude >= 65520 becomes inf where
- * the fp32 reference stays finite.  Every kernel that converts an fp32 value to an fp16 operand watches the magnitudes it converts and, on
- * the first saturation, stores a code into a pinned host word (the code names the producer family in mi355_last_error):
+/* fp16 range guard, per calling thread.  The default operand format (precision 1) is IEEE half: a finite fp32 value of magnitude >= 65520
+ * becomes inf where the fp32 reference stays finite.  Every kernel that converts an fp32 value to an fp16 operand watches the magnitudes it
+ * converts and, on the first saturation, stores a code into a pinned host word of the thread that issued the launch (the thread slots of
+ * mi355_sync_status; the code names the producer family in mi355_last_error):
  *   1 mi355_cast16_fwd (and the input cast inside mi355_linear16_x32_fwd)     2 mi355_layernorm16_fwd, the 16-bit LayerNorm-in-GEMM operands
  *   3 every GEMM epilogue with a 16-bit output (mi355_linear16*_fwd, mi355_mhsa_fwd's qkv, the patch embedding's 16-bit path)
  *   4 the fused block kernels (mi355_mlp_fused_fwd / mi355_proj_mlp_fused_fwd / mi355_cswin_stripe_attn_fwd / mi355_mixer_token_fwd ...)
@@ -199,15 +205,16 @@ int         mi355_sync_status(void);
  *   7 the fp16 q / k / v staging of the fp32-I/O attention cores (mi355_sdpa_fwd, mi355_sdpa_general_fwd with io16 = 0,
  *     mi355_cswin_lepe_attn_fwd); their probabilities are in [0, 1] and need no check
  *   8 the DoubleAttention kernels (mi355_double_attn_fwd: x, the A product, G, M' and the weights; the softmax factors are bounded)
- * Not yet reporting: XCA on an fp32 qkv input (mi355_xca16_fwd with qkv_is16 = 0).  mi355_range_status() reads that word WITHOUT a device
- * synchronisation: MI355_OK = nothing pending; MI355_ERANGE = some launch that has already executed produced inf from finite values
+ * Not yet reporting: XCA on an fp32 qkv input (mi355_xca16_fwd with qkv_is16 = 0).  mi355_range_status() reads the calling thread's word
+ * WITHOUT a device synchronisation: MI355_OK = nothing pending; MI355_ERANGE = some launch of this thread that has already executed produced inf from finite values
  * (cleared by the report).  A host that wants certainty for a forward synchronises the stream first.  Remedy: run the module in
  * precision 0 (strict: bf16 hi/lo split, fp32 range) or precision 2 (bf16).  bf16 operands are never flagged. */
 int         mi355_range_status(void);
-/* "Is the range word final for what I have launched?" without draining the device (round 6).  mi355_range_arm(on) arms the calling thread's
- * current device (on >= 1) or disarms it (0): while armed, the entries that launch fp16 producers are counted.  mi355_range_wait() records
- * (if it has not happened yet) ONE event behind the last producer, synchronises on it -- launches queued behind that event keep running --
- * and returns the range status (MI355_OK / MI355_ERANGE, cleared by the report); with no producer since the arm it returns the status
+/* "Is the range word final for what I have launched?" without draining the device (round 6), per calling thread.  mi355_range_arm(on) arms
+ * the calling thread on its current device (on >= 1) or disarms it (0): while armed, the entries this thread launches fp16 producers with are
+ * counted; other threads' launches are not, and their arm state, counts and events are their own.  mi355_range_wait() records
+ * (if it has not happened yet) ONE event behind the thread's last producer, synchronises on it -- launches queued behind that event keep
+ * running -- and returns the thread's range status (MI355_OK / MI355_ERANGE, cleared by the report); with no producer since the arm it returns the status
  * without waiting.  on = 1 + k (k >= 1) carries a prediction, "the k-th producer entry since this call is the last one" (what
  * mi355_range_launches() returned after the caller's previous forward of the same module): the event is then recorded in front of the
  * first launch that follows that producer, so the wait does not cover the non-reporting tail of the forward (attention core, fp32-output
@@ -216,7 +223,7 @@ int         mi355_range_status(void);
  * again in precision 0 (option "range_fallback" = 1, per device; 0 = no wait, the next call reports MI355_ERANGE). */
 int         mi355_range_arm(int on);
 int         mi355_range_wait(void);
-long        mi355_range_launches(void);   /* producer entries since the last mi355_range_arm(on >= 1) on this device */
+long        mi355_range_launches(void);   /* producer entries of this thread since its last mi355_range_arm(on >= 1) on this device */
 
 /* ---- channel / spatial attention family: NCHW fp32, HBM-bound ------------------------------------ */
 

@@ -184,51 +184,106 @@ void ws_forget_range(const void* base, size_t bytes) {
     }
 }
 
-// ---- exchange-kernel failure word + fp16 range word (common.h): ONE PAIR PER DEVICE ---------------------------------------------
-// One pinned, device-visible 4 KB block, 64 bytes per device ordinal: word 0 = exchange failure code, word 4 = range code.  A kernel
-// reports into the words of the device it runs on and the host checks the words of the calling thread's current device, so one
-// device's time-out (or fp16 overflow) never fails another device's next call.
+// ---- exchange-kernel failure word + fp16 range word (common.h): ONE PAIR PER CALLING THREAD AND DEVICE -------------------------
+// One pinned, device-visible allocation, made once (never inside a stream capture): THREAD_SLOTS + 1 slots of 64 bytes per device
+// ordinal; in a device's 64 bytes, word 0 = exchange failure code, word 4 = range code.  A launch hands its kernel the words of the
+// thread that issues it, on the device it runs on, and the host checks the calling thread's words on its current device: one thread's
+// time-out or fp16 overflow never fails another thread's next call, and one thread's mi355_range_wait never absorbs (clears) another
+// thread's report -- a serving process that runs one module per thread on one GPU.  A thread takes a free slot on first use and hands it
+// back when it exits; a slot is cleared when it is handed out again.  Threads beyond THREAD_SLOTS alive at once share the last
+// (overflow) slot and see each other's reports, as every thread of a device did before.  A hipGraph captured on thread T holds T's words
+// in its kernel nodes: its replays report into T's slot, whichever thread replays it -- check from T (or after T has exited, from
+// whichever thread holds the slot then).
 namespace {
+constexpr int THREAD_SLOTS = 64;
+constexpr size_t SLOT_WORDS = 16 * MAX_DEV;
 std::once_flag g_sync_once;
 unsigned* g_sync_block = nullptr;
+std::mutex g_slot_mu;
+bool g_slot_used[THREAD_SLOTS] = {};
+struct ThreadSlot {
+    int idx = -1;                                      // THREAD_SLOTS = the shared overflow slot
+    ~ThreadSlot() {
+        if (idx < 0 || idx >= THREAD_SLOTS) return;
+        std::lock_guard<std::mutex> lk(g_slot_mu);
+        g_slot_used[idx] = false;
+    }
+};
+thread_local ThreadSlot t_slot;
+// the calling thread's words on its current device; null while the block does not exist (or its allocation failed)
+unsigned* thread_words() {
+    if (!g_sync_block) return nullptr;
+    if (t_slot.idx < 0) {
+        std::lock_guard<std::mutex> lk(g_slot_mu);
+        int i = 0;
+        while (i < THREAD_SLOTS && g_slot_used[i]) ++i;
+        if (i < THREAD_SLOTS) {
+            g_slot_used[i] = true;
+            std::memset(g_sync_block + i * SLOT_WORDS, 0, SLOT_WORDS * sizeof(unsigned));   // a previous owner's codes are not ours
+        }
+        t_slot.idx = i;
+    }
+    return g_sync_block + t_slot.idx * SLOT_WORDS + 16 * cur_dev();
+}
 }  // namespace
 unsigned* sync_err_word() {
     std::call_once(g_sync_once, [] {
+        const size_t bytes = (THREAD_SLOTS + 1) * SLOT_WORDS * sizeof(unsigned);
         void* p = nullptr;
-        if (hipHostMalloc(&p, 64 * MAX_DEV, hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable) == hipSuccess && p) {
-            std::memset(p, 0, 64 * MAX_DEV);
+        if (hipHostMalloc(&p, bytes, hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable) == hipSuccess && p) {
+            std::memset(p, 0, bytes);
             g_sync_block = static_cast<unsigned*>(p);
         } else {
             (void)hipGetLastError();
         }
     });
-    return g_sync_block ? g_sync_block + 16 * cur_dev() : nullptr;
+    return thread_words();
 }
 unsigned* sync_err_word_on(hipStream_t st) {
     if (!g_sync_block && stream_is_capturing(st)) return nullptr;         // never allocate pinned memory inside a capture
     return sync_err_word();
 }
 // ---- "which launch do I have to wait for before the range word is final?" (round 6: mi355_range_arm / mi355_range_wait) ---------------
-// While a device is ARMED, every launcher that hands a kernel the range word (range_word() below: the fp16 producers) counts itself and
-// marks the device dirty.  mi355_range_wait() must synchronise on an event that lies BEHIND the last producer; recording one behind every
+// While a thread has armed its current device, every launcher that hands a kernel the range word (range_word() below: the fp16 producers)
+// counts itself and marks the device dirty.  mi355_range_wait() must synchronise on an event that lies BEHIND the last producer; recording one behind every
 // producer would put ~50 marker packets into a ViT-Base forward (measured: +0.13 ms of 12.1), so the caller PREDICTS the last producer --
 // mi355_range_arm(1 + k): "the k-th producer since this call is the last one", the count its previous forward of the same module reported
 // (mi355_range_launches) -- and the ONE event of the forward is recorded in front of the first launch that follows the k-th producer
 // (TraceScope's constructor sits in front of every instrumented launch).  The non-reporting launches queued behind it (attention core,
 // fp32-output projections, fc2) then keep the GPU busy while the host already returns.  A wrong or missing prediction costs slack, never
 // correctness: a producer launched after the event marks the device dirty again and mi355_range_wait() records a second event at the tail.
+// The marks are per calling thread and device (like the words above): arm, count, event and stream of one thread never see another's
+// launches.  At thread exit the events go back to a per-device pool that later threads draw from (no HIP call at thread exit, which may
+// come after the runtime has shut down); the pool never holds more events than threads have been alive at once.
 namespace {
 struct RangeMark {
-    std::atomic<int> armed{0}, dirty{0}, fresh{0}, have{0}, count{0}, expect{0};
+    int armed = 0, dirty = 0, fresh = 0, have = 0, count = 0, expect = 0;
     hipEvent_t ev = nullptr;
     hipStream_t st = nullptr;
 };
-RangeMark g_rmark[MAX_DEV];
-void range_mark_record(RangeMark& m) {
-    m.dirty.store(0, std::memory_order_relaxed);
-    if (stream_is_capturing(m.st)) return;                                // never record the shared event into a graph
-    if (!m.ev && hipEventCreateWithFlags(&m.ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); m.ev = nullptr; return; }
-    if (hipEventRecord(m.ev, m.st) == hipSuccess) m.have.store(1, std::memory_order_relaxed);
+std::mutex g_ev_mu;
+std::vector<hipEvent_t> g_ev_pool[MAX_DEV];
+struct ThreadMarks {
+    RangeMark m[MAX_DEV];
+    ~ThreadMarks() {
+        std::lock_guard<std::mutex> lk(g_ev_mu);
+        for (int d = 0; d < MAX_DEV; ++d)
+            if (m[d].ev) g_ev_pool[d].push_back(m[d].ev);
+    }
+};
+thread_local ThreadMarks t_marks;
+RangeMark& rmark(int dev) { return t_marks.m[dev]; }
+void range_mark_record(RangeMark& m, int dev) {
+    m.dirty = 0;
+    if (stream_is_capturing(m.st)) return;                                // never record the thread's event into a graph
+    if (!m.ev) {
+        {
+            std::lock_guard<std::mutex> lk(g_ev_mu);
+            if (!g_ev_pool[dev].empty()) { m.ev = g_ev_pool[dev].back(); g_ev_pool[dev].pop_back(); }
+        }
+        if (!m.ev && hipEventCreateWithFlags(&m.ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); m.ev = nullptr; return; }
+    }
+    if (hipEventRecord(m.ev, m.st) == hipSuccess) m.have = 1;
     else (void)hipGetLastError();
 }
 }  // namespace
@@ -236,53 +291,55 @@ void range_mark_record(RangeMark& m) {
 // MI355_LAUNCH_CHECK marks the device dirty, and no event is ever recorded while an entry is open -- so the event always lies behind every
 // launch of the producer it covers.
 void range_mark_before_launch() {                                          // TraceScope: in front of every instrumented launch
-    RangeMark& m = g_rmark[cur_dev()];
-    if (!m.dirty.load(std::memory_order_relaxed) || m.fresh.load(std::memory_order_relaxed)) return;
-    const int e = m.expect.load(std::memory_order_relaxed);
-    if (e > 0 && m.count.load(std::memory_order_relaxed) >= e) range_mark_record(m);
+    const int dev = cur_dev();
+    RangeMark& m = rmark(dev);
+    if (!m.dirty || m.fresh) return;
+    if (m.expect > 0 && m.count >= m.expect) range_mark_record(m, dev);
 }
 void range_mark_entry_done() {                                             // MI355_LAUNCH_CHECK: the launches of the current entry are all enqueued
-    RangeMark& m = g_rmark[cur_dev()];
-    if (!m.fresh.load(std::memory_order_relaxed)) return;
-    m.fresh.store(0, std::memory_order_relaxed);
-    m.dirty.store(1, std::memory_order_relaxed);
+    RangeMark& m = rmark(cur_dev());
+    if (!m.fresh) return;
+    m.fresh = 0;
+    m.dirty = 1;
 }
 unsigned* range_word(hipStream_t st) {
     if (!g_sync_block && stream_is_capturing(st)) return nullptr;         // never allocate pinned memory inside a capture
     unsigned* w = sync_err_word();
     if (w) {
-        RangeMark& m = g_rmark[cur_dev()];
-        if (m.armed.load(std::memory_order_relaxed)) {
+        RangeMark& m = rmark(cur_dev());
+        if (m.armed) {
             m.st = st;
-            m.count.fetch_add(1, std::memory_order_relaxed);
-            m.fresh.store(1, std::memory_order_relaxed);                   // an open producer entry ("pending")
+            ++m.count;
+            m.fresh = 1;                                                   // an open producer entry ("pending")
         }
     }
-    return w ? w + 4 : nullptr;                                            // second quarter of the device's 64 bytes
+    return w ? w + 4 : nullptr;                                            // second quarter of the thread's 64 bytes of the device
 }
 int range_arm(int on) {
-    RangeMark& m = g_rmark[cur_dev()];
-    m.dirty.store(0, std::memory_order_relaxed);
-    m.fresh.store(0, std::memory_order_relaxed);
-    m.have.store(0, std::memory_order_relaxed);
-    if (on) m.count.store(0, std::memory_order_relaxed);                   // a disarm keeps the count for mi355_range_launches()
-    m.expect.store(on > 1 ? on - 1 : 0, std::memory_order_relaxed);
-    m.armed.store(on ? 1 : 0, std::memory_order_relaxed);
+    RangeMark& m = rmark(cur_dev());
+    m.dirty = 0;
+    m.fresh = 0;
+    m.have = 0;
+    if (on) m.count = 0;                                                   // a disarm keeps the count for mi355_range_launches()
+    m.expect = on > 1 ? on - 1 : 0;
+    m.armed = on ? 1 : 0;
     return MI355_OK;
 }
-long range_launches() { return g_rmark[cur_dev()].count.load(std::memory_order_relaxed); }
+long range_launches() { return rmark(cur_dev()).count; }
 int range_wait() {
-    RangeMark& m = g_rmark[cur_dev()];
-    if (m.fresh.load(std::memory_order_relaxed)) { m.fresh.store(0, std::memory_order_relaxed); m.dirty.store(1, std::memory_order_relaxed); }
-    if (m.dirty.load(std::memory_order_relaxed)) range_mark_record(m);     // no event behind the last producer yet: at the tail of the stream
-    if (m.have.load(std::memory_order_relaxed) && m.ev) {
+    const int dev = cur_dev();
+    RangeMark& m = rmark(dev);
+    if (m.fresh) { m.fresh = 0; m.dirty = 1; }
+    if (m.dirty) range_mark_record(m, dev);                                // no event behind the last producer yet: at the tail of the stream
+    if (m.have && m.ev) {
         if (hipEventSynchronize(m.ev) != hipSuccess) return fail(MI355_EHIP, "mi355_range_wait: hipEventSynchronize -> %s", hipGetErrorString(hipGetLastError()));
-        m.have.store(0, std::memory_order_relaxed);
+        m.have = 0;
     }
     return range_pending("mi355_range_wait");
 }
 int range_pending(const char* who) {
-    unsigned* w = g_sync_block ? g_sync_block + 16 * cur_dev() + 4 : nullptr;
+    unsigned* w = thread_words();
+    if (w) w += 4;
     if (!w || !__atomic_load_n(w, __ATOMIC_ACQUIRE)) return MI355_OK;
     const unsigned code = __atomic_exchange_n(w, 0u, __ATOMIC_ACQ_REL);
     if (!code) return MI355_OK;

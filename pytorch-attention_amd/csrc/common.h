@@ -56,20 +56,21 @@ bool  stream_is_capturing(hipStream_t st);      // hipGraph capture in progress 
 void  ws_forget_range(const void* base, size_t bytes);
 long  opt_cbam_single();
 // ---- exchange-kernel failure reporting (api.hip) ----------------------------------------------------------------------------
-// The single-read kernels bound their inter-workgroup polls.  A poll that runs out stores a non-zero code into ONE pinned,
-// device-visible host word (system-scope store, no synchronisation needed to read it); every later library entry that launches an
-// exchange kernel -- and mi355_sync_status() -- looks at that word first and fails with MI355_ESYNC instead of returning OK over
-// garbage.  spin_limit() is the poll budget (option "spin_limit", default 1 << 22 sweeps ~ a second).
-unsigned* sync_err_word();            // device-visible pinned host word (null if the allocation failed: reporting falls back to the workspace word)
+// The single-read kernels bound their inter-workgroup polls.  A poll that runs out stores a non-zero code into a pinned,
+// device-visible host word of the LAUNCHING thread (system-scope store, no synchronisation needed to read it); every later library entry
+// on that thread that launches an exchange kernel -- and mi355_sync_status() -- looks at that word first and fails with MI355_ESYNC
+// instead of returning OK over garbage.  spin_limit() is the poll budget (option "spin_limit", default 1 << 22 sweeps ~ a second).
+unsigned* sync_err_word();            // the calling thread's word on its current device (api.hip: a slot per thread; null if the allocation failed: reporting falls back to the workspace word)
 // fp16 range guard (round 3): the producers of fp16 OPERAND tensors (mi355_cast16_fwd, mi355_layernorm16_fwd, the 16-bit-output GEMM
 // epilogues) keep the largest magnitude they convert; a finite value that saturates to inf in fp16 (|v| >= 65520) stores a code into
-// a second pinned host word.  mi355_range_status() reads it WITHOUT a device synchronisation (like mi355_sync_status); the Python
+// a second pinned host word of the launching thread.  mi355_range_status() reads the calling thread's word WITHOUT a device synchronisation (like mi355_sync_status); the Python
 // binding raises before the next 16-bit launch.  bf16 operands have the fp32 range and are not checked.  Null under hipGraph
 // capture when the word does not exist yet (hipHostMalloc is illegal there): the launch then runs unguarded.
 unsigned* range_word(hipStream_t st);
 int   range_pending(const char* who);  // MI355_OK or MI355_ERANGE (reported once)
-// round 6 (api.hip): while the device is armed (mi355_range_arm), launchers that call range_word() are counted; ONE event is recorded in front
-// of the first instrumented launch behind the predicted last producer (or at the tail); mi355_range_wait() waits for it and returns the status
+// round 6 (api.hip): while the calling thread has armed its device (mi355_range_arm), its launchers that call range_word() are counted; ONE event
+// is recorded in front of the first instrumented launch behind the predicted last producer (or at the tail); mi355_range_wait() waits for it
+// and returns the status.  Marks, counts and events are per thread and device.
 void  range_mark_before_launch();
 void  range_mark_entry_done();
 int   range_arm(int on);

@@ -5,6 +5,7 @@ per-stream workspace) with torch -- device memory and streams are torch's job, t
 library's -- and raises ``Mi355Error`` on any non-zero return code.
 """
 import ctypes
+import threading
 import weakref
 
 import torch
@@ -18,6 +19,15 @@ ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2     # ACT_RELU: fp32-in engine only (line
 _default_precision = PREC_FP16
 
 
+class _StrictOverride(threading.local):
+    depth = 0                                 # > 0 inside a _forced_strict context ON THIS THREAD
+
+
+_strict_override = _StrictOverride()
+_strict_active = 0                            # _forced_strict contexts open on ANY thread: _prec() skips the thread-local read while 0
+_strict_lock = threading.Lock()
+
+
 def set_default_precision(p):
     """Process-wide default MFMA operand precision for modules that do not pin one (0 strict / 1 fp16 / 2 bf16)."""
     global _default_precision
@@ -27,10 +37,15 @@ def set_default_precision(p):
 
 
 def default_precision():
-    return _default_precision
+    """The precision a module without its own setting runs in on the calling thread: strict inside a strict re-run of this thread."""
+    return PREC_STRICT if _strict_active and _strict_override.depth else _default_precision
 
 
 def _prec(p):
+    """Effective precision of an op or module setting `p` (None = the default) on the calling thread.  A strict re-run of this thread
+    (_forced_strict) beats both the process default and an explicit `precision=`."""
+    if _strict_active and _strict_override.depth:
+        return PREC_STRICT
     return _default_precision if p is None else p
 
 
@@ -84,27 +99,27 @@ def _all_finite(obj):
 
 
 class _forced_strict:
-    """Strict mode for a re-run: the package default AND every sub-module that was built with an explicit 16-bit `precision=`
-    (an explicit setting beats the default, so switching the default alone would recompute those modules in fp16)."""
+    """Strict mode for a re-run, on the CALLING THREAD only: _prec() and default_precision() return strict inside the context, ahead of
+    the process default and of any explicit 16-bit `precision=` of a module (switching the default alone would recompute such modules
+    in fp16).  Neither the process default nor any module attribute is touched, so overlapping re-runs on several threads, a module
+    shared between threads, and a third thread that never re-runs all keep their own precision.  Every module reads its precision
+    through _prec() (modules/*.py: `_fast`, `F._prec(self.precision)`, or an F.* call that resolves `precision=` itself)."""
 
-    def __init__(self, module):
-        self.module, self.saved, self.old = module, [], None
+    def __init__(self, module=None):
+        self.module = module
 
     def __enter__(self):
-        self.old = default_precision()
-        set_default_precision(PREC_STRICT)
-        mods = self.module.modules() if isinstance(self.module, torch.nn.Module) else ()
-        for m in mods:
-            p = m.__dict__.get("precision", None)
-            if p is not None and p != PREC_STRICT:
-                self.saved.append((m, p))
-                m.precision = PREC_STRICT
+        global _strict_active
+        with _strict_lock:
+            _strict_active += 1
+        _strict_override.depth += 1
         return self
 
     def __exit__(self, *exc):
-        for m, p in self.saved:
-            m.precision = p
-        set_default_precision(self.old)
+        global _strict_active
+        _strict_override.depth -= 1
+        with _strict_lock:
+            _strict_active -= 1
         return False
 
 
@@ -153,14 +168,17 @@ def range_fallback_forward(module, forward, args, kwargs):
     weight scale (ViT.py:79-89, cswin.py:176-197 compute in fp32), so the zero-edit drop-in must too.  The OUTERMOST drop-in forward on
     this thread arms the library (mi355_range_arm: the launch check behind every fp16 producer records one re-used event), runs the
     forward in the package's precision, then waits for the LAST producer of the forward only (mi355_range_wait) -- the launches queued
-    behind it (attention core, fp32-output projections) keep the GPU busy while the host returns -- and reads the device's range word.
+    behind it (attention core, fp32-output projections) keep the GPU busy while the host returns -- and reads this thread's range word.
     The event is recorded ONCE per forward, in front of the first launch behind the producer the previous forward of this module
     counted as its last (mi355_range_launches -> `_mi355_nprod`; a first call records at the tail).
     Clean: the result is returned, no device synchronisation happened.  Fired (here or in a pre-launch check inside the forward): ONE
     warning, the device is drained, the forward runs again in strict mode (bf16 hi / lo split: fp32 range, fp32-class accuracy), also
     for sub-modules built with an explicit 16-bit `precision=`.  Option "range_fallback" = 0 (per device) restores the round-3 contract:
     no wait, Mi355RangeError on the next call.  Not active under hipGraph capture (an event wait is illegal there), in strict / bf16
-    mode nothing can fire and the wait finds no event."""
+    mode nothing can fire and the wait finds no event.
+    Per calling thread: arm, wait and range word belong to the thread (include/mi355attn.h), and the strict re-run is strict for this
+    thread only (_forced_strict), so modules forwarded concurrently on other threads -- on other streams, or the same module -- neither
+    absorb this forward's report nor run strict because of it."""
     if _guard.depth:
         return forward(module, *args, **kwargs)
     try:
