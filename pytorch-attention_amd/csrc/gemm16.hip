@@ -793,6 +793,7 @@ int mi355_ln_linear16_fwd(const float* X, const void* W16, const float* bias, vo
     if (workers < 1) workers = 1;
     if (workers > tiles_m) workers = tiles_m;
     const int grid = tiles_n * workers;
+    MI355_TRACE(st, "gemm16_ws_kernel<ln,%s> M=%d N=%d K=%d", out16 ? "out16" : "out32", M, N, K);
 #define WSL(T_, O_, BN_, KK_) gemm16_ws_kernel<T_, O_, BN_, KK_, true><<<grid, 512, 0, st>>>(g, workers)
 #define WSL_BY_SHAPE(T_, O_)                                                   \
     do {                                                                       \

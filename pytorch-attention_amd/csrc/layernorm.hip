@@ -223,6 +223,7 @@ extern "C" int mi355_layernorm16_t_fwd(const float* x, const float* weight, cons
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(NP / 32, B);
     const size_t lds = (size_t)C * 17 * 4;
+    MI355_TRACE(st, "layernorm16_t_kernel B=%d N=%d C=%d NP=%d", B, N, C, NP);
 #define LNT(T_, KC_) layernorm16_t_kernel<T_, KC_><<<grid, 256, lds, st>>>(x, weight, bias, static_cast<T_*>(ut16), N, C, NP, eps)
 #define LNT_BY_C(T_) do { if (C <= 256) LNT(T_, 4); else if (C <= 512) LNT(T_, 8); else LNT(T_, 16); } while (0)
     if (precision == MI355_PREC_FP16) LNT_BY_C(_Float16); else LNT_BY_C(__bf16);

@@ -315,6 +315,8 @@ int launch(SdpaArgs a, int B, int precision, hipStream_t st) {
     sdpa_kargs<IO16> ka{};
     static_cast<SdpaArgs&>(ka) = a;
     if constexpr (!IO16) ka.ovf = precision == 1 ? mi355::range_word(st) : nullptr;    // fp32 q / k / v staged to fp16: a producer
+    if (IO16 && precision != 1 && precision != 2) return mi355::fail(MI355_EINVAL, "mi355_sdpa_general_fwd: 16-bit I/O needs precision 1 or 2");
+    MI355_TRACE(st, "sdpa_stream_kernel<d=%d,prec %d%s> B=%d heads=%d Nq=%d", D, precision, IO16 ? ",io16" : "", B, a.heads, a.Nq);
     if (precision == 1) sdpa_stream_kernel<1, D, DV, IO16><<<grid, NWV * 64, 0, st>>>(ka);
     else if (precision == 2) sdpa_stream_kernel<2, D, DV, IO16><<<grid, NWV * 64, 0, st>>>(ka);
     else {

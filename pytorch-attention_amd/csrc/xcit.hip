@@ -766,6 +766,8 @@ int mi355_xca_fwd(const float* qkv, const float* temperature, float* out, int B,
     MI355_CHECK_ARG(aligned16(qkv) && aligned16(out));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int grid = B * heads;
+    if (d != 32 && d != 48 && d != 64) return mi355::fail(MI355_EUNSUPPORTED, "mi355_xca_fwd: head dim %d (built: 32, 48, 64)", d);
+    MI355_TRACE(st, "xca_kernel<d=%d> B=%d N=%d heads=%d", d, B, N, heads);
     switch (d) {
         case 32: xca_kernel<32><<<grid, 256, 0, st>>>(qkv, temperature, out, N, heads); break;
         case 48: xca_kernel<48><<<grid, 256, 0, st>>>(qkv, temperature, out, N, heads); break;

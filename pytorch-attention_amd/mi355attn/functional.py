@@ -588,10 +588,26 @@ def token_mix(weight, x, bias=None, act=ACT_NONE, resid=None, precision=None):
     T = weight.shape[0]
     if weight.shape[1] != N:
         raise ValueError("token_mix: weight in_features != sequence length")
+    if N % 4:                      # the kernel reads W and x rows as float4: zero-pad the reduction axis (7 x 7 patch grids: N = 49)
+        NP = -(-N // 4) * 4
+        weight = weight32_padk(weight, NP)
+        xp = torch.zeros(B, NP, C, dtype=torch.float32, device=x.device)
+        xp[:, :N] = x
+        x, N = xp, NP
     y = torch.empty(B, T, C, dtype=torch.float32, device=x.device)
     check(lib().mi355_token_mix_fwd(dptr(weight), dptr(x), dptr(bias), dptr(resid), dptr(y), B, T, N, C, act,
                                     _prec(precision), stream_ptr(x.device)), "mi355_token_mix_fwd")
     return y
+
+
+def weight32_padk(w, K):
+    """fp32 copy of a weight (N, k) zero-padded along in_features to K (cached with the parameter)."""
+    def build():
+        out = torch.zeros(w.shape[0], K, dtype=torch.float32, device=w.device)
+        out[:, :w.shape[1]] = w.detach()
+        return out
+    tag = (w._version, w.data_ptr(), tuple(w.shape))
+    return _derived_get((w,), ("w32padk", K), tag, build)
 
 
 def layernorm(x, weight, bias, eps=1e-5):

@@ -10,6 +10,9 @@ Writes, under tests/golden/live/:
   fourier.npz         the reference's pre-projection Fourier position features, whole (tests/test_helper_modules.py);
   chan.npz            input, weights and SE / CBAM / ECA outputs of the ragged channel-attention shapes (tests/test_oracle_golden.py);
   lepe.npz            qkv, get_v weights and LePEAttention output of the three LePE modes (tests/test_oracle_golden.py);
+  routes.npz          per row of tests/route_cases.py (non-trivial parameters, prep_nontrivial): 257 strided samples, sum and
+                      absolute sum of the reference module's output, and fp64 checksums of its parameters and of the input
+                      (tests/test_routes_cpu.py); --routes-only rewrites this file alone;
 and tests/golden/reference_names.json: the public names of every reference module a drop-in shim mirrors (tests/test_signatures.py).
 """
 import argparse
@@ -45,6 +48,7 @@ LEPE_MODES = ((8, 0, 2, 32, 2), (8, 1, 4, 32, 1), (6, -1, 6, 64, 4))      # reso
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", required=True, help="the reference checkout")
+    ap.add_argument("--routes-only", action="store_true", help="write tests/golden/live/routes.npz only")
     args = ap.parse_args()
     ref_root = os.path.abspath(args.ref)
     sys.dont_write_bytecode = True
@@ -53,6 +57,8 @@ def main():
     from make_golden import _stub_timm
     from make_signatures import public_names, shim_modules
     from test_aten_seq_cpu import CASES                      # shapes of the cases (drop-in side; imported before the reference is)
+    from route_cases import ROWS, prep_nontrivial
+    from cases import sample_index
     shapes = {c[0]: c[2] for c in CASES}
     # the drop-in package exports the same import paths: forget its modules, then import the reference's
     sys.path.insert(0, os.path.join(ROOT, "pytorch-attention_amd"))
@@ -72,6 +78,27 @@ def main():
 
     files = {}
     with torch.no_grad():
+        routes = {"ids": np.array([r["id"] for r in ROWS])}
+        for r in ROWS:
+            torch.manual_seed(1234)
+            m = ref_cls(r["mod"], r["cls"])(*r.get("args", ()), **r.get("kwargs", {})).eval()
+            prep_nontrivial(m)
+            torch.manual_seed(4321)
+            x = torch.randn(*r["shape"])
+            y = m(x, *r.get("fwd_args", ()))
+            sd = m.state_dict()
+            yf = y.reshape(-1)
+            routes.update({r["id"] + "__y_samples": yf[sample_index(yf.numel())].numpy(), r["id"] + "__y_shape": np.array(list(y.shape)),
+                           r["id"] + "__y_sum": np.array(float(yf.double().sum())), r["id"] + "__y_abs": np.array(float(yf.double().abs().sum())),
+                           r["id"] + "__x_sum": np.array(float(x.double().sum())), r["id"] + "__p_keys": np.array(list(sd)),
+                           r["id"] + "__p_sum": np.array([float(v.double().sum()) for v in sd.values()]),
+                           r["id"] + "__p_abs": np.array([float(v.double().abs().sum()) for v in sd.values()])})
+        files["routes"] = routes
+        if args.routes_only:
+            os.makedirs(os.path.join(HERE, "live"), exist_ok=True)
+            np.savez_compressed(os.path.join(HERE, "live", "routes.npz"), **routes)
+            print("wrote routes.npz (%d rows)" % len(ROWS))
+            return
         for name, (mod, cls, a, kw) in REF_CLASSES.items():
             torch.manual_seed(1234)
             m = ref_cls(mod, cls)(*a, **kw).eval()
