@@ -110,7 +110,8 @@ def cswin_forward(img, p, embed_dim=64, depth=(1, 2, 21, 1), split_size=(1, 2, 7
 
     stem = Conv2d(3, C, 7, stride 4, pad 2) -> tokens (b, h*w, c) -> LayerNorm (:247-251); per stage the CSWinBlocks; between
     stages Merge_Block = tokens -> NCHW -> Conv2d(C, 2C, 3, stride 2, pad 1) -> tokens -> LayerNorm (:224-233); final LayerNorm,
-    mean over tokens, head.  Convolutions are the ATen conv2d the reference's nn.Conv2d runs.
+    mean over tokens, head (the features themselves when num_classes=0: no head.* keys, nn.Identity at :298).  Convolutions are the
+    ATen conv2d the reference's nn.Conv2d runs.
     """
     x = _t(img, dtype)
     B, _, H, _ = x.shape
@@ -129,8 +130,10 @@ def cswin_forward(img, p, embed_dim=64, depth=(1, 2, 21, 1), split_size=(1, 2, 7
         for bi in range(depth[si]):
             x = cswin_block_forward(x, _sub(p, f"stage{si + 1}.{bi}."), reso, num_heads[si], split_size[si], last_stage=(si == 3),
                                     dtype=dtype)
-    x = layernorm(x, _t(p["norm.weight"], dtype), _t(p["norm.bias"], dtype))
-    return linear(x.mean(dim=1), _t(p["head.weight"], dtype), _t(p["head.bias"], dtype))
+    x = layernorm(x, _t(p["norm.weight"], dtype), _t(p["norm.bias"], dtype)).mean(dim=1)
+    if "head.weight" not in p:
+        return x
+    return linear(x, _t(p["head.weight"], dtype), _t(p["head.bias"], dtype))
 
 
 # ---- the same block in the reference's ATen op sequence (bench.py's CPU leg) ----------------------------------------------------------

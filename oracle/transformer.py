@@ -145,11 +145,13 @@ def vit_position_rows(pe, patch, H, W, dtype=torch.float32):
     return torch.cat([pe[:, 0:1], body[None]], dim=1)
 
 
-def vit_forward(img, p, num_heads, depth, dtype=torch.float32):
+def vit_forward(img, p, num_heads, depth, dtype=torch.float32, global_pool="token"):
     """VisionTransformer.forward -- vision_transformers/ViT.py:180-192.
 
     Tokens = [patch_0..patch_{n-1}, cls] (cls appended LAST, :183), + position rows (interpolated off the native resolution,
-    :160-178), `depth` encoder blocks, logits = head(token 0) (global_pool="token", :187-188); no final LayerNorm.
+    :160-178), `depth` encoder blocks, no final LayerNorm.  Pooling (:187-190): global_pool="token" -> head(token 0);
+    "avg" -> head(mean of tokens 1..) -- token 0 is the first PATCH token, the cls token (last) is averaged in; any other value ->
+    head on every token (B, N+1, classes).
     """
     w = p["patch_embedding.proj.weight"]
     x = vit_patch_embed_forward(img, w, p["patch_embedding.proj.bias"], dtype)
@@ -158,7 +160,11 @@ def vit_forward(img, p, num_heads, depth, dtype=torch.float32):
     x = torch.cat([x, cls], dim=1) + vit_position_rows(p["position_embedding"], w.shape[-1], img.shape[-2], img.shape[-1], dtype)
     for i in range(depth):
         x = vit_encoder_forward(x, _sub(p, f"blocks.{i}."), num_heads, dtype)
-    return linear(x[:, 0], _t(p["head.weight"], dtype), _t(p["head.bias"], dtype))
+    if global_pool == "token":
+        x = x[:, 0]
+    elif global_pool == "avg":
+        x = x[:, 1:].mean(dim=1)
+    return linear(x, _t(p["head.weight"], dtype), _t(p["head.bias"], dtype))
 
 
 def mixer_layer_forward(x, p, dtype=torch.float32):

@@ -117,9 +117,10 @@ def conv_patch_embed_forward(img, p, dtype=torch.float32, eps=1e-5):
     return x.flatten(2).transpose(1, 2), (Hp, Wp)
 
 
-def class_attention_block_forward(x, p, num_heads, dtype=torch.float32, tokens_norm=False):
+def class_attention_block_forward(x, p, num_heads, dtype=torch.float32, tokens_norm=False, qk_scale=None):
     """ClassAttentionBlock.forward -- xcit.py:218-231 with ClassAttention.forward :174-188.  tokens_norm=True (xcit.py:221-222, the
-    XCiT-S/M/L configurations): norm2 is applied to EVERY token after the first residual, not to the cls token only.
+    XCiT-S/M/L configurations): norm2 is applied to EVERY token after the first residual, not to the cls token only.  eta=None
+    (:210-214): no gamma1 / gamma2 parameters, both scales are the number 1.0.  qk_scale (:167): replaces d**-0.5 when given.
 
     The attention returns cat(proj(cls attention), NORMED patch tokens) (:187), so the first residual gives patch tokens
     x + gamma1*LN1(x); norm2 is applied to the cls token only (:223); the second residual adds x_res to cat(gamma2*mlp(cls), x[1:])
@@ -128,20 +129,23 @@ def class_attention_block_forward(x, p, num_heads, dtype=torch.float32, tokens_n
     x = _t(x, dtype)
     B, N, C = x.shape
     d = C // num_heads
+    scale = qk_scale or d ** -0.5
+    g1 = _t(p["gamma1"], dtype) if "gamma1" in p else 1.0
+    g2 = _t(p["gamma2"], dtype) if "gamma2" in p else 1.0
     u = layernorm(x, _t(p["norm1.weight"], dtype), _t(p["norm1.bias"], dtype))
     qkv = linear(u, _t(p["attn.qkv.weight"], dtype), _t(p["attn.qkv.bias"], dtype) if "attn.qkv.bias" in p else None)
     q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
     cls = torch.empty(B, C, dtype=dtype)
     for i in range(num_heads):
         sl = slice(i * d, (i + 1) * d)
-        s = (q[:, 0:1, sl] * k[:, :, sl]).sum(dim=-1) * (d ** -0.5)                 # (B, N)
+        s = (q[:, 0:1, sl] * k[:, :, sl]).sum(dim=-1) * scale                       # (B, N)
         s = s - s.amax(dim=-1, keepdim=True)
         e = torch.exp(s)
         a = e / e.sum(dim=-1, keepdim=True)
         cls[:, sl] = torch.einsum("bn,bnd->bd", a, v[:, :, sl])
     cls = linear(cls, _t(p["attn.proj.weight"], dtype), _t(p["attn.proj.bias"], dtype))
     att = torch.cat([cls[:, None, :], u[:, 1:]], dim=1)
-    x = x + _t(p["gamma1"], dtype) * att
+    x = x + g1 * att
     if tokens_norm:
         x = layernorm(x, _t(p["norm2.weight"], dtype), _t(p["norm2.bias"], dtype))
     else:
@@ -149,15 +153,18 @@ def class_attention_block_forward(x, p, num_heads, dtype=torch.float32, tokens_n
         x = torch.cat([c, x[:, 1:]], dim=1)
     m = _sub(p, "mlp.")
     h = gelu(linear(x[:, 0:1], _t(m["fc1.weight"], dtype), _t(m["fc1.bias"], dtype)))
-    c = _t(p["gamma2"], dtype) * linear(h, _t(m["fc2.weight"], dtype), _t(m["fc2.bias"], dtype))
+    c = g2 * linear(h, _t(m["fc2.weight"], dtype), _t(m["fc2.bias"], dtype))
     return x + torch.cat([c, x[:, 1:]], dim=1)
 
 
-def xcit_forward(img, p, num_heads=4, depth=12, cls_layers=2, dtype=torch.float32, tokens_norm=False):
-    """XCiT.forward -- xcit.py:392-414 (xcit_nano_12_p16 :416-420): ConvPatchEmbed, + Fourier position rows, `depth` XCABlocks,
-    cls token prepended, `cls_layers` ClassAttentionBlocks, LayerNorm, cls row, head."""
+def xcit_forward(img, p, num_heads=4, depth=12, cls_layers=2, dtype=torch.float32, tokens_norm=False, use_pos=True):
+    """XCiT.forward -- xcit.py:392-414 (xcit_nano_12_p16 :416-420): ConvPatchEmbed (four convs at patch 16, three at patch 8,
+    :99-117), + Fourier position rows when use_pos (:370-372), `depth` XCABlocks, cls token prepended, `cls_layers`
+    ClassAttentionBlocks, LayerNorm, cls row, head (the cls features themselves when num_classes=0: nn.Identity, :349)."""
     x, (Hp, Wp) = conv_patch_embed_forward(img, _sub(p, "patch_embed."), dtype)
-    x = x + fourier_position_rows(Hp, Wp, p["pos_embeder.token_projection.weight"], p["pos_embeder.token_projection.bias"], dtype=dtype)
+    if use_pos:
+        x = x + fourier_position_rows(Hp, Wp, p["pos_embeder.token_projection.weight"], p["pos_embeder.token_projection.bias"],
+                                      dtype=dtype)
     for i in range(depth):
         x = xca_block_forward(x, _sub(p, f"blocks.{i}."), num_heads, Hp, Wp, dtype)
     B = x.shape[0]
@@ -165,4 +172,6 @@ def xcit_forward(img, p, num_heads=4, depth=12, cls_layers=2, dtype=torch.float3
     for i in range(cls_layers):
         x = class_attention_block_forward(x, _sub(p, f"cls_attn_blocks.{i}."), num_heads, dtype, tokens_norm)
     x = layernorm(x, _t(p["norm.weight"], dtype), _t(p["norm.bias"], dtype))[:, 0]
+    if "head.weight" not in p:
+        return x
     return linear(x, _t(p["head.weight"], dtype), _t(p["head.bias"], dtype))

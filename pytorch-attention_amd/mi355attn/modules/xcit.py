@@ -302,8 +302,8 @@ class ClassAttentionBlock(nn.Module):
             out = F.layernorm(t1, w2, b2, self.norm2.eps)
         else:
             out = torch.empty_like(x)
-            # patch tokens: 2 * (x + g1 * LN1(x)); the cls rows written here are replaced below
-            F.axpby(x, out, B * N, C, C, C, alpha=2.0, u=u, ldu=C, gamma=None if g1 is None else _twice(self, g1))
+            # patch tokens: 2 * (x + g1 * LN1(x)), g1 = 1.0 without LayerScale; the cls rows written here are replaced below
+            F.axpby(x, out, B * N, C, C, C, alpha=2.0, u=u, ldu=C, gamma=_twos(self, C, x.device) if g1 is None else _twice(self, g1))
         # cls token: c1 = x0 + g1 * proj(attn); c2 = LN2(c1); out0 = c2 + g2 * mlp(c2)
         c1 = torch.empty(B, C, dtype=torch.float32, device=x.device)
         F.axpby(x, c1, B, C, N * C, C, u=self.attn.cls_out(u), ldu=C, gamma=g1)
@@ -323,6 +323,15 @@ def _twice(owner, g, slot="_g1x2"):
         hit = (tag, buf)
         setattr(owner, slot, hit)
     return hit[1]
+
+
+def _twos(owner, C, device):
+    """The doubled gamma1 of a block without LayerScale (eta=None: gamma1 is the number 1.0, xcit.py:214): a constant row of 2s."""
+    hit = getattr(owner, "_twos", None)
+    if hit is None or hit.numel() != C or hit.device != device:
+        hit = torch.full((C,), 2.0, dtype=torch.float32, device=device)
+        owner._twos = hit
+    return hit
 
 
 class XCiT(nn.Module):

@@ -13,6 +13,10 @@ Writes, under tests/golden/live/:
   routes.npz          per row of tests/route_cases.py (non-trivial parameters, prep_nontrivial): 257 strided samples, sum and
                       absolute sum of the reference module's output, and fp64 checksums of its parameters and of the input
                       (tests/test_routes_cpu.py); --routes-only rewrites this file alone;
+  models.npz          per row of tests/model_cases.py (whole models, prep_nontrivial + prep_model): the reference's output (whole when
+                      it holds at most 257 values, else 257 strided samples), its sum and absolute sum, fp64 checksums of the state_dict
+                      and of the input, and for `error` rows the name of the exception the reference raises (tests/test_models_cpu.py);
+                      --models-only rewrites this file alone;
 and tests/golden/reference_names.json: the public names of every reference module a drop-in shim mirrors (tests/test_signatures.py).
 """
 import argparse
@@ -45,10 +49,36 @@ CHAN_SHAPES = (((1, 48, 7, 9), 48, 16), ((3, 32, 5, 5), 32, 4), ((2, 80, 13, 1),
 LEPE_MODES = ((8, 0, 2, 32, 2), (8, 1, 4, 32, 1), (6, -1, 6, 64, 4))      # reso, idx, split, dim, heads
 
 
+def _model_records(model_cases, ref_cls, sample_index):
+    """models.npz: per row of tests/model_cases.py, built from the reference's class by model_cases.build_row."""
+    rec = {"ids": np.array([r["id"] for r in model_cases.ROWS])}
+    for r in model_cases.ROWS:
+        cls = ref_cls(r["mod"], r["cls"])
+        if "error" in r:
+            try:
+                model_cases.build_row(r, cls)
+            except Exception as e:               # the type is what the record keeps
+                rec[r["id"] + "__error"] = np.array(type(e).__name__)
+                continue
+            raise AssertionError("%s: the reference accepts this configuration" % r["id"])
+        m, x = model_cases.build_row(r, cls)
+        y = m(x, *r.get("fwd_args", ()))
+        sd = m.state_dict()
+        yf = y.reshape(-1)
+        rid = r["id"] + "__"
+        rec.update({rid + "y": (yf if yf.numel() <= 257 else yf[sample_index(yf.numel())]).numpy(), rid + "y_shape": np.array(list(y.shape)),
+                    rid + "y_sum": np.array(float(yf.double().sum())), rid + "y_abs": np.array(float(yf.double().abs().sum())),
+                    rid + "x_sum": np.array(float(x.double().sum())), rid + "p_keys": np.array(list(sd)),
+                    rid + "p_sum": np.array([float(v.double().sum()) for v in sd.values()]),
+                    rid + "p_abs": np.array([float(v.double().abs().sum()) for v in sd.values()])})
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", required=True, help="the reference checkout")
     ap.add_argument("--routes-only", action="store_true", help="write tests/golden/live/routes.npz only")
+    ap.add_argument("--models-only", action="store_true", help="write tests/golden/live/models.npz only")
     args = ap.parse_args()
     ref_root = os.path.abspath(args.ref)
     sys.dont_write_bytecode = True
@@ -58,6 +88,7 @@ def main():
     from make_signatures import public_names, shim_modules
     from test_aten_seq_cpu import CASES                      # shapes of the cases (drop-in side; imported before the reference is)
     from route_cases import ROWS, prep_nontrivial
+    import model_cases
     from cases import sample_index
     shapes = {c[0]: c[2] for c in CASES}
     # the drop-in package exports the same import paths: forget its modules, then import the reference's
@@ -78,6 +109,12 @@ def main():
 
     files = {}
     with torch.no_grad():
+        files["models"] = _model_records(model_cases, ref_cls, sample_index)
+        if args.models_only:
+            os.makedirs(os.path.join(HERE, "live"), exist_ok=True)
+            np.savez_compressed(os.path.join(HERE, "live", "models.npz"), **files["models"])
+            print("wrote models.npz (%d rows)" % len(model_cases.ROWS))
+            return
         routes = {"ids": np.array([r["id"] for r in ROWS])}
         for r in ROWS:
             torch.manual_seed(1234)
