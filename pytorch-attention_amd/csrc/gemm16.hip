@@ -423,6 +423,63 @@ __global__ __launch_bounds__(256) void cast16_kernel(const float* __restrict__ s
     if constexpr (std::is_same<T, _Float16>::value) rg_report(rgmax, ovf, 1u);
 }
 
+template <typename T, bool OUT16, bool LNA>
+void launch_ws_bn(const G16Args& g, int bn, int grid, int workers, hipStream_t st) {
+    if (g.K == 64) {
+        if (bn == 256)      gemm16_ws_kernel<T, OUT16, 256, 64, LNA><<<grid, 512, 0, st>>>(g, workers);
+        else if (bn == 128) gemm16_ws_kernel<T, OUT16, 128, 64, LNA><<<grid, 512, 0, st>>>(g, workers);
+        else                gemm16_ws_kernel<T, OUT16, 64, 64, LNA><<<grid, 512, 0, st>>>(g, workers);
+    } else {
+        if (bn == 256)      gemm16_ws_kernel<T, OUT16, 256, 128, LNA><<<grid, 512, 0, st>>>(g, workers);
+        else if (bn == 128) gemm16_ws_kernel<T, OUT16, 128, 128, LNA><<<grid, 512, 0, st>>>(g, workers);
+        else                gemm16_ws_kernel<T, OUT16, 64, 128, LNA><<<grid, 512, 0, st>>>(g, workers);
+    }
+}
+
+// gemm16_ws_kernel at K = 64 / 128, inside the caller's trace scope: column tiles of bn = 256 / 128 / 64, the widest N fills, each walked
+// down its 128-row tiles by `workers` workgroups -- per_cu per CU over all column tiles, at least one, at most one per row tile.
+template <bool LNA>
+void launch_ws(const G16Args& g, int out16, int precision, int per_cu, int ncu, hipStream_t st) {
+    const int bn = g.N >= 256 ? 256 : (g.N >= 128 ? 128 : 64);
+    const int tiles_n = cdiv(g.N, bn), tiles_m = cdiv(g.M, 128);
+    int workers = (ncu * per_cu) / tiles_n;
+    if (workers < 1) workers = 1;
+    if (workers > tiles_m) workers = tiles_m;
+    const int grid = tiles_n * workers;
+    if (precision == MI355_PREC_FP16) {
+        if (out16) launch_ws_bn<_Float16, true, LNA>(g, bn, grid, workers, st); else launch_ws_bn<_Float16, false, LNA>(g, bn, grid, workers, st);
+    } else {
+        if (out16) launch_ws_bn<__bf16, true, LNA>(g, bn, grid, workers, st); else launch_ws_bn<__bf16, false, LNA>(g, bn, grid, workers, st);
+    }
+}
+
+// What linear16_dispatch returns for the answer rc of a kernel's launcher: MI355_OK once the launch is checked (the test and text of
+// MI355_LAUNCH_CHECK there), MI355_EUNSUPPORTED when the kernel refused the call (nothing launched: the dispatch tries its next step),
+// or the error.
+int checked(int rc) {
+    if (rc != MI355_OK) return rc;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return mi355::fail(MI355_EHIP, "linear16_dispatch: kernel launch -> %s", hipGetErrorString(e));
+    mi355::range_mark_entry_done();
+    return MI355_OK;
+}
+
+// The body of mi355_linear16_stats_fwd and mi355_linear16_ln16_fwd: Y = resid + X16 . W16^T + bias (fp32) on gemm16_wreg, whose epilogue
+// also writes what the caller asked for in g (row statistics, or the next LayerNorm in the 16-bit operand format).  `entry` names the
+// caller in the error texts, `instead` what to use where the kernel is not built for the shape.  MI355_OK: launched, not yet checked.
+int linear16_wreg_fwd(G16Args& g, const void* X16, const void* W16, const float* bias, const float* resid, float* Y, int M, int N, int K,
+                      int ldx, int ldy, int precision, hipStream_t st, const char* entry, const char* instead) {
+    if (!aligned16(X16) || !aligned16(W16) || !aligned16(Y) || !aligned16(resid) || (bias && !aligned16(bias)) || !mi355::opt_gemm_wreg())
+        return mi355::fail(MI355_EUNSUPPORTED, "%s: 16-byte aligned buffers and option gemm_wreg = 1 required", entry);
+    g.A = X16; g.B = W16; g.C = Y; g.bias = bias; g.resid = resid;
+    g.M = M; g.N = N; g.K = K; g.lda = ldx; g.ldb = K; g.ldc = ldy; g.act = MI355_ACT_NONE;
+    if (g.ln16_out && precision == MI355_PREC_FP16) g.ovf = mi355::range_word(st);     // U16 is an fp16 operand tensor: a producer
+    const int rc = mi355::gemm16_wreg(g, 0, precision, st);
+    if (rc == MI355_EUNSUPPORTED)
+        return mi355::fail(rc, "%s: built for N = K = 256 / 384, M >= 32 (got M=%d N=%d K=%d): use mi355_linear16_fwd %s", entry, M, N, K, instead);
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -492,16 +549,11 @@ int mi355_linear16_stats_fwd(const void* X16, const void* W16, const float* bias
                              int ldy, int precision, float* row_stats, float eps, mi355_stream_t stream) {
     MI355_CHECK_ARG(X16 && W16 && resid && Y && row_stats && M > 0 && N > 0 && K > 0 && ldx >= K && ldy >= N);
     MI355_CHECK_ARG(precision == MI355_PREC_FP16 || precision == MI355_PREC_BF16);
-    if (!aligned16(X16) || !aligned16(W16) || !aligned16(Y) || !aligned16(resid) || (bias && !aligned16(bias)) || !mi355::opt_gemm_wreg())
-        return mi355::fail(MI355_EUNSUPPORTED, "mi355_linear16_stats_fwd: 16-byte aligned buffers and option gemm_wreg = 1 required");
     G16Args g{};
-    g.A = X16; g.B = W16; g.C = Y; g.bias = bias; g.resid = resid;
-    g.M = M; g.N = N; g.K = K; g.lda = ldx; g.ldb = K; g.ldc = ldy; g.act = MI355_ACT_NONE;
     g.row_stats = row_stats; g.ln_eps = eps;
-    const int rc = mi355::gemm16_wreg(g, 0, precision, static_cast<hipStream_t>(stream));
-    if (rc == MI355_EUNSUPPORTED)
-        return mi355::fail(rc, "mi355_linear16_stats_fwd: built for N = K = 256 / 384, M >= 32 (got M=%d N=%d K=%d): use mi355_linear16_fwd and a statistics pass", M, N, K);
-    if (rc != MI355_OK) return rc;
+    if (const int rc = linear16_wreg_fwd(g, X16, W16, bias, resid, Y, M, N, K, ldx, ldy, precision, static_cast<hipStream_t>(stream),
+                                         "mi355_linear16_stats_fwd", "and a statistics pass"))
+        return rc;
     MI355_LAUNCH_CHECK();
     return MI355_OK;
 }
@@ -511,18 +563,11 @@ int mi355_linear16_ln16_fwd(const void* X16, const void* W16, const float* bias,
                             mi355_stream_t stream) {
     MI355_CHECK_ARG(X16 && W16 && resid && Y && ln_w && ln_b && U16 && M > 0 && N > 0 && K > 0 && ldx >= K && ldy >= N && ldu >= N);
     MI355_CHECK_ARG(precision == MI355_PREC_FP16 || precision == MI355_PREC_BF16);
-    if (!aligned16(X16) || !aligned16(W16) || !aligned16(Y) || !aligned16(resid) || (bias && !aligned16(bias)) || !mi355::opt_gemm_wreg())
-        return mi355::fail(MI355_EUNSUPPORTED, "mi355_linear16_ln16_fwd: 16-byte aligned buffers and option gemm_wreg = 1 required");
     G16Args g{};
-    g.A = X16; g.B = W16; g.C = Y; g.bias = bias; g.resid = resid;
-    g.M = M; g.N = N; g.K = K; g.lda = ldx; g.ldb = K; g.ldc = ldy; g.act = MI355_ACT_NONE;
     g.ln16_out = U16; g.ln16_w = ln_w; g.ln16_b = ln_b; g.ln16_ld = ldu; g.ln_eps = eps;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (precision == MI355_PREC_FP16) g.ovf = mi355::range_word(st);                // U16 is an fp16 operand tensor: a producer
-    const int rc = mi355::gemm16_wreg(g, 0, precision, st);
-    if (rc == MI355_EUNSUPPORTED)
-        return mi355::fail(rc, "mi355_linear16_ln16_fwd: built for N = K = 256 / 384, M >= 32 (got M=%d N=%d K=%d): use mi355_linear16_fwd + mi355_layernorm16_fwd", M, N, K);
-    if (rc != MI355_OK) return rc;
+    if (const int rc = linear16_wreg_fwd(g, X16, W16, bias, resid, Y, M, N, K, ldx, ldy, precision, static_cast<hipStream_t>(stream),
+                                         "mi355_linear16_ln16_fwd", "+ mi355_layernorm16_fwd"))
+        return rc;
     MI355_LAUNCH_CHECK();
     return MI355_OK;
 }
@@ -530,82 +575,49 @@ int mi355_linear16_ln16_fwd(const void* X16, const void* W16, const float* bias,
 }  // extern "C"
 
 // Kernel choice of mi355_linear16_ws_fwd on a checked argument block (also the product of the patch embedding, gemm.hip, which
-// brings a periodic residual table: only the persistent and the plain tile kernels read one).
+// brings a periodic residual table: only the persistent and the plain tile kernels read one).  The policy reads top to bottom: each
+// step is a condition and a kernel to try; a kernel that refuses the call (MI355_EUNSUPPORTED, nothing launched) leaves it to the next
+// step, and the plain tile kernel takes whatever is left.  Where a kernel checks what it can take, the step states only the policy.
 int mi355::linear16_dispatch(const G16Args& g, int out16, int precision, void* ws, size_t ws_bytes, hipStream_t st) {
     const int M = g.M, N = g.N, K = g.K;
-    long variant = mi355::opt_gemm_variant();
-    if (g.resid_period) {
-        if (K == 64 || K == 128 || out16 || !g.resid) return MI355_EUNSUPPORTED;
+    if (g.resid_period && (K == 64 || K == 128 || out16 || !g.resid)) return MI355_EUNSUPPORTED;
+    const struct { long variant, wst, wslab, pa, pa16, pa_tail, wreg, w4; } opt = {
+        mi355::opt_gemm_variant(), mi355::opt_gemm_wst(), mi355::opt_gemm_wslab(), mi355::opt_gemm_pa(), mi355::opt_gemm_pa16(),
+        mi355::opt_gemm_pa_tail(), mi355::opt_gemm_wreg(), mi355::opt_gemm_w4()};
+    const int ncu = mi355::resident_slots(1);
+    const bool gelu = g.act == MI355_ACT_GELU;
+    long variant = opt.variant;
+    if (variant >= 15) {                   // one persistent kernel forced; a shape it does not take is an error
+        static const char* const what[] = {"persistent kernel",                   // 15: 256 x 256 (gemm16_p8.hip)
+                                           "the two-accumulator kernel",          // 16: two-accumulator 128 x 256 (gemm16_pa.hip)
+                                           "the one-wave-per-SIMD kernel"};       // 17: one wave per SIMD, 256 x 256 (gemm16_w4.hip)
+        const int rc = variant == 15 ? mi355::gemm16_p8(g, out16, precision, ws, ws_bytes, st)
+                     : variant == 16 ? mi355::gemm16_pa(g, out16, precision, st) : mi355::gemm16_w4(g, out16, precision, st);
+        if (rc == MI355_EUNSUPPORTED) return mi355::fail(rc, "mi355_linear16_fwd: %s does not take this shape", what[variant - 15]);
+        return checked(rc);
     }
-    if (variant == 15) {                   // persistent 256 x 256 kernel (gemm16_p8.hip)
-        const int rc = mi355::gemm16_p8(g, out16, precision, ws, ws_bytes, st);
-        if (rc == MI355_EUNSUPPORTED) return mi355::fail(rc, "mi355_linear16_fwd: persistent kernel does not take this shape");
-        if (rc != MI355_OK) return rc;
-        MI355_LAUNCH_CHECK();
-        return MI355_OK;
-    }
-    if (variant == 16) {                   // two-accumulator persistent 128 x 256 kernel (gemm16_pa.hip)
-        const int rc = mi355::gemm16_pa(g, out16, precision, st);
-        if (rc == MI355_EUNSUPPORTED) return mi355::fail(rc, "mi355_linear16_fwd: the two-accumulator kernel does not take this shape");
-        if (rc != MI355_OK) return rc;
-        MI355_LAUNCH_CHECK();
-        return MI355_OK;
-    }
-    if (variant == 17) {                   // one-wave-per-SIMD persistent 256 x 256 kernel (gemm16_w4.hip)
-        const int rc = mi355::gemm16_w4(g, out16, precision, st);
-        if (rc == MI355_EUNSUPPORTED) return mi355::fail(rc, "mi355_linear16_fwd: the one-wave-per-SIMD kernel does not take this shape");
-        if (rc != MI355_OK) return rc;
-        MI355_LAUNCH_CHECK();
-        return MI355_OK;
-    }
-    if (variant == 0 && out16 && K == 768 && (mi355::opt_gemm_wst() == 2 || mi355::opt_gemm_wst() == 4 || ((mi355::opt_gemm_wst() & 1) && g.act == MI355_ACT_NONE))) {
+    if (variant == 0) {
+        int rc;
         // ViT qkv / fc1, opt-in: a 192-column slab of W stays in the registers of a workgroup, X streams through LDS once per slab (gemm16_wst.hip)
-        const int rc = mi355::gemm16_wst(g, out16, precision, st);
-        if (rc == MI355_OK) {
+        if ((opt.wst == 2 || opt.wst == 4 || ((opt.wst & 1) && g.act == MI355_ACT_NONE)) &&
+            (rc = checked(mi355::gemm16_wst(g, out16, precision, st))) != MI355_EUNSUPPORTED)
+            return rc;
+        if ((K == 64 || K == 128) && M >= 2048 && (!out16 || (N & 7) == 0)) {       // short-K, HBM-bound: weight-stationary streaming kernel
+            MI355_TRACE(st, "gemm16_ws_kernel<%s> M=%d N=%d K=%d", out16 ? "out16" : "out32", M, N, K);
+            launch_ws<false>(g, out16, precision, K == 64 ? 2 : 1, ncu, st);
             MI355_LAUNCH_CHECK();
             return MI355_OK;
         }
-        if (rc != MI355_EUNSUPPORTED) return rc;
-    }
-    if (variant == 0 && (K == 64 || K == 128) && M >= 2048 && (!out16 || (N & 7) == 0)) {       // short-K, HBM-bound: weight-stationary streaming kernel
-        int ncu = 256, dev = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-        const int bn = N >= 256 ? 256 : (N >= 128 ? 128 : 64);
-        const int tiles_n = cdiv(N, bn), tiles_m = cdiv(M, 128);
-        const int per_cu = (K == 64 && bn <= 256) ? 2 : 1;
-        int workers = (ncu * per_cu) / tiles_n;
-        if (workers < 1) workers = 1;
-        if (workers > tiles_m) workers = tiles_m;
-        const int grid = tiles_n * workers;
-        MI355_TRACE(st, "gemm16_ws_kernel<%s> M=%d N=%d K=%d", out16 ? "out16" : "out32", M, N, K);
-#define WS(T_, O_, BN_, KK_) gemm16_ws_kernel<T_, O_, BN_, KK_><<<grid, 512, 0, st>>>(g, workers)
-#define WS_BY_SHAPE(T_, O_)                                                   \
-        do {                                                                  \
-            if (K == 64) { if (bn == 256) WS(T_, O_, 256, 64); else if (bn == 128) WS(T_, O_, 128, 64); else WS(T_, O_, 64, 64); }    \
-            else         { if (bn == 256) WS(T_, O_, 256, 128); else if (bn == 128) WS(T_, O_, 128, 128); else WS(T_, O_, 64, 128); } \
-        } while (0)
-        if (precision == MI355_PREC_FP16) { if (out16) WS_BY_SHAPE(_Float16, true); else WS_BY_SHAPE(_Float16, false); }
-        else                              { if (out16) WS_BY_SHAPE(__bf16, true); else WS_BY_SHAPE(__bf16, false); }
-#undef WS_BY_SHAPE
-#undef WS
-        MI355_LAUNCH_CHECK();
-        return MI355_OK;
-    }
-    if (variant == 0 && out16 && (K == 256 || K == 384 || K == 512) && !g.gamma && !g.resid &&
-        (mi355::opt_gemm_wslab() == 2 || (mi355::opt_gemm_wslab() == 1 && (g.act == MI355_ACT_GELU || (M & 255))))) {
         // short reductions, 16-bit output (XCiT / CSWin stage 3-4 / Mixer qkv and fc1): a column slab of W stationary in registers, X through LDS
         // once per slab, 32-row tiles (gemm16_wslab.hip; bit-identical to the tile kernels).  Default policy: where it measured faster -- GELU
         // epilogues (5-12 %) and row counts off the 256-row grid (which otherwise fall to gemm16_p8: 88-96 -> 65-69 us); plain epilogues are a tie.
-        const int rc = mi355::gemm16_wslab(g, out16, precision, st);
-        if (rc == MI355_OK) {
-            MI355_LAUNCH_CHECK();
-            return MI355_OK;
-        }
-        if (rc != MI355_EUNSUPPORTED) return rc;
-    }
-    if (variant == 0 && out16 && K >= 256 && !g.gamma && !g.resid && mi355::opt_gemm_pa() &&
-        (K <= 512 || (mi355::opt_gemm_pa16() >= 1 && g.act == MI355_ACT_GELU) || mi355::opt_gemm_pa16() >= 2)) {
+        if ((opt.wslab == 2 || (opt.wslab == 1 && (gelu || (M & 255)))) &&
+            (rc = checked(mi355::gemm16_wslab(g, out16, precision, st))) != MI355_EUNSUPPORTED)
+            return rc;
+        // The two-accumulator persistent kernel (gemm16_pa.hip) runs 128 x 256 tiles, or 256 x 128 (operand roles swapped) where N is a
+        // multiple of 128 but not of 256 (XCiT: N = 384); half a round of tiles is enough (round 4, CSWin stage 4 fc2: 196 tiles, 41 -> 36 us).
+        const long pa_tiles = (N & 255) ? (long)(M / 256) * (N / 128) : (long)cdiv(M, 128) * (N / 256);
+        const bool pa_fills = 2 * pa_tiles >= ncu;
         // 16-bit outputs with a SHORT reduction (4 .. 8 K-tiles: CSWin stage 3 / 4, XCiT, the Mixer's token mixing): on the persistent
         // 256 x 256 kernel the epilogue of such a tile (bias / GELU / convert / store, nothing to overlap it with) is as long as its
         // main loop; the two-accumulator kernel packs two or three convert pieces into every barrier interval of the next tile's
@@ -614,52 +626,33 @@ int mi355::linear16_dispatch(const G16Args& g, int out16, int precision, void* w
         // loop stages 1.5 x fewer bytes per flop, but its GELU epilogue is fully exposed (55 us of ViT-Base's fc1) where the pieces of
         // this kernel hide most of it (29 us): option "gemm_pa16" = 1 (default) sends GELU epilogues here (fc1 313 -> 291 us in a
         // same-process A/B), 2 every 16-bit output (qkv: 221 -> 207 on one kind of box, 197 -> 208 on the other: not the default), 0 neither.
-        const int ncu = mi355::resident_slots(1);
-        const long tiles = (N & 255) ? (long)(M / 256) * (N / 128) : (long)cdiv(M, 128) * (N / 256);
-        if (2 * tiles >= ncu) {
-            const int rc = mi355::gemm16_pa(g, out16, precision, st);
-            if (rc == MI355_OK) {
-                MI355_LAUNCH_CHECK();
-                return MI355_OK;
-            }
-            if (rc != MI355_EUNSUPPORTED) return rc;
-        }
-    }
-    if (variant == 0 && !out16 && N == K && (K == 256 || K == 384) && mi355::opt_gemm_wreg()) {
+        if (out16 && opt.pa && pa_fills && (K <= 512 || (opt.pa16 >= 1 && gelu) || opt.pa16 >= 2) &&
+            (rc = checked(mi355::gemm16_pa(g, out16, precision, st))) != MI355_EUNSUPPORTED)
+            return rc;
         // square short products with an fp32 (+ residual) output (XCiT proj 384 x 384, CSWin stage-3 proj 256 x 256): bound by the residual /
         // output stream, not by the matrix pipes -- weights stationary in registers, X / residual / Y each cross HBM once (gemm16_wreg.hip;
         // round 6: XCiT proj 70 -> see profiles/r06_gemm_wreg.md; bit-identical to the tile kernels)
-        const int rc = mi355::gemm16_wreg(g, out16, precision, st);
-        if (rc == MI355_OK) {
-            MI355_LAUNCH_CHECK();
-            return MI355_OK;
-        }
-        if (rc != MI355_EUNSUPPORTED) return rc;
-    }
-    if (variant == 0 && !out16 && (g.resid || N <= 768) && mi355::opt_gemm_pa()) {
-        // fp32 (+ residual) outputs: the two-accumulator persistent kernel (gemm16_pa.hip) hides the residual / store round trips of
-        // tile i under the main loop of tile i + 1 (ViT-Base proj 0.130 -> 0.106 ms, fc2 0.266 -> 0.259; profiles/r03_gemm_pa.md).
-        // No inter-workgroup exchange: safe under hipGraph capture, and a row's bits never depend on where its tile falls.
-        // Round 4: widths that are a multiple of 128 but not of 256 (XCiT: N = 384) run 256 x 128 tiles (operand roles swapped), and
-        // half a round of tiles is enough (CSWin stage 4 fc2: 196 tiles, 41 -> 36 us).
-        const int ncu = mi355::resident_slots(1);
-        const long tiles = (N & 255) ? (long)(M / 256) * (N / 128) : (long)cdiv(M, 128) * (N / 256);
-        if (2 * tiles >= ncu) {
+        if (opt.wreg && (rc = checked(mi355::gemm16_wreg(g, out16, precision, st))) != MI355_EUNSUPPORTED) return rc;
+        if (!out16 && (g.resid || N <= 768) && opt.pa && pa_fills) {
+            // fp32 (+ residual) outputs: the two-accumulator persistent kernel hides the residual / store round trips of tile i under the
+            // main loop of tile i + 1 (ViT-Base proj 0.130 -> 0.106 ms, fc2 0.266 -> 0.259; profiles/r03_gemm_pa.md).  No inter-workgroup
+            // exchange: safe under hipGraph capture, and a row's bits never depend on where its tile falls.
             // A last round that is nearly empty costs a whole tile time on a persistent kernel (the Mixer's fc2: 784 tiles = 3.06
             // rounds, XCiT's fc2: 588 = 2.30).  With a long reduction that is tens of microseconds, so the two-accumulator kernel
             // gets the rows of its whole rounds and the rest goes, as a second launch, to ring-pipelined small tiles that cover all
             // CUs (option "gemm_pa_tail").  Both kernels add a row's K-tiles in the same order: bit-identical to the unsplit launch.
             const int bmt = (N & 255) ? 256 : 128, tn = (N & 255) ? N / 128 : N / 256;
-            const long left = tiles % ncu, pct = mi355::opt_gemm_pa_tail();
-            if (pct > 0 && tiles > ncu && left > 0 && left * 100 <= pct * ncu && K >= 1024 && M % bmt == 0 && !g.resid_period && !g.lnc_a) {
-                const int rows1 = (int)((tiles - left) / tn) * bmt, rows2 = M - rows1;
+            const long left = pa_tiles % ncu;
+            if (opt.pa_tail > 0 && pa_tiles > ncu && left > 0 && left * 100 <= opt.pa_tail * ncu && K >= 1024 && M % bmt == 0 &&
+                !g.resid_period && !g.lnc_a) {
+                const int rows1 = (int)((pa_tiles - left) / tn) * bmt, rows2 = M - rows1;
                 G16Args g1 = g, g2 = g;
                 g1.M = rows1;
                 g2.M = rows2;
                 g2.A = static_cast<const char*>(g.A) + (size_t)rows1 * g.lda * 2;
                 g2.C = static_cast<char*>(g.C) + (size_t)rows1 * g.ldc * 4;
                 if (g.resid) g2.resid = g.resid + (size_t)rows1 * g.ldc;
-                const int rc = mi355::gemm16_pa(g1, out16, precision, st);
+                rc = mi355::gemm16_pa(g1, out16, precision, st);
                 if (rc == MI355_OK) {
                     MI355_LAUNCH_CHECK();
                     // 32 x 64 tiles, four waves, a ring of ten K-tiles (120 KB): 1 024 x 512 left-over outputs = one workgroup per CU.  The
@@ -675,52 +668,30 @@ int mi355::linear16_dispatch(const G16Args& g, int out16, int precision, void* w
                 }
                 if (rc != MI355_EUNSUPPORTED) return rc;
             }
-            const int rc = mi355::gemm16_pa(g, out16, precision, st);
-            if (rc == MI355_OK) {
-                MI355_LAUNCH_CHECK();
-                return MI355_OK;
-            }
-            if (rc != MI355_EUNSUPPORTED) return rc;
+            if ((rc = checked(mi355::gemm16_pa(g, out16, precision, st))) != MI355_EUNSUPPORTED) return rc;
         }
-    }
-    if (variant == 0 && (N & 7) == 0 && !(out16 && g.resid)) {
         // Persistent 256 x 256 kernel (gemm16_p8.hip) for every shape with at least one full round of tiles (one workgroup per CU)
         // and K >= 256: it is >= the best 3-workgroups-per-CU variant on all 17 shapes of profiles/r02_gemm_p8.md except CSWin s3 fc1
         // (inside the run-to-run band), shapes just above a round boundary included (the last partial round costs a whole tile time
         // either way; long reductions cut it along K).
-        const int ncu = mi355::resident_slots(1);
-        const long ntiles = (long)cdiv(M, 256) * cdiv(N, 256);
-        if (ntiles >= ncu && K >= 256) {
+        if ((long)cdiv(M, 256) * cdiv(N, 256) >= ncu && K >= 256) {
             // 16-bit outputs of a mid-length reduction (ViT qkv: K = 768): one wave per SIMD with 128 x 128 outputs each needs a third fewer LDS
             // bytes per flop and, with its two-slab pipelined epilogue, 5.8 k instead of ~11 k exposed cycles per tile (round 5, same process:
             // qkv 0.193-0.195 -> 0.179-0.182 ms).  Long reductions keep the split last round of the eight-wave kernel.
-            if (out16 && K >= 576 && K < 1536 && mi355::opt_gemm_w4()) {
-                const int rc = mi355::gemm16_w4(g, out16, precision, st);
-                if (rc == MI355_OK) {
-                    MI355_LAUNCH_CHECK();
-                    return MI355_OK;
-                }
-                if (rc != MI355_EUNSUPPORTED) return rc;
-            }
-            const int rc = mi355::gemm16_p8(g, out16, precision, ws, ws_bytes, st);
-            if (rc == MI355_OK) {
-                MI355_LAUNCH_CHECK();
-                return MI355_OK;
-            }
-            if (rc != MI355_EUNSUPPORTED) return rc;                 // e.g. MI355_ESYNC: an earlier launch failed, reported once
+            if (out16 && K >= 576 && K < 1536 && opt.w4 && (rc = checked(mi355::gemm16_w4(g, out16, precision, st))) != MI355_EUNSUPPORTED)
+                return rc;
+            // anything but MI355_EUNSUPPORTED is final, e.g. MI355_ESYNC: an earlier launch failed, reported once
+            if ((rc = checked(mi355::gemm16_p8(g, out16, precision, ws, ws_bytes, st))) != MI355_EUNSUPPORTED) return rc;
         }
-    }
-    if (variant == 0) {        // default (profiles/r01_gemm_variants.md): 8 waves on a 128x256 tile, single LDS buffer, 3 workgroups
-        variant = (N <= 64) ? 9 : (N < 256 ? 1 : 7);   // per CU; narrow outputs use 256x64 / 128x128 tiles instead
-        int ncu = 256, dev = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+        // default (profiles/r01_gemm_variants.md): 8 waves on a 128x256 tile, single LDS buffer, 3 workgroups per CU; narrow outputs use
+        // 256x64 / 128x128 tiles instead
+        variant = (N <= 64) ? 9 : (N < 256 ? 1 : 7);
         // fewer 128x256 tiles than CUs (CSWin stage 4: M = 12544, N = 512 -> 196 tiles): halve the tile so that the chip fills
         // (measured 57 -> 43 us on the K = 2048 fc2 of that stage, 25 -> 22 us on its proj)
         if (variant == 7 && (long)cdiv(M, 128) * cdiv(N, 256) < ncu) variant = 1;
     }
     else if (variant == 8) variant = 0;     // 8 = plain 128x128 without priority hints (tuning experiments)
-    MI355_TRACE(st, "gemm16_kernel<variant %ld,%s> M=%d N=%d K=%d%s", variant, out16 ? "out16" : "out32", M, N, K, g.act == MI355_ACT_GELU ? " gelu" : "");
+    MI355_TRACE(st, "gemm16_kernel<variant %ld,%s> M=%d N=%d K=%d%s", variant, out16 ? "out16" : "out32", M, N, K, gelu ? " gelu" : "");
 #define LAUNCH(T_, O_, BM_, BN_, WM_, WN_, P_, S_)                                                         \
     gemm16_kernel<T_, O_, BM_, BN_, WM_, WN_, P_, S_><<<cdiv(M, BM_) * cdiv(N, BN_), WM_ * WN_ * 64, 0, st>>>(g)
 #define BY_VARIANT(T_, O_)                                                 \
@@ -784,26 +755,9 @@ int mi355_ln_linear16_fwd(const float* X, const void* W16, const float* bias, vo
     g.M = M; g.N = N; g.K = K; g.lda = ldx; g.ldb = K; g.ldc = ldy; g.act = act;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (out16 && precision == MI355_PREC_FP16) g.ovf = mi355::range_word(st);
-    int ncu = 256, dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    const int bn = N >= 256 ? 256 : (N >= 128 ? 128 : 64);
-    const int tiles_n = cdiv(N, bn), tiles_m = cdiv(M, 128);
-    int workers = (ncu * 2) / tiles_n;
-    if (workers < 1) workers = 1;
-    if (workers > tiles_m) workers = tiles_m;
-    const int grid = tiles_n * workers;
+    const int ncu = mi355::resident_slots(1);
     MI355_TRACE(st, "gemm16_ws_kernel<ln,%s> M=%d N=%d K=%d", out16 ? "out16" : "out32", M, N, K);
-#define WSL(T_, O_, BN_, KK_) gemm16_ws_kernel<T_, O_, BN_, KK_, true><<<grid, 512, 0, st>>>(g, workers)
-#define WSL_BY_SHAPE(T_, O_)                                                   \
-    do {                                                                       \
-        if (K == 64) { if (bn == 256) WSL(T_, O_, 256, 64); else if (bn == 128) WSL(T_, O_, 128, 64); else WSL(T_, O_, 64, 64); }    \
-        else         { if (bn == 256) WSL(T_, O_, 256, 128); else if (bn == 128) WSL(T_, O_, 128, 128); else WSL(T_, O_, 64, 128); } \
-    } while (0)
-    if (precision == MI355_PREC_FP16) { if (out16) WSL_BY_SHAPE(_Float16, true); else WSL_BY_SHAPE(_Float16, false); }
-    else                              { if (out16) WSL_BY_SHAPE(__bf16, true); else WSL_BY_SHAPE(__bf16, false); }
-#undef WSL_BY_SHAPE
-#undef WSL
+    launch_ws<true>(g, out16, precision, 2, ncu, st);
     MI355_LAUNCH_CHECK();
     return MI355_OK;
 }

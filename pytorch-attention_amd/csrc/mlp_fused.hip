@@ -448,9 +448,7 @@ extern "C" int mi355_mlp_fused_fwd(const float* x, const void* w1_16, const floa
     // layernorm bit 1: the caller has PROVEN |gelu(H)| < 65504 from the folded weights (|LN(x)| <= sqrt(C - 1)): nothing to report, and the
     // launch is not a producer the host would have to wait for (mi355_range_wait)
     a.ovf = (precision == MI355_PREC_FP16 && !(layernorm & 2)) ? mi355::range_word(st) : nullptr;
-    int dev = 0, ncu = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    const int ncu = mi355::resident_slots(1);
     MI355_TRACE(st, "mlp_fused_kernel<C=%d> M=%ld", C, M);
     if (C == 128) {
         constexpr size_t sm = (size_t)2 * (32 * (128 + 8) + 128 * 36) * 2 + (size_t)8 * 16 * 68 * 4 + (size_t)512 * 4;
