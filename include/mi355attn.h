@@ -22,6 +22,10 @@
  *   - precision: 0 = strict (3-way split-bf16 MFMA, fp32-class accuracy), 1 = fp16 MFMA operands with fp32
  *     accumulate (default of the modules; within the 1e-3 parity tolerance), 2 = bf16 MFMA operands (fast,
  *     outside the tolerance; reported separately).  Vector (non-MFMA) math is always fp32.
+ *     The host mirror knows a fourth value, 3 = "logit-compensated": precision 1 everywhere except the logit path of ViT attention
+ *     (q / k columns of the qkv projection, the stored q and k, Q K^T), which runs in the strict operand format through the two entries
+ *     mi355_qkv_split16_fwd / mi355_sdpa16_split_fwd below.  It is a HOST mapping: every entry with a `precision` parameter takes 0, 1 or 2
+ *     and rejects 3 with MI355_EINVAL.
  */
 #ifndef MI355ATTN_H
 #define MI355ATTN_H
@@ -503,6 +507,27 @@ int mi355_sdpa16_fwd(const void* qkv16, void* out16, int B, int N, int heads, in
 int mi355_cswin_lepe_attn16_fwd(const void* qkv16, const float* getv_w, const float* getv_b, void* out16,
                                 int B, int reso, int Ctot, int c0, int Cb, int heads, int Hsp, int Wsp,
                                 float scale, int precision, mi355_stream_t stream);
+/* ---- precision 3 ("logit-compensated") ViT attention: split-bf16 logits, fp16 values -------------------------------------------------
+ * The 16-bit error of ViT attention that grows with the weight scale is made on the logit path -- where x and the q / k rows of the qkv
+ * weight are rounded, where q and k are stored, and in Q K^T; the value path (v, P, P V, proj) is scale-free (profiles/logit_mode.md).
+ * These two entries run the logit path in the strict operand format (bf16 hi + lo, hi.hi + hi.lo + lo.hi, fp32 accumulate) and the
+ * value path in fp16; neither takes a `precision`.
+ *
+ * mi355_qkv_split16_fwd: the whole qkv projection in one launch from fp32 rows,
+ *     [q | k | v] (M, 3C) = x (M, K; row stride ldx floats) . W^T + bias,
+ * with W pre-split by the caller: w_hi, w_lo (2C, K) bfloat16 = hi / lo parts of rows [0, 2C) of the (3C, K) weight (hi = bf16(W),
+ * lo = bf16(W - hi)), w_v16 (C, K) IEEE half = rows [2C, 3C); bias (3C) fp32 or NULL, added before the result is split.  Output qkv5
+ * (M, 5C) 16-bit, FIVE C-wide planes per token row:
+ *     [ q_hi | q_lo | k_hi | k_lo | v ]      q_hi, q_lo, k_hi, k_lo bfloat16 (q = q_hi + q_lo, k = k_hi + k_lo), v IEEE half.
+ * Envelope: C % 64 == 0, K % 64 == 0 (else MI355_EUNSUPPORTED), any M.  The fp16 conversions of the v columns (x operands: range code
+ * 1, results: code 3) report into the range word like mi355_cast16_fwd / mi355_linear16_fwd; bf16 is never flagged.  No workspace.
+ *
+ * mi355_sdpa16_split_fwd: softmax(q k^T scale) v per head on those rows, qkv5 (B, N, 5C) with C = heads * d -> out16 (B, N, C) IEEE half,
+ * ready for mi355_linear16_fwd (precision 1).  Q K^T on the bf16 pairs (three MFMAs per step), softmax in fp32, P and V in fp16.
+ * d in {32, 64}, N <= 224 (else MI355_EUNSUPPORTED). */
+int mi355_qkv_split16_fwd(const float* x, const void* w_hi, const void* w_lo, const void* w_v16, const float* bias, void* qkv5,
+                          int M, int C, int K, int ldx, mi355_stream_t stream);
+int mi355_sdpa16_split_fwd(const void* qkv5, void* out16, int B, int N, int heads, int d, float scale, mi355_stream_t stream);
 /* Both stripe branches of a CSWinBlock in ONE launch (cswin.py:155-165, 186-192): branch 0 = vertical stripes (H_sp = reso, W_sp =
  * split) on channels [0, Ctot/2) with get_v weights w0/b0, branch 1 = horizontal stripes on [Ctot/2, Ctot) with w1/b1; `heads` per branch.
  * Same arithmetic as two mi355_cswin_lepe_attn16_fwd calls. */

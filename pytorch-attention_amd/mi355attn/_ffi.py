@@ -79,6 +79,8 @@ SIGNATURES = {
     "mi355_linear16_ws_fwd": (c_int, [c_vp] * 6 + [c_int] * 8 + [c_vp, c_size, c_vp]),
     "mi355_sdpa16_fwd": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_float, c_int, c_vp]),
     "mi355_cswin_lepe_attn16_fwd": (c_int, [c_vp] * 4 + [c_int] * 8 + [c_float, c_int, c_vp]),
+    "mi355_qkv_split16_fwd": (c_int, [c_vp] * 6 + [c_int] * 4 + [c_vp]),
+    "mi355_sdpa16_split_fwd": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_float, c_vp]),
     "mi355_conv2d_tokens_fwd": (c_int, [c_vp] * 5 + [c_int] * 13 + [c_vp]),
     "mi355_token_mean_fwd": (c_int, [c_vp, c_vp, c_int, c_int, c_int, ctypes.c_long, c_vp]),
     "mi355_chan_stat_workspace_bytes": (ctypes.c_size_t, [c_int, c_int]),

@@ -14,6 +14,7 @@ from . import _ffi
 from ._ffi import check, dptr, lib, require_device_f32, stream_ptr, workspace
 
 PREC_STRICT, PREC_FP16, PREC_BF16 = 0, 1, 2
+PREC_LOGIT = 3       # "logit-compensated": precision 1 everywhere, except that the logit path of ViT attention runs in the strict operand format
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2     # ACT_RELU: fp32-in engine only (linear, conv2d_tokens)
 
 _default_precision = PREC_FP16
@@ -29,10 +30,11 @@ _strict_lock = threading.Lock()
 
 
 def set_default_precision(p):
-    """Process-wide default MFMA operand precision for modules that do not pin one (0 strict / 1 fp16 / 2 bf16)."""
+    """Process-wide default MFMA operand precision for modules that do not pin one (0 strict / 1 fp16 / 2 bf16 / 3 logit-compensated:
+    fp16 everywhere, the logit path of ViT attention in the strict format -- see modules.vit.Attention)."""
     global _default_precision
-    if p not in (PREC_STRICT, PREC_FP16, PREC_BF16):
-        raise ValueError("precision must be 0 (strict), 1 (fp16) or 2 (bf16)")
+    if p not in (PREC_STRICT, PREC_FP16, PREC_BF16, PREC_LOGIT):
+        raise ValueError("precision must be 0 (strict), 1 (fp16), 2 (bf16) or 3 (logit-compensated)")
     _default_precision = p
 
 
@@ -46,7 +48,16 @@ def _prec(p):
     (_forced_strict) beats both the process default and an explicit `precision=`."""
     if _strict_active and _strict_override.depth:
         return PREC_STRICT
-    return _default_precision if p is None else p
+    p = _default_precision if p is None else p
+    return PREC_FP16 if p == PREC_LOGIT else p             # 3 is 1 to every op and module but ViT attention, which asks logit_mode()
+
+
+def logit_mode(p):
+    """True when setting `p` (None = the default) asks for precision 3 on the calling thread.  Only ViT attention asks; everything else
+    sees precision 1 through _prec().  A strict re-run (_forced_strict) wins over 3 as over any other setting."""
+    if _strict_active and _strict_override.depth:
+        return False
+    return (_default_precision if p is None else p) == PREC_LOGIT
 
 
 def _opt(t, name):
@@ -740,6 +751,26 @@ def weight16(param, precision=None):
     return _derived_get((param,), ("w16", p), tag, lambda: cast16(param.detach(), p))
 
 
+def split_qkv_weight(w):
+    """(w_hi, w_lo, w_v16) of a (3C, K) qkv weight for mi355_qkv_split16_fwd: the q and k rows [0, 2C) as a bfloat16 pair (hi = bf16(W),
+    lo = bf16(W - hi): hi + lo carries ~16 mantissa bits, the strict operand format of csrc/mma.h), the v rows [2C, 3C) as IEEE half
+    (what precision 1 feeds the same columns; on the device through cast16, so that a saturating weight is reported).  One-time
+    preparation on the weight's own device, not a hot path."""
+    w = w.detach()
+    C2 = w.shape[0] // 3 * 2
+    hi = w[:C2].to(torch.bfloat16)
+    lo = (w[:C2] - hi.float()).to(torch.bfloat16)
+    v16 = cast16(w[C2:], PREC_FP16) if w.is_cuda else w[C2:].to(torch.float16).contiguous()     # on the device: the reporting conversion
+    return hi.contiguous(), lo.contiguous(), v16
+
+
+def weight_split16(param):
+    """split_qkv_weight of a qkv weight, converted once and reused until the parameter is modified, moved or collected (the rules of
+    weight16; a v part that saturates fp16 is remembered and raises Mi355RangeError on every use, like any cached fp16 copy)."""
+    tag = (param._version, param.data_ptr(), tuple(param.shape))
+    return _derived_get((param,), ("wsplit16",), tag, lambda: split_qkv_weight(param))
+
+
 FP16_MIN_NORMAL = 2.0 ** -14
 
 
@@ -1175,6 +1206,52 @@ def sdpa16(qkv16, num_heads, scale, precision=None):
     out = torch.empty(B, N, C, dtype=qkv16.dtype, device=qkv16.device)
     check(lib().mi355_sdpa16_fwd(dptr(qkv16), dptr(out), B, N, num_heads, C // num_heads, float(scale), _prec(precision),
                                  stream_ptr(qkv16.device)), "mi355_sdpa16_fwd")
+    return out
+
+
+def logit_envelope(C, K, num_heads, n_tokens):
+    """Envelope of the precision-3 kernels (mi355_qkv_split16_fwd + mi355_sdpa16_split_fwd): head width 32 / 64, N <= 224, K % 64 == 0."""
+    return C % num_heads == 0 and C // num_heads in (32, 64) and n_tokens <= 224 and K % 64 == 0 and C % 64 == 0
+
+
+def qkv_split16(x, w_hi, w_lo, w_v16, bias=None):
+    """The qkv projection of precision 3 in one launch: x (..., K) fp32 -> (..., 5C) 16-bit rows [q_hi | q_lo | k_hi | k_lo | v] (returned
+    as an int16 tensor: four bfloat16 planes and one float16 plane; `qkv_split16_planes` gives typed views).  q, k columns through the
+    strict bf16 hi / lo product, v columns through fp16 (their fp16 conversions report to the range guard)."""
+    _range_check()
+    x = require_device_f32(x, "x")
+    C2, K = w_hi.shape
+    C = C2 // 2
+    if x.shape[-1] != K or tuple(w_lo.shape) != (C2, K) or tuple(w_v16.shape) != (C, K):
+        raise ValueError("qkv_split16: weight parts do not match each other or x")
+    for t_, name, dt in ((w_hi, "w_hi", torch.bfloat16), (w_lo, "w_lo", torch.bfloat16), (w_v16, "w_v16", torch.float16)):
+        if not t_.is_cuda or t_.dtype != dt or not t_.is_contiguous():
+            raise TypeError(f"qkv_split16: {name} must be a contiguous {dt} device tensor")
+    bias = _opt(bias, "bias")
+    M = x.numel() // K
+    y = torch.empty(*x.shape[:-1], 5 * C, dtype=torch.int16, device=x.device)
+    check(lib().mi355_qkv_split16_fwd(dptr(x), dptr(w_hi), dptr(w_lo), dptr(w_v16), dptr(bias), dptr(y), M, C, K, K,
+                                      stream_ptr(x.device)), "mi355_qkv_split16_fwd")
+    return y
+
+
+def qkv_split16_planes(qkv5):
+    """(q_hi, q_lo, k_hi, k_lo, v) typed views of a qkv_split16 result: four bfloat16 planes, one float16 plane, each (..., C)."""
+    C = qkv5.shape[-1] // 5
+    planes = [qkv5[..., i * C:(i + 1) * C] for i in range(5)]
+    return tuple(p_.view(torch.bfloat16) for p_ in planes[:4]) + (planes[4].view(torch.float16),)
+
+
+def sdpa16_split(qkv5, num_heads, scale):
+    """softmax(q k^T scale) v on a qkv_split16 result (B, N, 5C) -> (B, N, C) float16: Q K^T on the bf16 pairs, P V in fp16."""
+    if not qkv5.is_cuda or qkv5.dtype != torch.int16 or qkv5.dim() != 3:
+        raise TypeError("sdpa16_split: expected the (B, N, 5C) int16 device tensor qkv_split16 returns")
+    qkv5 = qkv5 if qkv5.is_contiguous() else qkv5.contiguous()
+    B, N, C5 = qkv5.shape
+    C = C5 // 5
+    out = torch.empty(B, N, C, dtype=torch.float16, device=qkv5.device)
+    check(lib().mi355_sdpa16_split_fwd(dptr(qkv5), dptr(out), B, N, int(num_heads), C // num_heads, float(scale),
+                                       stream_ptr(qkv5.device)), "mi355_sdpa16_split_fwd")
     return out
 
 

@@ -8,6 +8,11 @@
 
 Sub-modules hold parameters only (same creation order as the reference => same init stream under a seed).
 ``precision`` (None = package default) selects the MFMA operand format for every GEMM of the module.
+
+Precision 3 ("logit-compensated", F.PREC_LOGIT) is precision 1 with the logit path of `Attention` -- the q / k columns of the qkv
+projection, the stored q and k, Q K^T -- in the strict operand format (bf16 hi + lo, three MFMAs): the 16-bit error of the block that
+grows with the logit size is made there, the value path is scale-free (profiles/logit_mode.md).  Pick it for weights whose pre-softmax
+logits have a standard deviation above ~1, i.e. anything trained.  Everything outside `Attention` runs exactly as in precision 1.
 """
 import torch
 from torch import nn
@@ -80,7 +85,23 @@ class Attention(nn.Module):
                 F.sdpa(qkv, self.num_heads, self.scale, precision=self.precision)
         return F.sdpa_general(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], self.num_heads, self.scale, precision=self.precision)
 
+    def _forward_logit(self, x, resid):
+        """Precision 3: one projection launch that computes the q / k columns on bf16 hi / lo pairs and the v columns in fp16
+        (F.qkv_split16), the core with Q K^T on the pairs and P V in fp16 (F.sdpa16_split), then precision 1's fp16 proj GEMM with the
+        residual fused.  Outside those kernels' envelope (head width not 32 / 64, more than 224 tokens, in_features % 64 != 0) the block
+        runs its precision-0 path instead -- slower, never less accurate than asked."""
+        C = self.qkv.in_features
+        if not F.logit_envelope(C, C, self.num_heads, x.shape[-2]):
+            with F._forced_strict(self):
+                return self.forward(x, resid)
+        x = x if x.dtype == torch.float32 else x.float()
+        qkv5 = F.qkv_split16(x, *F.weight_split16(self.qkv.weight), _bias(self.qkv))                    # (B,N,5C)
+        ctx = F.sdpa16_split(qkv5, self.num_heads, self.scale)                                           # (B,N,C) fp16
+        return F.linear16(ctx, F.weight16(self.proj.weight, F.PREC_FP16), self.proj.bias, resid=resid, precision=F.PREC_FP16)
+
     def forward(self, x, resid=None):
+        if F.logit_mode(self.precision):
+            return self._forward_logit(x, resid)
         d = self.qkv.in_features // self.num_heads
         if d not in F.SDPA_WIDTHS:                                                           # odd head width: padded projections
             from .mhsa import _fused_qkv_attention
@@ -133,6 +154,11 @@ class TransformerEncoder(nn.Module):
 
     def forward_plain(self, x):
         """The default body: one LayerNorm launch in front of each half (the fold is opt-in: measured slower)."""
+        if F.logit_mode(self.attn.precision):
+            # precision 3: the projection kernel splits fp32 rows itself, so LayerNorm 1 stays fp32 (a 16-bit LayerNorm output would put
+            # the rounding the mode removes back in front of the q / k columns); the MLP half is precision 1's
+            x = self.attn(F.layernorm(x, self.layernorm1.weight, self.layernorm1.bias, self.layernorm1.eps), resid=x)
+            return self.mlp(self._norm(self.layernorm2, x, _fast(self.attn.precision, self.mlp.fc1, self.mlp.fc2)), resid=x)
         fast = self.attn.fast_ok(x.shape[1]) and _fast(self.attn.precision, self.mlp.fc1, self.mlp.fc2)
         x = self.attn(self._norm(self.layernorm1, x, fast), resid=x)
         return self.mlp(self._norm(self.layernorm2, x, fast), resid=x)
@@ -143,6 +169,8 @@ class TransformerEncoder(nn.Module):
         """The folded path applies: 16-bit dataflow, K/V-resident attention core, the producer kernel's shape envelope
         (rows % 128 == 0: B = 128, 256, ... at 197 tokens) and LayerNorm gains that keep gamma * W inside fp16."""
         if not F.ln_fold_enabled() or x.dim() != 3 or x.dtype != torch.float32 or not x.is_cuda:   # the option first: off by default
+            return False
+        if F.logit_mode(self.attn.precision):                   # the fold feeds the qkv GEMM 16-bit rows: not in precision 3
             return False
         B, N, C = x.shape
         p = F._prec(self.attn.precision)
