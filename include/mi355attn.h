@@ -257,6 +257,30 @@ int    mi355_cbam_fwd(const float* x, const float* w1, const float* w2, const fl
                       int B, int C, int Cr, int ks, int H, int W, int stage,
                       void* ws, size_t ws_bytes, mi355_stream_t stream);
 
+/* ---- the same three blocks on 16-bit activations (chan_io16.hip) ------------------------------------------------------------------
+ * x and y are NCHW in ONE 16-bit type selected by `io` (the precision codes: 1 = IEEE half, 2 = bfloat16); parameters stay fp32.
+ * All arithmetic is fp32 inside the kernels (pooling sums, excitation MLP, ECA taps, k x k conv, sigmoid, products); y is rounded once,
+ * to nearest even, at the store.  0 < gate < 1, so a finite product cannot overflow: these entries report nothing to
+ * mi355_range_status; inf / NaN in x propagate as in the reference.  Options "se_single" / "eca_single" / "cbam_single" choose between
+ * the single-read form (H*W % 8 == 0 and the fp32 kernels' other shape conditions; the row stays packed in registers, SE and CBAM use
+ * the fp32 kernels' granule exchange, workspace layout and error word) and a general pool / gate / scale form that takes any
+ * B, C, H, W >= 1.  "io16_occ" (2 .. 4, default 4) = workgroups per CU the single-read SE grid is sized for (capped by the register budget
+ * of the instantiation: four up to 1024 pixels per row, three up to 2048, two beyond).
+ * Validation (io, sizes, then pointers) precedes every HIP call: MI355_EINVAL with text in mi355_last_error. */
+
+/* SELayer on 16-bit x / y: arguments of mi355_se_fwd plus `io`.  Workspace: mi355_se_workspace_bytes applies. */
+int    mi355_se16_fwd(const void* x, const float* w1, const float* w2, void* y,
+                      int B, int C, int Cr, int H, int W, int io, void* ws, size_t ws_bytes, mi355_stream_t stream);
+/* ECALayer on 16-bit x / y: arguments of mi355_eca_fwd plus `io`.  Workspace: mi355_eca_workspace_bytes applies. */
+int    mi355_eca16_fwd(const void* x, const float* wconv, void* y,
+                       int B, int C, int k, int H, int W, int io, void* ws, size_t ws_bytes, mi355_stream_t stream);
+/* CBAM / ChannelAttention / SpatialAttention (stage 0 / 1 / 2) on 16-bit x / y: arguments of mi355_cbam_fwd plus `io`.  The workspace is
+ * the fp32 entry's plus one fp32 plane per image for the spatial gate of the general form: mi355_cbam16_workspace_bytes. */
+size_t mi355_cbam16_workspace_bytes(int B, int C, int H, int W);
+int    mi355_cbam16_fwd(const void* x, const float* w1, const float* w2, const float* wconv, void* y,
+                        int B, int C, int Cr, int ks, int H, int W, int stage, int io,
+                        void* ws, size_t ws_bytes, mi355_stream_t stream);
+
 /* DoubleAttention.forward  (attention_mechanisms/double_attention.py:32-48)
  *   wA (cm,C) bA (cm) | wB (cn,C) bB (cn) | wV (cn,C) bV (cn) | wP (C,cm) bP (C);  x,y (B,C,H,W). */
 size_t mi355_double_attn_workspace_bytes(int B, int C, int cm, int cn, int H, int W);

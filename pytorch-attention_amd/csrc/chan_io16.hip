@@ -1,0 +1,1088 @@
+// chan_io16.hip -- SELayer / ECALayer / CBAM on 16-bit activations (IEEE half or bfloat16 in, the same type out) for gfx950.
+//
+// x and y are NCHW in the I/O type, parameters are fp32, every piece of arithmetic (pooling sums, excitation MLP, ECA taps, k x k
+// conv, sigmoid, products) is fp32: the only rounding the path adds is the one store of y, to nearest even.  A finite product cannot
+// overflow (0 < gate < 1, so |y| <= |x|), hence no range report.
+// Range contract (tests/test_range_audit_cpu.py): this file converts fp32 to 16 bit but calls no rg_report and takes no range_word() on
+// purpose -- the converted values are OUTPUTS bounded by the 16-bit inputs, never MFMA operands that a larger fp32 value could saturate.
+//
+// Two forms per block:
+//   single read   the geometry and exchange protocols of chan_fused.hip / cbam_single.hip (8 channel rows per workgroup for SE / ECA,
+//                 a band of image rows of all channels for CBAM, kept in registers between pooling and scaling; SE and CBAM exchange
+//                 through the same tagged granules, ticket, epoch and error words), but the row stays PACKED in registers: 8 values per
+//                 16-byte load (SE / ECA), 4 per 8-byte load (CBAM) -- half the registers of the fp32 kernels, unpacked to fp32 only for
+//                 the sums and the products.
+//   general       any B, C, H, W >= 1: pool pass, gate kernel(s), scale pass; 16-byte lanes when H*W % 8 == 0 and the pointers allow,
+//                 2-byte lanes otherwise.  Correct everywhere, not tuned.
+#include "common.h"
+#include "bufops.h"
+
+namespace {
+
+typedef unsigned int u32;
+typedef unsigned short u16;
+typedef unsigned long long u64;
+typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+typedef u32 u32x2 __attribute__((ext_vector_type(2)));
+using v4f = float __attribute__((ext_vector_type(4)));
+typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+typedef __bf16 b2 __attribute__((ext_vector_type(2)));
+
+#define AGENT_RLX __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+
+// ---- packed 16-bit <-> fp32 (IO = 1: IEEE half, 2: bfloat16; the library's precision codes) -----------------------------------
+template <int IO> __device__ __forceinline__ float lo16(u32 w) {
+    if constexpr (IO == 1) return (float)__builtin_bit_cast(h2, w).x;
+    else return __uint_as_float(w << 16);
+}
+template <int IO> __device__ __forceinline__ float hi16(u32 w) {
+    if constexpr (IO == 1) return (float)__builtin_bit_cast(h2, w).y;
+    else return __uint_as_float(w & 0xffff0000u);
+}
+template <int IO> __device__ __forceinline__ u32 pack16(float a, float b) {          // round to nearest even, both halves
+    if constexpr (IO == 1) return __builtin_bit_cast(u32, h2{(_Float16)a, (_Float16)b});
+    else return __builtin_bit_cast(u32, b2{(__bf16)a, (__bf16)b});
+}
+template <int IO> __device__ __forceinline__ float from16(u16 h) {
+    if constexpr (IO == 1) return (float)__builtin_bit_cast(_Float16, h);
+    else return __uint_as_float((u32)h << 16);
+}
+template <int IO> __device__ __forceinline__ u16 to16(float v) {
+    if constexpr (IO == 1) return __builtin_bit_cast(u16, (_Float16)v);
+    else return __builtin_bit_cast(u16, (__bf16)v);
+}
+template <int IO> __device__ __forceinline__ v4f up4(u32x2 r) { return v4f{lo16<IO>(r.x), hi16<IO>(r.x), lo16<IO>(r.y), hi16<IO>(r.y)}; }
+template <int IO> __device__ __forceinline__ u32x2 down4(v4f v) { return u32x2{pack16<IO>(v.x, v.y), pack16<IO>(v.z, v.w)}; }
+// the 8 values of one 16-byte chunk into four running sums: ONE order for own rows and halo rows (ECA), so a mean does not depend on
+// which workgroup computes it
+template <int IO> __device__ __forceinline__ void add8(u32x4 r, float& s0, float& s1, float& s2, float& s3) {
+    s0 += lo16<IO>(r.x); s1 += hi16<IO>(r.x); s2 += lo16<IO>(r.y); s3 += hi16<IO>(r.y);
+    s0 += lo16<IO>(r.z); s1 += hi16<IO>(r.z); s2 += lo16<IO>(r.w); s3 += hi16<IO>(r.w);
+}
+template <int IO> __device__ __forceinline__ u32x4 scale8(u32x4 r, float g) {
+    return u32x4{pack16<IO>(lo16<IO>(r.x) * g, hi16<IO>(r.x) * g), pack16<IO>(lo16<IO>(r.y) * g, hi16<IO>(r.y) * g),
+                 pack16<IO>(lo16<IO>(r.z) * g, hi16<IO>(r.z) * g), pack16<IO>(lo16<IO>(r.w) * g, hi16<IO>(r.w) * g)};
+}
+
+constexpr int ECW = 8;          // channel rows per workgroup of the single-read SE / ECA kernels (chan_fused.hip)
+// Waves per SIMD the single-read kernels are compiled for (512 threads = 2 waves per SIMD and workgroup: 8 / 6 / 4 = four / three / two
+// workgroups per CU at <= 64 / 80 / 128 VGPRs), by 16-byte chunks per lane: the largest that compiles without scratch.  The packed row
+// of a 56 x 56 image (7 chunks) is 28 registers, but the SE kernel's scalar state sits at the SGPR limit and overflows into VGPRs, so
+// its long rows spill below 128.
+constexpr int se16_waves(int nv) { return nv <= 2 ? 8 : (nv <= 4 ? 6 : 4); }
+constexpr int eca16_waves(int nv) { return nv <= 4 ? 8 : (nv <= 7 ? 6 : 4); }
+
+// =====================================================================================================================================
+// single read: ECA (eca_halo_kernel of chan_fused.hip on packed rows; no exchange, halo rows re-summed)
+// =====================================================================================================================================
+template <int IO, int NV>
+__global__ __launch_bounds__(512, eca16_waves(NV)) void eca16_halo_kernel(const u16* __restrict__ x, const float* __restrict__ taps, u16* __restrict__ y,
+                                                           int C, int k, int HW, int gpi, int total, int per_xcd, int nts) {
+    __shared__ float s_mean[ECW + 8];                        // means of channels c0-pad .. c0+ECW+pad-1
+    const int s = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    if (s >= total) return;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int pad = (k - 1) >> 1;
+    const int b = s / gpi, c0 = (s - b * gpi) * ECW;
+    const float inv = 1.0f / (float)HW;
+    const u16* img = x + (long)b * C * HW;
+    const u32 cw = __builtin_amdgcn_readfirstlane((u32)(c0 + wave));
+    const rsrc_t rx = make_rsrc(img + (long)cw * HW, (u32)HW * 2u);   // lanes beyond the row read zeros, their stores are dropped
+    const u32 voff = (u32)lane * 16u;
+    u32x4 r[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) r[j] = __builtin_amdgcn_raw_buffer_load_b128(rx, voff, (u32)j * 1024u, 0);
+    int hc = -1, hslot = 0;
+    if (wave < 2 * pad) {
+        hc = (wave < pad) ? c0 - pad + wave : c0 + ECW + (wave - pad);
+        hslot = (wave < pad) ? wave : ECW + wave;
+    }
+    const bool halo_live = hc >= 0 && hc < C;                 // wave-uniform
+    float h0 = 0.f, h1 = 0.f, h2_ = 0.f, h3 = 0.f;
+    if (halo_live) {
+        const u32 hcw = __builtin_amdgcn_readfirstlane((u32)hc);
+        const rsrc_t rh = make_rsrc(img + (long)hcw * HW, (u32)HW * 2u);
+#pragma unroll
+        for (int j = 0; j < NV; ++j) add8<IO>(__builtin_amdgcn_raw_buffer_load_b128(rh, voff, (u32)j * 1024u, 0), h0, h1, h2_, h3);
+    }
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) add8<IO>(r[j], s0, s1, s2, s3);
+    const float mean = wave_sum_sw((s0 + s1) + (s2 + s3)) * inv;
+    if (lane == 0) s_mean[pad + wave] = mean;
+    if (wave < 2 * pad) {
+        const float hm = halo_live ? wave_sum_sw((h0 + h1) + (h2_ + h3)) * inv : 0.f;
+        if (lane == 0) s_mean[hslot] = hm;
+    }
+    __syncthreads();
+    float z = 0.f;
+    for (int j = 0; j < k; ++j) z += taps[j] * s_mean[wave + j];
+    const float g = sigmoidf_(z);
+    const rsrc_t ry = make_rsrc(y + ((long)b * C + cw) * HW, (u32)HW * 2u);
+    if (nts) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) __builtin_amdgcn_raw_buffer_store_b128(scale8<IO>(r[j], g), ry, voff, (u32)j * 1024u, AUX_NT);
+    } else {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) __builtin_amdgcn_raw_buffer_store_b128(scale8<IO>(r[j], g), ry, voff, (u32)j * 1024u, 0);
+    }
+}
+
+// =====================================================================================================================================
+// single read: SE (se_single_kernel of chan_fused.hip on packed rows; the same granules, ticket, epoch and error words)
+// =====================================================================================================================================
+struct Se16Args {
+    const u16* x; u16* y; const float* w1; const float* w2;
+    u64* gran; u32* ticket; u32* epoch; u32* err; u32* herr;
+    u32 spin;
+    int nts;
+    int C, Cr, HW, gpi, total;
+    float inv;
+};
+
+// How many workgroups per CU the launch uses is a grid size (option "io16_occ", capped by what se16_waves allows), not a template parameter.
+template <int IO, int NV, bool WLDS>
+__global__ __launch_bounds__(512, se16_waves(NV)) void se16_single_kernel(const Se16Args a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];      // p[C] | h[Cr] | (WLDS: W1[Cr*C] | W2[C*Cr])
+    __shared__ u32 s_tk[2];
+    __shared__ u32 s_ep;
+    __shared__ u32 s_ok[2][8];
+    float* s_p = smem;
+    float* s_h = smem + a.C;
+    float* s_w1 = s_h + a.Cr;
+    float* s_w2 = s_w1 + a.Cr * a.C;
+    const int t0 = threadIdx.x;
+    const float inv = a.inv;
+    const u32 last_draw = (u32)a.total + gridDim.x - 1u;              // the last draw of the launch resets the ticket and advances the epoch
+    auto draw = [&](u32 ep) -> u32 {
+        const u32 v = __hip_atomic_fetch_add(a.ticket, 1u, AGENT_RLX);
+        if (v == last_draw) {
+            __hip_atomic_store(a.ticket, 0u, AGENT_RLX);
+            __hip_atomic_store(a.epoch, ep + 1u, AGENT_RLX);
+        }
+        return v;
+    };
+    if (t0 == 0) {
+        // before the first draw (acquire): the epoch cannot move until this workgroup has drawn its stop ticket
+        const u32 ep = __hip_atomic_load(a.epoch, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+        s_ep = ep;
+        s_tk[0] = draw(ep);
+    }
+    if (WLDS) {
+        const int nw = a.Cr * a.C;
+        for (int i = t0; i < nw; i += 512) { s_w1[i] = a.w1[i]; s_w2[i] = a.w2[i]; }
+    }
+    __syncthreads();
+    const int C_ = a.C, Cr_ = a.Cr;
+    const u32 EP = __builtin_amdgcn_readfirstlane(s_ep);
+    const u32 GRAN_TAG = (EP + 1u) ? EP + 1u : 1u;                    // 0 is what a zeroed granule holds
+    int par = 0;
+    for (;;) {
+        __syncthreads();
+        const int t = threadIdx.x;
+        const int lane = t & 63, wave = t >> 6;
+        const u32 tk = __builtin_amdgcn_readfirstlane(s_tk[par]);
+        if (tk >= (u32)a.total) return;
+        const int b = tk / a.gpi, c0 = (tk - b * a.gpi) * ECW;
+        const u32 rw = __builtin_amdgcn_readfirstlane((u32)(b * C_ + c0 + wave));
+        const long row = (long)rw * a.HW;
+        const rsrc_t rx = make_rsrc(a.x + row, (u32)a.HW * 2u), ry = make_rsrc(a.y + row, (u32)a.HW * 2u);
+        const u32 voff = (u32)lane * 16u;                              // lanes beyond the row: zeros in, stores dropped (range check)
+        u32x4 r[NV];
+#pragma unroll
+        for (int j = 0; j < NV; ++j) r[j] = __builtin_amdgcn_raw_buffer_load_b128(rx, voff, (u32)j * 1024u, 0);
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) add8<IO>(r[j], s0, s1, s2, s3);
+        const float mean = wave_sum_sw((s0 + s1) + (s2 + s3)) * inv;
+        u64* gb = a.gran + (long)b * C_;
+        if (lane == 0)
+            __hip_atomic_store(gb + c0 + wave, ((u64)GRAN_TAG << 32) | (u64)__float_as_uint(mean), AGENT_RLX);
+
+        // sweep the image's granules until every tag is in (bounded by spin)
+        u32 spins = 0;
+        bool mine_done = false;                                        // C <= 512: one granule per thread; larger C loops
+        for (;;) {
+            bool ok = true;
+            if (C_ <= 512) {
+                if (t < C_ && !mine_done) {
+                    const u64 g = __hip_atomic_load(gb + (u32)t, AGENT_RLX);
+                    if ((u32)(g >> 32) == GRAN_TAG) { s_p[t] = __uint_as_float((u32)g); mine_done = true; }
+                    else ok = false;
+                }
+            } else {
+                for (int cc = t; cc < C_; cc += 512) {
+                    const u64 g = __hip_atomic_load(gb + cc, AGENT_RLX);
+                    if ((u32)(g >> 32) == GRAN_TAG) s_p[cc] = __uint_as_float((u32)g);
+                    else ok = false;
+                }
+            }
+            // workgroup-wide AND in one barrier: a ballot per wave, eight votes through LDS, two vote rows used alternately
+            const int vp = (int)(spins & 1u);
+            const bool wave_ok = __builtin_amdgcn_ballot_w64(!ok) == 0ull;
+            if ((t & 63) == 0) s_ok[vp][t >> 6] = wave_ok ? 1u : 0u;
+            __syncthreads();
+            const u32 votes = s_ok[vp][0] & s_ok[vp][1] & s_ok[vp][2] & s_ok[vp][3] & s_ok[vp][4] & s_ok[vp][5] & s_ok[vp][6] & s_ok[vp][7];
+            if (__builtin_amdgcn_readfirstlane(votes)) break;
+            __builtin_amdgcn_s_sleep(2);
+            if (++spins > a.spin) {
+                if (t == 0) {
+                    __hip_atomic_store(a.err, 1u, AGENT_RLX);
+                    if (a.herr) __hip_atomic_store(a.herr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                }
+                break;
+            }
+        }
+        // next slice's ticket: only now, when this workgroup no longer waits for anybody
+        if (t == 0) s_tk[par ^ 1] = draw(EP);
+        // excitation: h = relu(W1 p) (16 lanes per hidden unit), g = sigmoid(W2[c,:] h) (one wave per channel)
+        const float* w1 = WLDS ? s_w1 : a.w1;
+        const float* w2 = WLDS ? s_w2 : a.w2;
+        const int part = t & 15, jl = t >> 4;
+        for (int j0 = 0; j0 < Cr_; j0 += 32) {
+            const int j = j0 + jl;
+            float acc = 0.f;
+            if (j < Cr_) {
+                const float* wrow = w1 + (long)j * C_;
+                for (int cc = part; cc < C_; cc += 16) acc += wrow[cc] * s_p[cc];
+            }
+            acc += __shfl_xor(acc, 8, WAVE);
+            acc += __shfl_xor(acc, 4, WAVE);
+            acc += __shfl_xor(acc, 2, WAVE);
+            acc += __shfl_xor(acc, 1, WAVE);
+            if (part == 0 && j < Cr_) s_h[j] = relu_nan(acc);
+        }
+        __syncthreads();
+        const float* w2r = w2 + (long)(c0 + wave) * Cr_;
+        float z = 0.f;
+        for (int j = lane; j < Cr_; j += 64) z += w2r[j] * s_h[j];
+        const float g = sigmoidf_(wave_sum_sw(z));
+        if (a.nts) {
+#pragma unroll
+            for (int j = 0; j < NV; ++j) __builtin_amdgcn_raw_buffer_store_b128(scale8<IO>(r[j], g), ry, voff, (u32)j * 1024u, AUX_NT);
+        } else {
+#pragma unroll
+            for (int j = 0; j < NV; ++j) __builtin_amdgcn_raw_buffer_store_b128(scale8<IO>(r[j], g), ry, voff, (u32)j * 1024u, 0);
+        }
+        par ^= 1;
+    }
+}
+
+template <int IO, int NV>
+static void se16_go(bool wlds, int grid, size_t smem, hipStream_t st, const Se16Args& a) {
+    if (wlds) se16_single_kernel<IO, NV, true><<<grid, 512, smem, st>>>(a);
+    else      se16_single_kernel<IO, NV, false><<<grid, 512, smem, st>>>(a);
+}
+template <int IO>
+static void se16_go_nv(int nv, bool wlds, int grid, size_t smem, hipStream_t st, const Se16Args& a) {
+    if (nv <= 1) se16_go<IO, 1>(wlds, grid, smem, st, a);
+    else if (nv <= 2) se16_go<IO, 2>(wlds, grid, smem, st, a);
+    else if (nv <= 4) se16_go<IO, 4>(wlds, grid, smem, st, a);
+    else if (nv <= 7) se16_go<IO, 7>(wlds, grid, smem, st, a);
+    else se16_go<IO, 8>(wlds, grid, smem, st, a);
+}
+
+// =====================================================================================================================================
+// single read: CBAM (cbam_single_kernel of cbam_single.hip; a lane holds 4 pixels of a channel's band as ONE 8-byte register pair)
+// =====================================================================================================================================
+__device__ __forceinline__ void gran_put(rsrc_t g, u32 idx, float v0, float v1, u32 TAG) {
+    const u32x4 v = {__float_as_uint(v0), TAG, __float_as_uint(v1), TAG};
+    __builtin_amdgcn_raw_buffer_store_b128(v, g, idx * 16u, 0, AUX_SC1);      // one write-through 16-byte store
+}
+__device__ __forceinline__ bool gran_get(rsrc_t g, u32 idx, float& v0, float& v1, u32 TAG) {
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(g, idx * 16u, 0, AUX_SC1);
+    v0 = __uint_as_float(v.x);
+    v1 = __uint_as_float(v.z);
+    return v.y == TAG && v.w == TAG;
+}
+template <int CTRL>
+__device__ __forceinline__ float dpp(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float rdlane(float v, int lane) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
+}
+// sum / max over the SEG (16 or 32) lanes of a segment; the result is only guaranteed in the segment's lane 0 (fixed order)
+template <int SEG>
+__device__ __forceinline__ void seg_reduce(float& s, float& m, int lane) {
+    s += dpp<0xB1>(s);  m = fmaxf(m, dpp<0xB1>(m));                   // xor 1
+    s += dpp<0x4E>(s);  m = fmaxf(m, dpp<0x4E>(m));                   // xor 2
+    s += dpp<0x124>(s); m = fmaxf(m, dpp<0x124>(m));                  // row_ror 4
+    s += dpp<0x128>(s); m = fmaxf(m, dpp<0x128>(m));                  // row_ror 8
+    if (SEG == 32) {
+        const float s1 = rdlane(s, 16), s3 = rdlane(s, 48), m1 = rdlane(m, 16), m3 = rdlane(m, 48);
+        s += (lane < 32) ? s1 : s3;
+        m = fmaxf(m, (lane < 32) ? m1 : m3);
+    }
+}
+
+struct Cbam16Args {
+    const u16* x; u16* y; const float* w1; const float* w2; const float* wconv;
+    u32x4* g1; u32x4* g2; u32x4* g3; u32* ticket; u32* epoch; u32* err; u32* herr;
+    u32 spin;
+    int C, Cr, H, W, ks, R, Q, NB, cpb, total, nts, wlds;
+};
+
+template <int IO, int SEG, int NV, bool FULL>
+__global__ __launch_bounds__(512, 4) void cbam16_single_kernel(const Cbam16Args a) {
+    constexpr int NT = 512, CL = NT / SEG;                            // channel groups (segments) per workgroup
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ u32 s_tk[2];
+    __shared__ u32 s_ep;
+    const int C = a.C, Cr = a.Cr, W = a.W, H = a.H, ks = a.ks, pad = (ks - 1) >> 1;
+    const int HW = H * W, npx = a.R * W, TW = W + 2 * pad, TH = a.R + 2 * pad;
+    const int Cp = (CL * NV > C ? CL * NV : ((C + 3) & ~3)), Crp = (Cr + 3) & ~3, L2p = (a.NB * a.cpb + 3) & ~3;
+    float* s_a = smem;                                                // avg[C]
+    float* s_m = s_a + Cp;                                            // max[C]
+    float* s_gc = s_m + Cp;                                           // channel gates [C]
+    float* s_h = s_gc + Cp;                                           // hidden: relu(W1 avg)[Crp] | relu(W1 max)[Crp]
+    float* s_l2s = s_h + 2 * Crp;                                     // hop-1 landing: sums [NB*cpb]
+    float* s_l2m = s_l2s + L2p;                                       //                maxima
+    float* s_ps = s_l2m + L2p;                                        // per-group pixel partial sums [CL][SEG*4]
+    float* s_pm = s_ps + CL * SEG * 4;                                // per-group pixel partial maxima
+    float* s_t = s_pm + CL * SEG * 4;                                 // statistics tile [2][TH][TW], zero border
+    float* s_gs = s_t + ((2 * TH * TW + 3) & ~3);                     // spatial gate of the band [SEG*4 >= npx]
+    float* s_wc = s_gs + SEG * 4;                                     // conv taps [2*ks*ks (pad 4)]
+    float* s_w1 = s_wc + ((2 * ks * ks + 3) & ~3);                    // (wlds) W1 [Cr*C] | W2 [C*Cr]
+    float* s_w2 = s_w1 + Cr * C;
+
+    const int t = threadIdx.x, q = t & (SEG - 1), cl = t / SEG;
+    const bool qa = q < a.Q;
+    const u32 last_draw = (u32)a.total + gridDim.x - 1u;
+    auto draw = [&](u32 ep) -> u32 {
+        const u32 v = __hip_atomic_fetch_add(a.ticket, 1u, AGENT_RLX);
+        if (v == last_draw) {
+            __hip_atomic_store(a.ticket, 0u, AGENT_RLX);
+            __hip_atomic_store(a.epoch, ep + 1u, AGENT_RLX);
+        }
+        return v;
+    };
+    if (t == 0) {
+        const u32 ep = __hip_atomic_load(a.epoch, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+        s_ep = ep;
+        s_tk[0] = draw(ep);
+    }
+    for (int i = t; i < 2 * ks * ks; i += NT) s_wc[i] = a.wconv[i];
+    if (a.wlds)
+        for (int i = t; i < Cr * C; i += NT) { s_w1[i] = a.w1[i]; s_w2[i] = a.w2[i]; }
+    const float* w1 = a.wlds ? s_w1 : a.w1;
+    const float* w2 = a.wlds ? s_w2 : a.w2;
+    __syncthreads();
+    const u32 EP = s_ep;
+    const u32 TAG = (EP + 1u) ? EP + 1u : 1u;                         // 0 is what a zeroed granule holds
+    int par = 0;
+
+    for (;;) {
+        __syncthreads();
+        const u32 tk = s_tk[par];
+        if (tk >= (u32)a.total) return;
+        const int b = tk / a.NB, band = tk - b * a.NB, r0 = band * a.R;
+        const long img = (long)b * C * HW + (long)r0 * W;
+        u32 spins = 0;
+        bool timeout = false;
+
+        // ---- the band of every channel -> registers (packed) -----------------------------------------------------------------
+        u32x2 r[NV];
+        const u32 ext = ((u32)C * (u32)HW - (u32)r0 * (u32)W) * 2u;                  // bytes from the band start to the image end
+        const rsrc_t rx = make_rsrc(a.x + img, ext), ry = make_rsrc(a.y + img, ext);
+        const u32 off0 = qa ? ((u32)cl * (u32)HW + 4u * (u32)q) * 2u : OOB, offs = (u32)CL * (u32)HW * 2u;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            if (FULL) r[j] = __builtin_amdgcn_raw_buffer_load_b64(rx, off0, (u32)j * offs, 0);
+            else r[j] = __builtin_amdgcn_raw_buffer_load_b64(rx, (cl + CL * j < C) ? off0 + (u32)j * offs : OOB, 0, 0);
+        }
+        const rsrc_t rg1 = make_rsrc(a.g1 + (long)b * a.NB * C, (u32)a.NB * (u32)C * 16u);
+        const rsrc_t rg2 = make_rsrc(a.g2 + (long)b * C, (u32)C * 16u);
+        const rsrc_t rg3 = make_rsrc(a.g3 + (long)b * HW, (u32)HW * 16u);
+        for (int i = t; i < 2 * TH * TW; i += NT) s_t[i] = 0.f;
+
+        // ---- hop 1, publish: (sum, max) of this band for every channel ------------------------------------------------------
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c = cl + CL * j;
+            const v4f v = up4<IO>(r[j]);
+            float s = (v.x + v.y) + (v.z + v.w);
+            float m = qa ? fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)) : -INFINITY;
+            seg_reduce<SEG>(s, m, t & 63);
+            if (q == 0 && c < C) gran_put(rg1, (u32)(band * C + c), s, m, TAG);
+        }
+        // ---- hop 1, consume: this band adds up channels ck0 .. ck0+nch-1 over all bands, publishes (avg, max) as hop 2 ------
+        const int ck0 = band * a.cpb;
+        const int nch = (ck0 >= C) ? 0 : ((C - ck0 < a.cpb) ? C - ck0 : a.cpb);
+        const int n1 = a.NB * nch;
+        for (;;) {
+            bool ok = true;
+            for (int i = t; i < n1; i += NT) {
+                const int bb = i / nch, cc = i - bb * nch;
+                float v0, v1;
+                if (gran_get(rg1, (u32)(bb * C + ck0 + cc), v0, v1, TAG)) { s_l2s[bb * a.cpb + cc] = v0; s_l2m[bb * a.cpb + cc] = v1; }
+                else ok = false;
+            }
+            if (__syncthreads_and(ok)) break;
+            __builtin_amdgcn_s_sleep(2);
+            if (++spins > a.spin) { timeout = true; break; }
+        }
+        if (t < nch) {
+            float s = 0.f, m = -INFINITY;
+            for (int bb = 0; bb < a.NB; ++bb) { s += s_l2s[bb * a.cpb + t]; m = fmaxf(m, s_l2m[bb * a.cpb + t]); }
+            gran_put(rg2, (u32)(ck0 + t), s / (float)HW, m, TAG);
+        }
+        // ---- hop 2, consume: (avg, max) of every channel of the image ---------------------------------------------------------
+        for (;;) {
+            bool ok = true;
+            for (int c = t; c < C; c += NT) {
+                float v0, v1;
+                if (gran_get(rg2, (u32)c, v0, v1, TAG)) { s_a[c] = v0; s_m[c] = v1; }
+                else ok = false;
+            }
+            if (__syncthreads_and(ok)) break;
+            __builtin_amdgcn_s_sleep(2);
+            if (++spins > a.spin) { timeout = true; break; }
+        }
+        // ---- channel gates: gc = sigmoid(W2 (relu(W1 avg) + relu(W1 max))) ----------------------------------------------------
+        {
+            const int half = t / (NT / 2), tt = t & (NT / 2 - 1), part = tt & 15, jl = tt >> 4;
+            const float* vec = half ? s_m : s_a;
+            float* s_hh = s_h + half * Crp;
+            for (int j0 = 0; j0 < Cr; j0 += NT / 32) {
+                const int j = j0 + jl;
+                float h0 = 0.f, h1 = 0.f;
+                if (j < Cr) {
+                    const float* wrow = w1 + (long)j * C;
+                    int cc = part;
+                    for (; cc + 16 < C; cc += 32) { h0 += wrow[cc] * vec[cc]; h1 += wrow[cc + 16] * vec[cc + 16]; }
+                    if (cc < C) h0 += wrow[cc] * vec[cc];
+                }
+                float h = h0 + h1;
+                h += dpp<0xB1>(h); h += dpp<0x4E>(h); h += dpp<0x124>(h); h += dpp<0x128>(h);
+                if (part == 0 && j < Cr) s_hh[j] = relu_nan(h);
+            }
+            __syncthreads();
+            for (int c = t; c < C; c += NT) {
+                const float* w2r = w2 + (long)c * Cr;
+                float z0 = 0.f, z1 = 0.f;
+                int j = 0;
+                for (; j + 1 < Cr; j += 2) {
+                    z0 += w2r[j] * (s_h[j] + s_h[Crp + j]);
+                    z1 += w2r[j + 1] * (s_h[j + 1] + s_h[Crp + j + 1]);
+                }
+                if (j < Cr) z0 += w2r[j] * (s_h[j] + s_h[Crp + j]);
+                s_gc[c] = sigmoidf_(z0 + z1);
+            }
+            __syncthreads();
+        }
+        // ---- per-pixel statistics of x' = x * gc over the channels -------------------------------------------------------------
+        {
+            v4f ps = {0.f, 0.f, 0.f, 0.f}, pm = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                const int c = cl + CL * j;
+                if (FULL || c < C) {
+                    const v4f v = up4<IO>(r[j]) * s_gc[c];
+                    ps += v;
+                    pm.x = fmaxf(pm.x, v.x); pm.y = fmaxf(pm.y, v.y); pm.z = fmaxf(pm.z, v.z); pm.w = fmaxf(pm.w, v.w);
+                }
+            }
+            reinterpret_cast<v4f*>(s_ps)[cl * SEG + q] = ps;
+            reinterpret_cast<v4f*>(s_pm)[cl * SEG + q] = pm;
+        }
+        __syncthreads();
+        if (t < npx) {
+            float s = 0.f, m = -INFINITY;
+#pragma unroll 4
+            for (int g = 0; g < CL; ++g) { s += s_ps[g * SEG * 4 + t]; m = fmaxf(m, s_pm[g * SEG * 4 + t]); }
+            s = s / (float)C;
+            const int ty = t / W, tx = t - ty * W;
+            s_t[(0 * TH + ty + pad) * TW + tx + pad] = s;
+            s_t[(1 * TH + ty + pad) * TW + tx + pad] = m;
+            gran_put(rg3, (u32)(r0 * W + t), s, m, TAG);                                  // hop 3, publish
+        }
+        // ---- hop 3, consume: halo rows of the neighbouring bands ------------------------------------------------------------------
+        {
+            const int up = (r0 < pad) ? r0 : pad;
+            const int dn = (H - (r0 + a.R) < pad) ? H - (r0 + a.R) : pad;
+            const int n3 = (up + dn) * W;
+            for (;;) {
+                bool ok = true;
+                for (int i = t; i < n3; i += NT) {
+                    const int hr = i / W, tx = i - hr * W;
+                    const int gy = (hr < up) ? r0 - up + hr : r0 + a.R + (hr - up);
+                    float v0, v1;
+                    if (gran_get(rg3, (u32)(gy * W + tx), v0, v1, TAG)) {
+                        const int ty = gy - r0 + pad;
+                        s_t[(0 * TH + ty) * TW + tx + pad] = v0;
+                        s_t[(1 * TH + ty) * TW + tx + pad] = v1;
+                    } else ok = false;
+                }
+                if (__syncthreads_and(ok)) break;
+                __builtin_amdgcn_s_sleep(2);
+                if (++spins > a.spin) { timeout = true; break; }
+            }
+        }
+        // nobody is waited for any more: take the next ticket (hidden behind the conv and the stores)
+        u32 next_tk = 0;
+        if (t == 0) {
+            next_tk = draw(EP);
+            if (timeout) {
+                __hip_atomic_store(a.err, 1u, AGENT_RLX);
+                if (a.herr) __hip_atomic_store(a.herr, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
+        // ---- spatial gate of the band: sigmoid(conv_ks x ks([mean, max])) -------------------------------------------------------
+        {
+            const int p = t >> 2, part = t & 3;
+            float acc = 0.f;
+            if (p < npx) {
+                const int ty = p / W, tx = p - ty * W;
+                for (int rr = part; rr < 2 * ks; rr += 4) {
+                    const int ch = rr / ks, dy = rr - ch * ks;
+                    const float* trow = s_t + (ch * TH + ty + dy) * TW + tx;
+                    const float* wrow = s_wc + rr * ks;
+                    float a0 = 0.f, a1 = 0.f;
+                    int dx = 0;
+                    for (; dx + 1 < ks; dx += 2) { a0 += wrow[dx] * trow[dx]; a1 += wrow[dx + 1] * trow[dx + 1]; }
+                    if (dx < ks) a0 += wrow[dx] * trow[dx];
+                    acc += a0 + a1;
+                }
+            }
+            acc += dpp<0xB1>(acc);
+            acc += dpp<0x4E>(acc);
+            if (p < npx && part == 0) s_gs[p] = sigmoidf_(acc);
+        }
+        __syncthreads();
+        // ---- y = (x * gc) * gs from registers, rounded once ------------------------------------------------------------------------
+        {
+            const v4f s4 = reinterpret_cast<const v4f*>(s_gs)[q & (SEG - 1)];       // lanes beyond the band: stores are dropped (OOB)
+            u32 ob = off0;
+            asm volatile("" : "+v"(ob));
+            if (a.nts) {
+#pragma unroll
+                for (int j = 0; j < NV; ++j) {
+                    const v4f v = (up4<IO>(r[j]) * s_gc[cl + CL * j]) * s4;
+                    const u32 vo = (FULL || cl + CL * j < C) ? ob + (u32)j * offs : OOB;
+                    __builtin_amdgcn_raw_buffer_store_b64(down4<IO>(v), ry, vo, 0, AUX_NT);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < NV; ++j) {
+                    const v4f v = (up4<IO>(r[j]) * s_gc[cl + CL * j]) * s4;
+                    const u32 vo = (FULL || cl + CL * j < C) ? ob + (u32)j * offs : OOB;
+                    __builtin_amdgcn_raw_buffer_store_b64(down4<IO>(v), ry, vo, 0, 0);
+                }
+            }
+        }
+        if (t == 0) s_tk[par ^ 1] = next_tk;
+        par ^= 1;
+    }
+}
+
+struct Geo {
+    int R, Q, NB, SEG, CL, NV, cpb;
+    size_t smem_base, smem_w;
+};
+
+// rows per band: the most pixels per band with R | H, (R*W) % 4 == 0 (8-byte lanes) and R*W <= 128 (four conv lanes per pixel)
+int band_rows(int H, int W) {
+    int best = 0;
+    for (int R = 1; R <= H; ++R) {
+        if (H % R || (R * W) % 4 || R * W > 128) continue;
+        best = R;
+    }
+    return best;
+}
+
+bool geometry(int C, int Cr, int H, int W, int ks, Geo& g) {
+    if (!(ks & 1) || ks > 15) return false;
+    const int best = band_rows(H, W);
+    if (!best) return false;
+    g.R = best;
+    g.Q = best * W / 4;
+    g.NB = H / best;
+    g.SEG = g.Q > 16 ? 32 : 16;
+    g.CL = 512 / g.SEG;
+    const int nv = (C + g.CL - 1) / g.CL;
+    if (nv > 16) return false;
+    g.NV = nv <= 4 ? 4 : (nv <= 8 ? 8 : 16);
+    g.cpb = (C + g.NB - 1) / g.NB;
+    const int pad = (ks - 1) / 2, TW = W + 2 * pad, TH = best + 2 * pad;
+    auto r4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
+    const size_t Cp = (size_t)g.CL * g.NV > (size_t)C ? (size_t)g.CL * g.NV : r4(C);
+    g.smem_base = (3 * Cp + 2 * r4(Cr) + 2 * r4((size_t)g.NB * g.cpb) + 2 * (size_t)g.CL * g.SEG * 4 +
+                   r4(2 * (size_t)TH * TW) + (size_t)g.SEG * 4 + r4(2 * (size_t)ks * ks)) * 4;
+    g.smem_w = 2 * (size_t)C * Cr * 4;
+    if (g.NV == 16 && C != g.CL * g.NV) return false;   // 16 partly filled register pairs per lane spill at 128 VGPRs: the general form takes these
+    return g.smem_base <= 40 * 1024;
+}
+
+// =====================================================================================================================================
+// general form: pool pass -> gate kernel(s) -> scale pass
+// =====================================================================================================================================
+// one wave per (b, c) row, four rows per workgroup: avg[row] = sum / HW, mx[row] = max (CBAM)
+template <int IO, bool WITH_MAX, bool VEC>
+__global__ __launch_bounds__(256) void pool16_kernel(const u16* __restrict__ x, float* __restrict__ avg, float* __restrict__ mx, long rows,
+                                                    int HW) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long row = (long)blockIdx.x * 4 + wave;
+    if (row >= rows) return;
+    const u16* p = x + row * HW;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, m = -INFINITY;
+    if constexpr (VEC) {
+        const u32x4* p8 = reinterpret_cast<const u32x4*>(p);
+        const int n8 = HW >> 3;
+        for (int i = lane; i < n8; i += 64) {
+            const u32x4 v = p8[i];
+            add8<IO>(v, s0, s1, s2, s3);
+            if constexpr (WITH_MAX) {
+                m = fmaxf(m, fmaxf(fmaxf(fmaxf(lo16<IO>(v.x), hi16<IO>(v.x)), fmaxf(lo16<IO>(v.y), hi16<IO>(v.y))),
+                                   fmaxf(fmaxf(lo16<IO>(v.z), hi16<IO>(v.z)), fmaxf(lo16<IO>(v.w), hi16<IO>(v.w)))));
+            }
+        }
+    } else {
+        for (int i = lane; i < HW; i += 64) {
+            const float v = from16<IO>(p[i]);
+            s0 += v;
+            if constexpr (WITH_MAX) m = fmaxf(m, v);
+        }
+    }
+    const float s = wave_sum((s0 + s1) + (s2 + s3));
+    if constexpr (WITH_MAX) m = wave_max(m);
+    if (lane == 0) {
+        avg[row] = s / (float)HW;
+        if constexpr (WITH_MAX) mx[row] = m;
+    }
+}
+
+__device__ __forceinline__ float dot16(const float* __restrict__ wrow, const float* s_p, int C, int part) {
+    float acc = 0.f;
+    for (int c = part; c < C; c += 16) acc += wrow[c] * s_p[c];
+    acc += __shfl_xor(acc, 8, WAVE);
+    acc += __shfl_xor(acc, 4, WAVE);
+    acc += __shfl_xor(acc, 2, WAVE);
+    acc += __shfl_xor(acc, 1, WAVE);
+    return acc;
+}
+
+// Gates of one image from its pooled vectors, IN PLACE over avg (the whole image is read into LDS before the first gate is written).
+//   MODE 0 SE:   g = sigmoid(W2 relu(W1 avg))      MODE 1 ECA: g_c = sigmoid(sum_j w[j] avg[c + j - pad]) (Cr = k)
+//   MODE 2 CBAM: g = sigmoid(W2 (relu(W1 avg) + relu(W1 max)))
+// smem: a[C] | m[C] | h[Cr]
+template <int MODE>
+__global__ __launch_bounds__(256) void chan_gates16_kernel(float* __restrict__ avg, const float* __restrict__ mx, const float* __restrict__ wa,
+                                                          const float* __restrict__ wb, int C, int Cr) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* s_a = smem;
+    float* s_m = smem + C;
+    float* s_h = s_m + C;
+    const int t = threadIdx.x;
+    float* ab = avg + (long)blockIdx.x * C;
+    for (int c = t; c < C; c += 256) {
+        s_a[c] = ab[c];
+        if (MODE == 2) s_m[c] = mx[(long)blockIdx.x * C + c];
+    }
+    __syncthreads();
+    if constexpr (MODE == 1) {
+        const int k = Cr, pad = (k - 1) / 2;
+        for (int c = t; c < C; c += 256) {
+            float z = 0.f;
+            for (int j = 0; j < k; ++j) {
+                const int cc = c + j - pad;
+                if (cc >= 0 && cc < C) z += wa[j] * s_a[cc];
+            }
+            ab[c] = sigmoidf_(z);
+        }
+    } else {
+        const int part = t & 15, jl = t >> 4;
+        for (int j0 = 0; j0 < Cr; j0 += 16) {
+            const int j = j0 + jl;
+            float ha = 0.f, hm = 0.f;
+            if (j < Cr) {
+                ha = dot16(wa + (long)j * C, s_a, C, part);
+                if (MODE == 2) hm = dot16(wa + (long)j * C, s_m, C, part);
+            }
+            if (part == 0 && j < Cr) s_h[j] = (MODE == 2) ? relu_nan(ha) + relu_nan(hm) : relu_nan(ha);
+        }
+        __syncthreads();
+        for (int c = t; c < C; c += 256) {
+            const float* w2r = wb + (long)c * Cr;
+            float z = 0.f;
+            for (int j = 0; j < Cr; ++j) z += w2r[j] * s_h[j];
+            ab[c] = sigmoidf_(z);
+        }
+    }
+}
+
+// per-pixel statistics over the channels of x' = x * gc (gc may be null): smap[b,0,p] = mean_c, smap[b,1,p] = max_c; a thread per pixel
+template <int IO>
+__global__ __launch_bounds__(256) void cbam16_stats_kernel(const u16* __restrict__ x, const float* __restrict__ gc, float* __restrict__ smap,
+                                                          int C, int HW, int tiles) {
+    const int b = blockIdx.x / tiles, p = (blockIdx.x % tiles) * 256 + threadIdx.x;
+    if (p >= HW) return;
+    const u16* xb = x + (long)b * C * HW + p;
+    float s = 0.f, m = -INFINITY;
+    for (int c = 0; c < C; ++c) {
+        const float v = from16<IO>(xb[(long)c * HW]) * (gc ? gc[(long)b * C + c] : 1.0f);
+        s += v;
+        m = fmaxf(m, v);
+    }
+    smap[((long)b * 2 + 0) * HW + p] = s / (float)C;
+    smap[((long)b * 2 + 1) * HW + p] = m;
+}
+
+// gs[b,p] = sigmoid(conv_ks x ks(smap[b]))  (2 -> 1 channels, zero pad ks / 2, no bias, cross-correlation); a thread per pixel
+__global__ __launch_bounds__(256) void cbam16_sgate_kernel(const float* __restrict__ smap, const float* __restrict__ wconv, float* __restrict__ gs,
+                                                          int H, int W, int ks, int tiles) {
+    const int HW = H * W, pad = ks / 2;
+    const int b = blockIdx.x / tiles, p = (blockIdx.x % tiles) * 256 + threadIdx.x;
+    if (p >= HW) return;
+    const int py = p / W, px = p - py * W;
+    float acc = 0.f;
+    for (int ch = 0; ch < 2; ++ch) {
+        const float* sb = smap + ((long)b * 2 + ch) * HW;
+        for (int dy = 0; dy < ks; ++dy) {
+            const int gy = py + dy - pad;
+            if (gy < 0 || gy >= H) continue;
+            for (int dx = 0; dx < ks; ++dx) {
+                const int gx = px + dx - pad;
+                if (gx >= 0 && gx < W) acc += wconv[(ch * ks + dy) * ks + dx] * sb[gy * W + gx];
+            }
+        }
+    }
+    gs[(long)b * HW + p] = sigmoidf_(acc);
+}
+
+// y[row, i] = round((x[row, i] * gc[row]) * gs[b, i]); gc / gs may be null (= 1).  One wave per row, four rows per workgroup.
+template <int IO, bool VEC>
+__global__ __launch_bounds__(256) void scale16_kernel(const u16* __restrict__ x, const float* __restrict__ gc, const float* __restrict__ gs,
+                                                     u16* __restrict__ y, long rows, int C, int HW, int nts) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long row = (long)blockIdx.x * 4 + wave;
+    if (row >= rows) return;
+    const float g = gc ? gc[row] : 1.0f;
+    const float* gsb = gs ? gs + (row / C) * HW : nullptr;
+    const u16* xr = x + row * HW;
+    u16* yr = y + row * HW;
+    if constexpr (VEC) {
+        const u32x4* x8 = reinterpret_cast<const u32x4*>(xr);
+        u32x4* y8 = reinterpret_cast<u32x4*>(yr);
+        const int n8 = HW >> 3;
+        for (int i = lane; i < n8; i += 64) {
+            const u32x4 v = x8[i];
+            v4f a = v4f{lo16<IO>(v.x), hi16<IO>(v.x), lo16<IO>(v.y), hi16<IO>(v.y)} * g;
+            v4f c = v4f{lo16<IO>(v.z), hi16<IO>(v.z), lo16<IO>(v.w), hi16<IO>(v.w)} * g;
+            if (gsb) {
+                a = a * reinterpret_cast<const v4f*>(gsb)[2 * i];
+                c = c * reinterpret_cast<const v4f*>(gsb)[2 * i + 1];
+            }
+            const u32x4 o = {pack16<IO>(a.x, a.y), pack16<IO>(a.z, a.w), pack16<IO>(c.x, c.y), pack16<IO>(c.z, c.w)};
+            if (nts) __builtin_nontemporal_store(o, &y8[i]);
+            else y8[i] = o;
+        }
+    } else {
+        for (int i = lane; i < HW; i += 64) {
+            float v = from16<IO>(xr[i]) * g;
+            if (gsb) v = v * gsb[i];
+            yr[i] = to16<IO>(v);
+        }
+    }
+}
+
+inline size_t r16(size_t n) { return (n + 15) & ~(size_t)15; }
+inline size_t pooled_bytes(int B, int C) { return r16((size_t)B * C * sizeof(float)); }
+inline size_t cbam_multipass_bytes(int B, int C, int H, int W) { return 2 * r16((size_t)B * C * 4) + r16((size_t)B * 2 * H * W * 4); }
+
+#define BY_IO(io, CALL) do { if ((io) == 1) { CALL(1); } else { CALL(2); } } while (0)
+
+// ---- single-read launchers ------------------------------------------------------------------------------------------------------------
+bool eca16_single_ok(int C, int k, int H, int W) {
+    const long HW = (long)H * W;
+    return mi355::opt_eca_single() && (HW % 8 == 0) && (HW / 8 <= 8 * 64) && (C % ECW == 0) && (k - 1 <= 8) && (k & 1);
+}
+
+int eca16_single(const u16* x, const float* taps, u16* y, int B, int C, int k, int H, int W, int io, hipStream_t st) {
+    const int HW = H * W, n8 = HW / 8, gpi = C / ECW;
+    const long total_l = (long)B * gpi;
+    if (total_l > (1L << 30)) return mi355::fail(MI355_EUNSUPPORTED, "eca16_single: too many slices");
+    const int total = (int)total_l, per_xcd = (total + 7) / 8, grid = per_xcd * 8;
+    const int nv = (n8 + 63) / 64;
+    const int nts = (mi355::opt_nt() & 2) ? 1 : 0;
+    MI355_TRACE(st, "eca16_halo_kernel io=%d C=%d HW=%d", io, C, HW);
+#define GO(IO_, NV_) eca16_halo_kernel<IO_, NV_><<<grid, 512, 0, st>>>(x, taps, y, C, k, HW, gpi, total, per_xcd, nts)
+#define GO_IO(IO_)                      \
+    do {                                \
+        if (nv <= 1) GO(IO_, 1);        \
+        else if (nv <= 2) GO(IO_, 2);   \
+        else if (nv <= 4) GO(IO_, 4);   \
+        else if (nv <= 7) GO(IO_, 7);   \
+        else GO(IO_, 8);                \
+    } while (0)
+    BY_IO(io, GO_IO);
+#undef GO_IO
+#undef GO
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return mi355::fail(MI355_EHIP, "eca16_single: launch -> %s", hipGetErrorString(e));
+    return MI355_OK;
+}
+
+bool se16_single_ok(int C, int Cr, int H, int W) {
+    const long HW = (long)H * W;
+    // every slice of an image (C / 8 workgroups) has to be resident at the same time: two workgroups per CU are resident in every
+    // configuration (<= 128 VGPRs, <= 60 KB of LDS)
+    return mi355::opt_se_single() && (HW % 8 == 0) && (HW / 8 <= 8 * 64) && (C % ECW == 0) && ((size_t)(C + Cr) * 4 <= 48 * 1024) &&
+           C / ECW <= mi355::resident_slots(2);
+}
+
+// `state` = epoch | (B - 1 unused words) | ticket | err (fused_state_bytes), `gran` = B*C granules: the layout of the fp32 kernel
+int se16_single(const u16* x, const float* w1, const float* w2, u16* y, int B, int C, int Cr, int H, int W, int io, void* state, void* gran,
+                hipStream_t st) {
+    Se16Args a{};
+    a.x = x; a.y = y; a.w1 = w1; a.w2 = w2;
+    a.gran = static_cast<u64*>(gran);
+    a.ticket = static_cast<u32*>(state) + B;
+    a.epoch = static_cast<u32*>(state);
+    a.err = a.ticket + 1;
+    a.herr = mi355::sync_err_word_on(st); a.spin = mi355::spin_limit();
+    if (int rc = mi355::sync_pending("se16_single")) return rc;
+    a.C = C; a.Cr = Cr; a.HW = H * W; a.gpi = C / ECW;
+    a.inv = 1.0f / (float)a.HW;
+    a.nts = (mi355::opt_nt() & 2) ? 1 : 0;
+    const long total_l = (long)B * a.gpi;
+    if (total_l > (1L << 30)) return mi355::fail(MI355_EUNSUPPORTED, "se16_single: too many slices");
+    a.total = (int)total_l;
+    const bool wlds = (size_t)(C + Cr + 2 * (size_t)C * Cr) * sizeof(float) <= 60 * 1024;   // both weight matrices resident in LDS
+    const size_t smem = ((size_t)C + Cr + (wlds ? 2 * (size_t)C * Cr : 0)) * sizeof(float);
+    const int nv = (a.HW / 8 + 63) / 64;
+    int occ = (int)mi355::opt_io16_occ();                 // workgroups per CU the grid is sized for: 2 .. 4, as far as registers and LDS allow
+    if (occ > se16_waves(nv <= 1 ? 1 : nv <= 2 ? 2 : nv <= 4 ? 4 : nv <= 7 ? 7 : 8) / 2) occ = se16_waves(nv <= 1 ? 1 : nv <= 2 ? 2 : nv <= 4 ? 4 : nv <= 7 ? 7 : 8) / 2;
+    while (occ > 2 && smem * occ > 150 * 1024) --occ;
+    long grid = (long)mi355::resident_slots(occ);
+    if (a.gpi > (long)mi355::resident_slots(2))
+        return mi355::fail(MI355_EUNSUPPORTED, "se16_single: an image needs %d resident workgroups, the device holds %d", a.gpi, mi355::resident_slots(2));
+    if (grid > a.total) grid = a.total;
+    const unsigned long long key = ((unsigned long long)B << 32) ^ (unsigned long long)C ^ ((unsigned long long)grid << 44) ^ 0x5E16000000000000ull;
+    hipError_t e = hipSuccess;
+    if (!mi355::ws_known(state, key, st)) {               // unknown history: epoch, ticket, granules (contiguous)
+        e = mi355::ws_zero_async(state, mi355::fused_state_bytes(B) + mi355::se_single_extra_bytes(B, C), st);
+        if (e != hipSuccess) { mi355::ws_forget(state); return mi355::fail(MI355_EHIP, "se16_single: zeroing -> %s", hipGetErrorString(e)); }
+    }
+    {
+        MI355_TRACE(st, "se16_single_kernel io=%d C=%d HW=%d", io, C, a.HW);
+        if (io == 1) se16_go_nv<1>(nv, wlds, (int)grid, smem, st, a);
+        else         se16_go_nv<2>(nv, wlds, (int)grid, smem, st, a);
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) { mi355::ws_forget(state); return mi355::fail(MI355_EHIP, "se16_single: launch -> %s", hipGetErrorString(e)); }
+    return MI355_OK;
+}
+
+bool cbam16_single_ok(int C, int Cr, int H, int W, int ks) {
+    Geo g;
+    // all NB bands of an image must be resident together (two workgroups per CU); the exchange area is the fp32 kernel's
+    return mi355::opt_cbam_single() && geometry(C, Cr, H, W, ks, g) && g.NB <= mi355::resident_slots(2) &&
+           mi355::cbam_single_extra_bytes(1, C, H, W) != 0;
+}
+
+int cbam16_single(const u16* x, const float* w1, const float* w2, const float* wconv, u16* y, int B, int C, int Cr, int H, int W, int ks, int io,
+                  void* extra, hipStream_t st) {
+    Geo g;
+    if (!geometry(C, Cr, H, W, ks, g)) return mi355::fail(MI355_EUNSUPPORTED, "cbam16_single: unsupported shape");
+    Cbam16Args a{};
+    a.x = x; a.y = y; a.w1 = w1; a.w2 = w2; a.wconv = wconv;
+    a.g1 = static_cast<u32x4*>(extra);
+    a.g2 = a.g1 + (size_t)B * g.NB * C;
+    a.g3 = a.g2 + (size_t)B * C;
+    a.ticket = reinterpret_cast<u32*>(a.g3 + (size_t)B * H * W);
+    a.err = a.ticket + 1;
+    a.epoch = a.ticket + 2;
+    a.herr = mi355::sync_err_word_on(st); a.spin = mi355::spin_limit();
+    if (int rc = mi355::sync_pending("cbam16_single")) return rc;
+    a.C = C; a.Cr = Cr; a.H = H; a.W = W; a.ks = ks; a.R = g.R; a.Q = g.Q; a.NB = g.NB; a.cpb = g.cpb;
+    const long total_l = (long)B * g.NB;
+    if (total_l > (1L << 30)) return mi355::fail(MI355_EUNSUPPORTED, "cbam16_single: too many slices");
+    a.total = (int)total_l;
+    a.nts = (mi355::opt_nt() & 2) ? 1 : 0;
+    const bool full = (C == g.CL * g.NV);
+    a.wlds = (g.smem_base + g.smem_w <= (size_t)(120 * 1024) / 2) ? 1 : 0;
+    const size_t smem = g.smem_base + (a.wlds ? g.smem_w : 0);
+    long grid = (long)mi355::resident_slots(2);
+    if (g.NB > grid) return mi355::fail(MI355_EUNSUPPORTED, "cbam16_single: an image needs %d resident workgroups, the device holds %ld", g.NB, grid);
+    if (grid > a.total) grid = a.total;
+    const size_t extra_bytes = ((size_t)B * g.NB * C + (size_t)B * C + (size_t)B * H * W) * 16 + 16;
+    const unsigned long long key = ((unsigned long long)B << 48) ^ ((unsigned long long)C << 32) ^ ((unsigned long long)H << 16) ^ (unsigned long long)W ^ 0xCB16000000000000ull;
+    if (!mi355::ws_known(extra, key, st)) {
+        hipError_t e = mi355::ws_zero_async(extra, extra_bytes, st);
+        if (e != hipSuccess) { mi355::ws_forget(extra); return mi355::fail(MI355_EHIP, "cbam16_single: zeroing -> %s", hipGetErrorString(e)); }
+    }
+    {
+        MI355_TRACE(st, "cbam16_single_kernel io=%d C=%d H=%d W=%d", io, C, H, W);
+#define GO(IO_, SEG_, NV_)                                                                         \
+    do {                                                                                           \
+        if (full) cbam16_single_kernel<IO_, SEG_, NV_, true><<<(int)grid, 512, smem, st>>>(a);     \
+        else      cbam16_single_kernel<IO_, SEG_, NV_, false><<<(int)grid, 512, smem, st>>>(a);    \
+    } while (0)
+#define GO_IO(IO_)                                 \
+    do {                                           \
+        if (g.SEG == 32) {                         \
+            if (g.NV == 4) GO(IO_, 32, 4);         \
+            else if (g.NV == 8) GO(IO_, 32, 8);    \
+            else cbam16_single_kernel<IO_, 32, 16, true><<<(int)grid, 512, smem, st>>>(a);  \
+        } else {                                   \
+            if (g.NV == 4) GO(IO_, 16, 4);         \
+            else if (g.NV == 8) GO(IO_, 16, 8);    \
+            else cbam16_single_kernel<IO_, 16, 16, true><<<(int)grid, 512, smem, st>>>(a);  \
+        }                                          \
+    } while (0)
+        BY_IO(io, GO_IO);
+#undef GO_IO
+#undef GO
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { mi355::ws_forget(extra); return mi355::fail(MI355_EHIP, "cbam16_single: launch -> %s", hipGetErrorString(e)); }
+    return MI355_OK;
+}
+
+// ---- general-form launchers ------------------------------------------------------------------------------------------------------------
+template <int IO>
+void pool16(bool with_max, bool vec, const u16* x, float* avg, float* mx, long rows, int HW, hipStream_t st) {
+    const int grid = cdiv(rows, 4);
+    MI355_TRACE(st, "pool16_kernel io=%d HW=%d", IO, HW);
+    if (with_max) {
+        if (vec) pool16_kernel<IO, true, true><<<grid, 256, 0, st>>>(x, avg, mx, rows, HW);
+        else     pool16_kernel<IO, true, false><<<grid, 256, 0, st>>>(x, avg, mx, rows, HW);
+    } else {
+        if (vec) pool16_kernel<IO, false, true><<<grid, 256, 0, st>>>(x, avg, mx, rows, HW);
+        else     pool16_kernel<IO, false, false><<<grid, 256, 0, st>>>(x, avg, mx, rows, HW);
+    }
+}
+template <int IO>
+void scale16(bool vec, const u16* x, const float* gc, const float* gs, u16* y, long rows, int C, int HW, hipStream_t st) {
+    const int grid = cdiv(rows, 4);
+    const int nts = (mi355::opt_nt() & 2) ? 1 : 0;
+    MI355_TRACE(st, "scale16_kernel io=%d HW=%d", IO, HW);
+    if (vec) scale16_kernel<IO, true><<<grid, 256, 0, st>>>(x, gc, gs, y, rows, C, HW, nts);
+    else     scale16_kernel<IO, false><<<grid, 256, 0, st>>>(x, gc, gs, y, rows, C, HW, nts);
+}
+
+bool check_io16(int io, long B, long C, long H, long W) {
+    // element counts stay in 32-bit grid and row arithmetic
+    return (io == 1 || io == 2) && B * C <= (1L << 31) - 8 && H * W <= (1L << 30);
+}
+
+}  // namespace
+
+// =======================================================================================================================================
+// C ABI
+// =======================================================================================================================================
+extern "C" {
+
+size_t mi355_cbam16_workspace_bytes(int B, int C, int H, int W) {
+    return mi355_cbam_workspace_bytes(B, C, H, W) + r16((size_t)B * H * W * sizeof(float));
+}
+
+// mode 0: SE (wa = w1, wb = w2, Cr), mode 1: ECA (wa = taps, Cr = k)
+static int se_eca16(int mode, const void* xv, const float* wa, const float* wb, void* yv, int B, int C, int Cr, int H, int W, int io, void* ws,
+                    hipStream_t st) {
+    const u16* x = static_cast<const u16*>(xv);
+    u16* y = static_cast<u16*>(yv);
+    const int HW = H * W;
+    const bool vec = (HW % 8 == 0) && aligned16(x) && aligned16(y);
+    const size_t smem = (size_t)(2 * (size_t)C + (mode == 0 ? Cr : 0)) * sizeof(float);
+    if (smem > 64 * 1024) return mi355::fail(MI355_EUNSUPPORTED, "channel count %d too large for the gate stage", C);
+    if (mode == 0 && vec && se16_single_ok(C, Cr, H, W)) {
+        char* state = static_cast<char*>(ws) + pooled_bytes(B, C);
+        return se16_single(x, wa, wb, y, B, C, Cr, H, W, io, state, state + mi355::fused_state_bytes(B), st);
+    }
+    if (mode == 1 && vec && eca16_single_ok(C, Cr, H, W)) return eca16_single(x, wa, y, B, C, Cr, H, W, io, st);
+    float* pooled = static_cast<float*>(ws);
+    const long rows = (long)B * C;
+    if (io == 1) pool16<1>(false, vec, x, pooled, nullptr, rows, HW, st);
+    else         pool16<2>(false, vec, x, pooled, nullptr, rows, HW, st);
+    {
+        MI355_TRACE(st, "chan_gates16_kernel mode=%d C=%d", mode, C);
+        if (smem > 48 * 1024) {
+            const void* fn = mode == 0 ? (const void*)chan_gates16_kernel<0> : (const void*)chan_gates16_kernel<1>;
+            if (int rc = mi355::func_dynamic_lds(fn, (int)smem)) return rc;
+        }
+        if (mode == 0) chan_gates16_kernel<0><<<B, 256, smem, st>>>(pooled, nullptr, wa, wb, C, Cr);
+        else           chan_gates16_kernel<1><<<B, 256, smem, st>>>(pooled, nullptr, wa, nullptr, C, Cr);
+    }
+    if (io == 1) scale16<1>(vec, x, pooled, nullptr, y, rows, C, HW, st);
+    else         scale16<2>(vec, x, pooled, nullptr, y, rows, C, HW, st);
+    MI355_LAUNCH_CHECK();
+    return MI355_OK;
+}
+
+int mi355_se16_fwd(const void* x, const float* w1, const float* w2, void* y, int B, int C, int Cr, int H, int W, int io, void* ws,
+                   size_t ws_bytes, mi355_stream_t stream) {
+    MI355_CHECK_ARG(io == 1 || io == 2);
+    MI355_CHECK_ARG(B > 0 && C > 0 && Cr > 0 && H > 0 && W > 0);
+    MI355_CHECK_ARG(x && w1 && w2 && y && ws);
+    MI355_CHECK_ARG(check_io16(io, B, C, H, W));
+    MI355_CHECK_ARG(ws_bytes >= mi355_se_workspace_bytes(B, C, H, W));
+    return se_eca16(0, x, w1, w2, y, B, C, Cr, H, W, io, ws, static_cast<hipStream_t>(stream));
+}
+
+int mi355_eca16_fwd(const void* x, const float* wconv, void* y, int B, int C, int k, int H, int W, int io, void* ws, size_t ws_bytes,
+                    mi355_stream_t stream) {
+    MI355_CHECK_ARG(io == 1 || io == 2);
+    MI355_CHECK_ARG(B > 0 && C > 0 && k > 0 && (k & 1) && H > 0 && W > 0);
+    MI355_CHECK_ARG(x && wconv && y && ws);
+    MI355_CHECK_ARG(check_io16(io, B, C, H, W));
+    MI355_CHECK_ARG(ws_bytes >= mi355_eca_workspace_bytes(B, C, H, W));
+    return se_eca16(1, x, wconv, nullptr, y, B, C, k, H, W, io, ws, static_cast<hipStream_t>(stream));
+}
+
+int mi355_cbam16_fwd(const void* xv, const float* w1, const float* w2, const float* wconv, void* yv, int B, int C, int Cr, int ks, int H, int W,
+                     int stage, int io, void* ws, size_t ws_bytes, mi355_stream_t stream) {
+    MI355_CHECK_ARG(io == 1 || io == 2);
+    MI355_CHECK_ARG(stage >= 0 && stage <= 2);
+    MI355_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0);
+    MI355_CHECK_ARG(xv && yv && ws);
+    const bool do_c = stage != 2, do_s = stage != 1;
+    if (do_c) MI355_CHECK_ARG(w1 && w2 && Cr > 0);
+    if (do_s) MI355_CHECK_ARG(wconv && ks > 0 && (ks & 1));
+    MI355_CHECK_ARG(check_io16(io, B, C, H, W));
+    MI355_CHECK_ARG(ws_bytes >= mi355_cbam16_workspace_bytes(B, C, H, W));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const u16* x = static_cast<const u16*>(xv);
+    u16* y = static_cast<u16*>(yv);
+    char* wsp = static_cast<char*>(ws);
+    if (stage == 0 && aligned16(x) && aligned16(y) && cbam16_single_ok(C, Cr, H, W, ks))                  // x read once
+        return cbam16_single(x, w1, w2, wconv, y, B, C, Cr, H, W, ks, io, wsp + cbam_multipass_bytes(B, C, H, W), st);
+    const int HW = H * W;
+    const bool vec = (HW % 8 == 0) && aligned16(x) && aligned16(y);
+    const size_t bc = r16((size_t)B * C * 4);
+    float* avg = reinterpret_cast<float*>(wsp);                           // becomes the channel gates in place
+    float* mx = reinterpret_cast<float*>(wsp + bc);
+    float* smap = reinterpret_cast<float*>(wsp + 2 * bc);
+    float* gs = reinterpret_cast<float*>(wsp + mi355_cbam_workspace_bytes(B, C, H, W));
+    const long rows = (long)B * C;
+    const int tiles = cdiv(HW, 256);
+    if ((long)B * tiles > (1L << 31) - 1) return mi355::fail(MI355_EUNSUPPORTED, "mi355_cbam16_fwd: too many pixel tiles");
+    if (do_c) {
+        const size_t smem = (size_t)(2 * (size_t)C + Cr) * sizeof(float);
+        if (smem > 64 * 1024) return mi355::fail(MI355_EUNSUPPORTED, "channel count %d too large for the gate stage", C);
+        if (io == 1) pool16<1>(true, vec, x, avg, mx, rows, HW, st);
+        else         pool16<2>(true, vec, x, avg, mx, rows, HW, st);
+        MI355_TRACE(st, "chan_gates16_kernel mode=2 C=%d", C);
+        if (smem > 48 * 1024)
+            if (int rc = mi355::func_dynamic_lds((const void*)chan_gates16_kernel<2>, (int)smem)) return rc;
+        chan_gates16_kernel<2><<<B, 256, smem, st>>>(avg, mx, w1, w2, C, Cr);
+    }
+    if (do_s) {
+        {
+            MI355_TRACE(st, "cbam16_stats_kernel io=%d C=%d HW=%d", io, C, HW);
+            if (io == 1) cbam16_stats_kernel<1><<<B * tiles, 256, 0, st>>>(x, do_c ? avg : nullptr, smap, C, HW, tiles);
+            else         cbam16_stats_kernel<2><<<B * tiles, 256, 0, st>>>(x, do_c ? avg : nullptr, smap, C, HW, tiles);
+        }
+        {
+            MI355_TRACE(st, "cbam16_sgate_kernel ks=%d HW=%d", ks, HW);
+            cbam16_sgate_kernel<<<B * tiles, 256, 0, st>>>(smap, wconv, gs, H, W, ks, tiles);
+        }
+    }
+    if (io == 1) scale16<1>(vec, x, do_c ? avg : nullptr, do_s ? gs : nullptr, y, rows, C, HW, st);
+    else         scale16<2>(vec, x, do_c ? avg : nullptr, do_s ? gs : nullptr, y, rows, C, HW, st);
+    MI355_LAUNCH_CHECK();
+    return MI355_OK;
+}
+
+}  // extern "C"

@@ -24,6 +24,7 @@ long  opt_da_ranges();
 long  opt_eca_single();
 long  opt_se_single();
 long  opt_se_occ();
+long  opt_io16_occ();
 long  opt_ws_persistent();
 long  opt_ln_fold();
 long  opt_gemm_pa16();

@@ -51,6 +51,10 @@ SIGNATURES = {
     "mi355_eca_fwd": (c_int, [c_vp, c_vp, c_vp] + [c_int] * 5 + [c_vp, c_size, c_vp]),
     "mi355_cbam_workspace_bytes": (c_size, [c_int] * 4),
     "mi355_cbam_fwd": (c_int, [c_vp] * 5 + [c_int] * 7 + [c_vp, c_size, c_vp]),
+    "mi355_se16_fwd": (c_int, [c_vp, c_vp, c_vp, c_vp] + [c_int] * 6 + [c_vp, c_size, c_vp]),
+    "mi355_eca16_fwd": (c_int, [c_vp, c_vp, c_vp] + [c_int] * 6 + [c_vp, c_size, c_vp]),
+    "mi355_cbam16_workspace_bytes": (c_size, [c_int] * 4),
+    "mi355_cbam16_fwd": (c_int, [c_vp] * 5 + [c_int] * 8 + [c_vp, c_size, c_vp]),
     "mi355_double_attn_workspace_bytes": (c_size, [c_int] * 6),
     "mi355_double_attn_ws_bytes": (c_size, [c_int] * 7),
     "mi355_double_attn_fwd": (c_int, [c_vp] * 10 + [c_int] * 7 + [c_vp, c_size, c_vp]),
@@ -220,10 +224,26 @@ def require_device_f32(t, name):
             f"{name} lives on {t.device}: the mi355attn modules only run on an MI355X device tensor "
             "(move the module and its input to 'cuda'); there is no CPU path in this package.")
     if t.dtype != torch.float32:
-        raise TypeError(f"{name}: expected float32, got {t.dtype}")
+        raise TypeError(f"{name}: expected float32, got {t.dtype} (16-bit activations are accepted by SELayer, ECALayer, CBAM, "
+                        "ChannelAttention and SpatialAttention only)")
     if t.requires_grad and torch.is_grad_enabled():
         _warn_no_autograd()
     return t if t.is_contiguous() else t.contiguous()
+
+
+IO_CODES = {torch.float16: 1, torch.bfloat16: 2}      # the `io` argument of the mi355_*16_fwd channel-attention entries (precision codes)
+
+
+def require_device_io(t, name):
+    """Activation of the channel-attention family: a dense device tensor in fp32, fp16 or bf16.  Returns (tensor, io) with io = 0 for
+    fp32 (the fp32 entries) or the precision code of the 16-bit type."""
+    if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in IO_CODES:
+        if t.requires_grad and torch.is_grad_enabled():
+            _warn_no_autograd()
+        return (t if t.is_contiguous() else t.contiguous()), IO_CODES[t.dtype]
+    if isinstance(t, torch.Tensor) and not t.is_cuda and t.dtype in IO_CODES:
+        t = t.new_empty(0, dtype=torch.float32)           # the device check of the fp32 path raises the package's own error
+    return require_device_f32(t, name), 0
 
 
 _warned_autograd = False

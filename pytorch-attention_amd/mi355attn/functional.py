@@ -192,6 +192,9 @@ def range_fallback_forward(module, forward, args, kwargs):
     absorb this forward's report nor run strict because of it."""
     if _guard.depth:
         return forward(module, *args, **kwargs)
+    if args and isinstance(args[0], torch.Tensor) and args[0].dtype in _ffi.IO_CODES:
+        # 16-bit activations (SELayer / ECALayer / CBAM): fp32 arithmetic and |y| <= |x|, nothing can saturate -- no arm, no wait, no re-run
+        return forward(module, *args, **kwargs)
     try:
         passthrough = _ffi._capturing() or lib().mi355_get_option(b"range_fallback") != 1
     except RuntimeError:                                      # no HIP device in this process: the forward raises the package's own error
@@ -255,20 +258,35 @@ def _sync_check():
     sync_status(wait=os.environ.get("MI355_CHECK_SYNC") == "1")
 
 
+def param32(param, name):
+    """fp32 view of a parameter of the channel-attention family.  fp32 parameters (the autocast case) are used as they are; after
+    module.half() / .bfloat16() the 16-bit parameter is converted once and the copy is reused until the parameter is modified in place
+    (version bump), moved or collected -- the cache of weight16, in the other direction."""
+    if not isinstance(param, torch.Tensor) or param.dtype not in _ffi.IO_CODES or not param.is_cuda:
+        return require_device_f32(param, name)
+    tag = (param._version, param.data_ptr(), tuple(param.shape))
+    return _derived_get((param,), ("w32",), tag, lambda: param.detach().float().contiguous())
+
+
 def se_forward(x, w1, w2):
-    """SELayer forward: x (B,C,H,W), w1 (C/r,C), w2 (C,C/r)."""
-    x = require_device_f32(x, "x")
-    w1 = require_device_f32(w1, "fc.0.weight")
-    w2 = require_device_f32(w2, "fc.2.weight")
+    """SELayer forward: x (B,C,H,W) fp32 / fp16 / bf16 (output in the same type), w1 (C/r,C), w2 (C,C/r)."""
+    x, io = _ffi.require_device_io(x, "x")
+    w1 = param32(w1, "fc.0.weight")
+    w2 = param32(w2, "fc.2.weight")
     B, C, H, W = x.shape
     Cr = w1.shape[0]
     if tuple(w1.shape) != (Cr, C) or tuple(w2.shape) != (C, Cr):
         raise ValueError(f"SE weight shapes {tuple(w1.shape)}, {tuple(w2.shape)} do not match C={C}")
     y = torch.empty_like(x)
     n = lib().mi355_se_workspace_bytes(B, C, H, W)
-    ws = _ffi.workspace_dedicated(("se", B, C, H, W), n, x.device)
-    check(lib().mi355_se_fwd(dptr(x), dptr(w1), dptr(w2), dptr(y), B, C, Cr, H, W, dptr(ws), ws.numel(),
-                             stream_ptr(x.device)), "mi355_se_fwd")
+    if io:
+        ws = _ffi.workspace_dedicated(("se16", io, B, C, H, W), n, x.device)
+        check(lib().mi355_se16_fwd(dptr(x), dptr(w1), dptr(w2), dptr(y), B, C, Cr, H, W, io, dptr(ws), ws.numel(),
+                                   stream_ptr(x.device)), "mi355_se16_fwd")
+    else:
+        ws = _ffi.workspace_dedicated(("se", B, C, H, W), n, x.device)
+        check(lib().mi355_se_fwd(dptr(x), dptr(w1), dptr(w2), dptr(y), B, C, Cr, H, W, dptr(ws), ws.numel(),
+                                 stream_ptr(x.device)), "mi355_se_fwd")
     _sync_check()
     return y
 
@@ -447,41 +465,51 @@ def se_ex_forward(x, w1, b1, w2, b2, gate="sigmoid"):
 
 
 def eca_forward(x, wconv):
-    """ECALayer forward: x (B,C,H,W), wconv (1,1,k) or (k,)."""
-    x = require_device_f32(x, "x")
-    wconv = require_device_f32(wconv, "conv.weight").reshape(-1)
+    """ECALayer forward: x (B,C,H,W) fp32 / fp16 / bf16 (output in the same type), wconv (1,1,k) or (k,)."""
+    x, io = _ffi.require_device_io(x, "x")
+    wconv = param32(wconv, "conv.weight").reshape(-1)
     B, C, H, W = x.shape
     k = wconv.numel()
     y = torch.empty_like(x)
     n = lib().mi355_eca_workspace_bytes(B, C, H, W)
     ws = workspace(n, x.device)
-    check(lib().mi355_eca_fwd(dptr(x), dptr(wconv), dptr(y), B, C, k, H, W, dptr(ws), ws.numel(),
-                              stream_ptr(x.device)), "mi355_eca_fwd")
+    if io:
+        check(lib().mi355_eca16_fwd(dptr(x), dptr(wconv), dptr(y), B, C, k, H, W, io, dptr(ws), ws.numel(),
+                                    stream_ptr(x.device)), "mi355_eca16_fwd")
+    else:
+        check(lib().mi355_eca_fwd(dptr(x), dptr(wconv), dptr(y), B, C, k, H, W, dptr(ws), ws.numel(),
+                                  stream_ptr(x.device)), "mi355_eca_fwd")
     return y
 
 
 def cbam_forward(x, w1=None, w2=None, wconv=None, stage=0):
-    """CBAM forward (stage 0), ChannelAttention alone (1) or SpatialAttention alone (2)."""
-    x = require_device_f32(x, "x")
+    """CBAM forward (stage 0), ChannelAttention alone (1) or SpatialAttention alone (2); x fp32 / fp16 / bf16, output in the same type."""
+    x, io = _ffi.require_device_io(x, "x")
     B, C, H, W = x.shape
     Cr, ks = 0, 0
     if stage != 2:
-        w1 = require_device_f32(w1, "ca.fc.0.weight").reshape(w1.shape[0], -1)
-        w2 = require_device_f32(w2, "ca.fc.2.weight").reshape(w2.shape[0], -1)
+        w1 = param32(w1, "ca.fc.0.weight").reshape(w1.shape[0], -1)
+        w2 = param32(w2, "ca.fc.2.weight").reshape(w2.shape[0], -1)
         Cr = w1.shape[0]
         if tuple(w1.shape) != (Cr, C) or tuple(w2.shape) != (C, Cr):
             raise ValueError(f"CBAM channel weight shapes {tuple(w1.shape)}, {tuple(w2.shape)} do not match C={C}")
     if stage != 1:
-        wconv = require_device_f32(wconv, "sa.conv.weight")
+        wconv = param32(wconv, "sa.conv.weight")
         ks = wconv.shape[-1]
         if wconv.numel() != 2 * ks * ks:
             raise ValueError(f"CBAM spatial conv weight must be (1,2,k,k), got {tuple(wconv.shape)}")
     y = torch.empty_like(x)
-    n = lib().mi355_cbam_workspace_bytes(B, C, H, W)
-    ws = _ffi.workspace_dedicated(("cbam", B, C, H, W), n, x.device) if stage == 0 else workspace(n, x.device)
-    check(lib().mi355_cbam_fwd(dptr(x), dptr(w1 if stage != 2 else None), dptr(w2 if stage != 2 else None),
-                               dptr(wconv if stage != 1 else None), dptr(y), B, C, Cr, ks, H, W, stage,
-                               dptr(ws), ws.numel(), stream_ptr(x.device)), "mi355_cbam_fwd")
+    ptrs = (dptr(w1 if stage != 2 else None), dptr(w2 if stage != 2 else None), dptr(wconv if stage != 1 else None))
+    if io:
+        n = lib().mi355_cbam16_workspace_bytes(B, C, H, W)
+        ws = _ffi.workspace_dedicated(("cbam16", io, B, C, H, W), n, x.device) if stage == 0 else workspace(n, x.device)
+        check(lib().mi355_cbam16_fwd(dptr(x), *ptrs, dptr(y), B, C, Cr, ks, H, W, stage, io, dptr(ws), ws.numel(),
+                                     stream_ptr(x.device)), "mi355_cbam16_fwd")
+    else:
+        n = lib().mi355_cbam_workspace_bytes(B, C, H, W)
+        ws = _ffi.workspace_dedicated(("cbam", B, C, H, W), n, x.device) if stage == 0 else workspace(n, x.device)
+        check(lib().mi355_cbam_fwd(dptr(x), *ptrs, dptr(y), B, C, Cr, ks, H, W, stage, dptr(ws), ws.numel(),
+                                   stream_ptr(x.device)), "mi355_cbam_fwd")
     if stage == 0:
         _sync_check()
     return y

@@ -1,0 +1,99 @@
+#!/usr/bin/env python
+"""Time SELayer / ECALayer / CBAM on 16-bit activations against the fp32 kernels and against the cast-around a user had to write before.
+
+    python tools/io16_bench.py [--shape 256 256 56 56] [--rounds 9] [--iters 20] [--json out.json]
+
+One process, one device, all variants interleaved round by round (a round times every variant once, `iters` calls between two events),
+so drift hits every variant alike.  Per block and I/O type:
+    row 1   m(x16)                          the 16-bit kernels, single-read form where the shape allows   4 B / element
+    row 1g  m(x16), *_single options off    the 16-bit general form (pool, gates, scale)                  (reads x twice or three times)
+    row 2   m(x32)                          the fp32 kernels on the fp32 copy of the same tensor          8 B / element
+    row 3   m(x16.float()).to(x16.dtype)    what a user wrote before this path existed                    20 B / element
+Prints a markdown table (median, min .. max over the rounds, achieved GB/s at the row's algorithmic bytes) and one JSON line."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "pytorch-attention_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import torch  # noqa: E402
+
+BYTES = {"1": 4, "1g": 4, "2": 8, "3": 20}
+SINGLE_OPTS = ("se_single", "eca_single", "cbam_single")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shape", type=int, nargs=4, default=[256, 256, 56, 56])
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    import mi355attn
+    from mi355attn.modules import CBAM, ECALayer, SELayer
+    B, C, H, W = a.shape
+    n = B * C * H * W
+    torch.manual_seed(1234)
+    mods = {"SE": SELayer(C).eval().cuda(), "ECA": ECALayer(C).eval().cuda(), "CBAM": CBAM(C).eval().cuda()}
+    torch.manual_seed(4321)
+    x32 = torch.randn(B, C, H, W, device="cuda")
+    xs = {torch.float16: x32.half(), torch.bfloat16: x32.bfloat16()}
+
+    def general(m, x):
+        old = {k: mi355attn.get_option(k) for k in SINGLE_OPTS}
+        for k in SINGLE_OPTS:
+            mi355attn.set_option(k, 0)
+        try:
+            return m(x)
+        finally:
+            for k, v in old.items():
+                mi355attn.set_option(k, v)
+
+    variants = []
+    for name, m in mods.items():
+        for dt, x16 in xs.items():
+            tag = "fp16" if dt == torch.float16 else "bf16"
+            xf = x16.float()
+            variants.append((name, tag, "1", lambda m=m, x=x16: m(x)))
+            variants.append((name, tag, "1g", lambda m=m, x=x16: general(m, x)))
+            variants.append((name, tag, "2", lambda m=m, x=xf: m(x)))
+            variants.append((name, tag, "3", lambda m=m, x=x16: m(x.float()).to(x.dtype)))
+    times = {v[:3]: [] for v in variants}
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    with torch.no_grad():
+        for _, _, _, fn in variants:                                   # warm-up: workspaces, first-use zeroing, clocks
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        for _ in range(a.rounds):
+            for name, tag, row, fn in variants:
+                start.record()
+                for _ in range(a.iters):
+                    fn()
+                stop.record()
+                stop.synchronize()
+                times[(name, tag, row)].append(start.elapsed_time(stop) / a.iters)
+    mi355attn.sync_status(wait=True)
+    print(f"shape {tuple(a.shape)}, {a.rounds} rounds x {a.iters} calls, ms per call")
+    print("| block | io | row | median ms | min .. max ms | GB/s at algorithmic bytes |")
+    print("|---|---|---|---|---|---|")
+    out = []
+    for (name, tag, row), ts in times.items():
+        med = statistics.median(ts)
+        gbs = n * BYTES[row] / (med * 1e-3) / 1e9
+        print(f"| {name} | {tag} | {row} | {med:.4f} | {min(ts):.4f} .. {max(ts):.4f} | {gbs:.0f} |")
+        out.append({"block": name, "io": tag, "row": row, "median_ms": med, "min_ms": min(ts), "max_ms": max(ts), "gbs": gbs})
+    line = json.dumps({"shape": a.shape, "rounds": a.rounds, "iters": a.iters, "rows": out})
+    print(line)
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
