@@ -168,6 +168,9 @@ const char* mi355_last_error(void);         /* thread-local message of the last 
  *   "range_fallback" 1 (default) = the host mirror's modules re-run a forward whose fp16 operands saturated in precision 0 (one warning;
  *                   mi355_range_arm / mi355_range_wait below: no device synchronisation unless it fires); 0 = they do not wait and the NEXT call
  *                   reports MI355_ERANGE (the round-3 contract).  Host policy: the C entries themselves never re-run anything.
+ *   "vit_tail"      1 (default) = the host mirror's VisionTransformer with global_pool = "token" runs its LAST encoder block through
+ *                   mi355_vit_tail_fwd (only the rows the pooled token needs; bit-identical logits); 0 = the full block.  Host policy:
+ *                   the C entries do not read it.
  * Unknown key or a value outside the key's range -> MI355_EINVAL. */
 int         mi355_set_option(const char* key, long value);          /* current device */
 int         mi355_set_default_option(const char* key, long value);  /* process default: devices without an own setting */
@@ -697,6 +700,26 @@ size_t mi355_mhsa_workspace_bytes(int B, int N, int C, int x_is16);
 int mi355_mhsa_fwd(const void* x, int x_is16, const void* Wqkv16, const float* b_qkv, const void* Wproj16, const float* b_proj,
                    const float* resid, float* y, int B, int N, int C, int heads, float scale, int precision, void* workspace,
                    size_t workspace_bytes, mi355_stream_t stream);
+
+/* mi355_sdpa16_fwd limited to the first q_rows queries of every image: K and V of all N tokens are staged as usual, only the query
+ * tiles that hold rows < q_rows run, and only those rows are written -- to out16 (B, out_rows, heads*d), out_rows >= q_rows (out_rows = N is
+ * the layout of mi355_sdpa16_fwd; nothing else of the buffer is touched).  A query's arithmetic does not depend on its neighbours: the
+ * rows written are bit-identical to mi355_sdpa16_fwd's.  d in {32, 64}, N <= 224, precision 1 or 2. */
+int mi355_sdpa16_rows_fwd(const void* qkv16, void* out16, int B, int N, int heads, int d, float scale, int q_rows, int out_rows,
+                          int precision, mi355_stream_t stream);
+
+/* The LAST encoder block of a ViT whose head reads token 0 only (ViT.py:116-119 under ViT.py:186: head(x[:, 0])), as ONE call:
+ *   y[b, :] = TransformerEncoder(x)[b, 0, :]      x (B,N,C) fp32, y (B,C) fp32
+ * LayerNorm 1 and the k / v projection run on every token, the q projection, the attention core, proj (+ residual), LayerNorm 2, fc1 +
+ * GELU and fc2 + GELU (+ residual) on one row per image.  Wqkv16 (3C,C), Wproj16 (C,C), Wfc1_16 (hidden,C), Wfc2_16 (C,hidden): 16-bit
+ * copies in the operand format of `precision`; biases fp32 or NULL; eps1 / eps2 of the two LayerNorms.  The kernels are the library's own
+ * (row-independent, one K order): y equals row 0 of the composed block bit for bit.  Envelope: precision 1 or 2, head_dim in {32, 64},
+ * N <= 224, C % 64 == 0, C <= 2048, hidden % 64 == 0; anything else MI355_EUNSUPPORTED with nothing launched.  Capture-safe. */
+size_t mi355_vit_tail_workspace_bytes(int B, int N, int C, int hidden);
+int mi355_vit_tail_fwd(const float* x, const float* ln1_w, const float* ln1_b, float eps1, const void* Wqkv16, const float* b_qkv,
+                       const void* Wproj16, const float* b_proj, const float* ln2_w, const float* ln2_b, float eps2, const void* Wfc1_16,
+                       const float* b_fc1, const void* Wfc2_16, const float* b_fc2, float* y, int B, int N, int C, int hidden, int heads,
+                       float scale, int precision, void* workspace, size_t workspace_bytes, mi355_stream_t stream);
 
 /* General multi-head attention core (the plain softmax(QK^T*s)V pattern of setr.py:62-72, pvt.py:73-91,
  * segformer.py:33-50, cmt.py:93-111, moat.py:74-84, bvit.py:66-76 ...): any N_q / N_kv, online softmax over 64-key tiles.

@@ -18,7 +18,7 @@ static thread_local char g_err[512] = "";
 // or, in a test, sabotage -- one device without the others seeing it.  A block starts from the defaults below.
 constexpr int MAX_DEV = 64;
 enum Opt { O_CHUNK_IMAGES, O_NT, O_REVERSE, O_GEMM_VARIANT, O_ECA_SINGLE, O_SE_SINGLE, O_CBAM_SINGLE, O_WS_PERSISTENT, O_STEM_DIRECT,
-           O_ZOO_SINGLE, O_SPIN_LIMIT, O_GEMM_PA, O_GEMM_SPLITK, O_DA_FUSED, O_DA_RANGES, O_SE_OCC, O_LN_FOLD, O_GEMM_PA16, O_GEMM_PA_BLOCK, O_GEMM_PA_TAIL, O_LPI_PATCH, O_MIXER_FUSED, O_MIXER_EARLY, O_GEMM_SMALL, O_MLP_TT4, O_MIXER_STATS, O_ATTN_NW, O_GEMM_W4, O_RANGE_FALLBACK, O_GEMM_WREG, O_XCA_TR, O_MLP_WIDE, O_GEMM_WST, O_GEMM_WSLAB, O_IO16_OCC, O_COUNT };
+           O_ZOO_SINGLE, O_SPIN_LIMIT, O_GEMM_PA, O_GEMM_SPLITK, O_DA_FUSED, O_DA_RANGES, O_SE_OCC, O_LN_FOLD, O_GEMM_PA16, O_GEMM_PA_BLOCK, O_GEMM_PA_TAIL, O_LPI_PATCH, O_MIXER_FUSED, O_MIXER_EARLY, O_GEMM_SMALL, O_MLP_TT4, O_MIXER_STATS, O_ATTN_NW, O_GEMM_W4, O_RANGE_FALLBACK, O_GEMM_WREG, O_XCA_TR, O_MLP_WIDE, O_GEMM_WST, O_GEMM_WSLAB, O_IO16_OCC, O_VIT_TAIL, O_COUNT };
 struct OptDesc { const char* key; long def, lo, hi; };
 // key, default, accepted range.  spin_limit additionally accepts 0 (forces the time-out path in tests: every exchange then fails on
 // its first unsuccessful poll; real budgets start at 1024 sweeps)
@@ -62,6 +62,8 @@ static const OptDesc kOpts[O_COUNT] = {
     {"gemm_wslab", 1, 0, 2},               // 16-bit outputs with K = 256 / 384 / 512 (XCiT / CSWin stage 3-4 / Mixer qkv and fc1): a column slab of W stationary in
                                            // registers (gemm16_wslab.hip); 1 = GELU epilogues and M % 256 != 0 (where it measured faster), 2 = every product it takes
     {"io16_occ", 4, 2, 4},                 // single-read SE on 16-bit activations (chan_io16.hip): workgroups per CU the grid is sized for, capped by the kernel's register budget
+    {"vit_tail", 1, 0, 1},                 // host policy (read by the binding): 1 = a ViT that pools token 0 runs its LAST encoder block through mi355_vit_tail_fwd
+                                           // (only the rows that token needs: vit_tail.hip); 0 = the full block
 };
 static_assert(sizeof(kOpts) / sizeof(kOpts[0]) == O_COUNT, "one table row per option, in enum order");
 namespace {
@@ -122,6 +124,7 @@ long opt_xca_tr() { return opt(O_XCA_TR); }
 long opt_mlp_wide() { return opt(O_MLP_WIDE); }
 long opt_gemm_wst() { return opt(O_GEMM_WST); }
 long opt_gemm_wslab() { return opt(O_GEMM_WSLAB); }
+long opt_vit_tail() { return opt(O_VIT_TAIL); }
 
 // ---- workspaces of the granule-exchange kernels (chan_fused.hip, cbam_single.hip, chan_stat.hip) ---------------------------------
 // A granule is valid when it carries the tag of the CURRENT launch = the workspace's epoch word + 1 (advanced on the device by the

@@ -49,8 +49,13 @@ struct AttnPair {
 struct AttnPairRg : AttnPair {
     unsigned* ovf;
 };
-template <bool IO16>
-using attn_kargs = typename std::conditional<IO16, AttnPair, AttnPairRg>::type;
+// The query-limited instantiations (QLIM: 16-bit I/O only) take the limit behind the pair -- again a type of their own, for the same reason.
+struct AttnPairQ : AttnPair {
+    int q_tiles, q_rows;   // only the query tiles [0, q_tiles) run, and of those only the query slots < q_rows are loaded and stored
+    int out_rows;          // rows per image of the output buffer (B, out_rows, Ctot), >= q_rows (the full core writes (B, L, Ctot))
+};
+template <bool IO16, bool QLIM = false>
+using attn_kargs = typename std::conditional<QLIM, AttnPairQ, typename std::conditional<IO16, AttnPair, AttnPairRg>::type>::type;
 template <bool IO16>
 const attn_kargs<IO16>& attn_pick(const AttnPairRg& p) { return p; }
 
@@ -63,8 +68,13 @@ const attn_kargs<IO16>& attn_pick(const AttnPairRg& p) { return p; }
 #ifndef MI355_ATTN_FMA_SM
 #define MI355_ATTN_FMA_SM 1
 #endif
-template <int PREC, int D, int KT, bool LEPE, bool IO16, int NW, int OCC = 1, int TFULL = -1>
-__global__ __launch_bounds__(NW * 64, OCC) void win_attn_kernel(const attn_kargs<IO16> pr) {
+// QLIM: the pooled-token tail of a ViT (vit_tail.hip) needs the context of the first query rows only.  Every wave still takes part in the
+// K / V staging and the barrier; then only the waves that own a query tile below q_tiles go on, the query slots at or beyond q_rows are
+// loaded as zeros (the out-of-range descriptor path) and only rows below q_rows are stored.  A query column's arithmetic does not depend
+// on the other columns of its tile, so the rows that are written carry the bits of the full launch.
+template <int PREC, int D, int KT, bool LEPE, bool IO16, int NW, int OCC = 1, int TFULL = -1, bool QLIM = false>
+__global__ __launch_bounds__(NW * 64, OCC) void win_attn_kernel(const attn_kargs<IO16, QLIM> pr) {
+    static_assert(!QLIM || (IO16 && !LEPE), "the query limit exists for the plain 16-bit-I/O core");
     constexpr bool FMA_SM = MI355_ATTN_FMA_SM != 0;
     // XCD-aware block order: hardware hands consecutive block ids to the 8 XCDs round-robin, but consecutive LOGICAL ids are the heads
     // of one window, whose q / k / v slices are adjacent 64-byte (d = 32) pieces of the same token rows -- neighbours that should
@@ -110,7 +120,14 @@ __global__ __launch_bounds__(NW * 64, OCC) void win_attn_kernel(const attn_kargs
     auto tok = [&](int s) { const int r = srow(s); return (wy0 + r) * a.reso + wx0 + (s - r * a.Wsp); };   // window slot -> token
 
     const int l15 = lane & 15, g = lane >> 4;
-    const int nqt = (T + 15) >> 4;
+    int nqt = (T + 15) >> 4;
+    int qmax = T;                                                     // query slots below this are loaded and stored
+    if constexpr (QLIM) {
+        nqt = pr.q_tiles < nqt ? pr.q_tiles : nqt;
+        qmax = pr.q_rows < T ? pr.q_rows : T;
+    }
+    int orows = a.L;                                                  // rows per image of the output
+    if constexpr (QLIM) orows = pr.out_rows;
     // ---- everything this wave will need from HBM is requested up front (one memory latency per workgroup): its Q fragments
     //      (16-bit I/O path), its LePE taps, then the K / V staging loads below --------------------------------------------------
     constexpr int NQ = (KT + NW - 1) / NW;                         // query tiles per wave
@@ -127,8 +144,9 @@ __global__ __launch_bounds__(NW * 64, OCC) void win_attn_kernel(const attn_kargs
         for (int iq = 0; iq < NQ; ++iq) {
             const int qs = (wave + iq * NW) * 16 + l15;
             const int tq = tok(qs < T ? qs : 0);
+            const bool ql = QLIM ? (qs < qmax && wave + iq * NW < nqt) : qs < T;
 #pragma unroll
-            for (int ks = 0; ks < D / 32; ++ks) qraw[iq][ks] = ld16(qs < T, tq, ks * 32 + g * 8);
+            for (int ks = 0; ks < D / 32; ++ks) qraw[iq][ks] = ld16(ql, tq, ks * 32 + g * 8);
         }
     }
     // LePE taps + bias of this head's D channels: parked in LDS ([channel][10]) instead of 20 registers per lane
@@ -420,8 +438,8 @@ __global__ __launch_bounds__(NW * 64, OCC) void win_attn_kernel(const attn_kargs
             for (int it = 0; it < 16 / RPI; ++it) {
                 const int r = it * RPI + lane / LPR, c8 = (lane % LPR) * 8;
                 const int qslot = qt * 16 + r;
-                if (qslot < T)
-                    *reinterpret_cast<v8*>(static_cast<gel*>(a.out) + ((long)b * a.L + tok(qslot)) * a.Ctot + och0 + c8) =
+                if (QLIM ? qslot < qmax : qslot < T)
+                    *reinterpret_cast<v8*>(static_cast<gel*>(a.out) + ((long)b * orows + tok(qslot)) * a.Ctot + och0 + c8) =
                         *reinterpret_cast<const v8*>(slab + r * OP + c8);
             }
         } else {
@@ -484,15 +502,40 @@ int launch_attn(const AttnArgs& a, int B, int precision, hipStream_t st, const A
     return MI355_OK;
 }
 
+// The plain 16-bit-I/O core limited to the first q_rows queries of every image (one window = the sequence).  The key-tile count follows
+// launch_attn; the compile-time count of full key tiles and the occupancy hint are left out (neither changes a value).
+template <int D>
+int launch_attn_rows(const AttnArgs& a, int B, int q_rows, int out_rows, int precision, hipStream_t st) {
+    AttnPairQ pr{};
+    pr.a0 = a;
+    pr.split = B * a.nwin * a.heads;
+    pr.q_rows = q_rows;
+    pr.q_tiles = (q_rows + 15) >> 4;
+    pr.out_rows = out_rows;
+    const int grid = pr.split;
+    MI355_TRACE(st, "win_attn_kernel<d=%d,io16,rows> B=%d heads=%d tokens=%d q_rows=%d", D, B, a.heads, a.T, q_rows);
+#define GOQ(P, KT_, NW_) win_attn_kernel<P, D, KT_, false, true, NW_, 1, -1, true><<<grid, NW_ * 64, 0, st>>>(pr)
+#define BYKTQ(P) do { if (a.T <= 64) GOQ(P, 4, 4); else if (a.T <= 128) GOQ(P, 8, 4); else GOQ(P, 14, 8); } while (0)
+    if (precision == MI355_PREC_FP16) BYKTQ(1); else BYKTQ(2);
+#undef BYKTQ
+#undef GOQ
+    return MI355_OK;
+}
+
 }  // namespace
 
-static int sdpa_common(const void* qkv, void* out, int B, int N, int heads, int d, float scale, int precision, bool io16,
-                       hipStream_t st) {
+static AttnArgs sdpa_args(const void* qkv, void* out, int N, int heads, int d, float scale) {
     AttnArgs a{};
     a.qkv = qkv; a.out = out; a.L = N; a.Ctot = heads * d; a.c0 = 0; a.heads = heads;
     a.koff = a.Ctot; a.voff = 2 * a.Ctot; a.oc0 = 0;
     a.reso = N; a.Hsp = 1; a.Wsp = N; a.nWx = 1; a.nwin = 1; a.T = N; a.scale = scale; a.pre_scale = 0;
     a.wsp_magic = (unsigned)(((1ull << 32) + (unsigned)N - 1) / (unsigned)N);
+    return a;
+}
+
+static int sdpa_common(const void* qkv, void* out, int B, int N, int heads, int d, float scale, int precision, bool io16,
+                       hipStream_t st) {
+    const AttnArgs a = sdpa_args(qkv, out, N, heads, d, scale);
     if (d == 64) return io16 ? launch_attn<64, false, true>(a, B, precision, st) : launch_attn<64, false, false>(a, B, precision, st);
     return io16 ? launch_attn<32, false, true>(a, B, precision, st) : launch_attn<32, false, false>(a, B, precision, st);
 }
@@ -546,6 +589,19 @@ int mi355_sdpa16_fwd(const void* qkv, void* out, int B, int N, int heads, int d,
     SDPA_CHECKS("mi355_sdpa16_fwd");
     int rc = sdpa_common(qkv, out, B, N, heads, d, scale, precision, true, static_cast<hipStream_t>(stream));
     if (rc) return rc;
+    MI355_LAUNCH_CHECK();
+    return MI355_OK;
+}
+
+int mi355_sdpa16_rows_fwd(const void* qkv, void* out, int B, int N, int heads, int d, float scale, int q_rows, int out_rows, int precision,
+                          mi355_stream_t stream) {
+    SDPA_CHECKS("mi355_sdpa16_rows_fwd");
+    MI355_CHECK_ARG(q_rows > 0 && q_rows <= N && out_rows >= q_rows);
+    MI355_CHECK_ARG(precision == MI355_PREC_FP16 || precision == MI355_PREC_BF16);
+    const AttnArgs a = sdpa_args(qkv, out, N, heads, d, scale);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (d == 64) launch_attn_rows<64>(a, B, q_rows, out_rows, precision, st);
+    else         launch_attn_rows<32>(a, B, q_rows, out_rows, precision, st);
     MI355_LAUNCH_CHECK();
     return MI355_OK;
 }

@@ -42,6 +42,10 @@ long  opt_xca_tr();
 long  opt_mlp_wide();
 long  opt_gemm_wst();
 long  opt_gemm_wslab();
+long  opt_vit_tail();
+// LayerNorm of strided rows plus an addend, written in the 16-bit operand format (layernorm.hip; the pooled-token tail of vit_tail.hip)
+int   layernorm16_rows(const float* x, long ldx, const float* add, float* xs, const float* weight, const float* bias, void* y16, int rows,
+                       int cols, float eps, int precision, hipStream_t st);
 // fused LayerNorm + MLP for C = 256 / 384 (mlp_wide.hip): waves split the weights, fragments go global -> VGPR
 bool  mlp_wide_applicable(int C, int hidden);
 int   mlp_wide(const float* x, const void* w1_16, const float* b1, const void* w2_16, const float* b2, const float* gamma, float* y, long M, int C,

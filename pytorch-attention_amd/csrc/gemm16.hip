@@ -719,6 +719,24 @@ int mi355::linear16_dispatch(const G16Args& g, int out16, int precision, void* w
     return MI355_OK;
 }
 
+// A product with FEW rows (the pooled-token tail of a ViT, vit_tail.hip: one row per image) on the ring-pipelined 32 x 64 tiles that
+// linear16_dispatch gives the left-over rows of the two-accumulator kernel: 256 rows are 96 workgroups at N = 768 and 384 at N = 3072, where
+// the engine's 128-row tiles would leave most of the chip idle.  Same K order as every other kernel of the engine: a row's bits do not
+// depend on the kernel that computes it.  g as mi355_linear16_ws_fwd fills it (lda / ldc are free: rows may be strided).
+int mi355::gemm16_rows(const G16Args& g, int out16, int precision, hipStream_t st) {
+    const int grid = cdiv(g.M, 32) * cdiv(g.N, 64);
+    MI355_TRACE(st, "gemm16_kernel<rows 32x64,%s> M=%d N=%d K=%d%s", out16 ? "out16" : "out32", g.M, g.N, g.K, g.act == MI355_ACT_GELU ? " gelu" : "");
+    if (precision == MI355_PREC_FP16) {
+        if (out16) gemm16_kernel<_Float16, true, 32, 64, 1, 4, false, 10><<<grid, 256, 0, st>>>(g);
+        else       gemm16_kernel<_Float16, false, 32, 64, 1, 4, false, 10><<<grid, 256, 0, st>>>(g);
+    } else {
+        if (out16) gemm16_kernel<__bf16, true, 32, 64, 1, 4, false, 10><<<grid, 256, 0, st>>>(g);
+        else       gemm16_kernel<__bf16, false, 32, 64, 1, 4, false, 10><<<grid, 256, 0, st>>>(g);
+    }
+    MI355_LAUNCH_CHECK();
+    return MI355_OK;
+}
+
 extern "C" {
 
 int mi355_linear16_tr_fwd(const void* X16, const void* W16, const float* bias, const float* resid, float* Y, int M, int N, int K,

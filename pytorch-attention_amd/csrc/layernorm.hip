@@ -77,6 +77,82 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     if constexpr (std::is_same<OT, _Float16>::value) rg_report(rgmax, ovf, 2u);
 }
 
+// layernorm_kernel on STRIDED rows with an optional addend (the pooled-token tail of a ViT, vit_tail.hip: one row per image): row r is
+// x[r * ldx ...] + add[r * cols ...], the sum is also written to xs[r * cols ...] (fp32: the residual stream), and the LayerNorm of the sum
+// to y[r * cols ...].  Lane layout, statistics and the normalise expression are layernorm_kernel's, so a row gets the bits that kernel
+// gives the same values; the sum x + add is the residual add of a GEMM epilogue (one rounding, commutative).
+template <int LPR, int NV, typename OT>
+__global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* __restrict__ x, long ldx, const float* __restrict__ add,
+                                                            float* __restrict__ xs, const float* __restrict__ w, const float* __restrict__ b,
+                                                            OT* __restrict__ y, long rows, int cols, float eps, unsigned* ovf) {
+    float rgmax = 0.f;
+    constexpr int RPW = 64 / LPR;
+    const int lane = threadIdx.x & 63, sub = lane % LPR, rsel = lane / LPR;
+    const long wave0 = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (long)gridDim.x * 4;
+    const int n4 = cols >> 2;
+    const float inv = 1.0f / (float)cols;
+    for (long r0 = wave0 * RPW; r0 < rows; r0 += nwaves * RPW) {
+        const long row = r0 + rsel;
+        const bool rok = row < rows;
+        const v4f* xr = reinterpret_cast<const v4f*>(x + (rok ? row : 0) * ldx);
+        const v4f* ar = reinterpret_cast<const v4f*>(add + (rok ? row : 0) * cols);
+        v4f v[NV];
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int i = sub + LPR * j;
+            v[j] = (rok && i < n4) ? xr[i] + ar[i] : v4f{0.f, 0.f, 0.f, 0.f};
+            s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
+        }
+        const float mean = group_sum<LPR>(s) * inv;
+        float q = 0.f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int i = sub + LPR * j;
+            if (i < n4) {
+                const v4f d = v[j] - mean;
+                q += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
+            }
+        }
+        const float rstd = 1.0f / sqrtf(group_sum<LPR>(q) * inv + eps);
+        if (!rok) continue;
+        OT* yr = y + row * cols;
+        float* sr = xs + row * cols;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int i = sub + LPR * j;
+            if (i < n4) {
+                const v4f ww = reinterpret_cast<const v4f*>(w)[i], bb = reinterpret_cast<const v4f*>(b)[i];
+                const v4f o = (v[j] - mean) * rstd * ww + bb;
+                if constexpr (std::is_same<OT, _Float16>::value) rgmax = rg_absmax4(rgmax, o);
+                *reinterpret_cast<v4f*>(sr + 4 * i) = v[j];
+                store4<OT>(yr + 4 * i, o);
+            }
+        }
+    }
+    if constexpr (std::is_same<OT, _Float16>::value) rg_report(rgmax, ovf, 2u);
+}
+
+template <typename OT>
+void launch_ln_rows(const float* x, long ldx, const float* add, float* xs, const float* weight, const float* bias, OT* y, int rows, int cols,
+                    float eps, hipStream_t st) {
+    unsigned* ovf = std::is_same<OT, _Float16>::value ? mi355::range_word(st) : nullptr;
+    MI355_TRACE(st, "layernorm_rows_kernel<out16> rows=%d cols=%d", rows, cols);
+#define LNR(LPR_, NV_)                                                                                                      \
+    do {                                                                                                                    \
+        const long waves = ((long)rows + (64 / LPR_) - 1) / (64 / LPR_);                                                   \
+        const int grid = (int)((waves + 3) / 4 < 8192 ? (waves + 3) / 4 : 8192);                                           \
+        layernorm_rows_kernel<LPR_, NV_, OT><<<grid, 256, 0, st>>>(x, ldx, add, xs, weight, bias, y, rows, cols, eps, ovf); \
+    } while (0)
+    if (cols <= 64)        LNR(16, 1);                  // the width classes of launch_ln (the lane layout decides the summation order)
+    else if (cols <= 128)  LNR(32, 1);
+    else if (cols <= 256)  LNR(64, 1);
+    else if (cols <= 512)  LNR(64, 2);
+    else if (cols <= 1024) LNR(64, 4);
+    else                   LNR(64, 8);
+#undef LNR
+}
+
 // any width / alignment: three sweeps over the (cache-resident) row
 template <typename OT>
 __global__ __launch_bounds__(256) void layernorm_generic_kernel(const float* __restrict__ x, const float* __restrict__ w,
@@ -127,6 +203,19 @@ int launch_ln(const float* x, const float* weight, const float* bias, OT* y, int
     return MI355_OK;
 }
 }  // namespace
+
+// y16 = LayerNorm(x + add) in the operand format, xs = x + add in fp32: rows of x are ldx floats apart, add / xs / y16 are dense.
+// MI355_EUNSUPPORTED (nothing launched) outside the vector kernel's envelope: cols % 4, cols > 2048, rows not 16-byte aligned.
+int mi355::layernorm16_rows(const float* x, long ldx, const float* add, float* xs, const float* weight, const float* bias, void* y16, int rows,
+                            int cols, float eps, int precision, hipStream_t st) {
+    if ((cols & 3) || cols > 2048 || (ldx & 3) || !aligned16(x) || !aligned16(add) || !aligned16(xs) || !aligned16(y16) || !aligned16(weight) ||
+        !aligned16(bias))
+        return MI355_EUNSUPPORTED;
+    if (precision == MI355_PREC_FP16) launch_ln_rows<_Float16>(x, ldx, add, xs, weight, bias, static_cast<_Float16*>(y16), rows, cols, eps, st);
+    else                              launch_ln_rows<__bf16>(x, ldx, add, xs, weight, bias, static_cast<__bf16*>(y16), rows, cols, eps, st);
+    MI355_LAUNCH_CHECK();
+    return MI355_OK;
+}
 
 extern "C" {
 

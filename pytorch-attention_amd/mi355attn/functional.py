@@ -1237,6 +1237,57 @@ def sdpa16(qkv16, num_heads, scale, precision=None):
     return out
 
 
+def sdpa16_rows(qkv16, num_heads, scale, q_rows, out=None, precision=None):
+    """sdpa16 for the first q_rows queries of every image (mi355_sdpa16_rows_fwd): out (B, out_rows, C) with out_rows >= q_rows, by
+    default (B, q_rows, C); rows at or beyond q_rows of a larger buffer are left as they are."""
+    qkv16 = _require16(qkv16, "qkv16", precision)
+    B, N, C3 = qkv16.shape
+    C = C3 // 3
+    if out is None:
+        out = torch.empty(B, q_rows, C, dtype=qkv16.dtype, device=qkv16.device)
+    if out.dtype != qkv16.dtype or out.dim() != 3 or out.shape[0] != B or out.shape[2] != C or not out.is_contiguous():
+        raise ValueError("sdpa16_rows: out must be a dense (B, out_rows, C) tensor of qkv16's type")
+    check(lib().mi355_sdpa16_rows_fwd(dptr(qkv16), dptr(out), B, N, num_heads, C // num_heads, float(scale), int(q_rows), out.shape[1],
+                                      _prec(precision), stream_ptr(qkv16.device)), "mi355_sdpa16_rows_fwd")
+    return out
+
+
+def vit_tail_enabled():
+    """Option "vit_tail" of the current device (default 1): the last block of a token-pooled ViT computes the pooled token's rows only."""
+    return _ffi.get_option("vit_tail") == 1
+
+
+def vit_tail_envelope(C, hidden, num_heads, n_tokens):
+    """Envelope of mi355_vit_tail_fwd: head width 32 / 64, N <= 224, C % 64 == 0, C <= 2048, hidden % 64 == 0."""
+    return (C % num_heads == 0 and C // num_heads in (32, 64) and n_tokens <= 224 and C % 64 == 0 and C <= 2048 and hidden % 64 == 0)
+
+
+def vit_tail16(x, ln1, wqkv16, bqkv, wproj16, bproj, ln2, wfc1_16, bfc1, wfc2_16, bfc2, num_heads, scale, precision=None):
+    """Row 0 of a ViT encoder block (ViT.py:116-119) for every image, as one C call (mi355_vit_tail_fwd): x (B,N,C) fp32 -> (B,C) fp32.
+    ln1 / ln2: the block's nn.LayerNorm modules; the weights in the 16-bit operand format (weight16)."""
+    _range_check()
+    p = _prec(precision)
+    x = require_device_f32(x, "x")
+    B, N, C = x.shape
+    hidden = wfc1_16.shape[0]
+    ws16 = [_require16(t, n, p) for t, n in ((wqkv16, "wqkv16"), (wproj16, "wproj16"), (wfc1_16, "wfc1_16"), (wfc2_16, "wfc2_16"))]
+    if [tuple(t.shape) for t in ws16] != [(3 * C, C), (C, C), (hidden, C), (C, hidden)]:
+        raise ValueError("vit_tail16: weight shapes do not match the embedding width")
+    if tuple(ln1.normalized_shape) != (C,) or tuple(ln2.normalized_shape) != (C,):
+        raise ValueError("vit_tail16: LayerNorm width does not match the embedding width")
+    bqkv, bproj, bfc1, bfc2 = _opt(bqkv, "qkv.bias"), _opt(bproj, "proj.bias"), _opt(bfc1, "fc1.bias"), _opt(bfc2, "fc2.bias")
+    lnp = [require_device_f32(t, n) for t, n in ((ln1.weight, "layernorm1.weight"), (ln1.bias, "layernorm1.bias"),
+                                                  (ln2.weight, "layernorm2.weight"), (ln2.bias, "layernorm2.bias"))]
+    y = torch.empty(B, C, dtype=torch.float32, device=x.device)
+    nws = lib().mi355_vit_tail_workspace_bytes(B, N, C, hidden)
+    ws = _ffi.workspace_named("mhsa", nws, x.device)          # the blocks run one after the other on one stream: the attention block's buffer
+    check(lib().mi355_vit_tail_fwd(dptr(x), dptr(lnp[0]), dptr(lnp[1]), float(ln1.eps), dptr(ws16[0]), dptr(bqkv), dptr(ws16[1]), dptr(bproj),
+                                   dptr(lnp[2]), dptr(lnp[3]), float(ln2.eps), dptr(ws16[2]), dptr(bfc1), dptr(ws16[3]), dptr(bfc2), dptr(y),
+                                   B, N, C, hidden, int(num_heads), float(scale), p, dptr(ws), nws, stream_ptr(x.device)),
+          "mi355_vit_tail_fwd")
+    return y
+
+
 def logit_envelope(C, K, num_heads, n_tokens):
     """Envelope of the precision-3 kernels (mi355_qkv_split16_fwd + mi355_sdpa16_split_fwd): head width 32 / 64, N <= 224, K % 64 == 0."""
     return C % num_heads == 0 and C // num_heads in (32, 64) and n_tokens <= 224 and K % 64 == 0 and C % 64 == 0

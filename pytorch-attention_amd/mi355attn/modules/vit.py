@@ -232,6 +232,27 @@ class VisionTransformer(nn.Module):
             nn.init.zeros_(m.bias)
             nn.init.ones_(m.weight)
 
+    def _tail_ok(self, blk, tok):
+        """The last block may compute the pooled token's rows only (F.vit_tail16, csrc/vit_tail.hip): logits come from token 0, the
+        option is on and the fold off, the block is the plain 16-bit dataflow inside the entry's envelope, and nobody can observe the
+        block's full output -- a forward (pre-)hook on the block or on anything inside it keeps the full path."""
+        if self.global_pool != "token" or F.ln_fold_enabled() or not F.vit_tail_enabled():
+            return False
+        if type(blk) is not TransformerEncoder or type(blk.attn) is not Attention or type(blk.mlp) is not Mlp:
+            return False
+        at, mlp = blk.attn, blk.mlp
+        if F.logit_mode(at.precision) or tok.dim() != 3 or tok.dtype != torch.float32 or not tok.is_cuda:
+            return False
+        p = F._prec(at.precision)
+        B, N, C = tok.shape
+        if p not in (F.PREC_FP16, F.PREC_BF16) or F._prec(mlp.precision) != p or mlp.fc1.in_features != C or mlp.fc2.out_features != C:
+            return False
+        if not (at.fast_ok(N) and _fast(p, mlp.fc1, mlp.fc2) and F.vit_tail_envelope(C, mlp.fc1.out_features, at.num_heads, N)):
+            return False
+        if nn.modules.module._global_forward_hooks or nn.modules.module._global_forward_pre_hooks:
+            return False
+        return not any(m._forward_hooks or m._forward_pre_hooks for m in blk.modules())
+
     def forward(self, x):
         B, _, H, W = x.shape
         ps = self.patch_embedding.patch_size
@@ -242,13 +263,22 @@ class VisionTransformer(nn.Module):
         # fold eligibility is decided ONCE per forward (the token tensor keeps its shape through the blocks): with the option off -- the
         # default -- no per-block option reads / envelope checks / cache look-ups happen at all
         elig = [blk.fold_ok(tok) for blk in blocks] if F.ln_fold_enabled() else None
+        tail = blocks.pop() if blocks and self._tail_ok(blocks[-1], tok) else None
         for i, blk in enumerate(blocks):
             if elig is not None and elig[i]:                      # LayerNorms folded into the GEMMs; the state travels block to block
                 nxt_ok = i + 1 < len(blocks) and elig[i + 1]
                 tok, state = blk.forward_folded(tok, state, blocks[i + 1].layernorm1.eps if nxt_ok else None)
             else:
                 tok, state = blk(tok), None                       # module call (hooks intact); its own fold check is one option read
-        if self.global_pool == "token":
+        if tail is not None:
+            # nothing but row 0 of the last block's output is read below: LayerNorm 1 and k / v for every token, everything else for one
+            # row per image, in one C call; the same kernels' arithmetic, bit-identical logits (option "vit_tail" = 0: the full block)
+            at, mlp = tail.attn, tail.mlp
+            p = F._prec(at.precision)
+            pooled = F.vit_tail16(tok, tail.layernorm1, F.weight16(at.qkv.weight, p), _bias(at.qkv), F.weight16(at.proj.weight, p),
+                                  at.proj.bias, tail.layernorm2, F.weight16(mlp.fc1.weight, p), mlp.fc1.bias,
+                                  F.weight16(mlp.fc2.weight, p), mlp.fc2.bias, at.num_heads, at.scale, precision=p)
+        elif self.global_pool == "token":
             pooled = tok[:, 0]                                   # row-strided view, consumed in place by the GEMM
         elif self.global_pool == "avg":
             pooled = F.token_mean(tok, skip_first=1)
