@@ -15,57 +15,14 @@ static thread_local char g_err[512] = "";
 // ---- tuning options: ONE BLOCK PER DEVICE --------------------------------------------------------------------------------------
 // mi355_set_option / mi355_get_option act on the block of the calling thread's CURRENT device (hipGetDevice), and every launch reads
 // the block of the device it launches on: a host that drives eight GPUs from one process (one thread per GPU) can tune --
-// or, in a test, sabotage -- one device without the others seeing it.  A block starts from the defaults below.
+// or, in a test, sabotage -- one device without the others seeing it.  A block starts from the defaults in options.h.
 constexpr int MAX_DEV = 64;
-enum Opt { O_CHUNK_IMAGES, O_NT, O_REVERSE, O_GEMM_VARIANT, O_ECA_SINGLE, O_SE_SINGLE, O_CBAM_SINGLE, O_WS_PERSISTENT, O_STEM_DIRECT,
-           O_ZOO_SINGLE, O_SPIN_LIMIT, O_GEMM_PA, O_GEMM_SPLITK, O_DA_FUSED, O_DA_RANGES, O_SE_OCC, O_LN_FOLD, O_GEMM_PA16, O_GEMM_PA_BLOCK, O_GEMM_PA_TAIL, O_LPI_PATCH, O_MIXER_FUSED, O_MIXER_EARLY, O_GEMM_SMALL, O_MLP_TT4, O_MIXER_STATS, O_ATTN_NW, O_GEMM_W4, O_RANGE_FALLBACK, O_GEMM_WREG, O_XCA_TR, O_MLP_WIDE, O_GEMM_WST, O_GEMM_WSLAB, O_IO16_OCC, O_VIT_TAIL, O_COUNT };
 struct OptDesc { const char* key; long def, lo, hi; };
-// key, default, accepted range.  spin_limit additionally accepts 0 (forces the time-out path in tests: every exchange then fails on
-// its first unsuccessful poll; real budgets start at 1024 sweeps)
-static const OptDesc kOpts[O_COUNT] = {
-    {"chunk_images", 0, 0, 1L << 40},    // 0 = auto (about 200 MB of x per chunk)
-    {"nt", 3, 0, 3},                       // bit0: non-temporal loads, bit1: non-temporal stores in the final pass
-    {"reverse", 0, 0, 1},
-    {"gemm_variant", 0, 0, 17},            // tile/schedule variant of the 16-bit GEMM (gemm16.hip); 0 = dispatch by shape
-    {"eca_single", 1, 0, 1},               // ECA: one read + one write of x, halo channel rows re-summed per workgroup (chan_fused.hip)
-    {"se_single", 1, 0, 1},                // SE: x read once, channel means exchanged as 8-byte {mean, tag} granules (chan_fused.hip)
-    {"cbam_single", 1, 0, 1},              // CBAM: x read once, row bands in registers, granule hops per band (cbam_single.hip)
-    {"ws_persistent", 0, 0, 1},            // 1 = caller keeps workspace contents between calls: granule exchanges skip their zeroing
-    {"stem_direct", 1, 0, 1},              // narrow conv stems: direct fp32 kernel (stem_conv.hip) vs implicit GEMM
-    {"zoo_single", 1, 0, 1},               // SimAM / SRM / GCT / LCT: single-read register-resident path (chan_stat.hip) vs two passes
-    {"spin_limit", 1L << 22, 1024, 1L << 30},   // poll budget of the exchange kernels (sweeps) before they give up with an error code
-    {"gemm_pa", 1, 0, 1},                  // fp32-output GEMMs: two-accumulator persistent kernel where it applies (gemm16_pa.hip)
-    {"gemm_splitk", 1, 0, 1},              // persistent GEMM: cut the tiles of the last partial round along K (gemm16_p8.hip)
-    {"da_fused", 1, 0, 1},                 // DoubleAttention: fused kernels where they apply (double_attn_fused.hip, double_attn_small.hip)
-    {"da_ranges", 0, 0, 32},               // ... pixel ranges per image in pass 1: 0 = from the batch size, 1..32 = fixed
-    {"se_occ", 3, 2, 3},                   // single-read SE: workgroups per CU (2: <= 128 VGPRs, 3: <= 80 VGPRs)
-    {"ln_fold", 0, 0, 1},                  // ViT encoder chain: 1 = LayerNorm folded into the neighbouring GEMMs (ln_fold.hip); measured slower
-                                           // than the LayerNorm launches it removes, so it is opt-in
-    {"gemm_pa16", 1, 0, 2},                // 16-bit outputs with K >= 576 on the two-accumulator kernel: 0 never, 1 GELU epilogues, 2 all
-    {"gemm_pa_block", 1, 0, 1},            // two-accumulator kernel: blocked tile order (8 row x 4 column tiles per XCD round) for wide outputs
-    {"gemm_pa_tail", 10, 0, 100},          // two-accumulator kernel, K >= 1024: a last round at most this many percent full goes to the small-tile ring kernel (0 = off)
-    {"lpi_patch", 1, 0, 1},                // LPI at 14 x 14 tokens, C % 32 == 0: 2 x 2 patches per lane on channel-quad-major LDS planes (xcit.hip)
-    {"mixer_fused", 1, 0, 1},              // MixerLayer token mixing (host mirror): one kernel where the geometry allows (mixer_fused.hip)
-    {"mixer_early", 0, 0, 1},              // mixer_token_kernel: all residual loads of the epilogue before its first store (A/B switch)
-    {"gemm_small", 1, 0, 1},               // mi355_linear_fwd: outputs under an eighth of a round of 128 x 128 tiles on one-wave 16 x 32 tiles (gemm_small.hip)
-    {"mlp_tt4", 0, 0, 1},                  // fused MLP at C = 64 (CSWin stage 1): 8 waves x 4 token tiles at 256 VGPRs instead of 16 x 2 at 128 (A/B switch)
-    {"mixer_stats", 0, 0, 1},              // mixer_token_kernel at C = 512: LayerNorm row statistics inside the kernel (1) or by the row_stats_kernel pre-pass (0, default: measured equal)
-    {"attn_nw", 8, 7, 8},                  // ViT attention core at 193 .. 208 tokens (13 query tiles): waves per workgroup, 8 (13 / 16 balance) or 7 (13 / 14)
-    {"gemm_w4", 1, 0, 1},                  // 16-bit outputs, 576 <= K < 1536, whole 256 x 256 tiles: the one-wave-per-SIMD persistent kernel (gemm16_w4.hip) instead of gemm16_p8
-    {"range_fallback", 1, 0, 1},           // host policy of the drop-in modules (read by the binding): 1 = a forward whose fp16 operands saturated is re-run in strict mode, 0 = raise on the next call
-    {"gemm_wreg", 1, 0, 1},                // fp32 (+ residual) outputs with N = K = 256 / 384: weight-stationary-in-registers streaming kernel (gemm16_wreg.hip)
-    {"xca_tr", 1, 0, 1},                   // XCA core with 16-bit q / k / v and N <= 224: covariance on the 16-bit matrix pipe from one transposed LDS image (xcit.hip xca_tr_kernel)
-    {"mlp_wide", 0, 0, 1},                 // 1 = mi355_mlp_fused_fwd takes C = 256 / 384 (hidden 4C) on the weight-split kernel (mlp_wide.hip); measured SLOWER than LayerNorm + two GEMMs
-                                           // (profiles/r06_mlp_wide.md), hence opt-in; 0 (default) = those shapes are MI355_EUNSUPPORTED
-    {"gemm_wst", 0, 0, 4},                 // 16-bit outputs with K = 768, N % 192 == 0 (ViT qkv / fc1): weights stationary in registers (gemm16_wst.hip); 1 = products without
-                                           // activation, 2 = GELU epilogues too; 3 / 4 = the same on the one-wave-per-SIMD kernel with W in AGPRs.  Measured slower than the tile kernels (profiles/r06_gemm_wst.md): opt-in
-    {"gemm_wslab", 1, 0, 2},               // 16-bit outputs with K = 256 / 384 / 512 (XCiT / CSWin stage 3-4 / Mixer qkv and fc1): a column slab of W stationary in
-                                           // registers (gemm16_wslab.hip); 1 = GELU epilogues and M % 256 != 0 (where it measured faster), 2 = every product it takes
-    {"io16_occ", 4, 2, 4},                 // single-read SE on 16-bit activations (chan_io16.hip): workgroups per CU the grid is sized for, capped by the kernel's register budget
-    {"vit_tail", 1, 0, 1},                 // host policy (read by the binding): 1 = a ViT that pools token 0 runs its LAST encoder block through mi355_vit_tail_fwd
-                                           // (only the rows that token needs: vit_tail.hip); 0 = the full block
+static const OptDesc kOpts[O_COUNT] = {             // from the same list as enum Opt (common.h), so row i describes option i
+#define MI355_OPT(id, key, def, lo, hi) {key, def, lo, hi},
+#include "options.h"
+#undef MI355_OPT
 };
-static_assert(sizeof(kOpts) / sizeof(kOpts[0]) == O_COUNT, "one table row per option, in enum order");
 namespace {
 constexpr long OPT_UNSET = (long)0x8000000000000000ull;              // a device block entry that follows the process default
 struct OptBlock { std::atomic<long> v[O_COUNT]; };
@@ -77,19 +34,19 @@ int cur_dev() {
     if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
     return dev >= 0 && dev < MAX_DEV ? dev : 0;
 }
-void opt_init() {
+void init_opts() {
     std::call_once(g_opt_once, [] {
         for (int i = 0; i < O_COUNT; ++i) g_def[i].store(kOpts[i].def, std::memory_order_relaxed);
         for (auto& b : g_opt)
             for (int i = 0; i < O_COUNT; ++i) b.v[i].store(OPT_UNSET, std::memory_order_relaxed);
     });
 }
-inline long opt(Opt o) {
-    opt_init();
+}  // namespace
+long opt(Opt o) {
+    init_opts();
     const long v = g_opt[cur_dev()].v[o].load(std::memory_order_relaxed);
     return v != OPT_UNSET ? v : g_def[o].load(std::memory_order_relaxed);
 }
-}  // namespace
 
 char* err_buf() { return g_err; }
 
@@ -100,31 +57,6 @@ int fail(int code, const char* fmt, ...) {
     va_end(ap);
     return code;
 }
-long opt_chunk_images() { return opt(O_CHUNK_IMAGES); }
-long opt_nt() { return opt(O_NT); }
-long opt_reverse() { return opt(O_REVERSE); }
-long opt_eca_single() { return opt(O_ECA_SINGLE); }
-long opt_se_single() { return opt(O_SE_SINGLE); }
-long opt_cbam_single() { return opt(O_CBAM_SINGLE); }
-long opt_ws_persistent() { return opt(O_WS_PERSISTENT); }
-long opt_ln_fold() { return opt(O_LN_FOLD); }
-long opt_gemm_pa16() { return opt(O_GEMM_PA16); }
-long opt_gemm_pa_block() { return opt(O_GEMM_PA_BLOCK); }
-long opt_gemm_pa_tail() { return opt(O_GEMM_PA_TAIL); }
-long opt_lpi_patch() { return opt(O_LPI_PATCH); }
-long opt_mixer_early() { return opt(O_MIXER_EARLY); }
-long opt_gemm_small() { return opt(O_GEMM_SMALL); }
-long opt_mlp_tt4() { return opt(O_MLP_TT4); }
-long opt_mixer_stats() { return opt(O_MIXER_STATS); }
-long opt_attn_nw() { return opt(O_ATTN_NW); }
-long opt_gemm_w4() { return opt(O_GEMM_W4); }
-long opt_range_fallback() { return opt(O_RANGE_FALLBACK); }
-long opt_gemm_wreg() { return opt(O_GEMM_WREG); }
-long opt_xca_tr() { return opt(O_XCA_TR); }
-long opt_mlp_wide() { return opt(O_MLP_WIDE); }
-long opt_gemm_wst() { return opt(O_GEMM_WST); }
-long opt_gemm_wslab() { return opt(O_GEMM_WSLAB); }
-long opt_vit_tail() { return opt(O_VIT_TAIL); }
 
 // ---- workspaces of the granule-exchange kernels (chan_fused.hip, cbam_single.hip, chan_stat.hip) ---------------------------------
 // A granule is valid when it carries the tag of the CURRENT launch = the workspace's epoch word + 1 (advanced on the device by the
@@ -151,7 +83,7 @@ bool stream_is_capturing(hipStream_t st) {
 // region was zeroed for this shape.  Under stream capture an unknown region stays unknown (the memset the caller records runs at
 // replay time, not now); a known one needs nothing.
 bool ws_known(const void* region, unsigned long long key, hipStream_t st) {
-    if (!opt_ws_persistent()) return false;
+    if (!opt(O_WS_PERSISTENT)) return false;
     std::lock_guard<std::mutex> lk(g_ws_mu);
     auto it = g_ws.find(region);
     if (it != g_ws.end() && it->second.key == key) return true;
@@ -484,15 +416,6 @@ int resident_slots(int per_cu) {
     return ncu * per_cu;
 }
 
-long opt_zoo_single() { return opt(O_ZOO_SINGLE); }
-long opt_stem_direct() { return opt(O_STEM_DIRECT); }
-long opt_se_occ() { return opt(O_SE_OCC); }
-long opt_io16_occ() { return opt(O_IO16_OCC); }
-long opt_gemm_variant() { return opt(O_GEMM_VARIANT); }
-long opt_gemm_splitk() { return opt(O_GEMM_SPLITK); }
-long opt_gemm_pa() { return opt(O_GEMM_PA); }
-long opt_da_fused() { return opt(O_DA_FUSED); }
-long opt_da_ranges() { return opt(O_DA_RANGES); }
 static int opt_index(const char* key) {
     for (int i = 0; i < O_COUNT; ++i)
         if (std::strcmp(key, kOpts[i].key) == 0) return i;
@@ -503,7 +426,7 @@ int opt_set(const char* key, long value, bool as_default) {
     if (i < 0) return fail(MI355_EINVAL, "mi355_set_option: unknown key '%s'", key);
     const bool ok = (value >= kOpts[i].lo && value <= kOpts[i].hi) || (i == O_SPIN_LIMIT && value == 0);
     if (!ok) return fail(MI355_EINVAL, "mi355_set_option: '%s' accepts %ld .. %ld, got %ld", key, kOpts[i].lo, kOpts[i].hi, value);
-    opt_init();
+    init_opts();
     if (as_default) g_def[i].store(value, std::memory_order_relaxed);
     else g_opt[cur_dev()].v[i].store(value, std::memory_order_relaxed);
     return MI355_OK;

@@ -485,7 +485,7 @@ int launch_attn(const AttnArgs& a, int B, int precision, hipStream_t st, const A
         else if (IO16 && P != 0) {                                                                                    \
             /* 193 .. 208 tokens = 13 query tiles: on 8 waves five waves carry two tiles and three carry one (13 / 16), on 7 waves */ \
             /* six carry two and one carries one (13 / 14): option "attn_nw" (A/B switch, round 5) */                    \
-            if (a.T >= 192 && a.T <= 208 && mi355::opt_attn_nw() == 7) GO_FULL(P, 14, 7, 1, 12);                          \
+            if (a.T >= 192 && a.T <= 208 && mi355::opt(mi355::O_ATTN_NW) == 7) GO_FULL(P, 14, 7, 1, 12);                          \
             else if (a.T >= 192) GO_FULL(P, 14, 8, 1, 12); else GO(P, 14, 8); }                                          \
         else GO(P, 14, 4);                               \
     } while (0)

@@ -425,7 +425,7 @@ size_t cbam_single_extra_bytes(int B, int C, int H, int W) {
 bool cbam_single_applicable(int C, int Cr, int H, int W, int ks) {
     Geo g;
     // all NB bands of an image must be resident together (two workgroups per CU): ADVICE r1, e.g. H = 1024 at R = 1
-    return opt_cbam_single() && pick_geometry(C, Cr, H, W, ks, g) && g.NB <= resident_slots(2);
+    return opt(O_CBAM_SINGLE) && pick_geometry(C, Cr, H, W, ks, g) && g.NB <= resident_slots(2);
 }
 
 int cbam_single(const float* x, const float* w1, const float* w2, const float* wconv, float* y, int B, int C, int Cr, int H, int W,
@@ -446,7 +446,7 @@ int cbam_single(const float* x, const float* w1, const float* w2, const float* w
     const long total_l = (long)B * g.NB;
     if (total_l > (1L << 30)) return fail(MI355_EUNSUPPORTED, "cbam_single: too many slices");
     a.total = (int)total_l;
-    a.nts = (opt_nt() & 2) ? 1 : 0;
+    a.nts = (opt(O_NT) & 2) ? 1 : 0;
     const bool full = (C == g.CL * g.NV);
     const int per_cu = 2;
     a.wlds = (g.smem_base + g.smem_w <= (size_t)(120 * 1024) / per_cu) ? 1 : 0;

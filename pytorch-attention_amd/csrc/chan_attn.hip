@@ -420,16 +420,16 @@ struct Tune { int chunk; int ntl; int nts; int reverse; };
 
 inline Tune resolve_tune(int B, long bytes_per_image) {
     Tune t;
-    long ci = mi355::opt_chunk_images();
+    long ci = mi355::opt(mi355::O_CHUNK_IMAGES);
     if (ci <= 0) {   // auto: ~200 MB of x per chunk, so the chunk's re-read(s) are served by the 256 MiB Infinity Cache
         ci = (200L << 20) / (bytes_per_image > 0 ? bytes_per_image : 1);
         if (ci < 1) ci = 1;
     }
     t.chunk = ci > B ? B : (int)ci;
-    const long nt = mi355::opt_nt();
+    const long nt = mi355::opt(mi355::O_NT);
     t.ntl = (nt & 1) != 0;
     t.nts = (nt & 2) != 0;
-    t.reverse = mi355::opt_reverse() != 0;
+    t.reverse = mi355::opt(mi355::O_REVERSE) != 0;
     return t;
 }
 

@@ -313,7 +313,7 @@ size_t fused_state_bytes(int B) { return (((size_t)B + 2) * sizeof(u32) + 15) & 
 
 bool eca_single_applicable(int C, int k, int H, int W) {
     const long HW = (long)H * W;
-    return opt_eca_single() && (HW % 4 == 0) && (HW / 4 <= 16 * 64) && (C % ECW == 0) && (k - 1 <= 8) && (k & 1);
+    return opt(O_ECA_SINGLE) && (HW % 4 == 0) && (HW / 4 <= 16 * 64) && (C % ECW == 0) && (k - 1 <= 8) && (k & 1);
 }
 
 int eca_single(const float* x, const float* taps, float* y, int B, int C, int k, int H, int W, hipStream_t st) {
@@ -322,7 +322,7 @@ int eca_single(const float* x, const float* taps, float* y, int B, int C, int k,
     if (total_l > (1L << 30)) return fail(MI355_EUNSUPPORTED, "eca_single: too many slices");
     const int total = (int)total_l, per_xcd = (total + 7) / 8, grid = per_xcd * 8;
     const int nv = (n4 + 63) / 64;
-    const long nt = opt_nt();
+    const long nt = opt(O_NT);
     // loads are always plain: the halo rows are the neighbours' resident rows and should stay in the XCD's L2 (measured on MI355X
     // at the C2 shape: 0.307 ms plain vs 0.358 ms with non-temporal loads); "nt" bit1 still selects non-temporal stores.
 #define GO(NV_)                                                                                                        \
@@ -349,7 +349,7 @@ bool se_single_applicable(int C, int Cr, int H, int W) {
     const long HW = (long)H * W;
     // every slice of an image (C / 8 workgroups) has to be resident at the same time, or the image's workgroups wait for granules
     // nobody can publish: at least two workgroups per CU are resident in every configuration of the kernel
-    return opt_se_single() && (HW % 4 == 0) && (HW / 4 <= 16 * 64) && (C % ECW == 0) && ((size_t)(C + Cr) * 4 <= 48 * 1024) &&
+    return opt(O_SE_SINGLE) && (HW % 4 == 0) && (HW / 4 <= 16 * 64) && (C % ECW == 0) && ((size_t)(C + Cr) * 4 <= 48 * 1024) &&
            C / ECW <= resident_slots(2);
 }
 
@@ -373,7 +373,7 @@ int se_single(const float* x, const float* w1, const float* w2, float* y, int B,
     const int nv = (a.n4 + 63) / 64;
     // three workgroups per CU (<= 80 VGPRs) only while the row leaves room beside it: 13 float4 per lane (56 x 56) is the limit,
     // 16 (64 x 64) would spill 100+ bytes per lane and runs two per CU at 112 registers instead
-    const int occ = (opt_se_occ() == 3 && nv <= 13 && (!wlds || (size_t)(C + Cr + 2 * C * Cr) * 4 <= 50 * 1024)) ? 3 : 2;
+    const int occ = (opt(O_SE_OCC) == 3 && nv <= 13 && (!wlds || (size_t)(C + Cr + 2 * C * Cr) * 4 <= 50 * 1024)) ? 3 : 2;
     long grid = (long)resident_slots(occ);                // 512-thread workgroups per CU: 2 (<= 128 VGPRs) or 3 (<= 80)
     if (a.gpi > grid) return fail(MI355_EUNSUPPORTED, "se_single: an image needs %d resident workgroups, the device holds %ld", a.gpi, grid);
     if (grid > a.total) grid = a.total;
@@ -384,7 +384,7 @@ int se_single(const float* x, const float* w1, const float* w2, float* y, int B,
         if (e != hipSuccess) { ws_forget(state); return fail(MI355_EHIP, "se_single: zeroing -> %s", hipGetErrorString(e)); }
     }
     const size_t smem = (size_t)(C + Cr + (wlds ? 2 * C * Cr : 0)) * sizeof(float);
-    const bool nts = (opt_nt() & 2) != 0;
+    const bool nts = (opt(O_NT) & 2) != 0;
     const bool extra = ex.b1 || ex.b2 || ex.gate;
     if (extra) se_launch_nv<true>(nv, occ, nts, wlds, (int)grid, smem, st, a);
     else       se_launch_nv<false>(nv, occ, nts, wlds, (int)grid, smem, st, a);

@@ -795,7 +795,7 @@ inline size_t cbam_multipass_bytes(int B, int C, int H, int W) { return 2 * r16(
 // ---- single-read launchers ------------------------------------------------------------------------------------------------------------
 bool eca16_single_ok(int C, int k, int H, int W) {
     const long HW = (long)H * W;
-    return mi355::opt_eca_single() && (HW % 8 == 0) && (HW / 8 <= 8 * 64) && (C % ECW == 0) && (k - 1 <= 8) && (k & 1);
+    return mi355::opt(mi355::O_ECA_SINGLE) && (HW % 8 == 0) && (HW / 8 <= 8 * 64) && (C % ECW == 0) && (k - 1 <= 8) && (k & 1);
 }
 
 int eca16_single(const u16* x, const float* taps, u16* y, int B, int C, int k, int H, int W, int io, hipStream_t st) {
@@ -804,7 +804,7 @@ int eca16_single(const u16* x, const float* taps, u16* y, int B, int C, int k, i
     if (total_l > (1L << 30)) return mi355::fail(MI355_EUNSUPPORTED, "eca16_single: too many slices");
     const int total = (int)total_l, per_xcd = (total + 7) / 8, grid = per_xcd * 8;
     const int nv = (n8 + 63) / 64;
-    const int nts = (mi355::opt_nt() & 2) ? 1 : 0;
+    const int nts = (mi355::opt(mi355::O_NT) & 2) ? 1 : 0;
     MI355_TRACE(st, "eca16_halo_kernel io=%d C=%d HW=%d", io, C, HW);
 #define GO(IO_, NV_) eca16_halo_kernel<IO_, NV_><<<grid, 512, 0, st>>>(x, taps, y, C, k, HW, gpi, total, per_xcd, nts)
 #define GO_IO(IO_)                      \
@@ -827,7 +827,7 @@ bool se16_single_ok(int C, int Cr, int H, int W) {
     const long HW = (long)H * W;
     // every slice of an image (C / 8 workgroups) has to be resident at the same time: two workgroups per CU are resident in every
     // configuration (<= 128 VGPRs, <= 60 KB of LDS)
-    return mi355::opt_se_single() && (HW % 8 == 0) && (HW / 8 <= 8 * 64) && (C % ECW == 0) && ((size_t)(C + Cr) * 4 <= 48 * 1024) &&
+    return mi355::opt(mi355::O_SE_SINGLE) && (HW % 8 == 0) && (HW / 8 <= 8 * 64) && (C % ECW == 0) && ((size_t)(C + Cr) * 4 <= 48 * 1024) &&
            C / ECW <= mi355::resident_slots(2);
 }
 
@@ -844,14 +844,14 @@ int se16_single(const u16* x, const float* w1, const float* w2, u16* y, int B, i
     if (int rc = mi355::sync_pending("se16_single")) return rc;
     a.C = C; a.Cr = Cr; a.HW = H * W; a.gpi = C / ECW;
     a.inv = 1.0f / (float)a.HW;
-    a.nts = (mi355::opt_nt() & 2) ? 1 : 0;
+    a.nts = (mi355::opt(mi355::O_NT) & 2) ? 1 : 0;
     const long total_l = (long)B * a.gpi;
     if (total_l > (1L << 30)) return mi355::fail(MI355_EUNSUPPORTED, "se16_single: too many slices");
     a.total = (int)total_l;
     const bool wlds = (size_t)(C + Cr + 2 * (size_t)C * Cr) * sizeof(float) <= 60 * 1024;   // both weight matrices resident in LDS
     const size_t smem = ((size_t)C + Cr + (wlds ? 2 * (size_t)C * Cr : 0)) * sizeof(float);
     const int nv = (a.HW / 8 + 63) / 64;
-    int occ = (int)mi355::opt_io16_occ();                 // workgroups per CU the grid is sized for: 2 .. 4, as far as registers and LDS allow
+    int occ = (int)mi355::opt(mi355::O_IO16_OCC);                 // workgroups per CU the grid is sized for: 2 .. 4, as far as registers and LDS allow
     if (occ > se16_waves(nv <= 1 ? 1 : nv <= 2 ? 2 : nv <= 4 ? 4 : nv <= 7 ? 7 : 8) / 2) occ = se16_waves(nv <= 1 ? 1 : nv <= 2 ? 2 : nv <= 4 ? 4 : nv <= 7 ? 7 : 8) / 2;
     while (occ > 2 && smem * occ > 150 * 1024) --occ;
     long grid = (long)mi355::resident_slots(occ);
@@ -877,7 +877,7 @@ int se16_single(const u16* x, const float* w1, const float* w2, u16* y, int B, i
 bool cbam16_single_ok(int C, int Cr, int H, int W, int ks) {
     Geo g;
     // all NB bands of an image must be resident together (two workgroups per CU); the exchange area is the fp32 kernel's
-    return mi355::opt_cbam_single() && geometry(C, Cr, H, W, ks, g) && g.NB <= mi355::resident_slots(2) &&
+    return mi355::opt(mi355::O_CBAM_SINGLE) && geometry(C, Cr, H, W, ks, g) && g.NB <= mi355::resident_slots(2) &&
            mi355::cbam_single_extra_bytes(1, C, H, W) != 0;
 }
 
@@ -899,7 +899,7 @@ int cbam16_single(const u16* x, const float* w1, const float* w2, const float* w
     const long total_l = (long)B * g.NB;
     if (total_l > (1L << 30)) return mi355::fail(MI355_EUNSUPPORTED, "cbam16_single: too many slices");
     a.total = (int)total_l;
-    a.nts = (mi355::opt_nt() & 2) ? 1 : 0;
+    a.nts = (mi355::opt(mi355::O_NT) & 2) ? 1 : 0;
     const bool full = (C == g.CL * g.NV);
     a.wlds = (g.smem_base + g.smem_w <= (size_t)(120 * 1024) / 2) ? 1 : 0;
     const size_t smem = g.smem_base + (a.wlds ? g.smem_w : 0);
@@ -956,7 +956,7 @@ void pool16(bool with_max, bool vec, const u16* x, float* avg, float* mx, long r
 template <int IO>
 void scale16(bool vec, const u16* x, const float* gc, const float* gs, u16* y, long rows, int C, int HW, hipStream_t st) {
     const int grid = cdiv(rows, 4);
-    const int nts = (mi355::opt_nt() & 2) ? 1 : 0;
+    const int nts = (mi355::opt(mi355::O_NT) & 2) ? 1 : 0;
     MI355_TRACE(st, "scale16_kernel io=%d HW=%d", IO, HW);
     if (vec) scale16_kernel<IO, true><<<grid, 256, 0, st>>>(x, gc, gs, y, rows, C, HW, nts);
     else     scale16_kernel<IO, false><<<grid, 256, 0, st>>>(x, gc, gs, y, rows, C, HW, nts);

@@ -323,7 +323,7 @@ int run(StatArgs a, int H, int W, void* ws, size_t ws_bytes, hipStream_t st) {
     const int B = a.B, C = a.C;
     a.HW = H * W;
     constexpr bool XCH = MODE >= M_GCTG;
-    const bool single = mi355::opt_zoo_single() && (a.HW % 4 == 0) && (a.HW / 4 <= 16 * 64) && (C % ECW == 0) && aligned16(a.x) &&
+    const bool single = mi355::opt(mi355::O_ZOO_SINGLE) && (a.HW % 4 == 0) && (a.HW / 4 <= 16 * 64) && (C % ECW == 0) && aligned16(a.x) &&
                         aligned16(a.y) && (size_t)C * 4 <= 48 * 1024 && (MODE != M_LCT || a.i0 <= C) &&
                         (!XCH || C / ECW <= mi355::resident_slots(2));     // an image's slices must all be resident to exchange granules
     if (single) {
@@ -353,7 +353,7 @@ int run(StatArgs a, int H, int W, void* ws, size_t ws_bytes, hipStream_t st) {
             }
         }
         const size_t smem = XCH ? (size_t)C * 4 : 0;
-        const bool nts = (mi355::opt_nt() & 2) != 0;
+        const bool nts = (mi355::opt(mi355::O_NT) & 2) != 0;
 #define GO(NV_)                                                                                        \
         do {                                                                                           \
             if (nts) stat_single_kernel<MODE, NV_, true><<<(int)grid, 512, smem, st>>>(a);             \

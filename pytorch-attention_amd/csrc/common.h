@@ -13,36 +13,14 @@
 namespace mi355 {
 char* err_buf();                      // thread-local 512-byte buffer (defined in api.hip)
 int   fail(int code, const char* fmt, ...);
-long  opt_chunk_images();
-long  opt_nt();
-long  opt_reverse();
-long  opt_gemm_variant();
-long  opt_gemm_splitk();
-long  opt_gemm_pa();
-long  opt_da_fused();
-long  opt_da_ranges();
-long  opt_eca_single();
-long  opt_se_single();
-long  opt_se_occ();
-long  opt_io16_occ();
-long  opt_ws_persistent();
-long  opt_ln_fold();
-long  opt_gemm_pa16();
-long  opt_gemm_pa_block();
-long  opt_gemm_pa_tail();
-long  opt_lpi_patch();
-long  opt_mixer_early();
-long  opt_gemm_small();
-long  opt_mlp_tt4();
-long  opt_mixer_stats();
-long  opt_attn_nw();
-long  opt_gemm_w4();
-long  opt_gemm_wreg();
-long  opt_xca_tr();
-long  opt_mlp_wide();
-long  opt_gemm_wst();
-long  opt_gemm_wslab();
-long  opt_vit_tail();
+// ---- tuning options: the list is options.h; opt() reads one on the calling thread's current device (api.hip) ----
+enum Opt {
+#define MI355_OPT(id, key, def, lo, hi) O_##id,
+#include "options.h"
+#undef MI355_OPT
+    O_COUNT
+};
+long  opt(Opt o);
 // LayerNorm of strided rows plus an addend, written in the 16-bit operand format (layernorm.hip; the pooled-token tail of vit_tail.hip)
 int   layernorm16_rows(const float* x, long ldx, const float* add, float* xs, const float* weight, const float* bias, void* y16, int rows,
                        int cols, float eps, int precision, hipStream_t st);
@@ -59,7 +37,6 @@ hipError_t ws_zero_async(void* p, size_t bytes, hipStream_t st);   // zero an ex
 unsigned* sync_err_word_on(hipStream_t st);     // sync_err_word(), but never allocates inside a stream capture (may return null there)
 bool  stream_is_capturing(hipStream_t st);      // hipGraph capture in progress on this stream
 void  ws_forget_range(const void* base, size_t bytes);
-long  opt_cbam_single();
 // ---- exchange-kernel failure reporting (api.hip) ----------------------------------------------------------------------------
 // The single-read kernels bound their inter-workgroup polls.  A poll that runs out stores a non-zero code into a pinned,
 // device-visible host word of the LAUNCHING thread (system-scope store, no synchronisation needed to read it); every later library entry
@@ -101,8 +78,6 @@ struct TraceScope {
 };
 #define MI355_TRACE(st, ...) mi355::TraceScope trace_scope_(st, __VA_ARGS__)
 int   func_dynamic_lds(const void* fn, int bytes);   // hipFuncAttributeMaxDynamicSharedMemorySize once per (kernel, device): api.hip
-long  opt_zoo_single();
-long  opt_stem_direct();
 bool  stem_conv_applicable(int Cin, int Cout, int KH, int KW, int in_layout, const float* bias, const float* pos, const float* y);
 int   stem_conv(const float* x, const float* w, const float* bias, const float* pos, float* y, int B, int Cin, int H, int W, int Cout, int KH,
                 int KW, int stride, int pad, int ldw, int in_layout, int act, hipStream_t st);

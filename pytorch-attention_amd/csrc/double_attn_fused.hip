@@ -539,9 +539,9 @@ inline size_t r256(size_t n) { return (n + 255) & ~(size_t)255; }
 int plan_ranges(int B, int tiles) {
     const int ncu = mi355::resident_slots(1);
     int S = (ncu + B - 1) / B;
-    if (mi355::opt_da_ranges() > 0) S = (int)mi355::opt_da_ranges();   // pinned: the summation order over pixels no longer depends on B
+    if (mi355::opt(mi355::O_DA_RANGES) > 0) S = (int)mi355::opt(mi355::O_DA_RANGES);   // pinned: the summation order over pixels no longer depends on B
     if (S > MAXS) S = MAXS;
-    if (S > tiles / 4 && mi355::opt_da_ranges() == 0) S = tiles / 4;
+    if (S > tiles / 4 && mi355::opt(mi355::O_DA_RANGES) == 0) S = tiles / 4;
     if (S > tiles) S = tiles;
     if (S < 1) S = 1;
     const int per = (tiles + S - 1) / S;

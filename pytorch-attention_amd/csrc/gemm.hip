@@ -509,7 +509,7 @@ int mi355_conv2d_tokens_fwd(const float* x, const float* weight, const float* bi
     MI355_CHECK_ARG(ldw >= K && (ldw & 3) == 0);
     if (!aligned16(x) || !aligned16(weight) || (in_layout == 1 && (Cin & 3)))
         return mi355::fail(MI355_EUNSUPPORTED, "mi355_conv2d_tokens_fwd: 16-byte aligned buffers and, for token-major input, Cin %% 4 == 0 (Cin=%d)", Cin);
-    if (act != MI355_ACT_RELU && mi355::opt_stem_direct() && mi355::stem_conv_applicable(Cin, Cout, KH, KW, in_layout, bias, pos, y)) {
+    if (act != MI355_ACT_RELU && mi355::opt(mi355::O_STEM_DIRECT) && mi355::stem_conv_applicable(Cin, Cout, KH, KW, in_layout, bias, pos, y)) {
         const int rc = mi355::stem_conv(x, weight, bias, pos, y, B, Cin, H, W, Cout, KH, KW, stride, pad, ldw, in_layout, act,
                                         static_cast<hipStream_t>(stream));       // narrow stem layers: direct fp32 kernel (stem_conv.hip)
         if (rc) return rc;

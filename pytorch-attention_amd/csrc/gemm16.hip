@@ -469,7 +469,7 @@ int checked(int rc) {
 // caller in the error texts, `instead` what to use where the kernel is not built for the shape.  MI355_OK: launched, not yet checked.
 int linear16_wreg_fwd(G16Args& g, const void* X16, const void* W16, const float* bias, const float* resid, float* Y, int M, int N, int K,
                       int ldx, int ldy, int precision, hipStream_t st, const char* entry, const char* instead) {
-    if (!aligned16(X16) || !aligned16(W16) || !aligned16(Y) || !aligned16(resid) || (bias && !aligned16(bias)) || !mi355::opt_gemm_wreg())
+    if (!aligned16(X16) || !aligned16(W16) || !aligned16(Y) || !aligned16(resid) || (bias && !aligned16(bias)) || !mi355::opt(mi355::O_GEMM_WREG))
         return mi355::fail(MI355_EUNSUPPORTED, "%s: 16-byte aligned buffers and option gemm_wreg = 1 required", entry);
     g.A = X16; g.B = W16; g.C = Y; g.bias = bias; g.resid = resid;
     g.M = M; g.N = N; g.K = K; g.lda = ldx; g.ldb = K; g.ldc = ldy; g.act = MI355_ACT_NONE;
@@ -513,7 +513,7 @@ int mi355_linear16_x32_fwd(const float* X32, const void* W16, const float* bias,
     MI355_CHECK_ARG(X32 && W16 && Y16 && M > 0 && N > 0 && K > 0 && ldx >= K && ldy >= N);
     MI355_CHECK_ARG(act == MI355_ACT_NONE || act == MI355_ACT_GELU);
     MI355_CHECK_ARG(precision == MI355_PREC_FP16 || precision == MI355_PREC_BF16);
-    if (!mi355::opt_gemm_wslab()) return MI355_EUNSUPPORTED;
+    if (!mi355::opt(mi355::O_GEMM_WSLAB)) return MI355_EUNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     G16Args g{};
     g.Af = X32; g.B = W16; g.C = Y16; g.bias = bias;
@@ -582,8 +582,8 @@ int mi355::linear16_dispatch(const G16Args& g, int out16, int precision, void* w
     const int M = g.M, N = g.N, K = g.K;
     if (g.resid_period && (K == 64 || K == 128 || out16 || !g.resid)) return MI355_EUNSUPPORTED;
     const struct { long variant, wst, wslab, pa, pa16, pa_tail, wreg, w4; } opt = {
-        mi355::opt_gemm_variant(), mi355::opt_gemm_wst(), mi355::opt_gemm_wslab(), mi355::opt_gemm_pa(), mi355::opt_gemm_pa16(),
-        mi355::opt_gemm_pa_tail(), mi355::opt_gemm_wreg(), mi355::opt_gemm_w4()};
+        mi355::opt(mi355::O_GEMM_VARIANT), mi355::opt(mi355::O_GEMM_WST), mi355::opt(mi355::O_GEMM_WSLAB), mi355::opt(mi355::O_GEMM_PA), mi355::opt(mi355::O_GEMM_PA16),
+        mi355::opt(mi355::O_GEMM_PA_TAIL), mi355::opt(mi355::O_GEMM_WREG), mi355::opt(mi355::O_GEMM_W4)};
     const int ncu = mi355::resident_slots(1);
     const bool gelu = g.act == MI355_ACT_GELU;
     long variant = opt.variant;

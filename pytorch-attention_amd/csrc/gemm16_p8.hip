@@ -466,7 +466,7 @@ static void p8_plan(int M, int N, int K, int ncu, P8Plan& pl, int& grid, size_t&
     const int nk = K / g16::BK;
     int S = pl.left > 0 ? ncu / pl.left : 1;
     // a chunk saves nk * (1 - 1/S) K-tiles of ~1.75 us and costs a slab round trip (~15-20 us): only long reductions split
-    if (nk < 24 || !opt_gemm_splitk()) S = 1;
+    if (nk < 24 || !opt(O_GEMM_SPLITK)) S = 1;
     if (S > nk / 8) S = nk / 8;
     if (S > 8) S = 8;
     if (S < 1) S = 1;

@@ -654,7 +654,7 @@ int gemm16_pa(const g16::G16Args& g, int out16, int precision, hipStream_t st, i
     const int tiles_m = swap ? g.M / 256 : g.M / 128;
     const long ntiles = (long)tiles_m * pl.tiles_n;
     // blocked tile order for wide outputs (>= 8 column tiles, a multiple of 4): 8 row tiles x 4 column tiles per block
-    if (opt_gemm_pa_block() && pl.tiles_n >= 8 && (pl.tiles_n & 3) == 0 && tiles_m >= 8) {
+    if (opt(O_GEMM_PA_BLOCK) && pl.tiles_n >= 8 && (pl.tiles_n & 3) == 0 && tiles_m >= 8) {
         pl.blk_rows = 8; pl.blk_cols = 4; pl.blk_lim = (tiles_m / 8) * 8;
     }
     if (ntiles >= (1L << 22) || pl.tiles_n >= 512) return MI355_EUNSUPPORTED;           // range of the magic-number quotients

@@ -306,7 +306,7 @@ int gemm16_wst(const G16Args& g, int out16, int precision, hipStream_t st) {
     if (nslab > ncu || (long)g.M < 32L * 8 * (ncu / nslab)) return MI355_EUNSUPPORTED;     // too few rows to amortise the resident weights
     MI355_TRACE(st, "gemm16_wst_kernel<%s,out16> M=%d N=%d K=%d%s", precision == MI355_PREC_FP16 ? "f16" : "bf16", g.M, g.N, g.K,
                 g.act == MI355_ACT_GELU ? " gelu" : "");
-    if (opt_gemm_wst() >= 3) {                                         // one wave per SIMD, weight fragments in AGPRs (256-column slabs, M % 32 == 0)
+    if (opt(O_GEMM_WST) >= 3) {                                         // one wave per SIMD, weight fragments in AGPRs (256-column slabs, M % 32 == 0)
         if ((g.N & 255) || (g.M & 31) || (long)g.lda * 32 * 2 >= (1L << 31)) return MI355_EUNSUPPORTED;
         const int ns = g.N / 256;
         if (g.act == MI355_ACT_GELU) {

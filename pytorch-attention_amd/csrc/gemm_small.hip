@@ -109,7 +109,7 @@ namespace mi355 {
 // MI355_EUNSUPPORTED (nothing launched) unless the product is small enough that the 128 x 128 engine would leave most CUs idle.
 int gemm_small_nt(const float* A, const float* B, const float* bias, float* C, int M, int N, int K, int lda, int ldb, int ldc, int precision,
                   hipStream_t st) {
-    if (!opt_gemm_small()) return MI355_EUNSUPPORTED;
+    if (!opt(O_GEMM_SMALL)) return MI355_EUNSUPPORTED;
     if ((K & 3) || (lda & 3) || (ldb & 3) || !aligned16(A) || !aligned16(B) || K < 32) return MI355_EUNSUPPORTED;
     const long big_tiles = (long)cdiv(M, 128) * cdiv(N, 128), tiles = (long)cdiv(M, 16) * cdiv(N, 32);
     const int ncu = resident_slots(1);

@@ -358,7 +358,7 @@ int mi355_mixer_token_fwd(const float* x, const float* ln_w, const float* ln_b, 
     hipStream_t st = static_cast<hipStream_t>(stream);
     float* stats = static_cast<float*>(ws);
     const long rows = (long)B * N;
-    const bool instats = mi355::opt_mixer_stats() != 0 && C == 512;    // statistics inside the token kernel (phase 0; built for C = 512) or by the pre-pass
+    const bool instats = mi355::opt(mi355::O_MIXER_STATS) != 0 && C == 512;    // statistics inside the token kernel (phase 0; built for C = 512) or by the pre-pass
     if (!instats) {
         const int sgrid = (int)(cdiv(rows, 4) < 8192 ? cdiv(rows, 4) : 8192);
         MI355_TRACE(st, "row_stats_kernel rows=%ld cols=%d", rows, C);
@@ -374,7 +374,7 @@ int mi355_mixer_token_fwd(const float* x, const float* ln_w, const float* ln_b, 
     const long grid = (long)B * a.halves;
     if (grid >= (1L << 31)) return mi355::fail(MI355_EUNSUPPORTED, "mi355_mixer_token_fwd: batch too large");
     a.ovf = precision == MI355_PREC_FP16 ? mi355::range_word(st) : nullptr;
-    const bool early = mi355::opt_mixer_early() != 0;
+    const bool early = mi355::opt(mi355::O_MIXER_EARLY) != 0;
     MI355_TRACE(st, "mixer_token_kernel%s%s B=%d C=%d", early ? "<early>" : "", instats ? "<stats>" : "", B, C);
 #define MIXER_LAUNCH(P_, E_, S_)                                                                                                      \
     do {                                                                                                                             \

@@ -433,7 +433,7 @@ extern "C" int mi355_mlp_fused_fwd(const float* x, const void* w1_16, const floa
     MI355_CHECK_ARG(layernorm >= 0 && layernorm <= 3);                          // flag word: bit 0 LayerNorm, bit 1 range proven
     if (!aligned16(x) || !aligned16(y) || !aligned16(w1_16) || !aligned16(w2_16))
         return mi355::fail(MI355_EUNSUPPORTED, "mi355_mlp_fused_fwd: 16-byte aligned buffers required");
-    if (mi355::mlp_wide_applicable(C, hidden) && mi355::opt_mlp_wide()) {        // C = 256 / 384: the weight-split kernel (mlp_wide.hip), W2 row-major
+    if (mi355::mlp_wide_applicable(C, hidden) && mi355::opt(mi355::O_MLP_WIDE)) {        // C = 256 / 384: the weight-split kernel (mlp_wide.hip), W2 row-major
         if ((b2 && !aligned16(b2)) || (gamma && !aligned16(gamma)) || !aligned16(b1))
             return mi355::fail(MI355_EUNSUPPORTED, "mi355_mlp_fused_fwd: 16-byte aligned bias / LayerScale vectors required at C = %d", C);
         if (int rc = mi355::mlp_wide(x, w1_16, b1, w2_16, b2, gamma, y, M, C, layernorm, eps, precision, static_cast<hipStream_t>(stream))) return rc;
@@ -467,7 +467,7 @@ extern "C" int mi355_mlp_fused_fwd(const float* x, const void* w1_16, const floa
     }
     constexpr size_t smem = mlp_smem<64, 256>();
     static_assert(smem <= 160 * 1024, "LDS budget");
-    const bool tt4 = mi355::opt_mlp_tt4() != 0;
+    const bool tt4 = mi355::opt(mi355::O_MLP_TT4) != 0;
     const long nchunk = (M + (tt4 ? 63 : 31)) / (tt4 ? 64 : 32);
     long grid = (nchunk + (tt4 ? 7 : 15)) / (tt4 ? 8 : 16);
     if (grid > ncu) grid = ncu;
@@ -523,7 +523,7 @@ extern "C" int mi355_proj_mlp_fused_fwd(const float* x, const void* ctx16, const
     }
     constexpr size_t smem = mlp_smem<64, 256>(true);
     static_assert(smem <= 160 * 1024, "LDS budget");
-    const bool tt4 = mi355::opt_mlp_tt4() != 0;
+    const bool tt4 = mi355::opt(mi355::O_MLP_TT4) != 0;
     const long nchunk = (M + (tt4 ? 63 : 31)) / (tt4 ? 64 : 32);
     long grid = (nchunk + (tt4 ? 7 : 15)) / (tt4 ? 8 : 16);
     if (grid > ncu) grid = ncu;

@@ -789,7 +789,7 @@ int mi355_xca16_fwd(const void* qkv, int qkv_is16, const float* temperature, voi
     MI355_CHECK_ARG(aligned16(qkv) && aligned16(out16));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int grid = B * heads;
-    if (qkv_is16 && N <= 224 && mi355::opt_xca_tr() && (d == 32 || d == 48 || d == 64)) {
+    if (qkv_is16 && N <= 224 && mi355::opt(mi355::O_XCA_TR) && (d == 32 || d == 48 || d == 64)) {
         // 16-bit q / k / v, at most 224 tokens: covariance on the 16-bit matrix pipe from ONE transposed LDS image (xca_tr_kernel)
         MI355_TRACE(st, "xca_tr_kernel<d=%d> B=%d N=%d heads=%d", d, B, N, heads);
 #define XTR(D_)                                                                                                                          \
@@ -832,7 +832,7 @@ static int lpi_launch(const float* x, const float* w1, const float* b1, const fl
                       const float* bn_var, float bn_eps, const float* w2, const float* b2, const float* gamma, const float* resid,
                       float* y, int B, int H, int W, int C, const float* stats, const float* ln_w, const float* ln_b, hipStream_t st) {
     if (H * W > 32 * LPI_TMAX) return mi355::fail(MI355_EUNSUPPORTED, "mi355_lpi_fwd: %dx%d token grid exceeds the LDS tile (<= 256 tokens)", H, W);
-    if (H == 14 && W == 14 && (C % LPI_CG) == 0 && mi355::opt_lpi_patch() && aligned16(x) && aligned16(y) && (!resid || aligned16(resid)) &&
+    if (H == 14 && W == 14 && (C % LPI_CG) == 0 && mi355::opt(mi355::O_LPI_PATCH) && aligned16(x) && aligned16(y) && (!resid || aligned16(resid)) &&
         (!stats || (aligned16(ln_w) && aligned16(ln_b)))) {
         // 2 x 2 patches per lane, channel-quad-major planes (see lpi_patch_kernel)
         constexpr int PLS = (8 * 8) | 1, CQS = lpi_quad_pitch(PLS);

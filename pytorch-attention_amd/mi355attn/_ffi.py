@@ -9,6 +9,7 @@ as /opt/rocm's), so loading torch first makes our library bind to the runtime to
 one HIP runtime per process, shared streams and device pointers.
 """
 import collections
+import contextlib
 import ctypes
 import os
 import threading
@@ -336,6 +337,25 @@ def set_option(key, value):
 
 def get_option(key):
     return lib().mi355_get_option(key.encode())
+
+
+@contextlib.contextmanager
+def options(**kw):
+    """Scoped set_option: `with options(se_single=0, nt=1): ...` sets the named options for the body and puts back, in reverse
+    order, the values they had on entry -- also when the body raises, and also when one of the keys is refused (the keys set before
+    it are restored, then the error propagates).  Like set_option it acts on the calling thread's CURRENT device, so the body must
+    not leave the block with another device current than it entered with.  The value put back is the effective one read on entry
+    (a device that followed the process default ends up pinned to that default's value)."""
+    saved = [(key, get_option(key)) for key in kw]
+    done = 0
+    try:
+        for key, value in kw.items():
+            set_option(key, value)          # raises on an unknown key or a value out of range
+            done += 1
+        yield
+    finally:
+        for key, old in reversed(saved[:done]):
+            set_option(key, old)
 
 
 def kernel_trace(fn):

@@ -196,7 +196,7 @@ def range_fallback_forward(module, forward, args, kwargs):
         # 16-bit activations (SELayer / ECALayer / CBAM): fp32 arithmetic and |y| <= |x|, nothing can saturate -- no arm, no wait, no re-run
         return forward(module, *args, **kwargs)
     try:
-        passthrough = _ffi._capturing() or lib().mi355_get_option(b"range_fallback") != 1
+        passthrough = _ffi._capturing() or _ffi.get_option("range_fallback") != 1
     except RuntimeError:                                      # no HIP device in this process: the forward raises the package's own error
         passthrough = True
     if passthrough:
@@ -843,7 +843,7 @@ def mlp_fused_ok(C, hidden, precision=None):
         return False
     if (C, hidden) in ((64, 256), (128, 512)):
         return True
-    return (C, hidden) in ((256, 1024), (384, 1536)) and lib().mi355_get_option(b"mlp_wide") == 1
+    return (C, hidden) in ((256, 1024), (384, 1536)) and _ffi.get_option("mlp_wide") == 1
 
 
 def proj_mlp_fused_ok(C, hidden, precision=None):
@@ -991,7 +991,7 @@ def linear16_stats(x16, w16, bias, resid, eps, precision=None):
     w16 = _require16(w16, "w16", p)
     N, K = w16.shape
     M = x16.numel() // K
-    if not (N == K and K in (256, 384) and M >= 32 and resid is not None and lib().mi355_get_option(b"gemm_wreg") == 1):
+    if not (N == K and K in (256, 384) and M >= 32 and resid is not None and _ffi.get_option("gemm_wreg") == 1):
         return None
     bias, resid = _opt(bias, "bias"), require_device_f32(resid, "resid")
     y = torch.empty(x16.shape[:-1] + (N,), dtype=torch.float32, device=x16.device)
@@ -1011,7 +1011,7 @@ def linear16_ln16(x16, w16, bias, resid, ln, precision=None):
     w16 = _require16(w16, "w16", p)
     N, K = w16.shape
     M = x16.numel() // K
-    if not (N == K and K == 256 and M >= 32 and resid is not None and lib().mi355_get_option(b"gemm_wreg") == 1):
+    if not (N == K and K == 256 and M >= 32 and resid is not None and _ffi.get_option("gemm_wreg") == 1):
         return None
     bias, resid = _opt(bias, "bias"), require_device_f32(resid, "resid")
     lw, lb = require_device_f32(ln.weight, "ln.weight"), require_device_f32(ln.bias, "ln.bias")

@@ -32,7 +32,7 @@ def test_poll_timeout_is_reported_by_the_next_call(which):
     torch.manual_seed(5)
     x = torch.randn(64, 256, 56, 56, device="cuda")
     mi355attn.sync_status(wait=True)                       # clean slate
-    old = mi355attn.get_option("spin_limit")
+
     def launch():
         """One launch with the zero budget.  True when its own post-launch check already saw (and thereby cleared) the failure
         word -- the kernel can finish before the binding returns -- False when the failure is still pending."""
@@ -54,8 +54,7 @@ def test_poll_timeout_is_reported_by_the_next_call(which):
             assert "poll budget" in str(e)
         mi355attn.sync_status(wait=True)
 
-    try:
-        mi355attn.set_option("spin_limit", 0)
+    with mi355attn.options(spin_limit=0):
         if not launch():
             torch.cuda.synchronize()
             with pytest.raises(mi355attn.Mi355Error, match="poll budget"):
@@ -63,15 +62,12 @@ def test_poll_timeout_is_reported_by_the_next_call(which):
         drain()                                            # reported once, then clear
         seen = launch()                                    # times out again ...
         torch.cuda.synchronize()
-        mi355attn.set_option("spin_limit", old)
-        if seen:
-            drain()
-        if not seen:
-            with pytest.raises(mi355attn.Mi355Error, match="poll budget"):
-                with torch.no_grad():
-                    m(x)                                   # ... and the next launch refuses to run over it
-    finally:
-        mi355attn.set_option("spin_limit", old)
+    if seen:
+        drain()
+    if not seen:
+        with pytest.raises(mi355attn.Mi355Error, match="poll budget"):
+            with torch.no_grad():
+                m(x)                                       # ... and the next launch refuses to run over it
     mi355attn.sync_status(wait=True)
     with torch.no_grad():
         y = m(x[:3].contiguous())
@@ -121,14 +117,8 @@ def test_nan_in_x_propagates_like_the_reference(which, single):
         ref = O.eca_forward(x, eca.conv.weight.cpu())
     else:
         ref = O.cbam_forward(x, cbam.ca.fc[0].weight.cpu(), cbam.ca.fc[2].weight.cpu(), cbam.sa.conv.weight.cpu())
-    key = which + "_single"
-    old = mi355attn.get_option(key)
-    try:
-        mi355attn.set_option(key, single)
-        with torch.no_grad():
-            y = m(x.cuda()).cpu()
-    finally:
-        mi355attn.set_option(key, old)
+    with mi355attn.options(**{which + "_single": single}), torch.no_grad():
+        y = m(x.cuda()).cpu()
     mi355attn.sync_status(wait=True)
     assert torch.equal(torch.isnan(y), torch.isnan(ref)), \
         f"{which}: NaN pattern differs ({int(torch.isnan(y).sum())} vs {int(torch.isnan(ref).sum())} NaNs)"

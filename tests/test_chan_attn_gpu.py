@@ -57,17 +57,11 @@ def test_eca_single_read_kernel(shape):
     torch.manual_seed(11)
     x = torch.randn(*shape)
     xd = x.cuda()
-    old = mi355attn.get_option("eca_single")
-    try:
-        mi355attn.set_option("eca_single", 1)
-        with torch.no_grad():
-            y1 = eca.cuda()(xd).cpu()
-            y1b = eca(xd).cpu()
-        mi355attn.set_option("eca_single", 0)
-        with torch.no_grad():
-            y0 = eca(xd).cpu()
-    finally:
-        mi355attn.set_option("eca_single", old)
+    with mi355attn.options(eca_single=1), torch.no_grad():
+        y1 = eca.cuda()(xd).cpu()
+        y1b = eca(xd).cpu()
+    with mi355attn.options(eca_single=0), torch.no_grad():
+        y0 = eca(xd).cpu()
     assert torch.equal(y1, y1b)
     assert_parity(y1, O.eca_forward(x, eca.conv.weight.cpu()), 1e-5, f"eca single {shape}")
     assert_parity(y1, y0, 1e-6, "eca single read vs two pass")
@@ -84,16 +78,11 @@ def test_se_single_read_kernel(shape, monkeypatch):
     torch.manual_seed(13)
     x = torch.randn(*shape)
     xd = x.cuda()
-    try:
-        mi355attn.set_option("se_single", 1)
-        with torch.no_grad():
-            y1 = se.cuda()(xd).cpu()
-            y1b = se(xd).cpu()
-        mi355attn.set_option("se_single", 0)
-        with torch.no_grad():
-            y0 = se(xd).cpu()
-    finally:
-        mi355attn.set_option("se_single", 1)
+    with mi355attn.options(se_single=1), torch.no_grad():
+        y1 = se.cuda()(xd).cpu()
+        y1b = se(xd).cpu()
+    with mi355attn.options(se_single=0), torch.no_grad():
+        y0 = se(xd).cpu()
     assert torch.equal(y1, y1b)
     assert_parity(y1, O.se_forward(x, se.fc[0].weight.cpu(), se.fc[2].weight.cpu()), 1e-5, f"se single {shape}")
     assert_parity(y1, y0, 1e-6, "se single read vs two pass")
@@ -133,16 +122,11 @@ def test_cbam_single_read_kernel(shape, monkeypatch):
     torch.manual_seed(17)
     x = torch.randn(*shape)
     xd = x.cuda()
-    try:
-        mi355attn.set_option("cbam_single", 1)
-        with torch.no_grad():
-            y1 = cbam.cuda()(xd).cpu()
-            y1b = cbam(xd).cpu()
-        mi355attn.set_option("cbam_single", 0)
-        with torch.no_grad():
-            y0 = cbam(xd).cpu()
-    finally:
-        mi355attn.set_option("cbam_single", 1)
+    with mi355attn.options(cbam_single=1), torch.no_grad():
+        y1 = cbam.cuda()(xd).cpu()
+        y1b = cbam(xd).cpu()
+    with mi355attn.options(cbam_single=0), torch.no_grad():
+        y0 = cbam(xd).cpu()
     sd = {k: v.cpu() for k, v in cbam.state_dict().items()}
     assert torch.equal(y1, y1b)
     assert_parity(y1, O.cbam_forward(x, sd["ca.fc.0.weight"], sd["ca.fc.2.weight"], sd["sa.conv.weight"]), 1e-5, f"cbam single {shape}")
@@ -179,17 +163,12 @@ def test_persistent_workspace_epochs(monkeypatch):
     with torch.no_grad():
         first = [m(x).clone() for m, x in mods]
         for rnd in range(12):
-            if rnd == 4:
-                mi355attn.set_option("ws_persistent", 0)
-            if rnd == 7:
-                mi355attn.set_option("ws_persistent", 1)
-            if rnd == 9:                                   # detour through the two-pass kernel on the same dedicated workspace
-                mi355attn.set_option("se_single", 0)
-                se_a(xa)
-                mi355attn.set_option("se_single", 1)
-            for (m, x), f in zip(mods, first):
-                assert torch.equal(m(x), f), f"round {rnd}"
-    mi355attn.set_option("ws_persistent", 1)
+            with mi355attn.options(ws_persistent=0 if 4 <= rnd < 7 else 1):
+                if rnd == 9:                               # detour through the two-pass kernel on the same dedicated workspace
+                    with mi355attn.options(se_single=0):
+                        se_a(xa)
+                for (m, x), f in zip(mods, first):
+                    assert torch.equal(m(x), f), f"round {rnd}"
 
 
 def test_eca_single_is_independent_of_batch_grouping():
@@ -222,17 +201,10 @@ def test_chunk_option_does_not_change_results():
     torch.manual_seed(9)
     x = torch.randn(13, 64, 28, 28).cuda()
     outs = []
-    old = {k: mi355attn.get_option(k) for k in ("chunk_images", "nt", "reverse", "se_single", "eca_single", "cbam_single")}
-    for k in ("se_single", "eca_single", "cbam_single"):
-        mi355attn.set_option(k, 0)
-    for chunk, nt, rev in ((0, 3, 0), (1, 0, 0), (5, 1, 1), (13, 2, 1), (4, 3, 1)):
-        mi355attn.set_option("chunk_images", chunk)
-        mi355attn.set_option("nt", nt)
-        mi355attn.set_option("reverse", rev)
-        with torch.no_grad():
-            outs.append((se.cuda()(x).clone(), eca.cuda()(x).clone(), cbam.cuda()(x).clone()))
-    for k, v in old.items():
-        mi355attn.set_option(k, v)
+    with mi355attn.options(se_single=0, eca_single=0, cbam_single=0):
+        for chunk, nt, rev in ((0, 3, 0), (1, 0, 0), (5, 1, 1), (13, 2, 1), (4, 3, 1)):
+            with mi355attn.options(chunk_images=chunk, nt=nt, reverse=rev), torch.no_grad():
+                outs.append((se.cuda()(x).clone(), eca.cuda()(x).clone(), cbam.cuda()(x).clone()))
     for o in outs[1:]:
         for a, b in zip(outs[0], o):
             assert torch.equal(a, b)
@@ -326,16 +298,13 @@ def test_zoo_gates_vs_oracle(shape, single, monkeypatch):
     torch.manual_seed(32)
     x = torch.randn(B, C, H, W)
     xd = x.cuda()
-    mi355attn.set_option("zoo_single", single)
-    try:
+    with mi355attn.options(zoo_single=single):
         for name, m in mods.items():
             with torch.no_grad():
                 y = m.cuda()(xd)
                 y2 = m(xd)
             assert torch.equal(y, y2), name
             assert_parity(y.cpu(), _zoo_ref(name, m, x), 2e-5, f"{name} {shape} single={single}")
-    finally:
-        mi355attn.set_option("zoo_single", 1)
 
 
 def test_zoo_single_and_two_pass_agree_and_repeat():
@@ -351,11 +320,8 @@ def test_zoo_single_and_two_pass_agree_and_repeat():
             for _ in range(100):
                 y = m(x)
             assert torch.equal(y, first), name
-            mi355attn.set_option("zoo_single", 0)
-            try:
+            with mi355attn.options(zoo_single=0):
                 two = m(x)
-            finally:
-                mi355attn.set_option("zoo_single", 1)
         assert_parity(first.cpu(), two.cpu(), 2e-6, f"{name}: single read vs two passes")
 
 
@@ -426,12 +392,8 @@ def test_exchange_kernels_under_graph_capture_at_the_bench_shape():
         with torch.no_grad():
             want = [m(x) for m in mods]
         assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), f"replay {rep}"
-    mi355attn.set_option("se_single", 0); mi355attn.set_option("cbam_single", 0)
-    try:
-        with torch.no_grad():
-            multi = [m(x) for m in mods]
-    finally:
-        mi355attn.set_option("se_single", 1); mi355attn.set_option("cbam_single", 1)
+    with mi355attn.options(se_single=0, cbam_single=0), torch.no_grad():
+        multi = [m(x) for m in mods]
     assert_parity(got[0].cpu(), multi[0].cpu(), 2e-6, "SE single-read (replayed) vs two-pass")
     assert_parity(got[1].cpu(), multi[1].cpu(), 2e-6, "CBAM single-read (replayed) vs three-pass")
     mi355attn.sync_status(wait=True)
@@ -480,12 +442,8 @@ def test_se_variants_bias_and_hard_sigmoid(shape, single):
     a, g = SELayerBias(C, 4).eval(), SqueezeExcite(C).eval()
     perturb_all(a); perturb_all(g)
     x = torch.randn(*shape)
-    mi355attn.set_option("se_single", single)
-    try:
-        with torch.no_grad():
-            ya, yg = a.cuda()(x.cuda()).cpu(), g.cuda()(x.cuda()).cpu()
-    finally:
-        mi355attn.set_option("se_single", 1)
+    with mi355attn.options(se_single=single), torch.no_grad():
+        ya, yg = a.cuda()(x.cuda()).cpu(), g.cuda()(x.cuda()).cpu()
     sa, sg = {k: v.cpu() for k, v in a.state_dict().items()}, {k: v.cpu() for k, v in g.state_dict().items()}
     assert_parity(ya, O.se_ex_forward(x, sa["fc.0.weight"], sa["fc.0.bias"], sa["fc.2.weight"], sa["fc.2.bias"]), 1e-5, "se + bias")
     assert_parity(yg, O.se_ex_forward(x, sg["conv_reduce.weight"], sg["conv_reduce.bias"], sg["conv_expand.weight"], sg["conv_expand.bias"],

@@ -203,7 +203,6 @@ def test_poll_timeout_is_reported_only_to_the_launching_thread():
     xb = x[:3].contiguous()
     ref = O.se_forward(xb.cpu(), se.fc[0].weight.detach().cpu(), se.fc[2].weight.detach().cpu())
     sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
-    old = mi355attn.get_option("spin_limit")
     _settle()
 
     def a(bar):
@@ -211,13 +210,11 @@ def test_poll_timeout_is_reported_only_to_the_launching_thread():
             post = F._sync_check
             F._sync_check = lambda: None                       # no post-launch check: the report stays in the word (B is parked)
             try:
-                mi355attn.set_option("spin_limit", 0)
-                with torch.no_grad():
+                with mi355attn.options(spin_limit=0), torch.no_grad():
                     se(x)
-                sa.synchronize()
+                    sa.synchronize()
             finally:
                 F._sync_check = post
-                mi355attn.set_option("spin_limit", old)
             bar.wait()                                         # 1: A's failed exchange has run
             bar.wait()                                         # 2: B is done
             with pytest.raises(mi355attn.Mi355Error, match=r"code -4\).*poll budget"):
@@ -240,7 +237,6 @@ def test_poll_timeout_is_reported_only_to_the_launching_thread():
     try:
         _, y = _run_threads(a, b)
     finally:
-        mi355attn.set_option("spin_limit", old)
         _settle()
     assert_parity(y, ref, 1e-5, "B's SE launch next to A's reported time-out")
 

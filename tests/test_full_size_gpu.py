@@ -72,17 +72,11 @@ def _check(name, module, shape, ref_fn, fwd_args=(), tol=1e-3, strict_tol=5e-5, 
         assert_parity(sub.cpu(), y[PICK].cpu(), path_tol, name + " [batch independence, default options]")
         # DoubleAttention's analogue: the number of pixel ranges an image is cut into follows the batch size ("da_ranges" pins it).
         # ViT encoder chain (round 4): the LayerNorm fold needs rows % 128 == 0, so B = 256 folds and B = 3 does not ("ln_fold" pins it).
-        old_pin = [(k, mi355attn.get_option(k)) for k, _ in pin]
-        for k, v in pin:
-            mi355attn.set_option(k, v)
-        try:
+        with mi355attn.options(**dict(pin)):
             with torch.no_grad():
                 y0 = m(x, *fwd_args)
                 sub0 = m(x[PICK].contiguous(), *fwd_args)
             torch.cuda.synchronize()
-        finally:
-            for k, v in old_pin:
-                mi355attn.set_option(k, v)
         assert torch.equal(y0[PICK], sub0), name + f": output of an image depends on its batch neighbours ({pin})"
         assert_parity(y0[PICK].cpu(), ref, tol, name + f" [B=256, {pin}]")
         del y0, sub0
@@ -160,12 +154,9 @@ def test_c5_vit_base_full_size_with_the_layernorm_fold():
     from mi355attn.modules import VisionTransformer
     m = _seeded(lambda: VisionTransformer(num_heads=12))
     sd = _sd(m)
-    mi355attn.set_option("ln_fold", 1)
-    try:
+    with mi355attn.options(ln_fold=1):
         _check("VisionTransformer(ViT-Base/16) + ln_fold", m, (B, 3, 224, 224), lambda xs: O.vit_forward(xs, sd, 12, 12),
                pin=(("gemm_splitk", 0), ("ln_fold", 0)), path_tol=1e-3)
-    finally:
-        mi355attn.set_option("ln_fold", 0)
 
 
 def test_mixer_layer_full_size():

@@ -9,7 +9,6 @@ The CU count enters the choice (tile counts against one round of workgroups), so
 was recorded on.
 """
 import collections
-import contextlib
 
 import pytest
 import torch
@@ -134,19 +133,6 @@ def _recorded_cu_count():
         pytest.skip("the table was recorded on a 256-CU MI355X; the CU count enters the kernel choice")
 
 
-@contextlib.contextmanager
-def _options(opts):
-    import mi355attn
-    old = {k: mi355attn.get_option(k) for k in opts}
-    try:
-        for k, v in opts.items():
-            mi355attn.set_option(k, v)
-        yield
-    finally:
-        for k, v in old.items():
-            mi355attn.set_option(k, v)
-
-
 def _call(entry, M, N, K, out16, act, inputs, prec):
     """The call of a row as a closure (inputs made here, outside the traced region)."""
     from mi355attn import _ffi
@@ -197,7 +183,7 @@ def run_row(row, prec):
     import mi355attn
     _, entry, (M, N, K), out16, act, inputs, opts, _ = row
     fn = _call(entry, M, N, K, out16, act, inputs, prec)
-    with _options(opts), torch.no_grad():
+    with mi355attn.options(**opts), torch.no_grad():
         try:
             fn()                                    # first call: one-time weight preparation stays out of the tally
             torch.cuda.synchronize()

@@ -105,13 +105,10 @@ def test_general_form_when_single_read_is_switched_off(dtype):
     shape = (2, 512, 28, 28)
     x = _input(shape, dtype)
     xd = x.cuda()
-    old = {k: mi355attn.get_option(k) for k in ("se_single", "eca_single", "cbam_single")}
     blocks = _blocks(512)
-    try:
-        with torch.no_grad():
-            single = {name: m(xd) for name, m, _ in blocks}
-        for k in old:
-            mi355attn.set_option(k, 0)
+    with torch.no_grad():
+        single = {name: m(xd) for name, m, _ in blocks}
+    with mi355attn.options(se_single=0, eca_single=0, cbam_single=0):
         for name, m, ref in blocks:
             with torch.no_grad():
                 rows = mi355attn.kernel_trace(lambda: m(xd))
@@ -124,9 +121,6 @@ def test_general_form_when_single_read_is_switched_off(dtype):
             d = _ulps(y, single[name])
             print(f"[io16] {name} single vs general: {d} ulp")
             assert d <= 1, f"{name}: single-read and general form differ by {d} ulps"
-    finally:
-        for k, v in old.items():
-            mi355attn.set_option(k, v)
     _status()
 
 

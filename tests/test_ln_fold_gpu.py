@@ -19,13 +19,11 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(autouse=True)
-def _fold_on():
+def _ln_fold_enabled():
     """The fold is opt-in (option "ln_fold", default 0: DESIGN.md 6.2c): these tests switch it on for their duration."""
     import mi355attn
-    old = mi355attn.get_option("ln_fold")
-    mi355attn.set_option("ln_fold", 1)
-    yield
-    mi355attn.set_option("ln_fold", old)
+    with mi355attn.options(ln_fold=1):
+        yield
 
 
 def _ref_ln(y, gamma, beta, eps=1e-5):
@@ -165,12 +163,9 @@ def test_transformer_encoder_folded_vs_oracle(scale):
     with torch.no_grad():
         y = blk(xd)
         y2 = blk(xd)
-        mi355attn.set_option("ln_fold", 0)
-        try:
+        with mi355attn.options(ln_fold=0):
             assert not blk.fold_ok(xd)
             y_unf = blk(xd)
-        finally:
-            mi355attn.set_option("ln_fold", 1)
     mi355attn.range_status(wait=True)
     assert torch.equal(y, y2), "run-to-run results differ"
     assert_parity(y[pick].cpu(), ref, 1e-3, f"folded TransformerEncoder at scale {scale:g}")

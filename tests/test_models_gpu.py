@@ -18,7 +18,7 @@ import torch
 
 from conftest import assert_parity, rel_fro
 from model_cases import BY_ID, ROWS, build_row, rescale_cached, second_state
-from test_routes_gpu import TOL, _check_route, _options, _run
+from test_routes_gpu import TOL, _check_route, _run
 
 pytestmark = pytest.mark.gpu
 
@@ -61,7 +61,7 @@ def test_model_matches_fp64(rid, prec):
     ref = _oracle(row, "base", m.state_dict(), x)
     m = m.cuda()
     xd = x.cuda()
-    with _options(row.get("options")):
+    with mi355attn.options(**row.get("options", {})):
         _check(row, prec, m, xd, ref, "first forward")
         if row["cached"]:
             # the model caches tensors derived from these parameters: rescale them in place, the result must follow

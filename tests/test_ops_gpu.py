@@ -760,11 +760,8 @@ def test_stem_direct_option_switches_between_two_agreeing_paths():
     f = F()
     assert mi355attn.get_option("stem_direct") == 1
     direct, _ = f.conv2d_tokens(x, w, b, 3, 2, 1, 0, precision=0, act=f.ACT_GELU, pos=pos)
-    mi355attn.set_option("stem_direct", 0)
-    try:
+    with mi355attn.options(stem_direct=0):
         gemm, _ = f.conv2d_tokens(x, w, b, 3, 2, 1, 0, precision=0, act=f.ACT_GELU, pos=pos)
-    finally:
-        mi355attn.set_option("stem_direct", 1)
     ref = torch.nn.functional.conv2d(x.double().cpu(), w.double().cpu(), b.double().cpu(), stride=2, padding=1).flatten(2).transpose(1, 2)
     ref = gelu64(ref + pos.double().cpu())
     assert_parity(direct.cpu(), ref.float(), 5e-6, "direct stem conv")

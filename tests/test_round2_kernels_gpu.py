@@ -49,22 +49,19 @@ def test_persistent_gemm_matches_round1_kernel_and_fp64(M, N, K, prec, dt):
     gamma = torch.rand(N, device="cuda") + 0.5
     resid = torch.randn(M, N, device="cuda")
     combos = [dict(bias=b, out16=True), dict(bias=b, act=F.ACT_GELU, out16=True), dict(bias=b, resid=resid), dict(bias=None, gamma=gamma, resid=resid, act=F.ACT_GELU)]
-    try:
-        mi355attn.set_option("gemm_splitk", 0)
+    with mi355attn.options(gemm_splitk=0):
         for kw in combos:
-            mi355attn.set_option("gemm_variant", 7)
-            y7 = F.linear16(x16, w16, precision=prec, **kw)
-            mi355attn.set_option("gemm_variant", 15)
-            y15 = F.linear16(x16, w16, precision=prec, **kw)
-            y15b = F.linear16(x16, w16, precision=prec, **kw)
+            with mi355attn.options(gemm_variant=7):
+                y7 = F.linear16(x16, w16, precision=prec, **kw)
+            with mi355attn.options(gemm_variant=15):
+                y15 = F.linear16(x16, w16, precision=prec, **kw)
+                y15b = F.linear16(x16, w16, precision=prec, **kw)
             assert torch.equal(y15, y15b), "run-to-run"
             assert torch.equal(y7, y15), f"persistent kernel differs from variant 7 with {sorted(kw)}"
         if M * N <= 3_000_000:
             ref = _ref_linear(x16.cpu(), w16.cpu(), b.cpu(), True, None, None)
-            assert_parity(F.linear16(x16, w16, b, act=F.ACT_GELU, precision=prec).cpu(), ref.float(), 2e-5 if prec == 1 else 2e-5, "fp64 product")
-    finally:
-        mi355attn.set_option("gemm_variant", 0)
-        mi355attn.set_option("gemm_splitk", 1)
+            with mi355attn.options(gemm_variant=15):
+                assert_parity(F.linear16(x16, w16, b, act=F.ACT_GELU, precision=prec).cpu(), ref.float(), 2e-5 if prec == 1 else 2e-5, "fp64 product")
 
 
 @pytest.mark.parametrize("M,N,K", [(50432, 768, 3072), (12544, 512, 2048), (20000, 1024, 1536), (770, 520, 4096)])
@@ -78,16 +75,12 @@ def test_persistent_gemm_split_last_round(M, N, K):
     w16 = (torch.randn(N, K, device="cuda") / K ** 0.5).half()
     b = torch.randn(N, device="cuda")
     resid = torch.randn(M, N, device="cuda")
-    try:
-        mi355attn.set_option("gemm_variant", 15)
-        mi355attn.set_option("gemm_splitk", 1)
-        ys = F.linear16(x16, w16, b, resid=resid, precision=1)
-        ys2 = F.linear16(x16, w16, b, resid=resid, precision=1)
-        mi355attn.set_option("gemm_splitk", 0)
-        yu = F.linear16(x16, w16, b, resid=resid, precision=1)
-    finally:
-        mi355attn.set_option("gemm_variant", 0)
-        mi355attn.set_option("gemm_splitk", 1)
+    with mi355attn.options(gemm_variant=15):
+        with mi355attn.options(gemm_splitk=1):
+            ys = F.linear16(x16, w16, b, resid=resid, precision=1)
+            ys2 = F.linear16(x16, w16, b, resid=resid, precision=1)
+        with mi355attn.options(gemm_splitk=0):
+            yu = F.linear16(x16, w16, b, resid=resid, precision=1)
     assert torch.equal(ys, ys2), "split-K result is not deterministic"
     assert_parity(ys.cpu(), yu.cpu(), 2e-6, "split vs unsplit")
     rows = torch.tensor([0, 1, M // 3, M // 2 + 5, M - 2, M - 1])
@@ -166,20 +159,15 @@ def test_split_round_poll_timeout_is_reported():
     x16 = torch.randn(M, K, device="cuda").half()
     w16 = (torch.randn(N, K, device="cuda") / K ** 0.5).half()
     mi355attn.sync_status(wait=True)
-    old = mi355attn.get_option("spin_limit")
-    try:
-        mi355attn.set_option("spin_limit", 0)
+    with mi355attn.options(spin_limit=0):
         F.linear16(x16, w16, precision=1)
         torch.cuda.synchronize()
-        mi355attn.set_option("spin_limit", old)
-        try:
-            mi355attn.sync_status()
-            timed_out = False
-        except mi355attn.Mi355Error as e:
-            assert "split last round" in str(e)
-            timed_out = True
-    finally:
-        mi355attn.set_option("spin_limit", old)
+    try:
+        mi355attn.sync_status()
+        timed_out = False
+    except mi355attn.Mi355Error as e:
+        assert "split last round" in str(e)
+        timed_out = True
     # a partner can legitimately have published before the very first poll: then there is nothing to report and the result is right
     y = F.linear16(x16, w16, precision=1)
     mi355attn.sync_status(wait=True)
@@ -211,11 +199,8 @@ def test_double_attention_two_pass_vs_oracle(B, C, H, W, prec, tol):
     y2 = F.double_attention_forward(*args, precision=prec)
     assert torch.equal(y, y2), "run-to-run"
     assert_parity(y.cpu(), ref, tol, f"two-pass DoubleAttention B={B} C={C} {H}x{W}")
-    try:
-        mi355attn.set_option("da_fused", 0)
+    with mi355attn.options(da_fused=0):
         yu = F.double_attention_forward(*args, precision=prec)
-    finally:
-        mi355attn.set_option("da_fused", 1)
     tol_u = tol if prec == 1 else 4e-2                          # bf16 through seven roundings of fp32 intermediates: looser on max |diff|
     assert_parity(yu.cpu(), ref, tol_u, "seven-launch pipeline")
     assert_parity(y.cpu(), yu.cpu(), tol_u, "two-pass vs seven-launch")

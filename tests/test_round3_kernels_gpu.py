@@ -60,20 +60,18 @@ def test_two_accumulator_gemm_bit_identical_to_tile_kernel(M, N, K, prec, dt):
               dict(bias=b, resid=resid), dict(bias=b, resid=resid, act=F.ACT_GELU), dict(bias=None, resid=resid), dict(bias=b), dict(bias=None)]
     if K < 640:
         combos = [kw for kw in combos if kw.get("out16")]     # the fp32 epilogue needs ten K-tiles of the next tile's main loop
-    try:
-        for kw in combos:
-            mi355attn.set_option("gemm_variant", 7)
+    for kw in combos:
+        with mi355attn.options(gemm_variant=7):
             y7 = F.linear16(x16, w16, precision=prec, **kw)
-            mi355attn.set_option("gemm_variant", 16)
+        with mi355attn.options(gemm_variant=16):
             y16 = F.linear16(x16, w16, precision=prec, **kw)
             y16b = F.linear16(x16, w16, precision=prec, **kw)
-            assert torch.equal(y16, y16b), f"run-to-run difference with {sorted(kw)}"
-            assert torch.equal(y7, y16), f"two-accumulator kernel differs from variant 7 with {sorted(kw)}"
-        if M * N <= 3_000_000 and K >= 640:
-            ref = _ref_linear(x16.cpu(), w16.cpu(), b.cpu(), True, resid.cpu())
+        assert torch.equal(y16, y16b), f"run-to-run difference with {sorted(kw)}"
+        assert torch.equal(y7, y16), f"two-accumulator kernel differs from variant 7 with {sorted(kw)}"
+    if M * N <= 3_000_000 and K >= 640:
+        ref = _ref_linear(x16.cpu(), w16.cpu(), b.cpu(), True, resid.cpu())
+        with mi355attn.options(gemm_variant=16):
             assert_parity(F.linear16(x16, w16, b, act=F.ACT_GELU, resid=resid, precision=prec).cpu(), ref.float(), 2e-5, "fp64 product")
-    finally:
-        mi355attn.set_option("gemm_variant", 0)
 
 
 def test_two_accumulator_gemm_is_the_default_for_fp32_residual_outputs_and_batch_independent():
@@ -89,11 +87,8 @@ def test_two_accumulator_gemm_is_the_default_for_fp32_residual_outputs_and_batch
         b = torch.randn(N, device="cuda")
         resid = torch.randn(M, N, device="cuda")
         y0 = F.linear16(x16, w16, b, resid=resid, precision=1)
-        try:
-            mi355attn.set_option("gemm_variant", 16)
+        with mi355attn.options(gemm_variant=16):
             y16 = F.linear16(x16, w16, b, resid=resid, precision=1)
-        finally:
-            mi355attn.set_option("gemm_variant", 0)
         assert torch.equal(y0, y16)
         Ms = 128 * 197                                        # half the batch: different tile -> workgroup assignment
         ys = F.linear16(x16[:Ms].contiguous(), w16, b, resid=resid[:Ms].contiguous(), precision=1)
@@ -105,14 +100,11 @@ def test_two_accumulator_gemm_refuses_what_it_does_not_take():
     from mi355attn import functional as F
     x16 = torch.randn(130, 768, device="cuda").half()          # M % 128 != 0
     w16 = torch.randn(256, 768, device="cuda").half()
-    try:
-        mi355attn.set_option("gemm_variant", 16)
+    with mi355attn.options(gemm_variant=16):
         with pytest.raises(RuntimeError, match="two-accumulator"):
             F.linear16(x16, w16, precision=1)
         with pytest.raises(RuntimeError, match="two-accumulator"):      # K too short for the nine epilogue K-tiles
             F.linear16(torch.randn(128, 512, device="cuda").half(), torch.randn(256, 512, device="cuda").half(), precision=1)
-    finally:
-        mi355attn.set_option("gemm_variant", 0)
     y = F.linear16(x16, w16, precision=1)                      # default dispatch falls through to the other kernels
     assert_parity(y.cpu(), (x16.double() @ w16.double().t()).float().cpu(), 2e-5, "fallback")
 
@@ -128,9 +120,7 @@ def test_split_k_gemm_under_graph_capture_and_replay():
     w16 = (torch.randn(N, K, device="cuda") / K ** 0.5).half()
     b = torch.randn(N, device="cuda")
     resid = torch.randn(M, N, device="cuda")
-    try:
-        mi355attn.set_option("gemm_pa", 0)                     # the persistent 256 x 256 kernel with its split last round is the default then
-        mi355attn.set_option("gemm_splitk", 1)
+    with mi355attn.options(gemm_pa=0, gemm_splitk=1):          # the persistent 256 x 256 kernel with its split last round is the default then
         y_eager = F.linear16(x16, w16, b, resid=resid, precision=1)          # also warms the workspace cache outside the capture
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
@@ -145,19 +135,15 @@ def test_split_k_gemm_under_graph_capture_and_replay():
             resid.copy_(torch.randn(M, N, device="cuda"))
             g.replay()
             torch.cuda.synchronize()
-            mi355attn.set_option("gemm_splitk", 0)
-            y_ref = F.linear16(x16, w16, b, resid=resid, precision=1)
-            mi355attn.set_option("gemm_splitk", 1)
+            with mi355attn.options(gemm_splitk=0):
+                y_ref = F.linear16(x16, w16, b, resid=resid, precision=1)
             assert_parity(y_cap.cpu(), y_ref.cpu(), 2e-6, f"replay {rep}")
         # eager launches after the replays still work (the workspace history was not corrupted by the capture)
         y2 = F.linear16(x16, w16, b, resid=resid, precision=1)
-        mi355attn.set_option("gemm_splitk", 0)
-        y3 = F.linear16(x16, w16, b, resid=resid, precision=1)
+        with mi355attn.options(gemm_splitk=0):
+            y3 = F.linear16(x16, w16, b, resid=resid, precision=1)
         assert_parity(y2.cpu(), y3.cpu(), 2e-6, "eager after replay")
         assert mi355attn.lib().mi355_sync_status() == 0
-    finally:
-        mi355attn.set_option("gemm_pa", 1)
-        mi355attn.set_option("gemm_splitk", 1)
     del y_eager
 
 
@@ -170,22 +156,18 @@ def test_split_k_gemm_stress_varying_inputs():
     torch.manual_seed(5)
     w16 = (torch.randn(N, K, device="cuda") / K ** 0.5).half()
     b = torch.randn(N, device="cuda")
-    try:
-        mi355attn.set_option("gemm_pa", 0)
+    with mi355attn.options(gemm_pa=0):
         worst = 0.0
         for it in range(40):
             x16 = torch.randn(M, K, device="cuda").half() * (1.0 + 0.1 * it)
-            mi355attn.set_option("gemm_splitk", 1)
-            ys = F.linear16(x16, w16, b, precision=1)
-            mi355attn.set_option("gemm_splitk", 0)
-            yu = F.linear16(x16, w16, b, precision=1)
+            with mi355attn.options(gemm_splitk=1):
+                ys = F.linear16(x16, w16, b, precision=1)
+            with mi355attn.options(gemm_splitk=0):
+                yu = F.linear16(x16, w16, b, precision=1)
             d = float((ys - yu).abs().max() / yu.abs().max())
             worst = max(worst, d)
             assert d < 2e-6, f"launch {it}: split result off by {d:.3e} (stale or half-written partial slab?)"
         assert mi355attn.lib().mi355_sync_status() == 0
-    finally:
-        mi355attn.set_option("gemm_pa", 1)
-        mi355attn.set_option("gemm_splitk", 1)
 
 
 # ---- boundary completion: the ViT attention block as one C call, helper classes on their own -------------------------------------
@@ -386,8 +368,7 @@ def test_range_guard_layernorm16_and_gemm_epilogues():
     for (M, N, K, variant) in ((512, 256, 768, 7), (50432, 512, 768, 15), (128 * 300, 256, 768, 16), (4096, 256, 64, 0)):
         x16 = (torch.randn(M, K, device="cuda") * 40).half()
         w16 = (torch.randn(N, K, device="cuda") * 0.5).half()
-        try:
-            mi355attn.set_option("gemm_variant", variant)
+        with mi355attn.options(gemm_variant=variant):
             y32 = F.linear16(x16, w16, out16=False, precision=1)    # fp32 output: nothing to saturate
             mi355attn.range_status(wait=True)
             assert float(y32.abs().max()) < 65000                   # ... and this scale stays inside fp16 anyway
@@ -400,8 +381,6 @@ def test_range_guard_layernorm16_and_gemm_epilogues():
                 mi355attn.range_status(wait=True)
             F.linear16((x16 * 200).to(torch.bfloat16), w16.to(torch.bfloat16), out16=True, precision=2)    # bf16: no guard needed
             mi355attn.range_status(wait=True)
-        finally:
-            mi355attn.set_option("gemm_variant", 0)
     _drain_range()
 
 

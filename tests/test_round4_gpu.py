@@ -52,12 +52,8 @@ def test_gct_lct_record_their_exchange_kernels_under_graph_capture():
         for a, b, m in zip(got, want, mods):
             assert torch.equal(a, b), f"replay {rep}: {type(m).__name__} differs from the eager launch"
     # the single-read kernels really were what ran: they must agree with the two-pass kernels only to fp32 noise, not bit for bit in general
-    mi355attn.set_option("zoo_single", 0)
-    try:
-        with torch.no_grad():
-            two = [m(x) for m in mods]
-    finally:
-        mi355attn.set_option("zoo_single", 1)
+    with mi355attn.options(zoo_single=0), torch.no_grad():
+        two = [m(x) for m in mods]
     for a, b, m in zip(got, two, mods):
         assert_parity(a.cpu(), b.cpu(), 2e-6, f"{type(m).__name__} single-read (replayed) vs two-pass")
     xc = x.cpu()
@@ -201,12 +197,10 @@ def test_left_over_rows_on_the_ring_kernel_are_bit_identical(M, N, K, which, pre
     w16 = (torch.randn(N, K, device="cuda") / K ** 0.5).to(dt)
     b = torch.randn(N, device="cuda")
     resid = torch.randn(M, N, device="cuda")
-    old = mi355attn.get_option("gemm_pa_tail")
-    try:
-        for kw in (dict(bias=b, resid=resid), dict(bias=None, resid=resid), dict(bias=b, resid=resid, act=F.ACT_GELU)):
-            mi355attn.set_option("gemm_pa_tail", 0)
+    for kw in (dict(bias=b, resid=resid), dict(bias=None, resid=resid), dict(bias=b, resid=resid, act=F.ACT_GELU)):
+        with mi355attn.options(gemm_pa_tail=0):
             y_off = F.linear16(x16, w16, precision=prec, **kw)
-            mi355attn.set_option("gemm_pa_tail", 30)
+        with mi355attn.options(gemm_pa_tail=30):
             tags = []
             y_on = [None]
 
@@ -216,19 +210,16 @@ def test_left_over_rows_on_the_ring_kernel_are_bit_identical(M, N, K, which, pre
             assert any(f"tail {which}" in t for t in tags), f"the ring kernel did not run: {tags}"
             y_on2 = F.linear16(x16, w16, precision=prec, **kw)
             torch.cuda.synchronize()
-            assert torch.equal(y_on[0], y_on2), "run-to-run difference"
-            assert torch.equal(y_off, y_on[0]), f"split launch differs from the single launch with {sorted(kw)}"
-        mi355attn.set_option("gemm_variant", 7)
-        y7 = F.linear16(x16, w16, b, resid=resid, precision=prec)
-        mi355attn.set_option("gemm_variant", 0)
+        assert torch.equal(y_on[0], y_on2), "run-to-run difference"
+        assert torch.equal(y_off, y_on[0]), f"split launch differs from the single launch with {sorted(kw)}"
+    with mi355attn.options(gemm_pa_tail=30):
+        with mi355attn.options(gemm_variant=7):
+            y7 = F.linear16(x16, w16, b, resid=resid, precision=prec)
         assert torch.equal(y7, F.linear16(x16, w16, b, resid=resid, precision=prec)), "differs from the round-1 tile kernel"
         # the last rows (the ring kernel's) against an fp64 product of the same 16-bit operands
         rows = slice(M - 96, M)
         ref = (x16[rows].double() @ w16.double().t() + b.double() + resid[rows].double()).float()
         assert_parity(F.linear16(x16, w16, b, resid=resid, precision=prec)[rows], ref, 2e-5, "fp64 product, last rows")
-    finally:
-        mi355attn.set_option("gemm_variant", 0)
-        mi355attn.set_option("gemm_pa_tail", old)
 
 
 def test_left_over_rows_split_is_recorded_under_graph_capture():
@@ -285,10 +276,8 @@ def test_lpi_patch_kernel_against_the_general_kernel_and_the_oracle(C, with_ln, 
     kw = dict(gamma=gd, resid=xd) if with_tail else {}
     if with_ln:
         kw["ln"] = ln
-    old = mi355attn.get_option("lpi_patch")
-    try:
-        with torch.no_grad():
-            mi355attn.set_option("lpi_patch", 1)
+    with torch.no_grad():
+        with mi355attn.options(lpi_patch=1):
             tags = []
             out = [None]
 
@@ -299,10 +288,8 @@ def test_lpi_patch_kernel_against_the_general_kernel_and_the_oracle(C, with_ln, 
             y1 = out[0]
             y1b = m(xd, H, W, **kw)
             y_one = m(xd[3:4].contiguous(), H, W, **({**kw, "resid": xd[3:4].contiguous()} if with_tail else kw))
-            mi355attn.set_option("lpi_patch", 0)
+        with mi355attn.options(lpi_patch=0):
             y0 = m(xd, H, W, **kw)
-    finally:
-        mi355attn.set_option("lpi_patch", old)
     torch.cuda.synchronize()
     assert torch.equal(y1, y1b), "run-to-run difference"
     assert torch.equal(y1[3:4], y_one), "a row's bits depend on the batch"
@@ -335,10 +322,8 @@ def test_mixer_token_mixing_in_one_kernel(B, C, prec, tol):
     ref = O.mixer_layer_forward(x, sd)
     m = m.cuda()
     xd = x.cuda()
-    old = mi355attn.get_option("mixer_fused")
-    try:
-        with torch.no_grad():
-            mi355attn.set_option("mixer_fused", 1)
+    with torch.no_grad():
+        with mi355attn.options(mixer_fused=1):
             out = [None]
 
             def run():
@@ -349,10 +334,8 @@ def test_mixer_token_mixing_in_one_kernel(B, C, prec, tol):
             y1 = out[0]
             y1b = m(xd)
             y_last = m(xd[B - 1:].contiguous())
-            mi355attn.set_option("mixer_fused", 0)
+        with mi355attn.options(mixer_fused=0):
             y0 = m(xd)
-    finally:
-        mi355attn.set_option("mixer_fused", old)
     torch.cuda.synchronize()
     assert torch.isfinite(y1).all()
     assert torch.equal(y1, y1b), "run-to-run difference"

@@ -93,18 +93,14 @@ def test_mixer_early_residual_variant_is_bit_identical(prec):
     torch.manual_seed(11)
     m = MixerLayer(512, 196, precision=prec).eval().cuda()
     x = torch.randn(7, 196, 512, device="cuda")
-    old = mi355attn.get_option("mixer_early")
-    try:
-        with torch.no_grad():
-            mi355attn.set_option("mixer_early", 0)
+    with torch.no_grad():
+        with mi355attn.options(mixer_early=0):
             y0 = m(x)
-            mi355attn.set_option("mixer_early", 1)
+        with mi355attn.options(mixer_early=1):
             seen = []
             def run():
                 seen.append(m(x))
             tags = [t for t, *_ in mi355attn.kernel_trace(run)]
-    finally:
-        mi355attn.set_option("mixer_early", old)
     assert any("mixer_token_kernel<early>" in t for t in tags), tags
     assert torch.equal(y0, seen[0])
 
@@ -185,16 +181,12 @@ def test_small_output_gemm_is_bit_identical_to_the_engine(M, N, K, stride, prec)
     x = base[:, :K]                                                   # row stride `stride`, consumed in place
     w = (torch.randn(N, K, device="cuda") / K ** 0.5).contiguous()
     b = torch.randn(N, device="cuda")
-    old = mi355attn.get_option("gemm_small")
-    try:
-        outs, tags = {}, {}
-        for v in (1, 0):
-            mi355attn.set_option("gemm_small", v)
+    outs, tags = {}, {}
+    for v in (1, 0):
+        with mi355attn.options(gemm_small=v):
             def run():
                 outs[v] = (F.linear(x, w, b, precision=prec), F.linear(x, w, None, precision=prec))
             tags[v] = [t for t, *_ in mi355attn.kernel_trace(run)]
-    finally:
-        mi355attn.set_option("gemm_small", old)
     assert all("gemm_small_kernel" in t for t in tags[1]) and len(tags[1]) >= 1, tags[1]
     assert not any("gemm_small_kernel" in t for t in tags[0]), tags[0]
     assert torch.equal(outs[1][0], outs[0][0]) and torch.equal(outs[1][1], outs[0][1])
@@ -223,15 +215,11 @@ def test_fused_mlp_four_tile_variant_is_bit_identical(prec):
     torch.manual_seed(21)
     m = CSWinBlock(64, 56, 2, split_size=1, qkv_bias=True, precision=prec).eval().cuda()
     x = torch.randn(3, 3136, 64, device="cuda")
-    old = mi355attn.get_option("mlp_tt4")
-    try:
-        with torch.no_grad():
-            mi355attn.set_option("mlp_tt4", 0)
+    with torch.no_grad():
+        with mi355attn.options(mlp_tt4=0):
             y0 = m(x)
-            mi355attn.set_option("mlp_tt4", 1)
+        with mi355attn.options(mlp_tt4=1):
             y1 = m(x)
-    finally:
-        mi355attn.set_option("mlp_tt4", old)
     assert torch.isfinite(y0).all() and torch.equal(y0, y1)
 
 
@@ -249,17 +237,13 @@ def test_mixer_statistics_inside_the_token_kernel_are_bit_identical(B, C, prec):
         m.norm1.weight.uniform_(0.5, 1.5)
         m.norm1.bias.normal_(0, 0.2)
     x = torch.randn(B, 196, C, device="cuda") * 1.7 + 0.3
-    old = mi355attn.get_option("mixer_stats")
-    try:
-        with torch.no_grad():
-            mi355attn.set_option("mixer_stats", 0)
+    with torch.no_grad():
+        with mi355attn.options(mixer_stats=0):
             t0 = [t for t, *_ in mi355attn.kernel_trace(lambda: m(x))]
             y0 = m(x)
-            mi355attn.set_option("mixer_stats", 1)
+        with mi355attn.options(mixer_stats=1):
             seen = []
             t1 = [t for t, *_ in mi355attn.kernel_trace(lambda: seen.append(m(x)))]
-    finally:
-        mi355attn.set_option("mixer_stats", old)
     assert any("row_stats_kernel" in t for t in t0), t0
     if C == 512:                                                       # phase 0 is built for C = 512 (two float4 per lane and row)
         assert not any("row_stats_kernel" in t for t in t1) and any("mixer_token_kernel<stats>" in t for t in t1), t1
@@ -275,15 +259,11 @@ def test_attention_core_on_seven_waves_is_bit_identical(prec):
     torch.manual_seed(3)
     m = Attention(768, 12, precision=prec).eval().cuda()
     x = torch.randn(5, 197, 768, device="cuda")
-    old = mi355attn.get_option("attn_nw")
-    try:
-        with torch.no_grad():
-            mi355attn.set_option("attn_nw", 8)
+    with torch.no_grad():
+        with mi355attn.options(attn_nw=8):
             y8 = m(x)
-            mi355attn.set_option("attn_nw", 7)
+        with mi355attn.options(attn_nw=7):
             y7 = m(x)
-    finally:
-        mi355attn.set_option("attn_nw", old)
     assert torch.isfinite(y8).all() and torch.equal(y8, y7)
 
 
@@ -316,11 +296,9 @@ def test_one_wave_per_simd_gemm_is_bit_identical_to_the_eight_wave_kernel(case, 
     w16 = (torch.randn(N, K, generator=g) / K ** 0.5).to(dev).to(dt)
     b = torch.randn(N, generator=g).to(dev) if bias else None
     act = F.ACT_GELU if gelu else F.ACT_NONE
-    old = mi355attn.get_option("gemm_variant")
     outs = {}
-    try:
-        for v in (17, 0, 15, 16, 17):
-            mi355attn.set_option("gemm_variant", v)
+    for v in (17, 0, 15, 16, 17):
+        with mi355attn.options(gemm_variant=v):
             try:
                 y = F.linear16(x16, w16, b, act=act, out16=True, precision=prec)
             except mi355attn.Mi355Error:
@@ -328,16 +306,11 @@ def test_one_wave_per_simd_gemm_is_bit_identical_to_the_eight_wave_kernel(case, 
                 continue
             torch.cuda.synchronize()
             outs.setdefault(v, []).append(y.clone())
-    finally:
-        mi355attn.set_option("gemm_variant", old)
     _drain_range()
     assert len(outs[17]) == 2 and torch.equal(outs[17][0], outs[17][1])
-    mi355attn.set_option("gemm_variant", 17)
-    try:
+    with mi355attn.options(gemm_variant=17):
         with pytest.raises(mi355attn.Mi355Error):
             F.linear16(x16, w16, b, act=act, out16=False, precision=prec)
-    finally:
-        mi355attn.set_option("gemm_variant", old)
     for v, ys in outs.items():
         assert torch.equal(ys[0], outs[17][0]), "variant %d differs from gemm16_w4 on %r" % (v, case)
     ref = x16.float() @ w16.float().t() + (b if b is not None else 0.0)
@@ -355,19 +328,15 @@ def test_qkv_shaped_products_take_the_one_wave_per_simd_kernel():
     x16 = torch.randn(256 * 300, 768, device=dev).half()
     w16 = (torch.randn(2304, 768, device=dev) / 27.7).half()
     b = torch.randn(2304, device=dev)
-    old = mi355attn.get_option("gemm_w4")
     res = {}
-    try:
-        for v in (1, 0):
-            mi355attn.set_option("gemm_w4", v)
+    for v in (1, 0):
+        with mi355attn.options(gemm_w4=v):
             box = {}
             def run():
                 box["y"] = F.linear16(x16, w16, b, out16=True, precision=1)
             tags = [t for t, *_ in mi355attn.kernel_trace(run)]
             torch.cuda.synchronize()
             res[v] = (box["y"].clone(), tags)
-    finally:
-        mi355attn.set_option("gemm_w4", old)
     assert any("gemm16_w4_kernel" in t for t in res[1][1]), res[1][1]
     assert any("gemm16_p8_kernel" in t for t in res[0][1]) and not any("gemm16_w4_kernel" in t for t in res[0][1]), res[0][1]
     assert torch.equal(res[0][0], res[1][0])

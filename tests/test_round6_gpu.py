@@ -120,20 +120,19 @@ def test_range_fallback_off_keeps_the_round3_contract():
     torch.manual_seed(4321)
     x = (torch.randn(4, 197, 768) * 1e5).cuda()
     mi355attn.range_status(wait=True)
-    mi355attn.set_option("range_fallback", 0)
     try:
-        with warnings.catch_warnings(record=True) as w:
-            warnings.simplefilter("always")
-            with torch.no_grad():
-                y = m(x)
-            torch.cuda.synchronize()
-        assert not [i for i in w if "strict mode" in str(i.message)]
-        assert not torch.isfinite(y).all()
-        with pytest.raises(mi355attn.Mi355RangeError):
-            with torch.no_grad():
-                m(x)
+        with mi355attn.options(range_fallback=0):
+            with warnings.catch_warnings(record=True) as w:
+                warnings.simplefilter("always")
+                with torch.no_grad():
+                    y = m(x)
+                torch.cuda.synchronize()
+            assert not [i for i in w if "strict mode" in str(i.message)]
+            assert not torch.isfinite(y).all()
+            with pytest.raises(mi355attn.Mi355RangeError):
+                with torch.no_grad():
+                    m(x)
     finally:
-        mi355attn.set_option("range_fallback", 1)
         try:
             mi355attn.range_status(wait=True)
         except mi355attn.Mi355RangeError:

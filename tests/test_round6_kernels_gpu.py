@@ -30,17 +30,12 @@ def test_weight_stationary_gemm_is_bit_identical_to_the_tile_kernels(M, K, resid
     r = torch.randn(M, K, device="cuda") if resid else None
     x16, w16 = F.cast16(x, prec), F.cast16(w, prec)
     outs, tags = {}, {}
-    old = mi355attn.get_option("gemm_wreg")
-    try:
-        for v in (1, 0):
-            mi355attn.set_option("gemm_wreg", v)
-
+    for v in (1, 0):
+        with mi355attn.options(gemm_wreg=v):
             def run():
                 outs[v] = F.linear16(x16, w16, b, resid=r, precision=prec)
             tags[v] = _tags(run)
             torch.cuda.synchronize()
-    finally:
-        mi355attn.set_option("gemm_wreg", old)
     assert any("gemm16_wreg_kernel" in t for t in tags[1]), tags[1]
     assert not any("gemm16_wreg_kernel" in t for t in tags[0]), tags[0]
     assert torch.equal(outs[1], outs[0]), "the weight-stationary kernel and the tile kernel differ in some bit"
@@ -100,17 +95,12 @@ def test_xca_core_on_the_16bit_pipe_matches_the_streaming_kernel(B, N, heads, d,
     qkv16 = F.cast16(torch.randn(B, N, 3 * C, device="cuda"), prec)
     temp = (0.5 + torch.rand(heads, device="cuda")) * 3.0
     outs, tags = {}, {}
-    old = mi355attn.get_option("xca_tr")
-    try:
-        for v in (1, 0):
-            mi355attn.set_option("xca_tr", v)
-
+    for v in (1, 0):
+        with mi355attn.options(xca_tr=v):
             def run():
                 outs[v] = F.xca_core(qkv16, temp, heads, precision=prec, out16=True)
             tags[v] = _tags(run)
             torch.cuda.synchronize()
-    finally:
-        mi355attn.set_option("xca_tr", old)
     assert any("xca_tr_kernel" in t for t in tags[1]) and not any("xca_tr_kernel" in t for t in tags[0]), (tags[1], tags[0])
     ref = _xca_ref(qkv16, temp, heads).float()
     tol = 1.5e-3 if prec == 1 else 1.2e-2                               # the output itself is rounded to fp16 / bf16
@@ -151,8 +141,7 @@ def test_wide_fused_mlp_matches_the_reference_expression(C, M, use_gamma, prec):
     xg = x.cuda()
     tol = 1e-3 if prec == 1 else 8e-3
     assert not F.mlp_fused_ok(C, 4 * C, prec), "opt-in: measured slower than the composition (profiles/r06_mlp_wide.md)"
-    mi355attn.set_option("mlp_wide", 1)
-    try:
+    with mi355attn.options(mlp_wide=1):
         assert F.mlp_fused_ok(C, 4 * C, prec)
         got = {}
 
@@ -163,8 +152,6 @@ def test_wide_fused_mlp_matches_the_reference_expression(C, M, use_gamma, prec):
         y = got["y"].view(M, C)
         again = F.mlp_fused(xg.view(1, M, C), ln, fc1, fc2, gamma=gd, precision=prec).view(M, C)
         sub = F.mlp_fused(xg[:200].contiguous().view(1, 200, C), ln, fc1, fc2, gamma=gd, precision=prec).view(200, C) if M > 300 else None
-    finally:
-        mi355attn.set_option("mlp_wide", 0)
     assert_parity(y.cpu(), ref, tol, "mlp_wide vs fp64")
     # the BRANCH alone (y - x): the residual must not hide an error of the MLP
     assert_parity((y - xg).cpu(), (ref.double() - xd).float(), 2 * tol, "mlp_wide branch vs fp64")
@@ -197,16 +184,12 @@ def test_wide_fused_mlp_reports_a_saturating_hidden_activation():
     ref = O.cswin_block_forward(x, sd, 14, 8, 7)
     md = m.cuda()
     mi355attn.range_status(wait=True)
-    mi355attn.set_option("mlp_wide", 1)
-    try:
-        with warnings.catch_warnings(record=True) as w:
-            warnings.simplefilter("always")
-            with torch.no_grad():
-                tags = _tags(lambda: md(x.cuda()))
-                y = md(x.cuda())
-            torch.cuda.synchronize()
-    finally:
-        mi355attn.set_option("mlp_wide", 0)
+    with mi355attn.options(mlp_wide=1), warnings.catch_warnings(record=True) as w:
+        warnings.simplefilter("always")
+        with torch.no_grad():
+            tags = _tags(lambda: md(x.cuda()))
+            y = md(x.cuda())
+        torch.cuda.synchronize()
     assert any("mlp_wide_kernel" in t for t in tags), tags
     assert len([i for i in w if "strict mode" in str(i.message)]) == 2, [str(i.message) for i in w]      # two forwards, each falls back
     assert_parity(y.cpu(), ref, 2e-4, "CSWin s3 with a saturating hidden activation [strict re-run]")
@@ -254,11 +237,8 @@ def test_xcablock_uses_the_statistics_of_the_proj_gemm():
     out = {}
     with torch.no_grad():
         tags = _tags(lambda: out.__setitem__("y", md(xd, 14, 14)))
-        mi355attn.set_option("gemm_wreg", 0)
-        try:
+        with mi355attn.options(gemm_wreg=0):
             tags0 = _tags(lambda: out.__setitem__("y0", md(xd, 14, 14)))
-        finally:
-            mi355attn.set_option("gemm_wreg", 1)
     assert any("resid+stats" in t for t in tags) and not any("ln_stats_kernel" in t for t in tags), tags
     assert any("ln_stats_kernel" in t for t in tags0), tags0
     assert_parity(out["y"].cpu(), ref, 1e-3, "XCABlock with the statistics fold")
@@ -336,15 +316,12 @@ def test_weight_stationary_k768_gemm_is_correct_when_opted_in(M, N, act, prec):
     outs, tags = {}, {}
     one_wave = N % 256 == 0 and M % 32 == 0                      # what options 3 / 4 take
     sub_m = (M // 2) // 32 * 32                                  # still above the launcher's "eight row tiles per workgroup" floor
-    try:
-        for v in (2, 4, 0) if one_wave else (2, 0):
-            mi355attn.set_option("gemm_wst", v)
+    for v in (2, 4, 0) if one_wave else (2, 0):
+        with mi355attn.options(gemm_wst=v):
             tags[v] = _tags(lambda: outs.__setitem__(v, F.linear16(x16, w16, b, act=a, out16=True, precision=prec)))
-        mi355attn.set_option("gemm_wst", 2)
+    with mi355attn.options(gemm_wst=2):
         again = F.linear16(x16, w16, b, act=a, out16=True, precision=prec)
         sub_tags = _tags(lambda: outs.__setitem__("sub", F.linear16(x16[:sub_m].contiguous(), w16, b, act=a, out16=True, precision=prec)))
-    finally:
-        mi355attn.set_option("gemm_wst", 0)
     torch.cuda.synchronize()
     assert any("gemm16_wst_kernel" in t for t in tags[2]) and not any("gemm16_wst_kernel" in t for t in tags[0]), (tags[2], tags[0])
     rows = torch.tensor([0, 1, 31, 32, 33, M // 2, M - 33, M - 32, M - 2, M - 1], device="cuda")
@@ -381,18 +358,14 @@ def test_slab_stationary_short_k_gemm_has_the_tile_kernels_bits(M, N, K, act, pr
     b = torch.randn(N, device="cuda")
     a = F.ACT_GELU if act else F.ACT_NONE
     outs, tags = {}, {}
-    old = mi355attn.get_option("gemm_wslab")
-    try:
-        for v in (2, 1, 0):
-            mi355attn.set_option("gemm_wslab", v)
+    for v in (2, 1, 0):
+        with mi355attn.options(gemm_wslab=v):
             tags[v] = _tags(lambda: outs.__setitem__(v, F.linear16(x16, w16, b, act=a, out16=True, precision=prec)))
-        mi355attn.set_option("gemm_wslab", 2)
+    with mi355attn.options(gemm_wslab=2):
         again = F.linear16(x16, w16, b, act=a, out16=True, precision=prec)
         nob = F.linear16(x16, w16, None, act=a, out16=True, precision=prec)
-        mi355attn.set_option("gemm_wslab", 0)
+    with mi355attn.options(gemm_wslab=0):
         nob0 = F.linear16(x16, w16, None, act=a, out16=True, precision=prec)
-    finally:
-        mi355attn.set_option("gemm_wslab", old)
     torch.cuda.synchronize()
     on = {v: any("gemm16_wslab_kernel" in t for t in tags[v]) for v in tags}
     enough_rows = M >= 4 * 32 * (512 if K != 512 else 256) // (N // (192 if K == 384 else 256))
@@ -417,15 +390,13 @@ def test_slab_stationary_gemm_reports_fp16_saturation():
     x16 = F.cast16(torch.full((M, K), 8.0, device="cuda"), 1)
     w16 = F.cast16(torch.full((N, K), 32.0, device="cuda"), 1)          # 8 * 32 * 384 = 98 304 > 65 504
     mi355attn.range_status(wait=True)
-    old = mi355attn.get_option("gemm_wslab")
     try:
-        mi355attn.set_option("gemm_wslab", 2)
-        tags = _tags(lambda: F.linear16(x16, w16, None, act=F.ACT_GELU, out16=True, precision=1))
-        assert any("gemm16_wslab_kernel" in t for t in tags), tags
-        with pytest.raises(mi355attn.Mi355RangeError):
-            mi355attn.range_status(wait=True)
+        with mi355attn.options(gemm_wslab=2):
+            tags = _tags(lambda: F.linear16(x16, w16, None, act=F.ACT_GELU, out16=True, precision=1))
+            assert any("gemm16_wslab_kernel" in t for t in tags), tags
+            with pytest.raises(mi355attn.Mi355RangeError):
+                mi355attn.range_status(wait=True)
     finally:
-        mi355attn.set_option("gemm_wslab", old)
         try:
             mi355attn.range_status(wait=True)
         except mi355attn.Mi355RangeError:
@@ -545,12 +516,8 @@ def test_block_entries_use_the_fused_cast_and_keep_their_bits():
     with torch.no_grad():
         xca(xd)
         tags = _tags(lambda: out.__setitem__("x", xca(xd)))
-        old = mi355attn.get_option("gemm_wslab")
-        try:
-            mi355attn.set_option("gemm_wslab", 0)
+        with mi355attn.options(gemm_wslab=0):
             tags0 = _tags(lambda: out.__setitem__("x0", xca(xd)))
-        finally:
-            mi355attn.set_option("gemm_wslab", old)
     assert any(",x32>" in t for t in tags) and not any("cast16" in t for t in tags), tags
     assert any("cast16" in t for t in tags0) and len(tags0) == len(tags) + 1, (tags, tags0)
     assert torch.equal(out["x"], out["x0"])

@@ -46,24 +46,6 @@ def _built(row, p):
     return m, x
 
 
-class _options:
-    def __init__(self, opts):
-        self.opts = opts or {}
-
-    def __enter__(self):
-        import mi355attn
-        self.old = {k: mi355attn.get_option(k) for k in self.opts}
-        for k, v in self.opts.items():
-            mi355attn.set_option(k, v)
-        return self
-
-    def __exit__(self, *exc):
-        import mi355attn
-        for k, v in self.old.items():
-            mi355attn.set_option(k, v)
-        return False
-
-
 def _run(m, x, fwd_args):
     """(output, kernel tags, range-fallback warnings) of one forward."""
     import mi355attn
@@ -102,7 +84,7 @@ def test_route_matches_fp64(rid, prec):
     sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
     m = m.cuda()
     xd = x.cuda()
-    with _options(row.get("options")):
+    with mi355attn.options(**row.get("options", {})):
         if "error" in row:
             with pytest.raises(mi355attn.Mi355Error, match=row["error"]):
                 with torch.no_grad():

@@ -6,8 +6,6 @@ Every kernel involved is row-independent and keeps the GEMM engine's K order, so
 the engine).  With default options the two paths may differ by that effect only: 5e-4, the figure tests/test_full_size_gpu.py uses
 for it.
 """
-import contextlib
-
 import pytest
 import torch
 
@@ -18,19 +16,6 @@ pytestmark = pytest.mark.gpu
 
 LIMITED = "win_attn_kernel<d=64,io16,rows>"
 FULL = "win_attn_kernel<d=64,io16>"
-
-
-@contextlib.contextmanager
-def _options(**kw):
-    import mi355attn
-    old = {k: mi355attn.get_option(k) for k in kw}
-    for k, v in kw.items():
-        mi355attn.set_option(k, v)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            mi355attn.set_option(k, v)
 
 
 def _model(seed=1234, nontrivial=True, **kw):
@@ -55,7 +40,8 @@ def _input(shape, seed=4321):
 
 
 def _fwd(m, x, **opts):
-    with _options(**opts), torch.no_grad():
+    import mi355attn
+    with mi355attn.options(**opts), torch.no_grad():
         y = m(x)
     torch.cuda.synchronize()
     return y
@@ -63,7 +49,7 @@ def _fwd(m, x, **opts):
 
 def _tags(m, x, **opts):
     import mi355attn
-    with _options(**opts), torch.no_grad():
+    with mi355attn.options(**opts), torch.no_grad():
         rows = mi355attn.kernel_trace(lambda: m(x))
     return {t.split(" ")[0]: c for t, c, *_ in rows}
 
@@ -237,13 +223,14 @@ def test_in_place_weight_rescale_is_seen():
 @pytest.mark.parametrize("prec", [1, 2])
 def test_graph_capture_replays_equal_eager(prec):
     m = _model(depths=2, num_heads=12, qkv_bias=True, num_classes=10, precision=prec)
+    import mi355attn
     x = _input((4, 3, 224, 224))
     eager = _fwd(m, x, vit_tail=1)
     assert _limited(_tags(m, x, vit_tail=1)) == 1
     xs = x.clone()
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
-    with _options(vit_tail=1), torch.no_grad(), torch.cuda.stream(s):
+    with mi355attn.options(vit_tail=1), torch.no_grad(), torch.cuda.stream(s):
         m(xs)                                           # warm-up on the capture stream: caches and workspaces exist
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
@@ -261,11 +248,12 @@ def test_fp16_range_report_reaches_the_tail():
     """A LayerNorm 2 gain that saturates fp16 inside the pruned block is reported like in the full block (code 2): with the range
     fall-back the forward re-runs strict and stays finite."""
     import warnings
+    import mi355attn
     m = _model(depths=1, num_heads=12, qkv_bias=True, num_classes=10, precision=1)
     x = _input((2, 3, 224, 224))
     with torch.no_grad():
         m.blocks[0].layernorm2.weight.mul_(1e6)
-    with _options(vit_tail=1), torch.no_grad(), warnings.catch_warnings(record=True) as w:
+    with mi355attn.options(vit_tail=1), torch.no_grad(), warnings.catch_warnings(record=True) as w:
         warnings.simplefilter("always")
         y = m(x)
     torch.cuda.synchronize()

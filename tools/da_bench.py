@@ -17,6 +17,5 @@ def t(fn, n=20):
     return a.elapsed_time(b) / n
 with torch.no_grad():
     print("fused   ms", t(lambda: m(x)))
-    mi355attn.set_option("da_fused", 0)
-    print("unfused ms", t(lambda: m(x)))
-    mi355attn.set_option("da_fused", 1)
+    with mi355attn.options(da_fused=0):
+        print("unfused ms", t(lambda: m(x)))

@@ -33,11 +33,11 @@ for (M, N, K), out16, bias_on, resid_on, gelu, prec in itertools.product(shapes,
     act = F.ACT_GELU if gelu else F.ACT_NONE
     ys = {}
     for v in (7, 16):
-        mi355attn.set_option("gemm_variant", v)
-        ys[v] = F.linear16(x16, w16, b, act=act, resid=resid, out16=out16, precision=prec).clone()
-        # a second call on the same buffers (races show up as run-to-run differences)
-        y2 = F.linear16(x16, w16, b, act=act, resid=resid, out16=out16, precision=prec)
-        torch.cuda.synchronize()
+        with mi355attn.options(gemm_variant=v):
+            ys[v] = F.linear16(x16, w16, b, act=act, resid=resid, out16=out16, precision=prec).clone()
+            # a second call on the same buffers (races show up as run-to-run differences)
+            y2 = F.linear16(x16, w16, b, act=act, resid=resid, out16=out16, precision=prec)
+            torch.cuda.synchronize()
         if v == 16 and not torch.equal(y2, ys[v]):
             print("RUN-TO-RUN DIFFERENCE", M, N, K, flush=True)
             bad += 1
@@ -55,7 +55,6 @@ for (M, N, K), out16, bias_on, resid_on, gelu, prec in itertools.product(shapes,
         rec["bad_cols"] = int(idx[:, 1].unique().numel())
     out.append(rec)
     print(rec, flush=True)
-mi355attn.set_option("gemm_variant", 0)
 print("PA_CHECK", "FAIL" if bad else "OK", bad, "of", len(out), flush=True)
 os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
 json.dump(out, open(os.path.join(ROOT, "gpurun_out", "gemm_pa_check.json"), "w"), indent=1)

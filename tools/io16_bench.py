@@ -45,14 +45,8 @@ def main():
     xs = {torch.float16: x32.half(), torch.bfloat16: x32.bfloat16()}
 
     def general(m, x):
-        old = {k: mi355attn.get_option(k) for k in SINGLE_OPTS}
-        for k in SINGLE_OPTS:
-            mi355attn.set_option(k, 0)
-        try:
+        with mi355attn.options(**{k: 0 for k in SINGLE_OPTS}):
             return m(x)
-        finally:
-            for k, v in old.items():
-                mi355attn.set_option(k, v)
 
     variants = []
     for name, m in mods.items():

@@ -9,10 +9,10 @@ blk = W.workload_mixer(256, "cuda")["blocks"][0]
 m, x = blk["module"].eval(), blk["x"]
 with torch.no_grad():
     for opt in (1, 0):
-        mi355attn.set_option("mixer_fused", opt)
-        for _ in range(3):
-            m(x)
-        rows = mi355attn.kernel_trace(lambda: [m(x) for _ in range(5)])
+        with mi355attn.options(mixer_fused=opt):
+            for _ in range(3):
+                m(x)
+            rows = mi355attn.kernel_trace(lambda: [m(x) for _ in range(5)])
         print(f"mixer_fused = {opt}: {sum(r[2] for r in rows) / 5:.1f} us per forward")
         for tag, cnt, tot, mn, mx in rows:
             print(f"   {tot / cnt:8.1f} us (min {mn:6.1f})  x{cnt // 5}  {tag}")

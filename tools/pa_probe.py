@@ -16,16 +16,14 @@ def run(N, K, out16, resid_on, gelu, v, reps=10):
     b = torch.randn(N, device=dev)
     resid = torch.randn(M, N, device=dev) if resid_on else None
     act = F.ACT_GELU if gelu else F.ACT_NONE
-    mi355attn.set_option("gemm_variant", v)
-    for _ in range(3):
-        F.linear16(x16, w16, b, act=act, resid=resid, out16=out16, precision=1)
-    torch.cuda.synchronize()
-    tm = StreamTimer(dev); tm.start()
-    for _ in range(reps):
-        F.linear16(x16, w16, b, act=act, resid=resid, out16=out16, precision=1)
-    ms = tm.stop_ms() / reps
-    mi355attn.set_option("gemm_variant", 0)
-    return ms
+    with mi355attn.options(gemm_variant=v):
+        for _ in range(3):
+            F.linear16(x16, w16, b, act=act, resid=resid, out16=out16, precision=1)
+        torch.cuda.synchronize()
+        tm = StreamTimer(dev); tm.start()
+        for _ in range(reps):
+            F.linear16(x16, w16, b, act=act, resid=resid, out16=out16, precision=1)
+        return tm.stop_ms() / reps
 for (N, K) in ((768, 768), (768, 1536), (768, 3072), (2304, 768)):
     for v in (15, 16):
         r = {}

@@ -33,9 +33,10 @@ def main():
         res = {0: [], 30: []}
         for _ in range(3):
             for pct in (0, 30):
-                mi355attn.set_option("gemm_pa_tail", pct)
-                res[pct].append(time_us(lambda: F.linear16(x, w, b, resid=r, precision=1)))
-        rows = mi355attn.kernel_trace(lambda: F.linear16(x, w, b, resid=r, precision=1))
+                with mi355attn.options(gemm_pa_tail=pct):
+                    res[pct].append(time_us(lambda: F.linear16(x, w, b, resid=r, precision=1)))
+        with mi355attn.options(gemm_pa_tail=30):
+            rows = mi355attn.kernel_trace(lambda: F.linear16(x, w, b, resid=r, precision=1))
         print(f"{name:32s} off {min(res[0]):7.1f} us  on {min(res[30]):7.1f} us   (all: {[round(v, 1) for v in res[0]]} / {[round(v, 1) for v in res[30]]})")
         for tag, cnt, tot, mn, mx in rows:
             print(f"      {tot:8.1f} us  {tag}")
@@ -47,8 +48,8 @@ def main():
         with torch.no_grad():
             for _ in range(3):
                 for pct in (0, 30):
-                    mi355attn.set_option("gemm_pa_tail", pct)
-                    res[pct].append(time_us(lambda: mod(xin, *extra), iters=20, warm=4))
+                    with mi355attn.options(gemm_pa_tail=pct):
+                        res[pct].append(time_us(lambda: mod(xin, *extra), iters=20, warm=4))
         print(f"{blk['name']:32s} off {min(res[0]):7.1f} us  on {min(res[30]):7.1f} us   (all: {[round(v, 1) for v in res[0]]} / {[round(v, 1) for v in res[30]]})")
 
 if __name__ == "__main__":

@@ -12,22 +12,16 @@ blk = W.workload_c5(256, dev)["blocks"][0]
 m, x = blk["module"], blk["x"]
 sets = [a for a in sys.argv[1:3]]
 rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 2
-defaults = {}
-def apply(spec):
-    for k, v in defaults.items():
-        mi355attn.set_option(k, v)
-    for kv in filter(None, spec.split(",")):
-        k, v = kv.split("=")
-        defaults.setdefault(k, mi355attn.get_option(k))
-        mi355attn.set_option(k, int(v))
+def parse(spec):
+    return {k: int(v) for k, v in (kv.split("=") for kv in filter(None, spec.split(",")))}
 with torch.no_grad():
     for r in range(rounds):
         for spec in sets:
-            apply(spec)
-            for _ in range(2):
-                m(x)
-            torch.cuda.synchronize()
-            rows = mi355attn.kernel_trace(lambda: m(x))
+            with mi355attn.options(**parse(spec)):
+                for _ in range(2):
+                    m(x)
+                torch.cuda.synchronize()
+                rows = mi355attn.kernel_trace(lambda: m(x))
             tot = sum(t for _, _, t, _, _ in rows)
             print("== round %d  [%s]  %.1f us traced" % (r, spec, tot))
             for tag, cnt, t, mn, mx in rows[:9]:

@@ -27,8 +27,8 @@ for name, M, N, K, act in SHAPES:
     b = torch.randn(N, device=dev)
     outs, tags = {}, {}
     for v in VARS:
-        mi355attn.set_option("gemm_wslab", v)
-        tags[v] = [t for t, *_ in mi355attn.kernel_trace(lambda: outs.__setitem__(v, F.linear16(x16, w16, b, act=act, out16=True, precision=1)))]
+        with mi355attn.options(gemm_wslab=v):
+            tags[v] = [t for t, *_ in mi355attn.kernel_trace(lambda: outs.__setitem__(v, F.linear16(x16, w16, b, act=act, out16=True, precision=1)))]
     torch.cuda.synchronize()
     rows = torch.tensor([0, 1, 15, 16, 17, 31, 32, M // 2, M // 2 + 5, M - 33, M - 17, M - 16, M - 2, M - 1], device=dev)
     ref = x16[rows].double() @ w16.double().t() + b.double()
@@ -41,14 +41,13 @@ for name, M, N, K, act in SHAPES:
     for r in range(rounds):
         ts = []
         for v in VARS:
-            mi355attn.set_option("gemm_wslab", v)
-            F.linear16(x16, w16, b, act=act, out16=True, precision=1)
-            torch.cuda.synchronize()
-            tm = StreamTimer(dev)
-            tm.start()
-            for _ in range(10):
+            with mi355attn.options(gemm_wslab=v):
                 F.linear16(x16, w16, b, act=act, out16=True, precision=1)
-            ts.append(tm.stop_ms() / 10 * 1e3)
+                torch.cuda.synchronize()
+                tm = StreamTimer(dev)
+                tm.start()
+                for _ in range(10):
+                    F.linear16(x16, w16, b, act=act, out16=True, precision=1)
+                ts.append(tm.stop_ms() / 10 * 1e3)
         flop = 2.0 * M * N * K
         print("    round %d: " % r + "   ".join("opt %d: %.1f us (%.0f TFLOP/s)" % (v, tt, flop / tt / 1e6) for v, tt in zip(VARS, ts)), flush=True)
-    mi355attn.set_option("gemm_wslab", 0)

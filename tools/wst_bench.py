@@ -24,8 +24,8 @@ for name, M, N, act in (("qkv", 50432, 2304, F.ACT_NONE), ("fc1", 50432, 3072, F
     b = torch.randn(N, device=dev)
     outs, tags = {}, {}
     for v in VARS:
-        mi355attn.set_option("gemm_wst", v)
-        tags[v] = [t for t, *_ in mi355attn.kernel_trace(lambda: outs.__setitem__(v, F.linear16(x16, w16, b, act=act, out16=True, precision=1)))]
+        with mi355attn.options(gemm_wst=v):
+            tags[v] = [t for t, *_ in mi355attn.kernel_trace(lambda: outs.__setitem__(v, F.linear16(x16, w16, b, act=act, out16=True, precision=1)))]
     torch.cuda.synchronize()
     rows = torch.tensor([0, 1, 15, 16, 17, M // 2, M // 2 + 5, M - 17, M - 16, M - 2, M - 1], device=dev)
     ref = x16[rows].double() @ w16.double().t() + b.double()
@@ -38,14 +38,13 @@ for name, M, N, act in (("qkv", 50432, 2304, F.ACT_NONE), ("fc1", 50432, 3072, F
     for r in range(rounds):
         ts = []
         for v in VARS:
-            mi355attn.set_option("gemm_wst", v)
-            F.linear16(x16, w16, b, act=act, out16=True, precision=1)
-            torch.cuda.synchronize()
-            tm = StreamTimer(dev)
-            tm.start()
-            for _ in range(10):
+            with mi355attn.options(gemm_wst=v):
                 F.linear16(x16, w16, b, act=act, out16=True, precision=1)
-            ts.append(tm.stop_ms() / 10 * 1e3)
+                torch.cuda.synchronize()
+                tm = StreamTimer(dev)
+                tm.start()
+                for _ in range(10):
+                    F.linear16(x16, w16, b, act=act, out16=True, precision=1)
+                ts.append(tm.stop_ms() / 10 * 1e3)
         flop = 2.0 * M * N * K
         print("    round %d: " % r + "   ".join("opt %d: %.1f us (%.0f TFLOP/s)" % (v, tt, flop / tt / 1e6) for v, tt in zip(VARS, ts)))
-    mi355attn.set_option("gemm_wst", 0)
