@@ -20,7 +20,7 @@ composition from shape / precision predicates (mi355attn/modules/{cswin,mixer,xc
   error     the forward raises Mi355Error matching this text at every precision (no kernel is built for the route)
 
 Every row gets non-trivial parameters from prep_nontrivial: LayerNorm affine parts, every bias, BatchNorm statistics and the
-XCiT LayerScales, drawn per channel.  GEMM weights keep their init scale (test_round3_kernels_gpu.py,
+XCiT LayerScales, drawn per channel.  GEMM weights keep their init scale (test_range_guard_gpu.py,
 test_non_default_init_weights_vit_and_cswin: larger weights measure softmax amplification, not the kernels).
 """
 import torch

@@ -1,9 +1,11 @@
-"""GPU tests (-m gpu): edge cases and full-size properties of the SE / ECA / CBAM kernels."""
+"""GPU tests (-m gpu): edge cases and full-size properties of the SE / ECA / CBAM kernels and the GCT / LCT family, their single-read
+exchange kernels under graph capture and under contention, and the helper classes of TripletAttention and BAM on their own."""
 import pytest
 import torch
 
 import oracle as O
 from conftest import assert_parity
+from kernel_cases import _bn_randomise, _sd
 
 pytestmark = pytest.mark.gpu
 
@@ -329,8 +331,9 @@ def test_exchange_kernels_under_graph_capture():
     """hipGraph capture of the channel-attention modules.  SE and CBAM record their single-read exchange kernels: the granule tag of a
     launch and the ticket word live in the workspace (epoch + 1; the last ticket draw of a launch resets the ticket and advances the
     epoch), so a replay is just another launch and eager calls may be interleaved with replays on the same workspace -- the results
-    are the same bits either way.  GCT records its single-read kernel the same way since round 4 (tests/test_round4_gpu.py checks
-    bit equality for GCT / LCT / Gaussian GCT); ECA has no exchange."""
+    are the same bits either way.  GCT records its single-read kernel the same way
+    (test_gct_lct_record_their_exchange_kernels_under_graph_capture below checks bit equality for GCT / LCT / Gaussian GCT); ECA has
+    no exchange."""
     from mi355attn.modules import GCT
     se, _, cbam = _mods(64)
     gct = GCT(64)
@@ -448,3 +451,151 @@ def test_se_variants_bias_and_hard_sigmoid(shape, single):
     assert_parity(ya, O.se_ex_forward(x, sa["fc.0.weight"], sa["fc.0.bias"], sa["fc.2.weight"], sa["fc.2.bias"]), 1e-5, "se + bias")
     assert_parity(yg, O.se_ex_forward(x, sg["conv_reduce.weight"], sg["conv_reduce.bias"], sg["conv_expand.weight"], sg["conv_expand.bias"],
                                       "hard_sigmoid"), 1e-5, "se + bias + hard sigmoid")
+
+
+# ---- GCT / LCT / Gaussian GCT under graph capture; SE / CBAM exchange kernels under contention --------------------------------------
+def test_gct_lct_record_their_exchange_kernels_under_graph_capture():
+    import mi355attn
+    from mi355attn.modules import GCT, GaussianGCT, LCT
+    torch.manual_seed(3)
+    gct, lct, gg = GCT(64), LCT(64, 8), GaussianGCT(64)
+    gct1 = GCT(64, mode="l1")
+    with torch.no_grad():
+        gct.gamma.add_(0.5); gct.beta.add_(0.1); gct1.gamma.add_(0.3)
+        lct.w.mul_(1.5); lct.b.add_(0.2)
+    mods = [m.cuda() for m in (gct, gct1, lct, gg)]
+    static_x = torch.randn(6, 64, 28, 28, device="cuda")
+    with torch.no_grad():
+        for m in mods:
+            m(static_x)                                    # loads the code objects, makes the eager workspaces known
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g), torch.no_grad():
+        outs = [m(static_x) for m in mods]
+    for rep in range(4):
+        x = torch.randn(6, 64, 28, 28, device="cuda")
+        static_x.copy_(x)
+        g.replay()
+        if rep == 2:
+            g.replay()                                     # two replays back to back: the epoch advances inside the graph
+        torch.cuda.synchronize()
+        got = [o.clone() for o in outs]
+        with torch.no_grad():
+            want = [m(x) for m in mods]                    # eager launches in between
+        for a, b, m in zip(got, want, mods):
+            assert torch.equal(a, b), f"replay {rep}: {type(m).__name__} differs from the eager launch"
+    # the single-read kernels really were what ran: they must agree with the two-pass kernels only to fp32 noise, not bit for bit in general
+    with mi355attn.options(zoo_single=0), torch.no_grad():
+        two = [m(x) for m in mods]
+    for a, b, m in zip(got, two, mods):
+        assert_parity(a.cpu(), b.cpu(), 2e-6, f"{type(m).__name__} single-read (replayed) vs two-pass")
+    xc = x.cpu()
+    assert_parity(got[0].cpu(), O.gct_forward(xc, gct.alpha.cpu(), gct.gamma.cpu(), gct.beta.cpu(), 1e-5, "l2"), 1e-5, "GCT l2 replay vs oracle")
+    assert_parity(got[2].cpu(), O.lct_forward(xc, lct.w.cpu(), lct.b.cpu(), 8), 1e-5, "LCT replay vs oracle")
+    assert_parity(got[3].cpu(), O.gct_gauss_forward(xc), 1e-5, "Gaussian GCT replay vs oracle")
+    mi355attn.sync_status(wait=True)
+
+
+def _chan_mods(C=256):
+    from mi355attn.modules import CBAM, SELayer
+    torch.manual_seed(1234)
+    return SELayer(C).eval(), CBAM(C).eval()
+
+
+@pytest.mark.parametrize("filler", [False, True], ids=["two_streams", "two_streams_plus_mfma_filler"])
+def test_single_read_exchange_kernels_under_contention(filler):
+    """SE and CBAM single-read launches poll for granules of peer workgroups of the SAME image.  Two such launches run concurrently on
+    two streams (each sized for the whole chip), optionally beside a register-operand MFMA loop (two 4-wave workgroups on every CU)
+    on a third stream.  Every output must equal the oracle; no MI355_ESYNC may be pending afterwards."""
+    import mi355attn
+    from mi355attn import functional as F
+    se, cb = _chan_mods()
+    sds = _sd(se), _sd(cb)
+    torch.manual_seed(99)
+    xa, xb = torch.randn(48, 256, 56, 56), torch.randn(48, 256, 56, 56)
+    ref = {"se_a": O.se_forward(xa[:2], sds[0]["fc.0.weight"], sds[0]["fc.2.weight"]),
+           "cb_b": O.cbam_forward(xb[:2], sds[1]["ca.fc.0.weight"], sds[1]["ca.fc.2.weight"], sds[1]["sa.conv.weight"]),
+           "cb_a": O.cbam_forward(xa[-2:], sds[1]["ca.fc.0.weight"], sds[1]["ca.fc.2.weight"], sds[1]["sa.conv.weight"]),
+           "se_b": O.se_forward(xb[-2:], sds[0]["fc.0.weight"], sds[0]["fc.2.weight"])}
+    se, cb = se.cuda(), cb.cuda()
+    se2, cb2 = _chan_mods()
+    se2, cb2 = se2.cuda(), cb2.cuda()                               # second module instances: their own exchange workspaces per stream anyway
+    xa, xb = xa.cuda(), xb.cuda()
+    mi355attn.sync_status(wait=True)
+    s1, s2, s3 = torch.cuda.Stream(), torch.cuda.Stream(), torch.cuda.Stream()
+    sink, rep = torch.zeros(4, device="cuda"), torch.zeros(4, dtype=torch.int64, device="cuda")
+    with torch.no_grad():
+        se(xa), cb(xb), se2(xb), cb2(xa)                               # code objects loaded, workspaces zeroed
+    torch.cuda.synchronize()
+    outs = []
+    for it in range(6):
+        if filler:
+            with torch.cuda.stream(s3):                                # ~10 ms of MFMA work on every CU
+                F.check(mi355attn.lib().mi355_mfma_yardstick(0, 1 << 17, F.dptr(sink), F.dptr(rep), F.stream_ptr(sink.device)), "yardstick")
+        with torch.no_grad():
+            with torch.cuda.stream(s1):
+                ya = se(xa)
+                ca = cb(xa)
+            with torch.cuda.stream(s2):
+                cbb = cb2(xb)
+                yb = se2(xb)
+        outs.append((ya, ca, cbb, yb))
+    torch.cuda.synchronize()
+    mi355attn.sync_status(wait=True)                                   # raises if any exchange ran out of its poll budget
+    for ya, ca, cbb, yb in outs:
+        assert_parity(ya[:2].cpu(), ref["se_a"], 1e-5, "SE stream 1")
+        assert_parity(ca[-2:].cpu(), ref["cb_a"], 1e-5, "CBAM stream 1")
+        assert_parity(cbb[:2].cpu(), ref["cb_b"], 1e-5, "CBAM stream 2")
+        assert_parity(yb[-2:].cpu(), ref["se_b"], 1e-5, "SE stream 2")
+    first = outs[0]
+    for o in outs[1:]:
+        assert all(torch.equal(p, q) for p, q in zip(first, o)), "results differ between contended repetitions"
+
+
+# ---- helper classes of TripletAttention and BAM on their own ------------------------------------------------------------------------
+@pytest.mark.parametrize("B,C,H,W,ks", [(2, 64, 32, 32, 7), (3, 20, 9, 13, 3), (1, 7, 5, 6, 5)])
+def test_triplet_helper_classes_stand_alone(B, C, H, W, ks):
+    """ZPool / BasicConv2d / AttentionGate forwards (triplet_attention.py:19-49) against the same math in torch on the CPU."""
+    from mi355attn.modules.axis import AttentionGate, BasicConv2d, ZPool
+    torch.manual_seed(7)
+    x = torch.randn(B, C, H, W)
+    z = ZPool()(x.cuda())
+    zr = torch.cat([x.mean(dim=1, keepdim=True), x.max(dim=1, keepdim=True)[0]], dim=1)
+    assert_parity(z.cpu(), zr, 1e-6, "ZPool")
+    g = AttentionGate(ks).eval()
+    _bn_randomise(g)
+    c = g.conv
+    with torch.no_grad():
+        gr = x * torch.sigmoid(torch.relu(c.bn(c.conv(zr))))
+        gy = g.cuda()(x.cuda())
+    assert_parity(gy.cpu(), gr, 2e-6, "AttentionGate")
+    bc = BasicConv2d(C, 12, ks).eval()
+    _bn_randomise(bc)
+    with torch.no_grad():
+        br = torch.relu(bc.bn(bc.conv(x)))
+        by = bc.cuda()(x.cuda())
+    assert by.shape == br.shape
+    assert_parity(by.cpu(), br, 5e-5, "BasicConv2d")
+
+
+@pytest.mark.parametrize("B,C,H,W", [(2, 64, 32, 32), (3, 32, 9, 14)])
+def test_bam_gates_stand_alone(B, C, H, W):
+    """ChannelGate / SpatialGate forwards (bam.py:16-61) against the same math in torch on the CPU, and consistency with BAM.forward."""
+    from mi355attn.modules.axis import BAM
+    torch.manual_seed(9)
+    m = BAM(C).eval()
+    _bn_randomise(m)
+    x = torch.randn(B, C, H, W)
+    ch, sp = m.channel_attn, m.spatial_attn
+    with torch.no_grad():
+        cr = ch.bn(ch.mlp(x.mean(dim=(2, 3)))).view(B, C, 1, 1).expand_as(x)
+        sr = sp.bn(sp.conv3(sp.conv2(sp.conv1(x)))).expand_as(x)
+        yr = x + x * torch.sigmoid(cr + sr)
+        m = m.cuda()
+        cy = m.channel_attn(x.cuda())
+        sy = m.spatial_attn(x.cuda())
+        yy = m(x.cuda())
+    assert cy.shape == x.shape and sy.shape == x.shape
+    assert_parity(cy.cpu(), cr, 1e-5, "ChannelGate")
+    assert_parity(sy.cpu(), sr, 1e-4, "SpatialGate")
+    assert_parity(yy.cpu(), yr, 1e-5, "BAM")

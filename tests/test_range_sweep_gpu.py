@@ -29,7 +29,7 @@ pytestmark = pytest.mark.gpu
 FP16_MAX = 65504.0
 X_PEAK = 4 * FP16_MAX
 W_SCALE = 1.0e6            # init-scale weights x inputs give O(0.1-1) products: x 1e6 puts them far beyond 65520
-FIRES_TOL = 2e-4           # the bar of the existing fallback test (test_round6_gpu.py)
+FIRES_TOL = 2e-4           # the bar of the existing fallback test (test_range_guard_gpu.py)
 FALLBACK_MSG = "re-running this forward in strict mode"
 
 VECTOR_ONLY = {"se64", "cbam64", "eca64", "se256", "cbam256", "eca256", "simam64", "srm64", "gctg64", "lct64", "gct64", "gct64_l1",

@@ -11,28 +11,9 @@ import torch
 
 import oracle as O
 from conftest import assert_parity
+from kernel_cases import DA_SHAPES, P8_SHAPES, STRIPES, _ref_linear
 
 pytestmark = pytest.mark.gpu
-
-
-def _ref_linear(x16, w16, b, act, gamma, resid):
-    y = x16.double() @ w16.double().t()
-    if b is not None:
-        y = y + b.double()
-    if act:
-        y = torch.nn.functional.gelu(y)
-    if gamma is not None:
-        y = y * gamma.double()
-    if resid is not None:
-        y = y + resid.double()
-    return y
-
-
-P8_SHAPES = [  # (M, N, K): all have >= one full round of 256x256 tiles on a 256-CU part unless forced through gemm_variant 15
-    (50432, 2304, 768), (50432, 768, 768), (12544, 1536, 512), (50176, 1152, 384),
-    (65536 + 40, 256 + 8, 256),          # ragged in both directions, 2 tile columns, the second almost empty
-    (300, 264, 128), (256, 256, 64), (1, 8, 64), (4097, 520, 192),
-]
 
 
 @pytest.mark.parametrize("prec,dt", [(1, torch.float16), (2, torch.bfloat16)])
@@ -84,13 +65,8 @@ def test_persistent_gemm_split_last_round(M, N, K):
     assert torch.equal(ys, ys2), "split-K result is not deterministic"
     assert_parity(ys.cpu(), yu.cpu(), 2e-6, "split vs unsplit")
     rows = torch.tensor([0, 1, M // 3, M // 2 + 5, M - 2, M - 1])
-    ref = _ref_linear(x16[rows].cpu(), w16.cpu(), b.cpu(), False, None, resid[rows].cpu())
+    ref = _ref_linear(x16[rows].cpu(), w16.cpu(), b.cpu(), False, resid[rows].cpu())
     assert_parity(ys[rows].cpu(), ref.float(), 2e-6, "fp64 product, sampled rows")
-
-
-STRIPES = [  # (C, reso, heads, split, B): tokens per stripe = reso * split <= 64
-    (64, 56, 2, 1, 3), (128, 28, 4, 2, 3), (64, 28, 2, 2, 2), (64, 8, 2, 2, 5), (128, 16, 4, 4, 2), (64, 16, 2, 1, 1), (128, 8, 4, 8, 2), (64, 7, 2, 7, 3),
-]
 
 
 @pytest.mark.parametrize("prec,tol", [(1, 1e-3), (2, 8e-3)])
@@ -173,11 +149,6 @@ def test_split_round_poll_timeout_is_reported():
     mi355attn.sync_status(wait=True)
     ref = x16[:64].double().cpu() @ w16.double().cpu().t()
     assert_parity(y[:64].cpu(), ref.float(), 2e-6, "after the zero-budget launch (timed out: %s)" % timed_out)
-
-
-DA_SHAPES = [  # (B, C, H, W): c_m = c_n = 128 -- the two-pass path; pixel counts with and without a ragged last 32-pixel tile
-    (3, 256, 56, 56), (1, 256, 56, 56), (2, 256, 14, 14), (5, 128, 28, 28), (2, 256, 10, 10), (1, 128, 2, 2), (2, 256, 6, 10), (37, 256, 8, 8), (2, 256, 9, 12), (300, 128, 6, 6),
-]
 
 
 @pytest.mark.parametrize("prec,tol", [(1, 1e-3), (2, 8e-3)])

@@ -1,66 +1,22 @@
 """Round-4 boundary items ("Next round" 7 and the advisor's findings):
 
-  * GCT / LCT / Gaussian GCT are recorded under hipGraph capture with their single-read exchange kernels (launch tag and ticket in the
-    workspace, like SE / CBAM since round 3): replays, back-to-back replays and interleaved eager launches, bit-equal;
   * a kernel whose dynamic LDS depends on the shape (DoubleAttention(64,32,32): HW * 64 + 43 KB) runs a small image first and a large
     one afterwards (the attribute used to stay at the first value);
   * PAM at DANet's own width (dim = 512 > the attention kernel's widest head) against the oracle;
   * XCiT(drop_rate > 0) is the reference's eval-mode identity, and refused in train mode;
-  * guarded_forward: a saturated intermediate of a fused kernel (non-finite output for finite input) triggers the strict re-run, and the
-    re-run overrides sub-modules that were built with an explicit 16-bit precision;
-  * the fp16 range guard still reports a saturating value when the same lane has seen an input inf.
-"""
-import warnings
+  * left-over rows of the two-accumulator GEMM on the ring-pipelined small tiles; LPI on 2 x 2 patches per lane.
 
+The GCT / LCT capture test is in tests/test_chan_attn_gpu.py, the guarded_forward and range-guard tests in tests/test_range_guard_gpu.py,
+the Mixer token-mixing tests in tests/test_mixer_gpu.py.
+"""
 import pytest
 import torch
 
 import oracle as O
 from conftest import assert_parity
+from kernel_cases import TAIL_SHAPES
 
 pytestmark = pytest.mark.gpu
-
-
-def test_gct_lct_record_their_exchange_kernels_under_graph_capture():
-    import mi355attn
-    from mi355attn.modules import GCT, GaussianGCT, LCT
-    torch.manual_seed(3)
-    gct, lct, gg = GCT(64), LCT(64, 8), GaussianGCT(64)
-    gct1 = GCT(64, mode="l1")
-    with torch.no_grad():
-        gct.gamma.add_(0.5); gct.beta.add_(0.1); gct1.gamma.add_(0.3)
-        lct.w.mul_(1.5); lct.b.add_(0.2)
-    mods = [m.cuda() for m in (gct, gct1, lct, gg)]
-    static_x = torch.randn(6, 64, 28, 28, device="cuda")
-    with torch.no_grad():
-        for m in mods:
-            m(static_x)                                    # loads the code objects, makes the eager workspaces known
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g), torch.no_grad():
-        outs = [m(static_x) for m in mods]
-    for rep in range(4):
-        x = torch.randn(6, 64, 28, 28, device="cuda")
-        static_x.copy_(x)
-        g.replay()
-        if rep == 2:
-            g.replay()                                     # two replays back to back: the epoch advances inside the graph
-        torch.cuda.synchronize()
-        got = [o.clone() for o in outs]
-        with torch.no_grad():
-            want = [m(x) for m in mods]                    # eager launches in between
-        for a, b, m in zip(got, want, mods):
-            assert torch.equal(a, b), f"replay {rep}: {type(m).__name__} differs from the eager launch"
-    # the single-read kernels really were what ran: they must agree with the two-pass kernels only to fp32 noise, not bit for bit in general
-    with mi355attn.options(zoo_single=0), torch.no_grad():
-        two = [m(x) for m in mods]
-    for a, b, m in zip(got, two, mods):
-        assert_parity(a.cpu(), b.cpu(), 2e-6, f"{type(m).__name__} single-read (replayed) vs two-pass")
-    xc = x.cpu()
-    assert_parity(got[0].cpu(), O.gct_forward(xc, gct.alpha.cpu(), gct.gamma.cpu(), gct.beta.cpu(), 1e-5, "l2"), 1e-5, "GCT l2 replay vs oracle")
-    assert_parity(got[2].cpu(), O.lct_forward(xc, lct.w.cpu(), lct.b.cpu(), 8), 1e-5, "LCT replay vs oracle")
-    assert_parity(got[3].cpu(), O.gct_gauss_forward(xc), 1e-5, "Gaussian GCT replay vs oracle")
-    mi355attn.sync_status(wait=True)
 
 
 def test_dynamic_lds_limit_follows_the_largest_request():
@@ -120,71 +76,7 @@ def test_xcit_dropout_rates_are_eval_identities():
         XCiT(drop_rate=1.5, **kw)
 
 
-def test_guarded_forward_catches_a_saturated_fused_intermediate():
-    """CSWinBlock stage 1 runs LayerNorm + fc1 + GELU + fc2 in ONE kernel whose 16-bit hidden activations never leave the registers
-    (no range word to report into).  With fc1 scaled so that the hidden units pass 65504 the block's output is inf / NaN for a finite
-    input: guarded_forward must re-run in strict mode -- including the sub-modules built with an explicit precision=1."""
-    import mi355attn
-    from mi355attn.modules import CSWinBlock
-    torch.manual_seed(1234)
-    blk = CSWinBlock(64, 56, 2, split_size=1, qkv_bias=True, precision=1).eval()
-    with torch.no_grad():
-        blk.mlp.fc1.weight.mul_(3.0e4)                         # hidden pre-activations ~ 3e4 * O(1): beyond the fp16 range
-        blk.mlp.fc2.weight.mul_(1.0e-4)                        # keeps the fp32 reference finite and moderate
-    sd = {k: v.detach().clone() for k, v in blk.state_dict().items()}
-    torch.manual_seed(4321)
-    x = torch.randn(2, 3136, 64)
-    ref = O.cswin_block_forward(x, sd, 56, 2, 1)
-    assert torch.isfinite(ref).all()
-    blk = blk.cuda()
-    from conftest import no_range_fallback
-    with torch.no_grad(), no_range_fallback():                 # the raw fp16 result (round 6: module(x) itself would fall back to strict)
-        y_fast = blk(x.cuda())
-    torch.cuda.synchronize()
-    try:
-        mi355attn.range_status(wait=True)
-    except mi355attn.Mi355RangeError:
-        pass
-    assert not torch.isfinite(y_fast).all(), "the construction no longer saturates the fused kernel: strengthen it"
-    with warnings.catch_warnings(record=True) as rec:
-        warnings.simplefilter("always")
-        with torch.no_grad(), no_range_fallback():             # guarded_forward is the explicit form of the fallback: tested on its own
-            y = mi355attn.guarded_forward(blk, x.cuda())
-    assert any("strict mode" in str(w.message) for w in rec)
-    assert torch.isfinite(y).all()
-    assert_parity(y.cpu(), ref, 2e-4, "CSWinBlock s1 after the strict re-run")
-    assert blk.precision == 1 and blk.mlp.precision == 1, "explicit precisions must be restored after the re-run"
-
-
-def test_range_guard_sees_a_saturation_next_to_an_input_inf():
-    """rg_absmax skips a group of four that holds an inf (the input's own, not reported) instead of poisoning the lane's running maximum:
-    a later finite value >= 65520 in the same lane is still reported."""
-    import mi355attn
-    from mi355attn import functional as F
-    try:
-        mi355attn.range_status(wait=True)
-    except mi355attn.Mi355RangeError:
-        pass
-    x = torch.zeros(1 << 16, device="cuda")
-    x[0] = float("inf")                                        # the first group of four of lane 0 ...
-    F.cast16(x, 1)
-    mi355attn.range_status(wait=True)                          # ... is the input's own inf: no report
-    n = x.numel()
-    x[n - 4096:] = 7.0e4                                       # finite values that saturate, later in the same grid-stride walks
-    F.cast16(x, 1)
-    with pytest.raises(mi355attn.Mi355RangeError):
-        mi355attn.range_status(wait=True)
-
-
 # ---- left-over rows of the two-accumulator GEMM on ring-pipelined small tiles (option "gemm_pa_tail"; gemm16.hip) -------------------
-TAIL_SHAPES = [  # (M, N, K, tail kernel expected)
-    (128 * 392, 512, 2048, "32x64"),      # MixerLayer fc2 at B = 256: 784 tiles = 3.06 rounds -> 49 152 rows + 1 024 rows (the default's case)
-    (256 * 196, 384, 1536, "32x64"),      # XCiT-S fc2: 588 swapped tiles = 2.30 rounds -> 43 520 rows + 6 656 rows (1 248 ring workgroups, five per CU in turn)
-    (128 * 264, 256, 1024, "32x64"),      # one column tile, eight left-over tiles, the shortest reduction that splits
-    (128 * 160, 512, 1088, "32x64"),      # 320 tiles: one round + 64 (4 096 rows); 17 K-tiles (more than the ring holds)
-]
-
-
 @pytest.mark.parametrize("prec,dt", [(1, torch.float16), (2, torch.bfloat16)])
 @pytest.mark.parametrize("M,N,K,which", TAIL_SHAPES)
 def test_left_over_rows_on_the_ring_kernel_are_bit_identical(M, N, K, which, prec, dt):
@@ -299,60 +191,3 @@ def test_lpi_patch_kernel_against_the_general_kernel_and_the_oracle(C, with_ln, 
     if with_tail:
         ref = x + gamma * ref
     assert_parity(y1.cpu(), ref, 2e-5, "patch kernel vs oracle")
-
-
-# ---- MixerLayer token mixing in one kernel (csrc/mixer_fused.hip; option "mixer_fused") -----------------------------------------------
-@pytest.mark.parametrize("prec,tol", [(1, 1e-3), (2, 8e-3)])
-@pytest.mark.parametrize("B,C", [(1, 256), (5, 512), (3, 768)])
-def test_mixer_token_mixing_in_one_kernel(B, C, prec, tol):
-    """N = 196 tokens, T = C / 2 hidden token units (128 / 256 / 384): the fused half (row statistics + one kernel) against the three-launch path it replaces,
-    against the oracle of the whole layer, run-to-run bit identity, and an image's independence of its batch."""
-    import mi355attn
-    from mi355attn.modules import MixerLayer
-    torch.manual_seed(B * 1000 + C)
-    m = MixerLayer(C, 196, precision=prec).eval()
-    with torch.no_grad():
-        for ln in (m.norm1, m.norm2):
-            ln.weight.uniform_(0.5, 1.5)
-            ln.bias.normal_(0, 0.2)
-        m.token_mlp.fc1.bias.normal_(0, 0.3)
-        m.token_mlp.fc2.bias.normal_(0, 0.3)
-    sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
-    x = torch.randn(B, 196, C) * 1.3 + 0.2
-    ref = O.mixer_layer_forward(x, sd)
-    m = m.cuda()
-    xd = x.cuda()
-    with torch.no_grad():
-        with mi355attn.options(mixer_fused=1):
-            out = [None]
-
-            def run():
-                out[0] = m(xd)
-            tags = [t for t, *_ in mi355attn.kernel_trace(run)]
-            assert any("mixer_token_kernel" in t for t in tags), tags
-            assert not any("layernorm16_t" in t for t in tags), tags
-            y1 = out[0]
-            y1b = m(xd)
-            y_last = m(xd[B - 1:].contiguous())
-        with mi355attn.options(mixer_fused=0):
-            y0 = m(xd)
-    torch.cuda.synchronize()
-    assert torch.isfinite(y1).all()
-    assert torch.equal(y1, y1b), "run-to-run difference"
-    assert torch.equal(y1[B - 1:], y_last), "an image's bits depend on the batch"
-    assert_parity(y1.cpu(), ref, tol, "fused token mixing vs oracle")
-    assert_parity(y0.cpu(), ref, tol, "three-launch token mixing vs oracle")
-    assert_parity(y1.cpu(), y0.cpu(), tol, "fused vs three launches")
-
-
-def test_mixer_token_entry_refuses_other_geometries():
-    import ctypes
-    import mi355attn
-    from mi355attn import _ffi
-    L = _ffi.lib()
-    x = torch.zeros(1, 49, 256, device="cuda")
-    buf = torch.zeros(1 << 16, dtype=torch.uint8, device="cuda")
-    p = lambda t_: ctypes.c_void_p(t_.data_ptr())
-    rc = L.mi355_mixer_token_fwd(p(x), p(buf), p(buf), 1e-5, p(buf), p(buf), p(buf), p(buf), p(x), 1, 49, 256, 256, 1, p(buf), 1 << 16,
-                                 _ffi.stream_ptr(None))
-    assert rc == -2, rc          # MI355_EUNSUPPORTED (include/mi355attn.h)

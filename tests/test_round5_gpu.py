@@ -2,34 +2,20 @@
 
   * LayerScale with the published deep-XCiT initialisation (eta = 1e-5): the branch y - x of XCABlock against fp64 (the host no longer folds
     a gamma whose products would land in the fp16 subnormals);
-  * the fused Mixer token-mixing kernel reports a saturating 16-bit intermediate into the range word, like the launches it replaced;
-  * its "mixer_early" epilogue variant is bit-identical to the default;
-  * the in-process kernel tally: a refused launch leaves no phantom tag, a report longer than the caller's buffer is handed out whole;
-  * the MFMA yardstick of the bench line;
-  * `bench.py --gpus 2 --dist-backend gloo`: the whole N > 1 path (self-launch, barrier-bracketed windows, ranks_seen, host-staged
-    gather) end to end with the real kernels, two ranks sharing the one visible GPU.
-"""
-import ctypes
-import json
-import os
-import subprocess
-import sys
+  * the small-output GEMM, the four-token-tile MLP variant, the attention core on seven waves and gemm16_w4.hip, each bit-identical to the
+    path it replaces.
 
+The Mixer tests are in tests/test_mixer_gpu.py, the kernel tally, the MFMA yardstick and the bench.py runs in tests/test_bench_gpu.py, the
+fused Mixer kernel's range report in tests/test_range_guard_gpu.py.
+"""
 import pytest
 import torch
 
 import oracle as O
-from conftest import ROOT, assert_parity, rel_fro
+from conftest import assert_parity, rel_fro
+from kernel_cases import W4_CASES, _drain_range
 
 pytestmark = pytest.mark.gpu
-
-
-def _drain_range():
-    import mi355attn
-    try:
-        mi355attn.range_status(wait=True)
-    except mi355attn.Mi355RangeError:
-        pass
 
 
 @pytest.mark.parametrize("eta", [1e-5, 1e-3, 1.0])
@@ -54,118 +40,6 @@ def test_xcablock_small_layerscale_branch_accuracy(eta):
     assert err <= 2e-3 + 4 * floor, f"eta={eta}: branch error {err:.3e} (cancellation floor {floor:.1e})"
     folded = F.weight16_scaled(m.attn.proj.weight, m.attn.proj.bias, m.gamma1, 1) is not None
     assert folded == (eta >= 0.1), "fold decision"
-
-
-def test_fused_mixer_kernel_reports_a_saturating_intermediate():
-    """ADVICE round 4 (low): LN(x) * w + b above 65504 inside mixer_token_kernel must raise Mi355RangeError at the next check."""
-    import mi355attn
-    from mi355attn.modules import MixerLayer
-    _drain_range()
-    torch.manual_seed(5)
-    m = MixerLayer(256, 196, precision=1).eval().cuda()
-    x = torch.randn(2, 196, 256, device="cuda")
-    from conftest import no_range_fallback
-    with torch.no_grad(), no_range_fallback():                     # the reporting contract itself (round 6: module(x) would absorb the report)
-        tags = [t for t, *_ in mi355attn.kernel_trace(lambda: m(x))]
-        assert any("mixer_token_kernel" in t for t in tags), tags
-        mi355attn.range_status(wait=True)                          # ordinary data: nothing to report
-        m.norm1.weight.mul_(1.0e5)                                  # LN output ~1e5: finite in fp32, inf in fp16
-        raised = False
-        try:
-            m(x)                                                   # a later 16-bit launch of the same forward may already see the report
-        except mi355attn.Mi355RangeError:
-            raised = True
-    if not raised:
-        with pytest.raises(mi355attn.Mi355RangeError, match="fused block kernel"):
-            mi355attn.range_status(wait=True)
-    _drain_range()
-    m2 = MixerLayer(256, 196, precision=2).eval().cuda()           # bf16 operands have the fp32 range: nothing to report
-    m2.load_state_dict(m.state_dict())
-    with torch.no_grad():
-        m2(x)
-    mi355attn.range_status(wait=True)
-
-
-@pytest.mark.parametrize("prec", [1, 2])
-def test_mixer_early_residual_variant_is_bit_identical(prec):
-    import mi355attn
-    from mi355attn.modules import MixerLayer
-    torch.manual_seed(11)
-    m = MixerLayer(512, 196, precision=prec).eval().cuda()
-    x = torch.randn(7, 196, 512, device="cuda")
-    with torch.no_grad():
-        with mi355attn.options(mixer_early=0):
-            y0 = m(x)
-        with mi355attn.options(mixer_early=1):
-            seen = []
-            def run():
-                seen.append(m(x))
-            tags = [t for t, *_ in mi355attn.kernel_trace(run)]
-    assert any("mixer_token_kernel<early>" in t for t in tags), tags
-    assert torch.equal(y0, seen[0])
-
-
-def test_trace_has_no_phantom_tags_and_long_reports_survive():
-    """A launch the two-accumulator kernel refuses (K too short for its fp32 epilogue) must not leave a tag; a report longer than the
-    caller's buffer is kept by the library and handed out whole on the second call."""
-    import mi355attn
-    from mi355attn import _ffi
-    from mi355attn import functional as F
-    x16 = torch.randn(512, 384, device="cuda").half()
-    w16 = torch.randn(256, 384, device="cuda").half()
-    res = torch.randn(512, 256, device="cuda")
-
-    def run():
-        F.linear16(x16, w16, None, resid=res, precision=1)            # fp32 out + residual, K = 384 < 640: not gemm16_pa's shape
-    rows = mi355attn.kernel_trace(run)
-    assert len(rows) == 1 and rows[0][1] == 1, rows                   # exactly one kernel ran, exactly one tag with one launch
-    assert all(mn > 0.5 for _, _, _, mn, _ in rows), rows             # no near-zero phantom interval
-    # long report: many distinct tags through a 64-byte buffer
-    L = _ffi.lib()
-    assert L.mi355_trace_begin() == 0
-    for k in (64, 128, 192, 256, 320):
-        F.linear16(torch.randn(256, k, device="cuda").half(), torch.randn(64, k, device="cuda").half(), None, out16=True, precision=1)
-    torch.cuda.synchronize()
-    small = ctypes.create_string_buffer(64)
-    need = L.mi355_trace_end(small, 64)
-    assert need > 64
-    big = ctypes.create_string_buffer(need + 1)
-    assert L.mi355_trace_end(big, need + 1) == need
-    lines = big.value.decode().splitlines()
-    assert len(lines) == 5 and all(len(l.split("\t", 4)) == 5 for l in lines), lines
-    assert big.value.decode().startswith(small.value.decode())
-    assert L.mi355_trace_end(big, need + 1) == 0                      # handed out whole: dropped
-
-
-def test_mfma_yardstick_reads_a_sane_rate_and_clock():
-    from mi355attn import functional as F
-    dev = torch.device("cuda", 0)
-    y0 = F.mfma_yardstick(dev, 0, target_ms=10.0)
-    y1 = F.mfma_yardstick(dev, 1, target_ms=10.0)
-    for y in (y0, y1):
-        assert 300.0 < y["TFLOPs"] < 2600.0, y                        # between a badly throttled part and the 2.5 PF nameplate
-    assert 500.0 < y1["sclk_MHz_issue"] < 2500.0, y1
-    if y1["sclk_MHz_counter"]:
-        assert 50.0 < y1["sclk_MHz_counter"] < 3000.0, y1
-
-
-@pytest.mark.parametrize("workload,first_key", [("c5", "ViTBase"), ("c2", "SE")])
-def test_bench_two_ranks_share_one_gpu_on_gloo(workload, first_key):
-    """c5: the end-of-forward gather path; c2 (round 6): the single-read SE / CBAM exchange kernels of two processes share the GPU -- each
-    launch polls for peer workgroups of its own grid while the other rank's grid occupies CUs (VERDICT round 5, weak #12)."""
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    env["OMP_NUM_THREADS"] = "4"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--workload", workload, "--batch", "16",
-           "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-strict", "--no-calib"]
-    r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-    # two ranks on ONE GPU: a launch-path run, reported as such (ADVICE round 5) -- n_gpus counts distinct devices
-    assert line["n_gpus"] == 1 and line["scaling"].startswith("none") and line["config"]["distinct_gpus"] == 1
-    assert line["config"]["ranks_seen"] == 2 and len(line["ms_per_step_by_rank"]) == 2
-    assert line["config"]["dist_backend"] == "gloo" and "gloo" in line["config"]["gather"]
-    assert len(line["ms_windows"]) == 3 and line["value"] > 0
-    assert line["blocks"][0]["key"] == first_key
 
 
 @pytest.mark.parametrize("prec", [0, 1, 2])
@@ -224,33 +98,6 @@ def test_fused_mlp_four_tile_variant_is_bit_identical(prec):
 
 
 @pytest.mark.parametrize("prec", [1, 2])
-@pytest.mark.parametrize("B,C", [(8, 512), (5, 512), (16, 256), (3, 768)])
-def test_mixer_statistics_inside_the_token_kernel_are_bit_identical(B, C, prec):
-    """Option "mixer_stats": LayerNorm row statistics computed inside mixer_token_kernel (phase 0, every workgroup of an image reads the
-    image's rows once more; the two workgroups of an image get block ids 8 apart when B % 8 == 0) against the row_stats_kernel pre-pass:
-    same per-lane sums in the same order, hence the same bits -- for one / two / three workgroups per image and both id mappings."""
-    import mi355attn
-    from mi355attn.modules import MixerLayer
-    torch.manual_seed(B * 100 + C)
-    m = MixerLayer(C, 196, precision=prec).eval().cuda()
-    with torch.no_grad():
-        m.norm1.weight.uniform_(0.5, 1.5)
-        m.norm1.bias.normal_(0, 0.2)
-    x = torch.randn(B, 196, C, device="cuda") * 1.7 + 0.3
-    with torch.no_grad():
-        with mi355attn.options(mixer_stats=0):
-            t0 = [t for t, *_ in mi355attn.kernel_trace(lambda: m(x))]
-            y0 = m(x)
-        with mi355attn.options(mixer_stats=1):
-            seen = []
-            t1 = [t for t, *_ in mi355attn.kernel_trace(lambda: seen.append(m(x)))]
-    assert any("row_stats_kernel" in t for t in t0), t0
-    if C == 512:                                                       # phase 0 is built for C = 512 (two float4 per lane and row)
-        assert not any("row_stats_kernel" in t for t in t1) and any("mixer_token_kernel<stats>" in t for t in t1), t1
-    assert torch.isfinite(y0).all() and torch.equal(y0, seen[0])
-
-
-@pytest.mark.parametrize("prec", [1, 2])
 def test_attention_core_on_seven_waves_is_bit_identical(prec):
     """Option "attn_nw" = 7: the 13 query tiles of a 197-token head on seven waves (six carry two tiles, one carries one) instead of eight
     (five carry two, three carry one).  A query tile's arithmetic does not depend on the wave that owns it: same bits."""
@@ -268,18 +115,6 @@ def test_attention_core_on_seven_waves_is_bit_identical(prec):
 
 
 # ---- gemm16_w4.hip: the one-wave-per-SIMD persistent kernel --------------------------------------------------------------------------
-W4_CASES = [  # M, N, K, gelu, bias
-    (2048, 2304, 768, False, True),        # fewer tiles than CUs (72)
-    (256 * 20, 768, 768, True, True),      # 60 tiles, GELU epilogue
-    (256 * 90, 768, 320, False, False),    # 270 tiles = 1 round + 14, odd number of K-tiles (5), no bias
-    (256 * 30, 512, 128, False, True),     # two K-tiles: the shortest stream the kernel takes
-    (256 * 33, 1024, 1024, True, False),   # 132 tiles, GELU, no bias
-    (256 * 131, 512, 576, False, True),    # 262 tiles = 1 round + 6
-    (256 * 197, 2304, 768, False, True),   # the qkv product of ViT-Base at the timed size (B = 256): 1773 tiles = 6.93 rounds
-    (256 * 197, 3072, 768, True, True),    # fc1 of ViT-Base at the timed size, GELU epilogue: 2364 tiles
-]
-
-
 @pytest.mark.parametrize("prec", [1, 2])
 @pytest.mark.parametrize("case", W4_CASES)
 def test_one_wave_per_simd_gemm_is_bit_identical_to_the_eight_wave_kernel(case, prec):
@@ -376,28 +211,3 @@ def test_one_wave_per_simd_gemm_under_graph_capture_and_on_a_side_stream():
     side.synchronize()
     assert torch.equal(y_side, y_ref)
     _drain_range()
-
-
-def test_bench_plain_run_times_its_steps_and_dumps_outputs(tmp_path):
-    """A plain bench.py run (no --full): the headline keys only, exactly --steps timed steps, and --dump-outputs writes the last timed
-    step's outputs, the same values on a second run with the same arguments."""
-    import numpy as np
-    import bench
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    lines = []
-    for d in ("a", "b"):
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "c2", "--batch", "4", "--steps", "3",
-               "--warmup", "1", "--dump-outputs", str(tmp_path / d)]
-        r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
-        assert r.returncode == 0, r.stderr[-3000:]
-        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
-    line = lines[0]
-    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
-        assert k in line, k
-    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
-    assert "roofline" not in line and "cpu_baseline" not in line
-    assert sorted(os.listdir(tmp_path / "a")) == ["CBAM.npy", "ECA.npy", "SE.npy"]
-    for n in ("SE", "CBAM", "ECA"):
-        a, b = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
-        assert a.dtype == np.float32 and a.size == min(4 * 256 * 56 * 56, bench.DUMP_ELEMS) and np.isfinite(a).all()
-        assert np.allclose(a, b, rtol=1e-5, atol=1e-6), n

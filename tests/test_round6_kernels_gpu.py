@@ -8,13 +8,9 @@ import pytest
 import torch
 
 from conftest import assert_parity
+from kernel_cases import _tags, _xca_ref
 
 pytestmark = pytest.mark.gpu
-
-
-def _tags(fn):
-    import mi355attn
-    return [t for t, *_ in mi355attn.kernel_trace(fn)]
 
 
 @pytest.mark.parametrize("prec", [1, 2])
@@ -68,18 +64,6 @@ def test_weight_stationary_gemm_output_may_alias_the_residual():
                                 _ffi.stream_ptr(y.device)) == 0
     torch.cuda.synchronize()
     assert torch.equal(y, want)
-
-
-def _xca_ref(qkv16, temperature, heads):
-    """fp64 evaluation of xcit.py:249-262 on the 16-bit inputs (what both kernels are given)."""
-    B, N, C3 = qkv16.shape
-    C = C3 // 3
-    d = C // heads
-    q, k, v = (qkv16.double().cpu().reshape(B, N, 3, heads, d).permute(2, 0, 3, 4, 1))      # (3, B, h, d, N)
-    q = q / q.norm(dim=-1, keepdim=True).clamp_min(1e-12)
-    k = k / k.norm(dim=-1, keepdim=True).clamp_min(1e-12)
-    a = ((q @ k.transpose(-2, -1)) * temperature.double().cpu().reshape(1, heads, 1, 1)).softmax(dim=-1)
-    return (a @ v).permute(0, 3, 1, 2).reshape(B, N, C)
 
 
 @pytest.mark.parametrize("prec", [1, 2])
@@ -164,35 +148,6 @@ def test_wide_fused_mlp_matches_the_reference_expression(C, M, use_gamma, prec):
     h16 = F.linear16(u16, F.weight16(fc1.weight, prec), fc1.bias, act=F.ACT_GELU, out16=True, precision=prec)
     comp = F.linear16(h16, F.weight16(fc2.weight, prec), fc2.bias, gamma=gd, resid=xg, precision=prec)
     assert_parity(y.cpu(), comp.cpu(), tol, "mlp_wide vs LayerNorm + two GEMMs")
-
-
-def test_wide_fused_mlp_reports_a_saturating_hidden_activation():
-    """fc1 scaled so that gelu(H) passes 65504: the static proof fails on the host, the kernel tracks and reports (code 4), and module(x)
-    of a CSWin stage-3 block falls back to strict mode like the reference (cswin.py:194-196 computes in fp32)."""
-    import warnings
-    import oracle as O
-    import mi355attn
-    from mi355attn.modules import CSWinBlock
-    torch.manual_seed(1234)
-    m = CSWinBlock(256, 14, 8, split_size=7, qkv_bias=True).eval()
-    with torch.no_grad():
-        m.mlp.fc1.weight.mul_(1e5)
-        m.mlp.fc2.weight.mul_(1e-4)
-    sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
-    torch.manual_seed(4321)
-    x = torch.randn(4, 196, 256)
-    ref = O.cswin_block_forward(x, sd, 14, 8, 7)
-    md = m.cuda()
-    mi355attn.range_status(wait=True)
-    with mi355attn.options(mlp_wide=1), warnings.catch_warnings(record=True) as w:
-        warnings.simplefilter("always")
-        with torch.no_grad():
-            tags = _tags(lambda: md(x.cuda()))
-            y = md(x.cuda())
-        torch.cuda.synchronize()
-    assert any("mlp_wide_kernel" in t for t in tags), tags
-    assert len([i for i in w if "strict mode" in str(i.message)]) == 2, [str(i.message) for i in w]      # two forwards, each falls back
-    assert_parity(y.cpu(), ref, 2e-4, "CSWin s3 with a saturating hidden activation [strict re-run]")
 
 
 @pytest.mark.parametrize("M,K", [(50176, 384), (4096 + 21, 256), (588, 384), (33, 256)])
