@@ -627,7 +627,15 @@ int mi355_xca16_fwd(const void* qkv, int qkv_is16, const float* temperature, voi
 
 /* XCiT LPI.forward (xcit.py:149-157) with BatchNorm2d in eval mode (running statistics):
  *   tokens (B,N=H*W,C) -> dw3x3(w1,b1) -> GELU -> (v - bn_mean)/sqrt(bn_var + bn_eps)*bn_w + bn_b -> dw3x3(w2,b2) -> tokens.
- *   w1,w2 (C,3,3); y = resid + gamma * LPI(x) when gamma / resid are non-NULL (XCABlock :292). */
+ *   w1,w2 (C,3,3); y = resid + gamma * LPI(x) when gamma / resid are non-NULL (XCABlock :292).
+ * Any grid H, W >= 1 and any C >= 1 (the same for the two LayerNorm-fused entries below):
+ *   14 x 14 tokens, C % 32 == 0, 16-byte aligned tensors, option "lpi_patch" = 1   lpi_patch_kernel (unchanged)
+ *   other grids of at most 256 tokens (16 x 16)                                     lpi_kernel: the whole zero-haloed grid of 32 channels in LDS
+ *   larger grids (patch 8 at 224 px: 28 x 28; patch 16 at 384 px: 24 x 24)          lpi_tile_kernel: a workgroup handles a tile of the grid with a
+ *     2-cell halo of input; the tile depends on (H, W) only (row bands of the full width while a band of >= 4 rows fits in 48 KB of LDS,
+ *     column tiles as well on wider grids), so an image's result does not depend on its batch.  Intermediate cells outside the grid are
+ *     zero (conv2's padding), those inside are recomputed; the per-element expressions are lpi_kernel's.  On these grids y must not
+ *     overlap x (neighbouring tiles read each other's rows); resid may be x. */
 size_t mi355_lpi_workspace_bytes(int B, int H, int W, int C);
 int    mi355_lpi_fwd(const float* x, const float* w1, const float* b1, const float* bn_w, const float* bn_b,
                      const float* bn_mean, const float* bn_var, float bn_eps, const float* w2, const float* b2,

@@ -10,7 +10,8 @@
 //
 // LPI (xcit.py:149-157): tokens -> (C,H,W) image -> dw3x3 -> GELU -> BatchNorm(eval) -> dw3x3 -> tokens, fused in one
 // kernel per (image, 32-channel group): the token tile and the intermediate sit in LDS, a lane owns 4 channels (16-byte LDS
-// and HBM accesses, 128-byte row pieces per token); LayerScale + residual fused.
+// and HBM accesses, 128-byte row pieces per token); LayerScale + residual fused.  Token grids above 16 x 16 (patch 8 at 224 px, patch 16
+// at 384 px) run the same block per (image, tile of the grid, 32-channel group) with a 2-cell halo: lpi_tile_kernel.
 #include <type_traits>
 #include "common.h"
 #include "mma.h"
@@ -713,6 +714,157 @@ __global__ __launch_bounds__(256, 4) void lpi_patch_kernel(const float* __restri
         if (mine(j)) *reinterpret_cast<f4*>(yp + (long)(tl + 32 * j) * C) = s[adr_of(tl + 32 * j)] + rr[j];
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Token grids above 16 x 16 (XCiT patch 8 at 224 px: 28 x 28; patch 16 at 384 px: 24 x 24; any H, W, C): lpi_kernel's block on a TILE of
+// the grid.  Workgroup = (image, tile, 32 channels); the tile is `rows` x `cols` output tokens and sits in LDS with a 2-cell halo of
+// INPUT, because two stacked 3 x 3 stencils reach that far.  Same structure as lpi_kernel: 32 token lanes x 8 channel quads, 16-byte
+// LDS / HBM accesses, the first conv's results wait in registers and overwrite the tile in place, no bounds logic in the stencils, the
+// same per-element expressions in the same order (separately rounded products and sums, gelu_fast4, BatchNorm as (v - mean) * rstd *
+// bw + bb, LayerNorm as (v - mean) * rstd * lw + lb from `stats`, which therefore holds a row for every halo token as well).
+//   * input cells outside the grid are zero (conv1's padding); every cell of the tile is written exactly once on the way in, so there
+//     is no separate zero fill;
+//   * the intermediate is needed on the 1-cell ring around the tile's outputs: ring cells INSIDE the grid are recomputed (conv1 + GELU
+//     + BatchNorm, what the neighbouring tile computes for its own outputs: same inputs, same expressions, same bits); ring cells
+//     OUTSIDE the grid are ZERO -- they are conv2's padding, not conv1 of padded input (that would be bn(gelu(b1)) != 0);
+//   * the outermost ring keeps its input values after the in-place overwrite; conv2 never reads it.
+// Tile shape: lpi_tile_shape below, from (H, W) alone -- at most 384 cells of 128 bytes (48 KB: three workgroups per CU, which is what
+// __launch_bounds__(256, 3) states), hence at most 320 ring-1 cells = LPI_TILE_TM per thread.  Cell coordinates advance by 32 cells per
+// step without a division (quotient and remainder of 32 by the pitch are workgroup constants).  y must not alias x: neighbouring
+// tiles read each other's rows.
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int LPI_TILE_CELLS = 384;   // (rows + 4) * (cols + 4) <= this
+constexpr int LPI_TILE_TM = 10;       // (rows + 2) * (cols + 2) <= 32 * this whenever the line above holds (a + b >= 2 sqrt(ab))
+
+template <bool LN>
+__global__ __launch_bounds__(256, 3) void lpi_tile_kernel(const float* __restrict__ x, const float* __restrict__ w1,
+                                                         const float* __restrict__ b1, const float* __restrict__ bn_w,
+                                                         const float* __restrict__ bn_b, const float* __restrict__ bn_m,
+                                                         const float* __restrict__ bn_v, float bn_eps, const float* __restrict__ w2,
+                                                         const float* __restrict__ b2, const float* __restrict__ gamma,
+                                                         const float* __restrict__ resid, float* __restrict__ y, int H, int W, int C,
+                                                         int groups, int R, int TW, int nby, int nbx, const float* __restrict__ stats,
+                                                         const float* __restrict__ ln_w, const float* __restrict__ ln_b) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* s_x = smem;                 // [(rows+4)][(cols+4)][32]: input tile with its 2-cell halo, then the intermediate on the inner ring
+    const int t = threadIdx.x, cq = t & 7, tl = t >> 3;              // channel quad, token lane
+    int bid = blockIdx.x;                                            // (image, tile row, tile column, channel group), group fastest
+    const int c = (bid % groups) * LPI_CG + cq * 4;
+    bid /= groups;
+    const int bx = bid % nbx;
+    bid /= nbx;
+    const int by = bid % nby, b = bid / nby;
+    const int r0 = by * R, c0 = bx * TW;                             // first output row / column of the tile
+    const int rows = min(R, H - r0), cols = min(TW, W - c0), PW = cols + 4;
+    const long N = (long)H * W;
+    const bool vec = ((C & 3) == 0) && (c + 3 < C);                  // whole quad in range and 16-byte aligned rows
+    const float* xb = x + (long)b * N * C;
+    auto ldc = [&](const float* p, int cc, float dflt) { return cc < C ? p[cc] : dflt; };
+    auto ld4 = [&](const float* p, float dflt) { return f4{ldc(p, c, dflt), ldc(p, c + 1, dflt), ldc(p, c + 2, dflt), ldc(p, c + 3, dflt)}; };
+    auto inside = [&](int gy, int gx) { return (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W; };
+    // ---- the tile with its halo: cell p = tl + 32 i, four loads in flight per thread ----
+    {
+        const f4 lw = LN ? ld4(ln_w, 0.f) : f4{1.f, 1.f, 1.f, 1.f}, lb = LN ? ld4(ln_b, 0.f) : f4{0.f, 0.f, 0.f, 0.f};
+        const int ncell = (rows + 4) * PW, q32 = 32 / PW, r32 = 32 - q32 * PW;
+        int ty = tl / PW, tx = tl - ty * PW;
+        for (int p0 = tl; p0 < ncell; p0 += 128) {
+            f4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int gy = r0 - 2 + ty, gx = c0 - 2 + tx;
+                v[u] = f4{0.f, 0.f, 0.f, 0.f};
+                if (p0 + 32 * u < ncell && inside(gy, gx)) {
+                    const long n = (long)gy * W + gx;
+                    const float* xr = xb + n * C;
+                    if (vec) v[u] = *reinterpret_cast<const f4*>(xr + c);
+                    else v[u] = f4{ldc(xr, c, 0.f), ldc(xr, c + 1, 0.f), ldc(xr, c + 2, 0.f), ldc(xr, c + 3, 0.f)};
+                    if (LN) {                                         // the expression of layernorm_kernel: same bits as the unfused LayerNorm
+                        const float mean = stats[((long)b * N + n) * 2], rstd = stats[((long)b * N + n) * 2 + 1];
+                        v[u] = (v[u] - mean) * rstd * lw + lb;
+                    }
+                }
+                tx += r32;
+                ty += q32;
+                if (tx >= PW) { tx -= PW; ++ty; }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (p0 + 32 * u < ncell) *reinterpret_cast<f4*>(s_x + (p0 + 32 * u) * LPI_CG + cq * 4) = v[u];
+        }
+    }
+    auto tap = [&](const float* p, int ch, int i) { return ch < C ? p[(long)ch * 9 + i] : 0.f; };     // dw weight (C,3,3)
+    auto taps = [&](const float* p, f4* k) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) k[i] = f4{tap(p, c, i), tap(p, c + 1, i), tap(p, c + 2, i), tap(p, c + 3, i)};
+    };
+    auto conv = [&](const f4* k, f4 bias, int at) {                  // 3x3 around tile cell `at`: nine 16-byte LDS reads, no bounds logic
+        f4 acc = bias;
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx)
+                acc = acc + k[(dy + 1) * 3 + dx + 1] * *reinterpret_cast<const f4*>(s_x + at + (dy * PW + dx) * LPI_CG);
+        return acc;
+    };
+    f4 k[9];
+    taps(w1, k);
+    const f4 bias1 = ld4(b1, 0.f);
+    const f4 mean = ld4(bn_m, 0.f), var = ld4(bn_v, 1.f), bw = ld4(bn_w, 0.f), bb = ld4(bn_b, 0.f);
+    const f4 rstd = f4{1.0f / sqrtf(var.x + bn_eps), 1.0f / sqrtf(var.y + bn_eps), 1.0f / sqrtf(var.z + bn_eps),
+                       1.0f / sqrtf(var.w + bn_eps)};
+    // ---- the intermediate on the tile's outputs and the ring around them: cell m = tl + 32 j of a (rows+2) x (cols+2) window ----
+    const int IW = cols + 2, nmid = (rows + 2) * IW;
+    int cell[LPI_TILE_TM];
+    f4 v0[LPI_TILE_TM];
+    __syncthreads();
+    {
+        const int q32 = 32 / IW, r32 = 32 - q32 * IW;
+        int iy = tl / IW, ix = tl - iy * IW;
+#pragma unroll
+        for (int j = 0; j < LPI_TILE_TM; ++j) {
+            cell[j] = ((iy + 1) * PW + ix + 1) * LPI_CG + cq * 4;
+            v0[j] = f4{0.f, 0.f, 0.f, 0.f};                           // outside the grid: conv2's zero padding
+            if (tl + 32 * j < nmid && inside(r0 - 1 + iy, c0 - 1 + ix)) {
+                const f4 u = conv(k, bias1, cell[j]);
+                const f4 v = gelu_fast4(u);   // |erf error| <= 1.5e-7, ~3x fewer instructions than erff
+                v0[j] = (v - mean) * rstd * bw + bb;
+            }
+            ix += r32;
+            iy += q32;
+            if (ix >= IW) { ix -= IW; ++iy; }
+        }
+    }
+    taps(w2, k);                          // the first conv's taps are dead: same registers
+    const f4 bias2 = ld4(b2, 0.f);
+    __syncthreads();                      // every neighbourhood of the input tile has been read
+#pragma unroll
+    for (int j = 0; j < LPI_TILE_TM; ++j)
+        if (tl + 32 * j < nmid) *reinterpret_cast<f4*>(s_x + cell[j]) = v0[j];
+    __syncthreads();
+    // ---- outputs: token o = tl + 32 j of the rows x cols interior ----
+    const f4 gm = gamma ? ld4(gamma, 1.f) : f4{1.f, 1.f, 1.f, 1.f};
+    const int nout = rows * cols, q32 = 32 / cols, r32 = 32 - q32 * cols;
+    int oy = tl / cols, ox = tl - oy * cols;
+#pragma unroll
+    for (int j = 0; j < LPI_TILE_TM; ++j) {
+        if (tl + 32 * j < nout) {
+            f4 v = conv(k, bias2, ((oy + 2) * PW + ox + 2) * LPI_CG + cq * 4);
+            const long o = ((long)b * N + (long)(r0 + oy) * W + c0 + ox) * C + c;
+            if (gamma) v = v * gm;
+            if (vec) {
+                if (resid) v = v + *reinterpret_cast<const f4*>(resid + o);
+                *reinterpret_cast<f4*>(y + o) = v;
+            } else {
+                const float vv[4] = {v.x, v.y, v.z, v.w};
+                for (int q = 0; q < 4; ++q)
+                    if (c + q < C) y[o + q] = vv[q] + (resid ? resid[o + q] : 0.f);
+            }
+        }
+        ox += r32;
+        oy += q32;
+        if (ox >= cols) { ox -= cols; ++oy; }
+    }
+}
+
 // (mean, rstd) of every token row: the statistics of layernorm_kernel (two-pass, biased variance, eps inside the sqrt), one wave per
 // row; what the LayerNorm-fused LPI above normalises with.  Reads x once, writes 8 bytes per row.
 __global__ __launch_bounds__(256) void ln_stats_kernel(const float* __restrict__ x, float* __restrict__ stats, long rows, int cols, float eps) {
@@ -828,10 +980,49 @@ size_t mi355_lpi_workspace_bytes(int B, int H, int W, int) {      // (mean, rstd
     return (size_t)B * H * W * 2 * sizeof(float) + 16;
 }
 
+// Tile of lpi_tile_kernel for an H x W token grid: R rows x TW columns of outputs, (R + 4) * (TW + 4) <= LPI_TILE_CELLS.  A function of
+// (H, W) only -- not of B, C or the CU count -- so an image's result does not depend on the batch it arrives in.
+//   * W <= 44 (a band of at least 4 rows fits): row bands of the full width, the tallest that fit, evened out over the grid
+//     (28 x 28: 4 bands of 7 rows, 44 KB; 24 x 24: 3 bands of 8 rows, 42 KB).  The kernel then loads (R + 4) / R and runs conv1 on
+//     about (R + 2) / R of what an untiled pass would.
+//   * wider grids: column tiles as well -- the number of tile columns that loads the fewest cells per output, rows as above.
+static void lpi_tile_shape(int H, int W, int* R, int* TW) {
+    auto band = [&](int tw) {                                        // evened-out band height for tile width tw (0: not even one row fits)
+        const int rmax = LPI_TILE_CELLS / (tw + 4) - 4;
+        if (rmax < 1) return 0;
+        return (int)cdiv(H, cdiv(H, rmax < H ? rmax : H));
+    };
+    *TW = W;
+    *R = band(W);
+    if (W <= 44) return;
+    double best = 1e30;
+    for (int nbx = 1; nbx <= W; ++nbx) {
+        const int tw = (int)cdiv(W, nbx), r = band(tw);
+        if (r > 0) {
+            const double cost = (double)(r + 4) * (tw + 4) / ((double)r * tw);
+            if (cost < best) { best = cost; *R = r; *TW = tw; }
+        }
+        if (tw <= 8) break;                                          // narrower tiles only load more halo
+    }
+}
+
 static int lpi_launch(const float* x, const float* w1, const float* b1, const float* bn_w, const float* bn_b, const float* bn_mean,
                       const float* bn_var, float bn_eps, const float* w2, const float* b2, const float* gamma, const float* resid,
                       float* y, int B, int H, int W, int C, const float* stats, const float* ln_w, const float* ln_b, hipStream_t st) {
-    if (H * W > 32 * LPI_TMAX) return mi355::fail(MI355_EUNSUPPORTED, "mi355_lpi_fwd: %dx%d token grid exceeds the LDS tile (<= 256 tokens)", H, W);
+    if ((long)H * W > 32 * LPI_TMAX) {
+        // above 16 x 16 tokens: tiles of the grid with a 2-cell halo (see lpi_tile_kernel)
+        int R, TW;
+        lpi_tile_shape(H, W, &R, &TW);
+        const int groups = cdiv(C, LPI_CG), nby = cdiv(H, R), nbx = cdiv(W, TW);
+        const long grid = (long)B * groups * nby * nbx;
+        if (grid > 0x7fffffffL) return mi355::fail(MI355_EINVAL, "mi355_lpi_fwd: B=%d %dx%d C=%d needs %ld workgroups", B, H, W, C, grid);
+        const size_t smem = (size_t)(R + 4) * (TW + 4) * LPI_CG * sizeof(float);
+        MI355_TRACE(st, "lpi_tile_kernel%s B=%d %dx%d C=%d tile=%dx%d", stats ? "<ln>" : "", B, H, W, C, R, TW);
+        if (stats) lpi_tile_kernel<true><<<(unsigned)grid, 256, smem, st>>>(x, w1, b1, bn_w, bn_b, bn_mean, bn_var, bn_eps, w2, b2, gamma, resid, y, H, W, C, groups, R, TW, nby, nbx, stats, ln_w, ln_b);
+        else       lpi_tile_kernel<false><<<(unsigned)grid, 256, smem, st>>>(x, w1, b1, bn_w, bn_b, bn_mean, bn_var, bn_eps, w2, b2, gamma, resid, y, H, W, C, groups, R, TW, nby, nbx, nullptr, nullptr, nullptr);
+        MI355_LAUNCH_CHECK();
+        return MI355_OK;
+    }
     if (H == 14 && W == 14 && (C % LPI_CG) == 0 && mi355::opt(mi355::O_LPI_PATCH) && aligned16(x) && aligned16(y) && (!resid || aligned16(resid)) &&
         (!stats || (aligned16(ln_w) && aligned16(ln_b)))) {
         // 2 x 2 patches per lane, channel-quad-major planes (see lpi_patch_kernel)
