@@ -260,7 +260,7 @@ int    mi355_cbam_fwd(const float* x, const float* w1, const float* w2, const fl
                       int B, int C, int Cr, int ks, int H, int W, int stage,
                       void* ws, size_t ws_bytes, mi355_stream_t stream);
 
-/* ---- the same three blocks on 16-bit activations (chan_io16.hip) ------------------------------------------------------------------
+/* ---- the same three blocks (and the SE variants) on 16-bit activations (chan_io16.hip) ------------------------------------------------------------------
  * x and y are NCHW in ONE 16-bit type selected by `io` (the precision codes: 1 = IEEE half, 2 = bfloat16); parameters stay fp32.
  * All arithmetic is fp32 inside the kernels (pooling sums, excitation MLP, ECA taps, k x k conv, sigmoid, products); y is rounded once,
  * to nearest even, at the store.  0 < gate < 1, so a finite product cannot overflow: these entries report nothing to
@@ -274,6 +274,10 @@ int    mi355_cbam_fwd(const float* x, const float* w1, const float* w2, const fl
 /* SELayer on 16-bit x / y: arguments of mi355_se_fwd plus `io`.  Workspace: mi355_se_workspace_bytes applies. */
 int    mi355_se16_fwd(const void* x, const float* w1, const float* w2, void* y,
                       int B, int C, int Cr, int H, int W, int io, void* ws, size_t ws_bytes, mi355_stream_t stream);
+/* The SE variants of the reference's CNNs on 16-bit x / y: arguments of mi355_se_ex_fwd (b1 / b2 fp32 or NULL, gate 0 sigmoid / 1 hard
+ * sigmoid) plus `io`; mi355_se16_fwd is this entry with NULL biases and gate 0.  The hard sigmoid reaches 0 and 1: 0 <= gate <= 1. */
+int    mi355_se16_ex_fwd(const void* x, const float* w1, const float* b1, const float* w2, const float* b2, void* y,
+                         int B, int C, int Cr, int H, int W, int gate, int io, void* ws, size_t ws_bytes, mi355_stream_t stream);
 /* ECALayer on 16-bit x / y: arguments of mi355_eca_fwd plus `io`.  Workspace: mi355_eca_workspace_bytes applies. */
 int    mi355_eca16_fwd(const void* x, const float* wconv, void* y,
                        int B, int C, int k, int H, int W, int io, void* ws, size_t ws_bytes, mi355_stream_t stream);
@@ -317,6 +321,29 @@ int mi355_lct_fwd(const float* x, const float* w, const float* b, float* y, int 
                   void* ws, size_t ws_bytes, mi355_stream_t stream);
 int mi355_gct_fwd(const float* x, const float* alpha, const float* gamma, const float* beta, float* y, int B, int C, int H, int W,
                   float epsilon, int mode_l1, int after_relu, void* ws, size_t ws_bytes, mi355_stream_t stream);
+
+/* The same five on 16-bit activations (chan_stat_io16.hip): x and y are NCHW in ONE 16-bit type selected by `io` (1 = IEEE half,
+ * 2 = bfloat16), parameters stay fp32, all arithmetic is fp32 and y is rounded once, to nearest even, at the store -- the contract of
+ * mi355_se16_fwd.  Each entry takes the fp32 entry's arguments with `int io` in front of the workspace, keeps its shape conditions
+ * (H*W > 1 for simam / srm, C % groups == 0 for lct) and its workspace size, mi355_chan_stat_workspace_bytes(B, C).  Single-read form
+ * (the row packed in registers, the fp32 kernels' granule exchange and error word) when H*W % 8 == 0, H*W <= 4096, C % 8 == 0 and x, y
+ * are 16-byte aligned; two passes otherwise or with "zoo_single" = 0.  A workspace remembers the I/O type it was last used with: fp32
+ * and 16-bit calls of one shape may share one, at the price of a re-zeroing whenever the type changes.
+ * The gates of simam, srm, gct_gauss and lct lie in (0, 1]: a finite x gives a finite y.  gct's gate 1 + tanh(.) lies in [0, 2], so an
+ * fp16 y may overflow: y is +-inf exactly where the fp32 entry's result rounded to fp16 is.  Outputs are not MFMA operands: these
+ * entries report nothing to mi355_range_status.
+ * Validation (io, sizes, then pointers) precedes every HIP call: MI355_EINVAL with text in mi355_last_error. */
+int mi355_simam16_fwd(const void* x, void* y, int B, int C, int H, int W, float e_lambda, int io, void* ws, size_t ws_bytes,
+                      mi355_stream_t stream);
+int mi355_srm16_fwd(const void* x, const float* cfc, const float* bn_weight, const float* bn_bias, const float* bn_mean,
+                    const float* bn_var, float bn_eps, void* y, int B, int C, int H, int W, int io, void* ws, size_t ws_bytes,
+                    mi355_stream_t stream);
+int mi355_gct_gauss16_fwd(const void* x, void* y, int B, int C, int H, int W, float c, float eps, int io, void* ws, size_t ws_bytes,
+                          mi355_stream_t stream);
+int mi355_lct16_fwd(const void* x, const float* w, const float* b, void* y, int B, int C, int groups, int H, int W, float eps, int io,
+                    void* ws, size_t ws_bytes, mi355_stream_t stream);
+int mi355_gct16_fwd(const void* x, const float* alpha, const float* gamma, const float* beta, void* y, int B, int C, int H, int W,
+                    float epsilon, int mode_l1, int after_relu, int io, void* ws, size_t ws_bytes, mi355_stream_t stream);
 
 /* ---- gates built from axis reductions (second group) ---------------------------------------------------------
  * x, y (B,C,H,W) fp32 contiguous; caller workspace of mi355_axis_attn_workspace_bytes (mi355_bam_workspace_bytes for BAM), no state

@@ -2,7 +2,7 @@
 //
 // x and y are NCHW in the I/O type, parameters are fp32, every piece of arithmetic (pooling sums, excitation MLP, ECA taps, k x k
 // conv, sigmoid, products) is fp32: the only rounding the path adds is the one store of y, to nearest even.  A finite product cannot
-// overflow (0 < gate < 1, so |y| <= |x|), hence no range report.
+// overflow (0 <= gate <= 1 -- the hard sigmoid of the SE variants reaches both ends -- so |y| <= |x|), hence no range report.
 // Range contract (tests/test_range_audit_cpu.py): this file converts fp32 to 16 bit but calls no rg_report and takes no range_word() on
 // purpose -- the converted values are OUTPUTS bounded by the 16-bit inputs, never MFMA operands that a larger fp32 value could saturate.
 //
@@ -16,53 +16,11 @@
 //                 2-byte lanes otherwise.  Correct everywhere, not tuned.
 #include "common.h"
 #include "bufops.h"
+#include "io16.h"
 
 namespace {
 
-typedef unsigned int u32;
-typedef unsigned short u16;
-typedef unsigned long long u64;
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-typedef u32 u32x2 __attribute__((ext_vector_type(2)));
-using v4f = float __attribute__((ext_vector_type(4)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-
 #define AGENT_RLX __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
-// ---- packed 16-bit <-> fp32 (IO = 1: IEEE half, 2: bfloat16; the library's precision codes) -----------------------------------
-template <int IO> __device__ __forceinline__ float lo16(u32 w) {
-    if constexpr (IO == 1) return (float)__builtin_bit_cast(h2, w).x;
-    else return __uint_as_float(w << 16);
-}
-template <int IO> __device__ __forceinline__ float hi16(u32 w) {
-    if constexpr (IO == 1) return (float)__builtin_bit_cast(h2, w).y;
-    else return __uint_as_float(w & 0xffff0000u);
-}
-template <int IO> __device__ __forceinline__ u32 pack16(float a, float b) {          // round to nearest even, both halves
-    if constexpr (IO == 1) return __builtin_bit_cast(u32, h2{(_Float16)a, (_Float16)b});
-    else return __builtin_bit_cast(u32, b2{(__bf16)a, (__bf16)b});
-}
-template <int IO> __device__ __forceinline__ float from16(u16 h) {
-    if constexpr (IO == 1) return (float)__builtin_bit_cast(_Float16, h);
-    else return __uint_as_float((u32)h << 16);
-}
-template <int IO> __device__ __forceinline__ u16 to16(float v) {
-    if constexpr (IO == 1) return __builtin_bit_cast(u16, (_Float16)v);
-    else return __builtin_bit_cast(u16, (__bf16)v);
-}
-template <int IO> __device__ __forceinline__ v4f up4(u32x2 r) { return v4f{lo16<IO>(r.x), hi16<IO>(r.x), lo16<IO>(r.y), hi16<IO>(r.y)}; }
-template <int IO> __device__ __forceinline__ u32x2 down4(v4f v) { return u32x2{pack16<IO>(v.x, v.y), pack16<IO>(v.z, v.w)}; }
-// the 8 values of one 16-byte chunk into four running sums: ONE order for own rows and halo rows (ECA), so a mean does not depend on
-// which workgroup computes it
-template <int IO> __device__ __forceinline__ void add8(u32x4 r, float& s0, float& s1, float& s2, float& s3) {
-    s0 += lo16<IO>(r.x); s1 += hi16<IO>(r.x); s2 += lo16<IO>(r.y); s3 += hi16<IO>(r.y);
-    s0 += lo16<IO>(r.z); s1 += hi16<IO>(r.z); s2 += lo16<IO>(r.w); s3 += hi16<IO>(r.w);
-}
-template <int IO> __device__ __forceinline__ u32x4 scale8(u32x4 r, float g) {
-    return u32x4{pack16<IO>(lo16<IO>(r.x) * g, hi16<IO>(r.x) * g), pack16<IO>(lo16<IO>(r.y) * g, hi16<IO>(r.y) * g),
-                 pack16<IO>(lo16<IO>(r.z) * g, hi16<IO>(r.z) * g), pack16<IO>(lo16<IO>(r.w) * g, hi16<IO>(r.w) * g)};
-}
 
 constexpr int ECW = 8;          // channel rows per workgroup of the single-read SE / ECA kernels (chan_fused.hip)
 // Waves per SIMD the single-read kernels are compiled for (512 threads = 2 waves per SIMD and workgroup: 8 / 6 / 4 = four / three / two
@@ -132,16 +90,18 @@ __global__ __launch_bounds__(512, eca16_waves(NV)) void eca16_halo_kernel(const 
 // single read: SE (se_single_kernel of chan_fused.hip on packed rows; the same granules, ticket, epoch and error words)
 // =====================================================================================================================================
 struct Se16Args {
-    const u16* x; u16* y; const float* w1; const float* w2;
+    const u16* x; u16* y; const float* w1; const float* w2; const float* b1; const float* b2;
     u64* gran; u32* ticket; u32* epoch; u32* err; u32* herr;
     u32 spin;
-    int nts;
+    int nts, gate;
     int C, Cr, HW, gpi, total;
     float inv;
 };
 
 // How many workgroups per CU the launch uses is a grid size (option "io16_occ", capped by what se16_waves allows), not a template parameter.
-template <int IO, int NV, bool WLDS>
+// EXTRA: the SE variants of the reference's CNNs (excitation biases, hard-sigmoid gate: SeExtra), as in se_single_kernel -- the plain
+// SELayer instantiation carries none of their pointers and selects and keeps its code.
+template <int IO, int NV, bool WLDS, bool EXTRA>
 __global__ __launch_bounds__(512, se16_waves(NV)) void se16_single_kernel(const Se16Args a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];      // p[C] | h[Cr] | (WLDS: W1[Cr*C] | W2[C*Cr])
     __shared__ u32 s_tk[2];
@@ -250,13 +210,13 @@ __global__ __launch_bounds__(512, se16_waves(NV)) void se16_single_kernel(const 
             acc += __shfl_xor(acc, 4, WAVE);
             acc += __shfl_xor(acc, 2, WAVE);
             acc += __shfl_xor(acc, 1, WAVE);
-            if (part == 0 && j < Cr_) s_h[j] = relu_nan(acc);
+            if (part == 0 && j < Cr_) s_h[j] = relu_nan(EXTRA ? acc + (a.b1 ? a.b1[j] : 0.f) : acc);
         }
         __syncthreads();
         const float* w2r = w2 + (long)(c0 + wave) * Cr_;
         float z = 0.f;
         for (int j = lane; j < Cr_; j += 64) z += w2r[j] * s_h[j];
-        const float g = sigmoidf_(wave_sum_sw(z));
+        const float g = EXTRA ? se_gate(wave_sum_sw(z) + (a.b2 ? a.b2[c0 + wave] : 0.f), a.gate) : sigmoidf_(wave_sum_sw(z));
         if (a.nts) {
 #pragma unroll
             for (int j = 0; j < NV; ++j) __builtin_amdgcn_raw_buffer_store_b128(scale8<IO>(r[j], g), ry, voff, (u32)j * 1024u, AUX_NT);
@@ -268,18 +228,18 @@ __global__ __launch_bounds__(512, se16_waves(NV)) void se16_single_kernel(const 
     }
 }
 
-template <int IO, int NV>
+template <int IO, int NV, bool EXTRA>
 static void se16_go(bool wlds, int grid, size_t smem, hipStream_t st, const Se16Args& a) {
-    if (wlds) se16_single_kernel<IO, NV, true><<<grid, 512, smem, st>>>(a);
-    else      se16_single_kernel<IO, NV, false><<<grid, 512, smem, st>>>(a);
+    if (wlds) se16_single_kernel<IO, NV, true, EXTRA><<<grid, 512, smem, st>>>(a);
+    else      se16_single_kernel<IO, NV, false, EXTRA><<<grid, 512, smem, st>>>(a);
 }
-template <int IO>
+template <int IO, bool EXTRA>
 static void se16_go_nv(int nv, bool wlds, int grid, size_t smem, hipStream_t st, const Se16Args& a) {
-    if (nv <= 1) se16_go<IO, 1>(wlds, grid, smem, st, a);
-    else if (nv <= 2) se16_go<IO, 2>(wlds, grid, smem, st, a);
-    else if (nv <= 4) se16_go<IO, 4>(wlds, grid, smem, st, a);
-    else if (nv <= 7) se16_go<IO, 7>(wlds, grid, smem, st, a);
-    else se16_go<IO, 8>(wlds, grid, smem, st, a);
+    if (nv <= 1) se16_go<IO, 1, EXTRA>(wlds, grid, smem, st, a);
+    else if (nv <= 2) se16_go<IO, 2, EXTRA>(wlds, grid, smem, st, a);
+    else if (nv <= 4) se16_go<IO, 4, EXTRA>(wlds, grid, smem, st, a);
+    else if (nv <= 7) se16_go<IO, 7, EXTRA>(wlds, grid, smem, st, a);
+    else se16_go<IO, 8, EXTRA>(wlds, grid, smem, st, a);
 }
 
 // =====================================================================================================================================
@@ -663,12 +623,13 @@ __device__ __forceinline__ float dot16(const float* __restrict__ wrow, const flo
 }
 
 // Gates of one image from its pooled vectors, IN PLACE over avg (the whole image is read into LDS before the first gate is written).
-//   MODE 0 SE:   g = sigmoid(W2 relu(W1 avg))      MODE 1 ECA: g_c = sigmoid(sum_j w[j] avg[c + j - pad]) (Cr = k)
+//   MODE 0 SE:   g = gate(W2 relu(W1 avg + b1) + b2), ex = the variants' biases (may be null) and gate code; the plain SELayer passes none
+//   MODE 1 ECA:  g_c = sigmoid(sum_j w[j] avg[c + j - pad]) (Cr = k)
 //   MODE 2 CBAM: g = sigmoid(W2 (relu(W1 avg) + relu(W1 max)))
 // smem: a[C] | m[C] | h[Cr]
 template <int MODE>
 __global__ __launch_bounds__(256) void chan_gates16_kernel(float* __restrict__ avg, const float* __restrict__ mx, const float* __restrict__ wa,
-                                                          const float* __restrict__ wb, int C, int Cr) {
+                                                          const float* __restrict__ wb, int C, int Cr, const mi355::SeExtra ex) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* s_a = smem;
     float* s_m = smem + C;
@@ -699,14 +660,14 @@ __global__ __launch_bounds__(256) void chan_gates16_kernel(float* __restrict__ a
                 ha = dot16(wa + (long)j * C, s_a, C, part);
                 if (MODE == 2) hm = dot16(wa + (long)j * C, s_m, C, part);
             }
-            if (part == 0 && j < Cr) s_h[j] = (MODE == 2) ? relu_nan(ha) + relu_nan(hm) : relu_nan(ha);
+            if (part == 0 && j < Cr) s_h[j] = (MODE == 2) ? relu_nan(ha) + relu_nan(hm) : relu_nan((MODE == 0 && ex.b1) ? ha + ex.b1[j] : ha);
         }
         __syncthreads();
         for (int c = t; c < C; c += 256) {
             const float* w2r = wb + (long)c * Cr;
             float z = 0.f;
             for (int j = 0; j < Cr; ++j) z += w2r[j] * s_h[j];
-            ab[c] = sigmoidf_(z);
+            ab[c] = (MODE == 0) ? se_gate(ex.b2 ? z + ex.b2[c] : z, ex.gate) : sigmoidf_(z);
         }
     }
 }
@@ -833,9 +794,9 @@ bool se16_single_ok(int C, int Cr, int H, int W) {
 
 // `state` = epoch | (B - 1 unused words) | ticket | err (fused_state_bytes), `gran` = B*C granules: the layout of the fp32 kernel
 int se16_single(const u16* x, const float* w1, const float* w2, u16* y, int B, int C, int Cr, int H, int W, int io, void* state, void* gran,
-                hipStream_t st) {
+                mi355::SeExtra ex, hipStream_t st) {
     Se16Args a{};
-    a.x = x; a.y = y; a.w1 = w1; a.w2 = w2;
+    a.x = x; a.y = y; a.w1 = w1; a.w2 = w2; a.b1 = ex.b1; a.b2 = ex.b2; a.gate = ex.gate;
     a.gran = static_cast<u64*>(gran);
     a.ticket = static_cast<u32*>(state) + B;
     a.epoch = static_cast<u32*>(state);
@@ -866,8 +827,14 @@ int se16_single(const u16* x, const float* w1, const float* w2, u16* y, int B, i
     }
     {
         MI355_TRACE(st, "se16_single_kernel io=%d C=%d HW=%d", io, C, a.HW);
-        if (io == 1) se16_go_nv<1>(nv, wlds, (int)grid, smem, st, a);
-        else         se16_go_nv<2>(nv, wlds, (int)grid, smem, st, a);
+        const bool extra = ex.b1 || ex.b2 || ex.gate;
+        if (extra) {
+            if (io == 1) se16_go_nv<1, true>(nv, wlds, (int)grid, smem, st, a);
+            else         se16_go_nv<2, true>(nv, wlds, (int)grid, smem, st, a);
+        } else {
+            if (io == 1) se16_go_nv<1, false>(nv, wlds, (int)grid, smem, st, a);
+            else         se16_go_nv<2, false>(nv, wlds, (int)grid, smem, st, a);
+        }
     }
     e = hipGetLastError();
     if (e != hipSuccess) { mi355::ws_forget(state); return mi355::fail(MI355_EHIP, "se16_single: launch -> %s", hipGetErrorString(e)); }
@@ -980,7 +947,7 @@ size_t mi355_cbam16_workspace_bytes(int B, int C, int H, int W) {
 
 // mode 0: SE (wa = w1, wb = w2, Cr), mode 1: ECA (wa = taps, Cr = k)
 static int se_eca16(int mode, const void* xv, const float* wa, const float* wb, void* yv, int B, int C, int Cr, int H, int W, int io, void* ws,
-                    hipStream_t st) {
+                    hipStream_t st, mi355::SeExtra ex = mi355::SeExtra{nullptr, nullptr, 0}) {
     const u16* x = static_cast<const u16*>(xv);
     u16* y = static_cast<u16*>(yv);
     const int HW = H * W;
@@ -989,7 +956,7 @@ static int se_eca16(int mode, const void* xv, const float* wa, const float* wb, 
     if (smem > 64 * 1024) return mi355::fail(MI355_EUNSUPPORTED, "channel count %d too large for the gate stage", C);
     if (mode == 0 && vec && se16_single_ok(C, Cr, H, W)) {
         char* state = static_cast<char*>(ws) + pooled_bytes(B, C);
-        return se16_single(x, wa, wb, y, B, C, Cr, H, W, io, state, state + mi355::fused_state_bytes(B), st);
+        return se16_single(x, wa, wb, y, B, C, Cr, H, W, io, state, state + mi355::fused_state_bytes(B), ex, st);
     }
     if (mode == 1 && vec && eca16_single_ok(C, Cr, H, W)) return eca16_single(x, wa, y, B, C, Cr, H, W, io, st);
     float* pooled = static_cast<float*>(ws);
@@ -1002,8 +969,8 @@ static int se_eca16(int mode, const void* xv, const float* wa, const float* wb, 
             const void* fn = mode == 0 ? (const void*)chan_gates16_kernel<0> : (const void*)chan_gates16_kernel<1>;
             if (int rc = mi355::func_dynamic_lds(fn, (int)smem)) return rc;
         }
-        if (mode == 0) chan_gates16_kernel<0><<<B, 256, smem, st>>>(pooled, nullptr, wa, wb, C, Cr);
-        else           chan_gates16_kernel<1><<<B, 256, smem, st>>>(pooled, nullptr, wa, nullptr, C, Cr);
+        if (mode == 0) chan_gates16_kernel<0><<<B, 256, smem, st>>>(pooled, nullptr, wa, wb, C, Cr, ex);
+        else           chan_gates16_kernel<1><<<B, 256, smem, st>>>(pooled, nullptr, wa, nullptr, C, Cr, ex);
     }
     if (io == 1) scale16<1>(vec, x, pooled, nullptr, y, rows, C, HW, st);
     else         scale16<2>(vec, x, pooled, nullptr, y, rows, C, HW, st);
@@ -1019,6 +986,16 @@ int mi355_se16_fwd(const void* x, const float* w1, const float* w2, void* y, int
     MI355_CHECK_ARG(check_io16(io, B, C, H, W));
     MI355_CHECK_ARG(ws_bytes >= mi355_se_workspace_bytes(B, C, H, W));
     return se_eca16(0, x, w1, w2, y, B, C, Cr, H, W, io, ws, static_cast<hipStream_t>(stream));
+}
+
+int mi355_se16_ex_fwd(const void* x, const float* w1, const float* b1, const float* w2, const float* b2, void* y, int B, int C, int Cr, int H,
+                      int W, int gate, int io, void* ws, size_t ws_bytes, mi355_stream_t stream) {
+    MI355_CHECK_ARG(io == 1 || io == 2);
+    MI355_CHECK_ARG(B > 0 && C > 0 && Cr > 0 && H > 0 && W > 0 && (gate == 0 || gate == 1));
+    MI355_CHECK_ARG(x && w1 && w2 && y && ws);
+    MI355_CHECK_ARG(check_io16(io, B, C, H, W));
+    MI355_CHECK_ARG(ws_bytes >= mi355_se_workspace_bytes(B, C, H, W));
+    return se_eca16(0, x, w1, w2, y, B, C, Cr, H, W, io, ws, static_cast<hipStream_t>(stream), mi355::SeExtra{b1, b2, gate});
 }
 
 int mi355_eca16_fwd(const void* x, const float* wconv, void* y, int B, int C, int k, int H, int W, int io, void* ws, size_t ws_bytes,
@@ -1066,7 +1043,7 @@ int mi355_cbam16_fwd(const void* xv, const float* w1, const float* w2, const flo
         MI355_TRACE(st, "chan_gates16_kernel mode=2 C=%d", C);
         if (smem > 48 * 1024)
             if (int rc = mi355::func_dynamic_lds((const void*)chan_gates16_kernel<2>, (int)smem)) return rc;
-        chan_gates16_kernel<2><<<B, 256, smem, st>>>(avg, mx, w1, w2, C, Cr);
+        chan_gates16_kernel<2><<<B, 256, smem, st>>>(avg, mx, w1, w2, C, Cr, mi355::SeExtra{nullptr, nullptr, 0});
     }
     if (do_s) {
         {

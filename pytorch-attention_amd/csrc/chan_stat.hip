@@ -15,96 +15,11 @@
 // gate + scale); both paths accumulate in fixed orders.
 #include "common.h"
 #include "bufops.h"
+#include "chan_stat.h"
 
 namespace {
 
-using v4f = float __attribute__((ext_vector_type(4)));
-typedef unsigned int u32;
-typedef unsigned long long u64;
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-#define AGENT_RLX __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
-enum { M_SIMAM = 1, M_SRM = 2, M_GCTG = 3, M_LCT = 4, M_GCT2 = 5, M_GCT1 = 6 };
-constexpr int ECW = 8;
-
-struct StatArgs {
-    const float* x; float* y;
-    const float* p0; const float* p1; const float* p2; const float* p3; const float* p4;   // per-channel parameter arrays (per mode)
-    float f0, f1;                         // lambda | bn eps | eps, c | eps | epsilon
-    int i0;                               // LCT: channels per group;  GCT1: after_relu
-    u64* gran; u32* ticket; u32* epoch; u32* err; u32* herr; float* stats;   // exchange area (single read) / row statistics (two pass)
-    int B, C, HW, n4, gpi, total;
-    u32 spin;
-};
-
-// gate of channel c from its own statistics and (exchange modes) the image's per-channel values s_p[0..C)
-// red0/red1: image-level reductions prepared by the caller (GCTG: mean, var of the channel means; GCT: mean_c e^2 or mean_c |e|)
-template <int MODE>
-__device__ __forceinline__ float gate_of(const StatArgs& a, int c, float mean, float cvar_sum, float own, float red0, float red1) {
-    if (MODE == M_SRM) {
-        const float stdv = sqrtf(cvar_sum / (float)(a.HW - 1));
-        const float z = a.p0[2 * c] * mean + a.p0[2 * c + 1] * stdv;
-        const float bn = (z - a.p3[c]) / sqrtf(a.p4[c] + a.f0) * a.p1[c] + a.p2[c];
-        return sigmoidf_(bn);
-    }
-    if (MODE == M_GCTG) {
-        const float yn = (own - red0) / sqrtf(red1 + a.f0);
-        return expf(-(yn * yn / 2.0f * a.f1));
-    }
-    if (MODE == M_LCT) {
-        const float yn = (own - red0) / sqrtf(red1 + a.f0);
-        return sigmoidf_(a.p0[c] * yn + a.p1[c]);
-    }
-    if (MODE == M_GCT2) {
-        const float e = sqrtf(own + a.f0) * a.p0[c];
-        const float norm = a.p1[c] / sqrtf(red0 + a.f0);
-        return 1.0f + tanhf(e * norm + a.p2[c]);
-    }
-    if (MODE == M_GCT1) {
-        const float e = own * a.p0[c];
-        const float norm = a.p1[c] / (red0 + a.f0);
-        return 1.0f + tanhf(e * norm + a.p2[c]);
-    }
-    return 1.0f;
-}
-
-// image-level reductions over the C published values in s_p, by the whole workgroup (NT threads), fixed order:
-//   GCTG: red0 = mean_c, red1 = mean_c(v^2) - mean_c^2;   GCT2: red0 = mean_c((v + eps) alpha^2);   GCT1: red0 = mean_c |v alpha|
-template <int MODE, int NT>
-__device__ __forceinline__ void image_reduce(const StatArgs& a, const float* s_p, float* s_red, float& red0, float& red1) {
-    int t = threadIdx.x;
-    asm volatile("" : "+v"(t));                                       // formed here, not hoisted out of the caller's slice loop
-    const int lane = t & 63, wave = t >> 6;
-    float u = 0.f, w = 0.f;
-    for (int c = t; c < a.C; c += NT) {
-        const float v = s_p[c];
-        if (MODE == M_GCTG) { u += v; w += v * v; }
-        if (MODE == M_GCT2) { const float e = sqrtf(v + a.f0) * a.p0[c]; u += e * e; }
-        if (MODE == M_GCT1) { u += fabsf(v * a.p0[c]); }
-    }
-    u = wave_sum_sw(u);
-    w = wave_sum_sw(w);
-    if (lane == 0) { s_red[wave] = u; s_red[16 + wave] = w; }
-    __syncthreads();
-    float su = 0.f, sw = 0.f;
-    for (int i = 0; i < NT / 64; ++i) { su += s_red[i]; sw += s_red[16 + i]; }
-    __syncthreads();
-    red0 = su / (float)a.C;
-    red1 = (MODE == M_GCTG) ? sw / (float)a.C - red0 * red0 : 0.f;
-}
-
-// LCT: mean / variance of the published means over the group of channel c (cpg channels), by one wave
-__device__ __forceinline__ void group_reduce(const float* s_p, int c, int cpg, float& red0, float& red1) {
-    int tl = threadIdx.x;
-    asm volatile("" : "+v"(tl));
-    const int lane = tl & 63, g0 = (c / cpg) * cpg;
-    float u = 0.f, w = 0.f;
-    for (int i = lane; i < cpg; i += 64) { const float v = s_p[g0 + i]; u += v; w += v * v; }
-    u = wave_sum_sw(u);
-    w = wave_sum_sw(w);
-    red0 = u / (float)cpg;
-    red1 = w / (float)cpg - red0 * red0;
-}
+typedef StatArgsT<float> StatArgs;
 
 template <int MODE, int NV, bool NTS>
 __global__ __launch_bounds__(512, (MODE == M_SIMAM ? (NV > 13 ? 2 : 4) : (NV > 13 ? 4 : 6))) void stat_single_kernel(const StatArgs a) {
@@ -189,8 +104,8 @@ __global__ __launch_bounds__(512, (MODE == M_SIMAM ? (NV > 13 ? 2 : 4) : (NV > 1
             // lanes beyond the row hold zeros: park them on the mean so that they add nothing (they are never stored)
 #pragma unroll
             for (int j = 0; j < NV; ++j)
-                if (64 * (j + 1) > a.n4) {                            // wave-uniform: only the last occupied slot(s) can be ragged
-                    const bool in = lane + 64 * j < a.n4;
+                if (64 * (j + 1) > a.nchunk) {                            // wave-uniform: only the last occupied slot(s) can be ragged
+                    const bool in = lane + 64 * j < a.nchunk;
                     r[j].x = in ? r[j].x : mean; r[j].y = in ? r[j].y : mean; r[j].z = in ? r[j].z : mean; r[j].w = in ? r[j].w : mean;
                 }
             float q0 = 0.f, q1 = 0.f, q2 = 0.f, q3 = 0.f;
@@ -327,11 +242,11 @@ int run(StatArgs a, int H, int W, void* ws, size_t ws_bytes, hipStream_t st) {
                         aligned16(a.y) && (size_t)C * 4 <= 48 * 1024 && (MODE != M_LCT || a.i0 <= C) &&
                         (!XCH || C / ECW <= mi355::resident_slots(2));     // an image's slices must all be resident to exchange granules
     if (single) {
-        a.n4 = a.HW / 4; a.gpi = C / ECW;
+        a.nchunk = a.HW / 4; a.gpi = C / ECW;
         const long total_l = (long)B * a.gpi;
         if (total_l > (1L << 30)) return mi355::fail(MI355_EUNSUPPORTED, "channel-statistics gate: too many slices");
         a.total = (int)total_l;
-        const int nv = (a.n4 + 63) / 64;
+        const int nv = (a.nchunk + 63) / 64;
         // workgroups per CU = what the kernel's launch bounds allow: three (<= 80 VGPRs) up to 13 float4 per lane, two beyond; SimAM's
         // per-element gate needs 120 registers (two per CU), 141 at 16 float4 per lane (one per CU)
         long grid = (long)mi355::resident_slots(MODE == M_SIMAM ? (nv > 13 ? 1 : 2) : (nv > 13 ? 2 : 3));

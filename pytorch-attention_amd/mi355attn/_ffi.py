@@ -53,6 +53,7 @@ SIGNATURES = {
     "mi355_cbam_workspace_bytes": (c_size, [c_int] * 4),
     "mi355_cbam_fwd": (c_int, [c_vp] * 5 + [c_int] * 7 + [c_vp, c_size, c_vp]),
     "mi355_se16_fwd": (c_int, [c_vp, c_vp, c_vp, c_vp] + [c_int] * 6 + [c_vp, c_size, c_vp]),
+    "mi355_se16_ex_fwd": (c_int, [c_vp] * 6 + [c_int] * 7 + [c_vp, c_size, c_vp]),
     "mi355_eca16_fwd": (c_int, [c_vp, c_vp, c_vp] + [c_int] * 6 + [c_vp, c_size, c_vp]),
     "mi355_cbam16_workspace_bytes": (c_size, [c_int] * 4),
     "mi355_cbam16_fwd": (c_int, [c_vp] * 5 + [c_int] * 8 + [c_vp, c_size, c_vp]),
@@ -94,6 +95,11 @@ SIGNATURES = {
     "mi355_gct_gauss_fwd": (c_int, [c_vp, c_vp] + [c_int] * 4 + [ctypes.c_float, ctypes.c_float, c_vp, ctypes.c_size_t, c_vp]),
     "mi355_lct_fwd": (c_int, [c_vp] * 4 + [c_int] * 5 + [ctypes.c_float, c_vp, ctypes.c_size_t, c_vp]),
     "mi355_gct_fwd": (c_int, [c_vp] * 5 + [c_int] * 4 + [ctypes.c_float, c_int, c_int, c_vp, ctypes.c_size_t, c_vp]),
+    "mi355_simam16_fwd": (c_int, [c_vp, c_vp] + [c_int] * 4 + [c_float, c_int, c_vp, c_size, c_vp]),
+    "mi355_srm16_fwd": (c_int, [c_vp] * 6 + [c_float, c_vp] + [c_int] * 5 + [c_vp, c_size, c_vp]),
+    "mi355_gct_gauss16_fwd": (c_int, [c_vp, c_vp] + [c_int] * 4 + [c_float, c_float, c_int, c_vp, c_size, c_vp]),
+    "mi355_lct16_fwd": (c_int, [c_vp] * 4 + [c_int] * 5 + [c_float, c_int, c_vp, c_size, c_vp]),
+    "mi355_gct16_fwd": (c_int, [c_vp] * 5 + [c_int] * 4 + [c_float, c_int, c_int, c_int, c_vp, c_size, c_vp]),
     "mi355_axis_attn_workspace_bytes": (ctypes.c_size_t, [c_int] * 4),
     "mi355_gc_fwd": (c_int, [c_vp] * 10 + [c_int] * 5 + [ctypes.c_float, c_vp, ctypes.c_size_t, c_vp]),
     "mi355_coordatt_fwd": (c_int, [c_vp] * 10 + [c_int] * 5 + [c_vp, ctypes.c_size_t, c_vp]),
@@ -229,7 +235,8 @@ def require_device_f32(t, name):
             "(move the module and its input to 'cuda'); there is no CPU path in this package.")
     if t.dtype != torch.float32:
         raise TypeError(f"{name}: expected float32, got {t.dtype} (16-bit activations are accepted by SELayer, ECALayer, CBAM, "
-                        "ChannelAttention and SpatialAttention only)")
+                        "ChannelAttention, SpatialAttention, SELayerBias, SELayerBias4, SELayerHidden, SqueezeExcite, simam_module, SRM, "
+                        "GaussianGCT, LCT and GCT only)")
     if t.requires_grad and torch.is_grad_enabled():
         _warn_no_autograd()
     return t if t.is_contiguous() else t.contiguous()

@@ -444,12 +444,19 @@ def tokens_to_nchw_axpy(tokens, x, alpha):
     return y
 
 
+def _opt32(t, name):
+    """Optional parameter of the channel-attention family (None -> NULL), fp32 or 16-bit (param32)."""
+    return None if t is None else param32(t, name)
+
+
 def se_ex_forward(x, w1, b1, w2, b2, gate="sigmoid"):
-    """SE with optional excitation biases and a choice of gate ("sigmoid" | "hard_sigmoid"): the variants inside the reference's CNNs."""
-    x = require_device_f32(x, "x")
+    """SE with optional excitation biases and a choice of gate ("sigmoid" | "hard_sigmoid"): the variants inside the reference's CNNs.
+    x fp32 / fp16 / bf16 (output in the same type)."""
+    x, io = _ffi.require_device_io(x, "x")
     B, C, H, W = x.shape
-    w1 = require_device_f32(w1, "w1").reshape(w1.shape[0], -1)
-    w2 = require_device_f32(w2, "w2").reshape(w2.shape[0], -1)
+    w1 = param32(w1, "w1").reshape(w1.shape[0], -1)
+    w2 = param32(w2, "w2").reshape(w2.shape[0], -1)
+    b1, b2 = (_opt32(b1, "b1"), _opt32(b2, "b2")) if io else (_opt(b1, "b1"), _opt(b2, "b2"))
     Cr = w1.shape[0]
     if tuple(w1.shape) != (Cr, C) or tuple(w2.shape) != (C, Cr):
         raise ValueError(f"SE weight shapes {tuple(w1.shape)}, {tuple(w2.shape)} do not match C={C}")
@@ -457,9 +464,15 @@ def se_ex_forward(x, w1, b1, w2, b2, gate="sigmoid"):
         raise ValueError("gate must be 'sigmoid' or 'hard_sigmoid'")
     y = torch.empty_like(x)
     n = lib().mi355_se_workspace_bytes(B, C, H, W)
-    ws = _ffi.workspace_dedicated(("se", B, C, H, W), n, x.device)
-    check(lib().mi355_se_ex_fwd(dptr(x), dptr(w1), dptr(_opt(b1, "b1")), dptr(w2), dptr(_opt(b2, "b2")), dptr(y), B, C, Cr, H, W,
-                                1 if gate == "hard_sigmoid" else 0, dptr(ws), ws.numel(), stream_ptr(x.device)), "mi355_se_ex_fwd")
+    code = 1 if gate == "hard_sigmoid" else 0
+    if io:
+        ws = _ffi.workspace_dedicated(("se16", io, B, C, H, W), n, x.device)
+        check(lib().mi355_se16_ex_fwd(dptr(x), dptr(w1), dptr(b1), dptr(w2), dptr(b2), dptr(y), B, C, Cr, H, W, code, io, dptr(ws),
+                                      ws.numel(), stream_ptr(x.device)), "mi355_se16_ex_fwd")
+    else:
+        ws = _ffi.workspace_dedicated(("se", B, C, H, W), n, x.device)
+        check(lib().mi355_se_ex_fwd(dptr(x), dptr(w1), dptr(b1), dptr(w2), dptr(b2), dptr(y), B, C, Cr, H, W, code, dptr(ws), ws.numel(),
+                                    stream_ptr(x.device)), "mi355_se_ex_fwd")
     _sync_check()
     return y
 
@@ -516,43 +529,66 @@ def cbam_forward(x, w1=None, w2=None, wconv=None, stage=0):
 
 
 def _zoo(kind, x):
-    """Common prologue of the channel-statistics gates: dense fp32 device x, output, dedicated workspace (exchange area)."""
-    x = require_device_f32(x, "x")
+    """Common prologue of the channel-statistics gates: dense device x in fp32, fp16 or bf16, output of the same type, dedicated workspace
+    (exchange area) -- one per I/O type, so that fp32 and 16-bit launches of one shape never share ticket state."""
+    x, io = _ffi.require_device_io(x, "x")
     B, C, H, W = x.shape
     n = lib().mi355_chan_stat_workspace_bytes(B, C)
-    return x, torch.empty_like(x), _ffi.workspace_dedicated((kind, B, C, H, W), n, x.device), (B, C, H, W)
+    key = (kind + "16", io, B, C, H, W) if io else (kind, B, C, H, W)
+    return x, io, torch.empty_like(x), _ffi.workspace_dedicated(key, n, x.device), (B, C, H, W)
+
+
+def _p(io, t, name):
+    """A parameter of these gates: fp32 as before on the fp32 path, fp32 or 16-bit (converted once and cached) on the 16-bit path."""
+    return param32(t, name) if io else require_device_f32(t, name)
 
 
 def simam_forward(x, e_lambda=1e-4):
-    x, y, ws, (B, C, H, W) = _zoo("simam", x)
-    check(lib().mi355_simam_fwd(dptr(x), dptr(y), B, C, H, W, float(e_lambda), dptr(ws), ws.numel(), stream_ptr(x.device)),
-          "mi355_simam_fwd")
+    x, io, y, ws, (B, C, H, W) = _zoo("simam", x)
+    if io:
+        check(lib().mi355_simam16_fwd(dptr(x), dptr(y), B, C, H, W, float(e_lambda), io, dptr(ws), ws.numel(), stream_ptr(x.device)),
+              "mi355_simam16_fwd")
+    else:
+        check(lib().mi355_simam_fwd(dptr(x), dptr(y), B, C, H, W, float(e_lambda), dptr(ws), ws.numel(), stream_ptr(x.device)),
+              "mi355_simam_fwd")
     return y
 
 
 def srm_forward(x, cfc, bn_weight, bn_bias, bn_mean, bn_var, bn_eps):
-    x, y, ws, (B, C, H, W) = _zoo("srm", x)
-    cfc = require_device_f32(cfc, "cfc.weight").reshape(C, 2)
-    ps = [require_device_f32(t, n) for t, n in ((bn_weight, "bn.weight"), (bn_bias, "bn.bias"), (bn_mean, "bn.running_mean"),
-                                                (bn_var, "bn.running_var"))]
-    check(lib().mi355_srm_fwd(dptr(x), dptr(cfc), dptr(ps[0]), dptr(ps[1]), dptr(ps[2]), dptr(ps[3]), float(bn_eps), dptr(y),
-                              B, C, H, W, dptr(ws), ws.numel(), stream_ptr(x.device)), "mi355_srm_fwd")
+    x, io, y, ws, (B, C, H, W) = _zoo("srm", x)
+    cfc = _p(io, cfc, "cfc.weight").reshape(C, 2)
+    ps = [_p(io, t, n) for t, n in ((bn_weight, "bn.weight"), (bn_bias, "bn.bias"), (bn_mean, "bn.running_mean"),
+                                    (bn_var, "bn.running_var"))]
+    if io:
+        check(lib().mi355_srm16_fwd(dptr(x), dptr(cfc), dptr(ps[0]), dptr(ps[1]), dptr(ps[2]), dptr(ps[3]), float(bn_eps), dptr(y),
+                                    B, C, H, W, io, dptr(ws), ws.numel(), stream_ptr(x.device)), "mi355_srm16_fwd")
+    else:
+        check(lib().mi355_srm_fwd(dptr(x), dptr(cfc), dptr(ps[0]), dptr(ps[1]), dptr(ps[2]), dptr(ps[3]), float(bn_eps), dptr(y),
+                                  B, C, H, W, dptr(ws), ws.numel(), stream_ptr(x.device)), "mi355_srm_fwd")
     return y
 
 
 def gct_gauss_forward(x, c=2, eps=1e-5):
-    x, y, ws, (B, C, H, W) = _zoo("gct_gauss", x)
-    check(lib().mi355_gct_gauss_fwd(dptr(x), dptr(y), B, C, H, W, float(c), float(eps), dptr(ws), ws.numel(), stream_ptr(x.device)),
-          "mi355_gct_gauss_fwd")
+    x, io, y, ws, (B, C, H, W) = _zoo("gct_gauss", x)
+    if io:
+        check(lib().mi355_gct_gauss16_fwd(dptr(x), dptr(y), B, C, H, W, float(c), float(eps), io, dptr(ws), ws.numel(),
+                                          stream_ptr(x.device)), "mi355_gct_gauss16_fwd")
+    else:
+        check(lib().mi355_gct_gauss_fwd(dptr(x), dptr(y), B, C, H, W, float(c), float(eps), dptr(ws), ws.numel(), stream_ptr(x.device)),
+              "mi355_gct_gauss_fwd")
     _sync_check()
     return y
 
 
 def lct_forward(x, w, b, groups, eps=1e-5):
-    x, y, ws, (B, C, H, W) = _zoo("lct", x)
-    w, b = require_device_f32(w, "w"), require_device_f32(b, "b")
-    check(lib().mi355_lct_fwd(dptr(x), dptr(w), dptr(b), dptr(y), B, C, int(groups), H, W, float(eps), dptr(ws), ws.numel(),
-                              stream_ptr(x.device)), "mi355_lct_fwd")
+    x, io, y, ws, (B, C, H, W) = _zoo("lct", x)
+    w, b = _p(io, w, "w"), _p(io, b, "b")
+    if io:
+        check(lib().mi355_lct16_fwd(dptr(x), dptr(w), dptr(b), dptr(y), B, C, int(groups), H, W, float(eps), io, dptr(ws), ws.numel(),
+                                    stream_ptr(x.device)), "mi355_lct16_fwd")
+    else:
+        check(lib().mi355_lct_fwd(dptr(x), dptr(w), dptr(b), dptr(y), B, C, int(groups), H, W, float(eps), dptr(ws), ws.numel(),
+                                  stream_ptr(x.device)), "mi355_lct_fwd")
     _sync_check()
     return y
 
@@ -560,11 +596,15 @@ def lct_forward(x, w, b, groups, eps=1e-5):
 def gct_forward(x, alpha, gamma, beta, epsilon=1e-5, mode="l2", after_relu=False):
     if mode not in ("l2", "l1"):
         raise ValueError("GCT mode must be 'l2' or 'l1'")
-    x, y, ws, (B, C, H, W) = _zoo("gct", x)
-    alpha, gamma, beta = (require_device_f32(t, n).reshape(-1) for t, n in ((alpha, "alpha"), (gamma, "gamma"), (beta, "beta")))
-    check(lib().mi355_gct_fwd(dptr(x), dptr(alpha), dptr(gamma), dptr(beta), dptr(y), B, C, H, W, float(epsilon),
-                              1 if mode == "l1" else 0, 1 if after_relu else 0, dptr(ws), ws.numel(), stream_ptr(x.device)),
-          "mi355_gct_fwd")
+    x, io, y, ws, (B, C, H, W) = _zoo("gct", x)
+    alpha, gamma, beta = (_p(io, t, n).reshape(-1) for t, n in ((alpha, "alpha"), (gamma, "gamma"), (beta, "beta")))
+    l1, relu = 1 if mode == "l1" else 0, 1 if after_relu else 0
+    if io:
+        check(lib().mi355_gct16_fwd(dptr(x), dptr(alpha), dptr(gamma), dptr(beta), dptr(y), B, C, H, W, float(epsilon), l1, relu, io,
+                                    dptr(ws), ws.numel(), stream_ptr(x.device)), "mi355_gct16_fwd")
+    else:
+        check(lib().mi355_gct_fwd(dptr(x), dptr(alpha), dptr(gamma), dptr(beta), dptr(y), B, C, H, W, float(epsilon), l1, relu,
+                                  dptr(ws), ws.numel(), stream_ptr(x.device)), "mi355_gct_fwd")
     _sync_check()
     return y
 
