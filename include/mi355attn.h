@@ -211,7 +211,8 @@ int         mi355_sync_status(void);
  *     mi355_conv2d_tokens_fwd, mi355_patch_embed_fwd and the im2col pass of mi355_patch_embed_ws_fwd)
  *   7 the fp16 q / k / v staging of the fp32-I/O attention cores (mi355_sdpa_fwd, mi355_sdpa_general_fwd with io16 = 0,
  *     mi355_cswin_lepe_attn_fwd); their probabilities are in [0, 1] and need no check
- *   8 the DoubleAttention kernels (mi355_double_attn_fwd: x, the A product, G, M' and the weights; the softmax factors are bounded)
+ *   8 the DoubleAttention kernels (mi355_double_attn_fwd: x, the A product, G, M' and the weights; the softmax factors are bounded;
+ *     mi355_double_attn16_fwd with io = 1: the same without x, which already is fp16)
  * Not yet reporting: XCA on an fp32 qkv input (mi355_xca16_fwd with qkv_is16 = 0).  mi355_range_status() reads the calling thread's word
  * WITHOUT a device synchronisation: MI355_OK = nothing pending; MI355_ERANGE = some launch of this thread that has already executed produced inf from finite values
  * (cleared by the report).  A host that wants certainty for a forward synchronises the stream first.  Remedy: run the module in
@@ -299,6 +300,27 @@ int    mi355_double_attn_fwd(const float* x, const float* wA, const float* bA, c
                              const float* wV, const float* bV, const float* wP, const float* bP, float* y,
                              int B, int C, int cm, int cn, int H, int W, int precision,
                              void* ws, size_t ws_bytes, mi355_stream_t stream);
+/* DoubleAttention on 16-bit x / y: NCHW in ONE 16-bit type selected by `io` (1 = IEEE half, 2 = bfloat16); parameters stay fp32.  The
+ * MFMA operand format is the tensor's own type (io = 1 runs the precision-1 arithmetic, io = 2 the precision-2 arithmetic), so x enters
+ * the MFMAs without any rounding; y is the fp32 accumulator rounded once, to nearest even.  An fp16 y beyond 65504 is inf and is NOT
+ * reported; the fp16 operands A, G, M' and the weights report range code 8 as in mi355_double_attn_fwd (bf16 reports nothing).
+ * Routes (option "da_fused" = 0 sends every shape down the general one):
+ *   one kernel     C = 64, c_m = c_n = 32, H*W <= 1024 and a multiple of 32: 16-bit rows loaded straight into the operand tile, 16-byte
+ *                  stores of y, no workspace traffic (the workspace query still names the general route's size for these
+ *                  shapes, as mi355_double_attn_ws_bytes does: parameters off 16-byte alignment take that route);
+ *   two passes     c_m = c_n = 128, C in {128, 256}, H*W a multiple of 4 (the fp32 entry's envelope): pass 1 stages 8-byte row pieces of
+ *                  x into the X^T operand image, pass 2 stores y in 16 bit; the 16-bit V tensor in between as in the fp32 entry;
+ *   general        everything else mi355_double_attn_fwd takes (H*W, C, c_m, c_n multiples of 4, else MI355_EUNSUPPORTED): x is transposed
+ *                  to 16-bit tokens directly where C % 64 == 0 and widened to fp32 in the workspace otherwise; the fp32 result of the
+ *                  last product is rounded into y.
+ * From the operand tile onwards the fused routes keep the tile size, tile order and wave ownership of the fp32-I/O kernels: y equals
+ * mi355_double_attn_fwd(precision = io) on the widened x, rounded once.  Precision 0 on 16-bit tensors is the caller's: widen, call
+ * mi355_double_attn_fwd, round.  Validation (io, sizes, pointers, workspace size) precedes every HIP call: MI355_EINVAL. */
+size_t mi355_double_attn16_ws_bytes(int B, int C, int cm, int cn, int H, int W, int io);
+int    mi355_double_attn16_fwd(const void* x, const float* wA, const float* bA, const float* wB, const float* bB,
+                               const float* wV, const float* bV, const float* wP, const float* bP, void* y,
+                               int B, int C, int cm, int cn, int H, int W, int io,
+                               void* ws, size_t ws_bytes, mi355_stream_t stream);
 
 /* ---- the rest of the channel-attention zoo: per-channel statistic -> tiny transform -> broadcast scale ------------
  * NCHW fp32, HBM-bound, x read once / y written once when HW % 4 == 0, HW <= 4096 and C % 8 == 0 (8 channel rows per workgroup stay

@@ -111,9 +111,10 @@ __global__ __launch_bounds__(256) void softmax_cols_reg_kernel(float* __restrict
 inline size_t r16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 // x (B, C, HW) fp32 -> xt (B, HW, C) in the 16-bit operand type: the token-major activation the fast GEMM engine wants as its row operand
-// (64 x 64 tiles through LDS: 256-byte runs in, 128-byte runs out).
-template <typename T>
-__global__ __launch_bounds__(256) void nchw_to_tokens16_kernel(const float* __restrict__ x, T* __restrict__ xt, int C, int HW,
+// (64 x 64 tiles through LDS: 256-byte runs in, 128-byte runs out).  S = T (16-bit I/O, mi355_double_attn16_fwd): x is already in the
+// operand type and the kernel is a pure transpose -- the widening into the fp32 tile and the narrowing out of it are both exact.
+template <typename T, typename S = float>
+__global__ __launch_bounds__(256) void nchw_to_tokens16_kernel(const S* __restrict__ x, T* __restrict__ xt, int C, int HW,
                                                                unsigned* ovf) {
     __shared__ float tile[64][65];
     const int b = blockIdx.z, p0 = blockIdx.x * 64, c0 = blockIdx.y * 64, t = threadIdx.x;
@@ -123,11 +124,11 @@ __global__ __launch_bounds__(256) void nchw_to_tokens16_kernel(const float* __re
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int cl = ty * 16 + r, c = c0 + cl, p = p0 + tx;
-            const float v = (c < C && p < HW) ? x[((long)b * C + c) * HW + p] : 0.f;
-            if constexpr (std::is_same<T, _Float16>::value) rgm = rg_max3abs(rgm, v, v);
+            const float v = (c < C && p < HW) ? (float)x[((long)b * C + c) * HW + p] : 0.f;
+            if constexpr (std::is_same<T, _Float16>::value && std::is_same<S, float>::value) rgm = rg_max3abs(rgm, v, v);
             tile[cl][tx] = v;
         }
-        if constexpr (std::is_same<T, _Float16>::value) rg_report_f(rgm, ovf, 8u);
+        if constexpr (std::is_same<T, _Float16>::value && std::is_same<S, float>::value) rg_report_f(rgm, ovf, 8u);
     }
     __syncthreads();
     const int pl = t >> 2, cq = t & 3, p = p0 + pl;
@@ -148,6 +149,34 @@ __global__ __launch_bounds__(256) void nchw_to_tokens16_kernel(const float* __re
             if (c0 + cq * 16 + k < C) dst[k] = (T)tile[cq * 16 + k][pl];
     }
 }
+
+// 16-bit I/O on the general route: x widened to fp32 where the first product takes an fp32 operand (C % 64 != 0), and the fp32 result
+// of the last product rounded once, to nearest even, into y.  Four elements per thread (the route needs C and H*W multiples of 4).
+// Unlike mi355_cast16_fwd the rounding reports nothing: an fp16 y beyond 65504 is inf, as m(x.float()).half() is.
+template <typename T>
+__global__ __launch_bounds__(256) void da_widen_kernel(const T* __restrict__ x, float* __restrict__ o, long n4) {
+    typedef T t4 __attribute__((ext_vector_type(4)));
+    typedef float f4_t __attribute__((ext_vector_type(4)));
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    const t4 v = reinterpret_cast<const t4*>(x)[i];
+    reinterpret_cast<f4_t*>(o)[i] = f4_t{(float)v.x, (float)v.y, (float)v.z, (float)v.w};
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void da_round16_kernel(const float* __restrict__ s, T* __restrict__ y, long n4) {
+    typedef T t4 __attribute__((ext_vector_type(4)));
+    typedef float f4_t __attribute__((ext_vector_type(4)));
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    const f4_t v = reinterpret_cast<const f4_t*>(s)[i];
+    reinterpret_cast<t4*>(y)[i] = t4{(T)v.x, (T)v.y, (T)v.z, (T)v.w};
+}
+
+// The seven-launch pipeline behind both entries.  Exactly one of x (fp32) and x16 (the operand type of `precision`, C % 64 == 0) is set.
+int general_route(const float* x, const void* x16, const float* wA, const float* bA, const float* wB, const float* bB,
+                  const float* wV, const float* bV, const float* wP, const float* bP, float* y, int B, int C, int cm, int cn, int HW,
+                  int precision, void* ws, mi355_stream_t stream);
 
 }  // namespace
 
@@ -174,15 +203,79 @@ int mi355_double_attn_fwd(const float* x, const float* wA, const float* bA, cons
     MI355_CHECK_ARG(x && wA && bA && wB && bB && wV && bV && wP && bP && y && ws);
     MI355_CHECK_ARG(B > 0 && C > 0 && cm > 0 && cn > 0 && H > 0 && W > 0);
     MI355_CHECK_ARG(ws_bytes >= mi355_double_attn_ws_bytes(B, C, cm, cn, H, W, precision));
-    const int HW = H * W, M3 = cm + 2 * cn;
+    const int HW = H * W;
     if (mi355::opt(mi355::O_DA_FUSED) != 0 && mi355::double_attn_small_ok(B, C, cm, cn, HW, precision) && aligned16(x) && aligned16(y) && aligned16(wA) &&
         aligned16(wB) && aligned16(wV) && aligned16(bV))
-        return mi355::double_attn_small(x, wA, bA, wB, bB, wV, bV, wP, bP, y, B, C, HW, precision, static_cast<hipStream_t>(stream));
+        return mi355::double_attn_small(x, wA, bA, wB, bB, wV, bV, wP, bP, y, B, C, HW, precision, false, static_cast<hipStream_t>(stream));
     if (mi355::double_attn_fused_ok(B, C, cm, cn, HW, precision) && aligned16(x) && aligned16(y) && aligned16(ws) && mi355::opt(mi355::O_DA_FUSED) != 0)
-        return mi355::double_attn_fused(x, wA, bA, wB, bB, wV, bV, wP, bP, y, B, C, HW, precision, ws, static_cast<hipStream_t>(stream));
+        return mi355::double_attn_fused(x, wA, bA, wB, bB, wV, bV, wP, bP, y, B, C, HW, precision, false, ws, static_cast<hipStream_t>(stream));
     if ((HW & 3) || (C & 3) || (cm & 3) || (cn & 3) || !aligned16(x) || !aligned16(y) || !aligned16(ws))
         return mi355::fail(MI355_EUNSUPPORTED, "mi355_double_attn_fwd: H*W, C, c_m, c_n must be multiples of 4 (HW=%d C=%d cm=%d cn=%d)",
                            HW, C, cm, cn);
+    return general_route(x, nullptr, wA, bA, wB, bB, wV, bV, wP, bP, y, B, C, cm, cn, HW, precision, ws, stream);
+}
+
+// workspace of the 16-bit-I/O entry: the two-pass path's own, else the general route's -- the fp32 result (+ the widened x where
+// C % 64 != 0) in front of the fp32 entry's workspace.  The one-kernel path uses none of it, but its shapes get the general size, as
+// in mi355_double_attn_ws_bytes: parameters that are not 16-byte aligned send such a call down the general route.
+size_t mi355_double_attn16_ws_bytes(int B, int C, int cm, int cn, int H, int W, int io) {
+    if ((io != 1 && io != 2) || B <= 0 || C <= 0 || cm <= 0 || cn <= 0 || H <= 0 || W <= 0) return 0;
+    if (mi355::opt(mi355::O_DA_FUSED) != 0 && mi355::double_attn_fused_ok(B, C, cm, cn, H * W, io))
+        return mi355::double_attn_fused_workspace(B, C, H * W);
+    const size_t n = (size_t)B * C * H * W;
+    return r16(n * 4) + ((C & 63) ? r16(n * 4) : 0) + mi355_double_attn_workspace_bytes(B, C, cm, cn, H, W);
+}
+
+int mi355_double_attn16_fwd(const void* x, const float* wA, const float* bA, const float* wB, const float* bB, const float* wV,
+                            const float* bV, const float* wP, const float* bP, void* y, int B, int C, int cm, int cn, int H, int W,
+                            int io, void* ws, size_t ws_bytes, mi355_stream_t stream) {
+    MI355_CHECK_ARG(io == 1 || io == 2);
+    MI355_CHECK_ARG(B > 0 && C > 0 && cm > 0 && cn > 0 && H > 0 && W > 0);
+    MI355_CHECK_ARG(x && wA && bA && wB && bB && wV && bV && wP && bP && y && ws);
+    MI355_CHECK_ARG(ws_bytes >= mi355_double_attn16_ws_bytes(B, C, cm, cn, H, W, io));
+    const int HW = H * W;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (mi355::opt(mi355::O_DA_FUSED) != 0 && mi355::double_attn_small_ok(B, C, cm, cn, HW, io) && aligned16(x) && aligned16(y) && aligned16(wA) &&
+        aligned16(wB) && aligned16(wV) && aligned16(bV))
+        return mi355::double_attn_small(x, wA, bA, wB, bB, wV, bV, wP, bP, y, B, C, HW, io, true, st);
+    if (mi355::double_attn_fused_ok(B, C, cm, cn, HW, io) && aligned16(x) && aligned16(y) && aligned16(ws) && mi355::opt(mi355::O_DA_FUSED) != 0)
+        return mi355::double_attn_fused(x, wA, bA, wB, bB, wV, bV, wP, bP, y, B, C, HW, io, true, ws, st);
+    // the general route refuses exactly what mi355_double_attn_fwd refuses
+    if ((HW & 3) || (C & 3) || (cm & 3) || (cn & 3) || !aligned16(x) || !aligned16(y) || !aligned16(ws))
+        return mi355::fail(MI355_EUNSUPPORTED, "mi355_double_attn16_fwd: H*W, C, c_m, c_n must be multiples of 4 (HW=%d C=%d cm=%d cn=%d)",
+                           HW, C, cm, cn);
+    const size_t n = (size_t)B * C * HW;
+    const long n4 = (long)(n / 4);
+    // (the size of the query for every shape that can get here; checked again because this route writes all of it)
+    MI355_CHECK_ARG(ws_bytes >= r16(n * 4) + ((C & 63) ? r16(n * 4) : 0) + mi355_double_attn_workspace_bytes(B, C, cm, cn, H, W));
+    char* p = static_cast<char*>(ws);
+    float* y32 = reinterpret_cast<float*>(p); p += r16(n * 4);
+    float* x32 = nullptr;
+    if (C & 63) {
+        x32 = reinterpret_cast<float*>(p); p += r16(n * 4);
+        MI355_TRACE(st, "da_widen_kernel io=%d n=%ld", io, (long)n);
+        if (io == 1) da_widen_kernel<_Float16><<<cdiv(n4, 256), 256, 0, st>>>(static_cast<const _Float16*>(x), x32, n4);
+        else         da_widen_kernel<__bf16><<<cdiv(n4, 256), 256, 0, st>>>(static_cast<const __bf16*>(x), x32, n4);
+    }
+    int rc = general_route(x32, x32 ? nullptr : x, wA, bA, wB, bB, wV, bV, wP, bP, y32, B, C, cm, cn, HW, io, p, stream);
+    if (rc) return rc;
+    {
+        MI355_TRACE(st, "da_round16_kernel io=%d n=%ld", io, (long)n);
+        if (io == 1) da_round16_kernel<_Float16><<<cdiv(n4, 256), 256, 0, st>>>(y32, static_cast<_Float16*>(y), n4);
+        else         da_round16_kernel<__bf16><<<cdiv(n4, 256), 256, 0, st>>>(y32, static_cast<__bf16*>(y), n4);
+    }
+    MI355_LAUNCH_CHECK();
+    return MI355_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+int general_route(const float* x, const void* x16, const float* wA, const float* bA, const float* wB, const float* bB,
+                  const float* wV, const float* bV, const float* wP, const float* bP, float* y, int B, int C, int cm, int cn, int HW,
+                  int precision, void* ws, mi355_stream_t stream) {
+    const int M3 = cm + 2 * cn;
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* p = static_cast<char*>(ws);
     float* Wcat = reinterpret_cast<float*>(p); p += r16((size_t)M3 * C * 4);
@@ -206,8 +299,15 @@ int mi355_double_attn_fwd(const float* x, const float* wA, const float* bA, cons
         void* xt16 = q; q += r16((size_t)B * HW * C * 2);
         void* w16 = q;
         const dim3 tgrid(cdiv(HW, 64), cdiv(C, 64), B);
-        if (precision == MI355_PREC_FP16) nchw_to_tokens16_kernel<_Float16><<<tgrid, 256, 0, st>>>(x, static_cast<_Float16*>(xt16), C, HW, mi355::range_word(st));
-        else                              nchw_to_tokens16_kernel<__bf16><<<tgrid, 256, 0, st>>>(x, static_cast<__bf16*>(xt16), C, HW, nullptr);
+        if (x16) {
+            MI355_TRACE(st, "nchw_to_tokens16_kernel<io16> io=%d C=%d HW=%d", precision, C, HW);
+            if (precision == MI355_PREC_FP16)
+                nchw_to_tokens16_kernel<_Float16, _Float16><<<tgrid, 256, 0, st>>>(static_cast<const _Float16*>(x16), static_cast<_Float16*>(xt16), C, HW, nullptr);
+            else
+                nchw_to_tokens16_kernel<__bf16, __bf16><<<tgrid, 256, 0, st>>>(static_cast<const __bf16*>(x16), static_cast<__bf16*>(xt16), C, HW, nullptr);
+        }
+        else if (precision == MI355_PREC_FP16) nchw_to_tokens16_kernel<_Float16><<<tgrid, 256, 0, st>>>(x, static_cast<_Float16*>(xt16), C, HW, mi355::range_word(st));
+        else                                   nchw_to_tokens16_kernel<__bf16><<<tgrid, 256, 0, st>>>(x, static_cast<__bf16*>(xt16), C, HW, nullptr);
         rc = mi355_cast16_fwd(Wcat, w16, (size_t)M3 * C, precision, stream);
         if (rc) return rc;
         rc = mi355_linear16_tr_fwd(xt16, w16, bcat, nullptr, ABV, B * HW, M3, C, C, HW, precision, stream);
@@ -246,4 +346,4 @@ int mi355_double_attn_fwd(const float* x, const float* wA, const float* bA, cons
     return MI355_OK;
 }
 
-}  // extern "C"
+}  // namespace

@@ -22,6 +22,13 @@
 //
 // HBM traffic per image: x once (fp32), V twice (16 bit, c_n / C of x each), y once -- 2.5x less than the unfused pipeline.
 // Envelope: 16-bit operand modes, c_m = c_n = 128, C in {128, 256}, H*W a multiple of 4; everything else takes double_attn.hip.
+//
+// 16-bit I/O (IO16: x and y in the operand type, mi355_double_attn16_fwd; the same envelope).  A tile row of x is 64 bytes, so the 1 KB
+// LDS-DMA blocks and the fp32 4 x 4 transposes of pass 1 do not apply: a thread loads the same 4 channels x 4 pixels it transposes in
+// the fp32 kernel as four 8-byte pieces (rows are 8-byte aligned for every H*W % 4 == 0), holds the NEXT tile's pieces in registers
+// while this tile is computed, and writes them into the X^T image with the fp32 kernel's lane map and 8-byte stores -- no conversion,
+// x IS the operand.  The 108 KB raw ring is gone, but at 168-244 VGPRs a workgroup is still alone on its CU.  Pass 2 rounds its slab once and stores 8 bytes per lane.
+// From the X^T image to the slab the arithmetic, tile order and wave ownership are the fp32-I/O kernels'.
 #include "common.h"
 #include "mma.h"
 
@@ -56,7 +63,7 @@ __device__ __forceinline__ void lds_dma16(const void* src, const void* dst) {
 }
 
 struct DaArgs {
-    const float* x;            // (B, C, HW) fp32
+    const void* x;             // (B, C, HW) fp32, or the operand type with 16-bit I/O
     const void* w16;           // (3 * 128, C) 16 bit: WA | log2e WB | log2e WV
     const float* bias;         // (3 * 128) fp32, the B and V parts in log2 units
     void* v16;                 // (B, HW, 128) 16 bit: softmax over channels of V, token-major
@@ -65,7 +72,7 @@ struct DaArgs {
     const void* wp16;          // (C, 128) 16 bit
     void* m16;                 // (B, C, 128) 16 bit: M' = WP G
     const float* bp;           // (C)
-    float* y;                  // (B, C, HW)
+    void* y;                   // (B, C, HW) fp32, or the operand type with 16-bit I/O
     int B, HW, S, tiles, tiles_per;
     unsigned* ovf;             // fp16 range word (precision 1, else null): x, A, G, M' and the weights staged to fp16 report code 8
 };
@@ -94,7 +101,7 @@ __global__ __launch_bounds__(256) void da_prep_kernel(const float* __restrict__ 
 }
 
 // ---- pass 1 ------------------------------------------------------------------------------------------------------------------------
-template <int PREC, int KS>
+template <int PREC, int KS, bool IO16 = false>
 __global__ __launch_bounds__(512) void da_pass1_kernel(const DaArgs a) {
     using M_ = Mma<PREC>;
     using v8 = typename M_::v8;
@@ -110,7 +117,9 @@ __global__ __launch_bounds__(512) void da_pass1_kernel(const DaArgs a) {
     constexpr int VP = CM + 8;                 // pitch of the V staging rows
     constexpr int NDMA = C / 64;               // 1 KB LDS-DMA instructions per wave and tile (C / 8 channel blocks over 8 waves)
     constexpr int RB = 8 * PT + 32;            // floats per 8-channel block of the raw tile: 1 KB of data + 128 bytes of padding
-    __shared__ __attribute__((aligned(16))) float s_raw[3][(C / 8) * RB];
+    // 16-bit I/O has no raw ring; the area only parks G^T at the end (S = 1): CM * (CM + 8) 16-bit values
+    constexpr int NRAW = IO16 ? 1 : 3, RAWN = IO16 ? CM * (CM + 8) / 2 : (C / 8) * RB;
+    __shared__ __attribute__((aligned(16))) float s_raw[NRAW][RAWN];
     __shared__ __attribute__((aligned(16))) unsigned short s_xt[PT * XP];
     __shared__ __attribute__((aligned(16))) unsigned short s_e[CM * EP];
     __shared__ __attribute__((aligned(16))) unsigned short s_v[PT * VP];
@@ -123,7 +132,8 @@ __global__ __launch_bounds__(512) void da_pass1_kernel(const DaArgs a) {
     const int b = blockIdx.x / a.S, sp = blockIdx.x - b * a.S;
     const int t0 = sp * a.tiles_per;
     const int n = min(a.tiles_per, a.tiles - t0);
-    const float* xb = a.x + (long)b * C * a.HW;
+    const float* xb = static_cast<const float*>(a.x) + (long)b * C * a.HW;
+    const el* xb16 = static_cast<const el*>(a.x) + (long)b * C * a.HW;
 
     // wave w moves channel blocks w * NDMA + i: 8 channels x 32 px = 8 x 128-byte row pieces = 1 KB, lane-linear in LDS.  Pixels
     // past the image (last tile) re-read the row's last 16 bytes: finite duplicates of this image's data, masked below.
@@ -148,10 +158,28 @@ __global__ __launch_bounds__(512) void da_pass1_kernel(const DaArgs a) {
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) wf[j][ks] = *reinterpret_cast<const v8*>(wg + (long)(j * CM + 16 * w + l15) * C + ks * 32 + g * 8);
     }
+    // 16-bit I/O: thread u of a 512-thread sweep holds channels 4 cg .. 4 cg + 3 of pixels 4 q .. 4 q + 3 (the (cg, q) map of the
+    // transposing sweep below) as four 8-byte row pieces; C = 128 keeps half the threads busy.  Pixels past the image re-read the
+    // row's last 8 bytes, as the DMA above does.
+    const bool xact = 2 * C >= 512 || t < 2 * C;
+    const int xcg = (t >> 6) * 8 + (t & 7), xq_ = (t >> 3) & 7;
+    v4 xq[4];
+    auto load_tile = [&](int tile) {
+        if (xact) {
+            const el* src = xb16 + (long)(4 * xcg) * a.HW + min(tile * PT + 4 * xq_, a.HW - 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) xq[j] = *reinterpret_cast<const v4*>(src + (long)j * a.HW);
+        }
+    };
+    (void)dma; (void)load_tile; (void)xb; (void)xb16;              // each I/O form uses its own
     if (t < 3 * CM) s_bias[t] = a.bias[t];                          // (visible after the barrier below)
-    dma(t0, 0);                                                     // three tiles in flight: 96 KB per CU, 24 MB on the device
-    if (n > 1) dma(t0 + 1, 1);
-    if (n > 2) dma(t0 + 2, 2);
+    if constexpr (IO16) {
+        load_tile(t0);
+    } else {
+        dma(t0, 0);                                                 // three tiles in flight: 96 KB per CU, 24 MB on the device
+        if (n > 1) dma(t0 + 1, 1);
+        if (n > 2) dma(t0 + 2, 2);
+    }
 
     f4 G[8];
 #pragma unroll
@@ -165,40 +193,56 @@ __global__ __launch_bounds__(512) void da_pass1_kernel(const DaArgs a) {
                 *reinterpret_cast<const uint4*>(&s_v[(t >> 4) * VP + (t & 15) * 8]);
     };
 
-    if (n > 2)      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NDMA) : "memory");   // weights and tile 0 landed
-    else if (n > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");
-    else            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if constexpr (!IO16) {
+        if (n > 2)      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NDMA) : "memory");   // weights and tile 0 landed
+        else if (n > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");
+        else            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
     __syncthreads();
 
     int buf = -1;
     for (int it = 0; it < n; ++it) {
         const int tile = t0 + it, px0 = tile * PT;
         buf = buf == 2 ? 0 : buf + 1;
-        // ---- raw (C x 32 px fp32) -> X^T (32 px x C, 16 bit): 4 channels x 4 pixels per thread ---------------------------------------
+        if constexpr (IO16) {
+            // ---- the pieces loaded one tile ahead -> X^T: the same four 8-byte stores per thread, nothing to convert ---------------------
+            if (xact) {
 #pragma unroll
-        for (int u0 = 0; u0 < 2 * C; u0 += 512) {
-            const int u = u0 + t;
-            if (2 * C >= 512 || u < 2 * C) {
-                // lane -> (channel group cg: 8 per wave, fastest; pixel quad q): the 8-byte stores of 16 consecutive lanes then cover all
-                // 32 banks once
-                const int cg = (u >> 6) * 8 + (u & 7), q = (u >> 3) & 7;
-                // (inline asm: a compiler-visible read of the LDS-DMA target would get a vmcnt(0) in front of it -- all tiles in flight)
-                f4 r[4];
-                const unsigned ra = lds_addr(&s_raw[buf][(cg >> 1) * RB + (8 * (4 * (cg & 1)) + (q ^ (4 * (cg & 1)))) * 4]);
-                asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:128\n\tds_read_b128 %2, %4 offset:256\n\t"
-                             "ds_read_b128 %3, %4 offset:384\n\ts_waitcnt lgkmcnt(0)"
-                             : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]) : "v"(ra) : "memory");
+                for (int i = 0; i < 4; ++i)
+                    *reinterpret_cast<v4*>(&s_xt[(4 * xq_ + i) * XP + 4 * xcg]) = v4{xq[0][i], xq[1][i], xq[2][i], xq[3][i]};
+            }
+
+        } else {
+            // ---- raw (C x 32 px fp32) -> X^T (32 px x C, 16 bit): 4 channels x 4 pixels per thread ---------------------------------------
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const f4 xv = f4{r[0][i], r[1][i], r[2][i], r[3][i]};
-                    if constexpr (PREC == 1) rgm = rg_max3abs4(rgm, xv);
-                    *reinterpret_cast<v4*>(&s_xt[(4 * q + i) * XP + 4 * cg]) = M_::cvt(xv);
+            for (int u0 = 0; u0 < 2 * C; u0 += 512) {
+                const int u = u0 + t;
+                if (2 * C >= 512 || u < 2 * C) {
+                    // lane -> (channel group cg: 8 per wave, fastest; pixel quad q): the 8-byte stores of 16 consecutive lanes then cover all
+                    // 32 banks once
+                    const int cg = (u >> 6) * 8 + (u & 7), q = (u >> 3) & 7;
+                    // (inline asm: a compiler-visible read of the LDS-DMA target would get a vmcnt(0) in front of it -- all tiles in flight)
+                    f4 r[4];
+                    const unsigned ra = lds_addr(&s_raw[buf][(cg >> 1) * RB + (8 * (4 * (cg & 1)) + (q ^ (4 * (cg & 1)))) * 4]);
+                    asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:128\n\tds_read_b128 %2, %4 offset:256\n\t"
+                                 "ds_read_b128 %3, %4 offset:384\n\ts_waitcnt lgkmcnt(0)"
+                                 : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]) : "v"(ra) : "memory");
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const f4 xv = f4{r[0][i], r[1][i], r[2][i], r[3][i]};
+                        if constexpr (PREC == 1) rgm = rg_max3abs4(rgm, xv);
+                        *reinterpret_cast<v4*>(&s_xt[(4 * q + i) * XP + 4 * cg]) = M_::cvt(xv);
+                    }
                 }
             }
         }
         DA_BAR();                                                   // B1: X^T complete; raw[buf] and s_v of the previous tile free to reuse / read
         if (it > 0) store_v(tile - 1);
-        if (it + 3 < n) dma(tile + 3, buf);
+        if constexpr (IO16) {
+            if (it + 1 < n) load_tile(tile + 1);                    // flies under this tile's math
+        } else {
+            if (it + 3 < n) dma(tile + 3, buf);
+        }
 
         // ---- S^T = X^T W^T (A, B: rows = pixels) and W X (V: rows = channels) ----------------------------------------------------------
         f4 acc[2][3];
@@ -287,9 +331,11 @@ __global__ __launch_bounds__(512) void da_pass1_kernel(const DaArgs a) {
                 s_stat[w][16 + l15][1] = s1;
             }
         }
-        if (it + 3 < n)      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NDMA) : "memory");   // tile it+1 landed; it+2, it+3 may still fly
-        else if (it + 2 < n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");
-        else                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (!IO16) {
+            if (it + 3 < n)      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NDMA) : "memory");   // tile it+1 landed; it+2, it+3 may still fly
+            else if (it + 2 < n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");
+            else                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
         DA_BAR();                                                   // B2: E, alpha, V statistics of every wave visible; raw of tile it+1 complete
 
         // ---- G^T rows 16w.. += A E^T -----------------------------------------------------------------------------------------------
@@ -449,10 +495,11 @@ __global__ __launch_bounds__(256) void da_combine_kernel(const DaArgs a, int C) 
 }
 
 // ---- pass 2: y = M' V + bP -----------------------------------------------------------------------------------------------------------
-template <int PREC, int CT>                    // CT = C / 128: output-channel tiles per wave
+template <int PREC, int CT, bool IO16 = false>  // CT = C / 128: output-channel tiles per wave
 __global__ __launch_bounds__(512, 2) void da_pass2_kernel(const DaArgs a, int nsub, int groups) {
     using M_ = Mma<PREC>;
     using v8 = typename M_::v8;
+    using v4 = typename M_::v4;
     using el = typename M_::e;
     constexpr int C = 128 * CT, PX = 64, SP = PX + 4;               // slab pitch (floats): 16 rows x 16 bytes on 64 distinct banks
     __shared__ __attribute__((aligned(16))) unsigned short s_vt[2][PX * CM];
@@ -521,12 +568,18 @@ __global__ __launch_bounds__(512, 2) void da_pass2_kernel(const DaArgs a, int ns
             for (int rb = 0; rb < 4; ++rb) *reinterpret_cast<f4*>(&slab[l15 * SP + 16 * rb + 4 * g]) = acc[rb][ct] + bp[ct];
             __builtin_amdgcn_wave_barrier();                       // lanes exchange through the wave's own slab: keep the compiler from
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // moving a lane's reads above its (different-address) writes
-            float* yo = a.y + ((long)b * C + 16 * (CT * w + ct)) * a.HW + px0;
+            const long yoff = ((long)b * C + 16 * (CT * w + ct)) * a.HW + px0;
+            float* yo = static_cast<float*>(a.y) + yoff;
+            el* yo16 = static_cast<el*>(a.y) + yoff;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int row = 4 * i + (lane >> 4), c4 = (lane & 15) * 4;
                 const f4 v = *reinterpret_cast<const f4*>(&slab[row * SP + c4]);
-                if (px0 + c4 < a.HW) __builtin_nontemporal_store(v, reinterpret_cast<f4*>(yo + (long)row * a.HW + c4));
+                if constexpr (IO16) {                                   // rounded once, to nearest even; 128-byte row segments
+                    if (px0 + c4 < a.HW) __builtin_nontemporal_store(M_::cvt(v), reinterpret_cast<v4*>(yo16 + (long)row * a.HW + c4));
+                } else {
+                    if (px0 + c4 < a.HW) __builtin_nontemporal_store(v, reinterpret_cast<f4*>(yo + (long)row * a.HW + c4));
+                }
             }
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -548,6 +601,33 @@ int plan_ranges(int B, int tiles) {
     return (tiles + per - 1) / per;                                  // no empty range
 }
 
+// the four launches in one operand format; 16-bit I/O files every launch under a tag of its own (mi355_trace_begin)
+template <int PREC, bool IO16>
+int launch_fused(const DaArgs& a, const float* wA, const float* bA, const float* wB, const float* bB, const float* wV, const float* bV,
+                 const float* wP, void* w16, float* bias, void* wp16, int B, int C, hipStream_t st) {
+    using el = typename Mma<PREC>::e;
+    const int pgrid = cdiv((long)CM * C, 256);
+    const int nsub = 2, groups = cdiv(a.HW, 64 * nsub);
+#define DA_GO(TAG_, ...)                                                                 \
+    do {                                                                                 \
+        if (IO16) {                                                                      \
+            MI355_TRACE(st, TAG_ "<io16> io=%d B=%d C=%d HW=%d S=%d", PREC, B, C, a.HW, a.S); \
+            __VA_ARGS__;                                                                 \
+        } else {                                                                         \
+            __VA_ARGS__;                                                                 \
+        }                                                                                \
+    } while (0)
+    DA_GO("da_prep_kernel", (da_prep_kernel<el><<<pgrid, 256, 0, st>>>(wA, wB, wV, bA, bB, bV, wP, static_cast<el*>(w16), bias, static_cast<el*>(wp16), C, a.ovf)));
+    if (C == 256) DA_GO("da_pass1_kernel", (da_pass1_kernel<PREC, 8, IO16><<<B * a.S, 512, 0, st>>>(a)));
+    else          DA_GO("da_pass1_kernel", (da_pass1_kernel<PREC, 4, IO16><<<B * a.S, 512, 0, st>>>(a)));
+    if (a.S > 1) DA_GO("da_combine_kernel", (da_combine_kernel<PREC><<<B, 256, 0, st>>>(a, C)));
+    if (C == 256) DA_GO("da_pass2_kernel", (da_pass2_kernel<PREC, 2, IO16><<<B * groups, 512, 0, st>>>(a, nsub, groups)));
+    else          DA_GO("da_pass2_kernel", (da_pass2_kernel<PREC, 1, IO16><<<B * groups, 512, 0, st>>>(a, nsub, groups)));
+#undef DA_GO
+    MI355_LAUNCH_CHECK();
+    return MI355_OK;
+}
+
 }  // namespace
 
 namespace mi355 {
@@ -563,8 +643,8 @@ size_t double_attn_fused_workspace(int B, int C, int HW) {
            r256((size_t)B * S * CM * CM * 4) + r256((size_t)B * S * 2 * CM * 4) + r256((size_t)B * C * CM * 2);
 }
 
-int double_attn_fused(const float* x, const float* wA, const float* bA, const float* wB, const float* bB, const float* wV, const float* bV,
-                      const float* wP, const float* bP, float* y, int B, int C, int HW, int precision, void* ws, hipStream_t st) {
+int double_attn_fused(const void* x, const float* wA, const float* bA, const float* wB, const float* bB, const float* wV, const float* bV,
+                      const float* wP, const float* bP, void* y, int B, int C, int HW, int precision, bool io16, void* ws, hipStream_t st) {
     DaArgs a;
     a.tiles = (HW + PT - 1) / PT;
     a.S = plan_ranges(B, a.tiles);
@@ -581,25 +661,11 @@ int double_attn_fused(const float* x, const float* wA, const float* bA, const fl
     a.m16 = p;
     a.x = x; a.w16 = w16; a.bias = bias; a.wp16 = wp16; a.bp = bP; a.y = y;
     a.ovf = precision == MI355_PREC_FP16 ? range_word(st) : nullptr;
-    const int pgrid = cdiv((long)CM * C, 256);
-    const int nsub = 2, groups = cdiv(HW, 64 * nsub);
-    if (precision == MI355_PREC_FP16) {
-        da_prep_kernel<_Float16><<<pgrid, 256, 0, st>>>(wA, wB, wV, bA, bB, bV, wP, static_cast<_Float16*>(w16), bias, static_cast<_Float16*>(wp16), C, a.ovf);
-        if (C == 256) da_pass1_kernel<1, 8><<<B * a.S, 512, 0, st>>>(a);
-        else          da_pass1_kernel<1, 4><<<B * a.S, 512, 0, st>>>(a);
-        if (a.S > 1) da_combine_kernel<1><<<B, 256, 0, st>>>(a, C);
-        if (C == 256) da_pass2_kernel<1, 2><<<B * groups, 512, 0, st>>>(a, nsub, groups);
-        else          da_pass2_kernel<1, 1><<<B * groups, 512, 0, st>>>(a, nsub, groups);
-    } else {
-        da_prep_kernel<__bf16><<<pgrid, 256, 0, st>>>(wA, wB, wV, bA, bB, bV, wP, static_cast<__bf16*>(w16), bias, static_cast<__bf16*>(wp16), C, nullptr);
-        if (C == 256) da_pass1_kernel<2, 8><<<B * a.S, 512, 0, st>>>(a);
-        else          da_pass1_kernel<2, 4><<<B * a.S, 512, 0, st>>>(a);
-        if (a.S > 1) da_combine_kernel<2><<<B, 256, 0, st>>>(a, C);
-        if (C == 256) da_pass2_kernel<2, 2><<<B * groups, 512, 0, st>>>(a, nsub, groups);
-        else          da_pass2_kernel<2, 1><<<B * groups, 512, 0, st>>>(a, nsub, groups);
-    }
-    MI355_LAUNCH_CHECK();
-    return MI355_OK;
+    if (precision == MI355_PREC_FP16)
+        return io16 ? launch_fused<1, true>(a, wA, bA, wB, bB, wV, bV, wP, w16, bias, wp16, B, C, st)
+                    : launch_fused<1, false>(a, wA, bA, wB, bB, wV, bV, wP, w16, bias, wp16, B, C, st);
+    return io16 ? launch_fused<2, true>(a, wA, bA, wB, bB, wV, bV, wP, w16, bias, wp16, B, C, st)
+                : launch_fused<2, false>(a, wA, bA, wB, bB, wV, bV, wP, w16, bias, wp16, B, C, st);
 }
 
 }  // namespace mi355

@@ -24,6 +24,11 @@
 //   computed from the V tile in LDS (A = V^T rows from LDS, B = M' rows) as D[pixel][channel]: a lane holds 4 consecutive pixels of
 //   one output channel = one 16-byte store; a wave's two tiles complete 128-byte lines of y.
 // HBM traffic: x once, y once -- nothing else (no workspace).
+//
+// 16-bit I/O (IO16: x and y in the operand type, mi355_double_attn16_fwd): a group's rows are 64 bytes, a lane's 16-byte load is eight
+// pixels of one channel and goes into the X^T tile as it is (no conversion: x IS the operand); the final store rounds the fp32
+// accumulator once and, after one swap between neighbouring lane groups, writes 16 bytes per lane (8-byte pieces measured slower
+// than the fp32 kernel: 32-byte runs of y).  Everything between the operand tile and the accumulator is the fp32-I/O kernel.
 #include "common.h"
 #include "mma.h"
 
@@ -33,13 +38,13 @@ constexpr int DS_C = 32;          // c_m = c_n
 constexpr int DS_GPX = 32;        // pixels per group (two 16-pixel MFMA tiles = K of the contraction over pixels)
 
 struct DsArgs {
-    const float* x; float* y;
+    const void* x; void* y;       // fp32, or the operand type of PREC with 16-bit I/O
     const float* wA; const float* bA; const float* wB; const float* bB; const float* wV; const float* bV; const float* wP; const float* bP;
     int HW;
     unsigned* ovf;                // fp16 range word (precision 1, else null): weights, x, A and M' staged to fp16 report code 8
 };
 
-template <int PREC, int C>
+template <int PREC, int C, bool IO16 = false>
 __global__ __launch_bounds__(512) void da_small_kernel(const DsArgs a) {
     using M_ = Mma<PREC>;
     using v8 = typename M_::v8;
@@ -56,7 +61,8 @@ __global__ __launch_bounds__(512) void da_small_kernel(const DsArgs a) {
     unsigned char* s_x = lds + (size_t)a.HW * 64;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, l15 = lane & 15, g = lane >> 4;
     const int b = blockIdx.x, HW = a.HW;
-    const float* xb = a.x + (long)b * C * HW;
+    const float* xb = static_cast<const float*>(a.x) + (long)b * C * HW;                  // fp32 I/O
+    const typename M_::e* xb16 = static_cast<const typename M_::e*>(a.x) + (long)b * C * HW;   // 16-bit I/O
     unsigned char* xt = s_x + w * (DS_GPX * XP);
     // fp16 range guard (common.h rg_max3abs, code 8): the unbounded values converted to fp16 -- the weights, x, A = WA x + bA and
     // M' = WP G.  The softmax factors (2^(b - max) and the channel softmax of V) are in [0, 1].
@@ -92,11 +98,21 @@ __global__ __launch_bounds__(512) void da_small_kernel(const DsArgs a) {
     // ---- streaming phase ---------------------------------------------------------------------------------------------------------
     const int ngroups = HW / DS_GPX;
     const int chs = lane >> 3, pq = lane & 7;        // load geometry: instruction i covers channels 8 i + chs, pixels 4 pq .. 4 pq + 3
-    f4 xr[NLD];
+    // 16-bit I/O: instruction i covers channels 16 i + chs16, pixels 8 pq8 .. 8 pq8 + 7 (64-byte runs per channel row)
+    constexpr int NLD16 = C / 16;
+    const int chs16 = lane >> 2, pq8 = lane & 3;
+    f4 xr[IO16 ? 1 : NLD];
+    v8 xr16[IO16 ? NLD16 : 1];
     auto load_group = [&](int grp) {
-        const float* p = xb + (long)chs * HW + grp * DS_GPX + pq * 4;
+        if constexpr (IO16) {
+            const el* p = xb16 + (long)chs16 * HW + grp * DS_GPX + pq8 * 8;
 #pragma unroll
-        for (int i = 0; i < NLD; ++i) xr[i] = *reinterpret_cast<const f4*>(p + (long)(8 * i) * HW);
+            for (int i = 0; i < NLD16; ++i) xr16[i] = *reinterpret_cast<const v8*>(p + (long)(16 * i) * HW);
+        } else {
+            const float* p = xb + (long)chs * HW + grp * DS_GPX + pq * 4;
+#pragma unroll
+            for (int i = 0; i < NLD; ++i) xr[i] = *reinterpret_cast<const f4*>(p + (long)(8 * i) * HW);
+        }
     };
     f4 gacc[2][2];                                   // partial G: [it][jt], lane = G[i = it*16 + g*4 + r][j = jt*16 + l15]
 #pragma unroll
@@ -108,14 +124,23 @@ __global__ __launch_bounds__(512) void da_small_kernel(const DsArgs a) {
     int grp = w;
     if (grp < ngroups) load_group(grp);
     for (; grp < ngroups; grp += 8) {
-        // park the group pixel-major in 16 bit: lane writes 4 pixels x 1 channel per load
+        // park the group pixel-major in 16 bit: lane writes 4 pixels x 1 channel per load (16-bit I/O: 8 pixels, as loaded)
+        if constexpr (IO16) {
 #pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const int ch = 8 * i + chs;
-            if constexpr (PREC == 1) rgm = rg_max3abs4(rgm, xr[i]);
-            const v4 h = M_::cvt(xr[i]);
+            for (int i = 0; i < NLD16; ++i) {
+                const int ch = 16 * i + chs16;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) *reinterpret_cast<el*>(xt + (pq * 4 + e) * XP + ch * 2) = h[e];
+                for (int e = 0; e < 8; ++e) *reinterpret_cast<el*>(xt + (pq8 * 8 + e) * XP + ch * 2) = xr16[i][e];
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NLD; ++i) {
+                const int ch = 8 * i + chs;
+                if constexpr (PREC == 1) rgm = rg_max3abs4(rgm, xr[i]);
+                const v4 h = M_::cvt(xr[i]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) *reinterpret_cast<el*>(xt + (pq * 4 + e) * XP + ch * 2) = h[e];
+            }
         }
         if (grp + 8 < ngroups) load_group(grp + 8);                       // next group's rows fly under this group's math
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -257,16 +282,44 @@ __global__ __launch_bounds__(512) void da_small_kernel(const DsArgs a) {
         mf[ct] = *reinterpret_cast<const v8*>(s_m + (size_t)(ct * 16 + l15) * 64 + g * 16);
         bp[ct] = a.bP[ct * 16 + l15];
     }
-    float* yb = a.y + (long)b * C * HW;
-    for (int gg = w; gg < ngroups; gg += 8) {
-#pragma unroll
-        for (int pt = 0; pt < 2; ++pt) {
-            const int px0 = gg * DS_GPX + pt * 16;
-            const v8 vf = *reinterpret_cast<const v8*>(s_v + (size_t)(px0 + l15) * 64 + g * 16);
+    float* yb = static_cast<float*>(a.y) + (long)b * C * HW;
+    el* yb16 = static_cast<el*>(a.y) + (long)b * C * HW;
+    if constexpr (IO16) {
+        // 16-bit I/O: a lane's 4 pixels are 8 bytes, and 8-byte pieces make 32-byte runs per channel row.  Both pixel tiles of the group
+        // are computed first; lane groups g and g ^ 1 then swap one rounded half (even g keeps tile 0, odd g tile 1), so that every lane
+        // stores 8 consecutive pixels = 16 bytes and an instruction writes the fp32 kernel's 64-byte runs.  Rounded once, to nearest
+        // even; |o| > 65504 -> inf in fp16.
+        const bool odd = g & 1;
+        for (int gg = w; gg < ngroups; gg += 8) {
+            const int px0 = gg * DS_GPX;
+            const v8 vf0 = *reinterpret_cast<const v8*>(s_v + (size_t)(px0 + l15) * 64 + g * 16);
+            const v8 vf1 = *reinterpret_cast<const v8*>(s_v + (size_t)(px0 + 16 + l15) * 64 + g * 16);
 #pragma unroll
             for (int ct = 0; ct < C / 16; ++ct) {
-                const f4 o = M_::mma(vf, mf[ct], f4{bp[ct], bp[ct], bp[ct], bp[ct]});
-                __builtin_nontemporal_store(o, reinterpret_cast<f4*>(yb + (long)(ct * 16 + l15) * HW + px0 + g * 4));
+                const f4 bias = f4{bp[ct], bp[ct], bp[ct], bp[ct]};
+                const uint2 h0 = __builtin_bit_cast(uint2, M_::cvt(M_::mma(vf0, mf[ct], bias)));
+                const uint2 h1 = __builtin_bit_cast(uint2, M_::cvt(M_::mma(vf1, mf[ct], bias)));
+                const uint2 send = odd ? h0 : h1;
+                uint2 recv;
+                recv.x = __shfl_xor(send.x, 16, WAVE);
+                recv.y = __shfl_xor(send.y, 16, WAVE);
+                // even g: tile 0, pixels 4g .. 4g + 7 = its own, then the partner's; odd g: tile 1, pixels 4(g - 1) ..: the partner's first
+                typedef unsigned u4 __attribute__((ext_vector_type(4)));
+                const u4 o = odd ? u4{recv.x, recv.y, h1.x, h1.y} : u4{h0.x, h0.y, recv.x, recv.y};
+                __builtin_nontemporal_store(o, reinterpret_cast<u4*>(yb16 + (long)(ct * 16 + l15) * HW + px0 + (odd ? 16 : 0) + (g >> 1) * 8));
+            }
+        }
+    } else {
+        for (int gg = w; gg < ngroups; gg += 8) {
+#pragma unroll
+            for (int pt = 0; pt < 2; ++pt) {
+                const int px0 = gg * DS_GPX + pt * 16;
+                const v8 vf = *reinterpret_cast<const v8*>(s_v + (size_t)(px0 + l15) * 64 + g * 16);
+#pragma unroll
+                for (int ct = 0; ct < C / 16; ++ct) {
+                    const f4 o = M_::mma(vf, mf[ct], f4{bp[ct], bp[ct], bp[ct], bp[ct]});
+                    __builtin_nontemporal_store(o, reinterpret_cast<f4*>(yb + (long)(ct * 16 + l15) * HW + px0 + g * 4));
+                }
             }
         }
     }
@@ -282,23 +335,30 @@ bool double_attn_small_ok(int B, int C, int cm, int cn, int HW, int precision) {
            HW >= DS_GPX && (HW % DS_GPX) == 0 && HW <= 1024 && B > 0;
 }
 
-int double_attn_small(const float* x, const float* wA, const float* bA, const float* wB, const float* bB, const float* wV, const float* bV,
-                      const float* wP, const float* bP, float* y, int B, int C, int HW, int precision, hipStream_t st) {
+int double_attn_small(const void* x, const float* wA, const float* bA, const float* wB, const float* bB, const float* wV, const float* bV,
+                      const float* wP, const float* bP, void* y, int B, int C, int HW, int precision, bool io16, hipStream_t st) {
     DsArgs a{x, y, wA, bA, wB, bB, wV, bV, wP, bP, HW, precision == MI355_PREC_FP16 ? range_word(st) : nullptr};
     // V tile + max(the eight X^T tiles, the merge area)
     const size_t xt = (size_t)8 * DS_GPX * (C * 2 + 16);
     const size_t merge = (size_t)(8 * 1024 + 8 * 32 * 2 + 1024) * 4 + (size_t)C * 64;
     const size_t smem = (size_t)HW * 64 + (xt > merge ? xt : merge);
-#define DS_GO(P_, C_)                                                                                       \
+#define DS_GO(P_, C_, IO_)                                                                                  \
     do {                                                                                                    \
-        if (int rc = func_dynamic_lds(reinterpret_cast<const void*>(da_small_kernel<P_, C_>), (int)smem)) return rc; \
-        da_small_kernel<P_, C_><<<B, 512, smem, st>>>(a);                                                   \
+        if (int rc = func_dynamic_lds(reinterpret_cast<const void*>(da_small_kernel<P_, C_, IO_>), (int)smem)) return rc; \
+        da_small_kernel<P_, C_, IO_><<<B, 512, smem, st>>>(a);                                              \
     } while (0)
-    if (precision == MI355_PREC_FP16) DS_GO(1, 64);
-    else                              DS_GO(2, 64);
+    if (io16) {
+        MI355_TRACE(st, "da_small_kernel<io16> io=%d B=%d HW=%d", precision, B, HW);
+        if (precision == MI355_PREC_FP16) DS_GO(1, 64, true);
+        else                              DS_GO(2, 64, true);
+    } else {
+        if (precision == MI355_PREC_FP16) DS_GO(1, 64, false);
+        else                              DS_GO(2, 64, false);
+    }
 #undef DS_GO
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MI355_EHIP, "mi355_double_attn_fwd: kernel launch -> %s", hipGetErrorString(e));
+    if (e != hipSuccess)
+        return fail(MI355_EHIP, "%s: kernel launch -> %s", io16 ? "mi355_double_attn16_fwd" : "mi355_double_attn_fwd", hipGetErrorString(e));
     return MI355_OK;
 }
 

@@ -60,6 +60,8 @@ SIGNATURES = {
     "mi355_double_attn_workspace_bytes": (c_size, [c_int] * 6),
     "mi355_double_attn_ws_bytes": (c_size, [c_int] * 7),
     "mi355_double_attn_fwd": (c_int, [c_vp] * 10 + [c_int] * 7 + [c_vp, c_size, c_vp]),
+    "mi355_double_attn16_ws_bytes": (c_size, [c_int] * 7),
+    "mi355_double_attn16_fwd": (c_int, [c_vp] * 10 + [c_int] * 7 + [c_vp, c_size, c_vp]),
     "mi355_linear_fwd": (c_int, [c_vp] * 6 + [c_int] * 7 + [c_vp]),
     "mi355_token_mix_fwd": (c_int, [c_vp] * 5 + [c_int] * 6 + [c_vp]),
     "mi355_layernorm_fwd": (c_int, [c_vp] * 4 + [c_int, c_int, c_float, c_vp]),
@@ -236,7 +238,7 @@ def require_device_f32(t, name):
     if t.dtype != torch.float32:
         raise TypeError(f"{name}: expected float32, got {t.dtype} (16-bit activations are accepted by SELayer, ECALayer, CBAM, "
                         "ChannelAttention, SpatialAttention, SELayerBias, SELayerBias4, SELayerHidden, SqueezeExcite, simam_module, SRM, "
-                        "GaussianGCT, LCT and GCT only)")
+                        "GaussianGCT, LCT, GCT and DoubleAttention only)")
     if t.requires_grad and torch.is_grad_enabled():
         _warn_no_autograd()
     return t if t.is_contiguous() else t.contiguous()

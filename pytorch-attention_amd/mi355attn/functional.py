@@ -192,8 +192,10 @@ def range_fallback_forward(module, forward, args, kwargs):
     absorb this forward's report nor run strict because of it."""
     if _guard.depth:
         return forward(module, *args, **kwargs)
-    if args and isinstance(args[0], torch.Tensor) and args[0].dtype in _ffi.IO_CODES:
-        # 16-bit activations (SELayer / ECALayer / CBAM): fp32 arithmetic and |y| <= |x|, nothing can saturate -- no arm, no wait, no re-run
+    if args and isinstance(args[0], torch.Tensor) and args[0].dtype in _ffi.IO_CODES \
+            and not (args[0].dtype == torch.float16 and getattr(module, "_mi355_fp16_io_saturates", False)):
+        # 16-bit activations (SELayer / ECALayer / CBAM): fp32 arithmetic and |y| <= |x|, nothing can saturate -- no arm, no wait, no re-run.
+        # Not so DoubleAttention on an fp16 x: its fp16 operands A, G and M' can (range code 8), so it is guarded like an fp32 forward.
         return forward(module, *args, **kwargs)
     try:
         passthrough = _ffi._capturing() or _ffi.get_option("range_fallback") != 1
@@ -610,19 +612,36 @@ def gct_forward(x, alpha, gamma, beta, epsilon=1e-5, mode="l2", after_relu=False
 
 
 def double_attention_forward(x, wA, bA, wB, bB, wV, bV, wP, bP, precision=None):
-    x = require_device_f32(x, "x")
+    """DoubleAttention forward: x (B,C,H,W) fp32 / fp16 / bf16 (output in the same type); weights (out, in[, 1, 1]) and biases in fp32
+    or, after module.half() / .bfloat16(), in 16 bit (param32: converted once, cached per parameter version).
+    (This holds for an fp32 x too: a module whose parameters were cast to 16 bit used to raise TypeError on fp32 input and now runs on
+    the widened parameters.)
+    fp32 x: `precision` (None = the package default) selects the MFMA operand format.  16-bit x: the operand format is the tensor's
+    own type -- fp16 runs the precision-1 arithmetic, bf16 the precision-2 arithmetic, x enters the MFMAs unrounded -- and a
+    `precision` of None, 1, 2 or 3 is ignored.  Precision 0 (explicit, the package default, or a strict re-run) still means fp32-class
+    arithmetic: x is widened, the strict route runs, and the result is rounded once to the type of x."""
+    x, io = _ffi.require_device_io(x, "x")
+    if io and _prec(precision) == PREC_STRICT:
+        return double_attention_forward(x.float(), wA, bA, wB, bB, wV, bV, wP, bP, precision=PREC_STRICT).to(x.dtype)
     B, C, H, W = x.shape
-    wA = require_device_f32(wA, "convA.weight").reshape(wA.shape[0], -1)
-    wB = require_device_f32(wB, "convB.weight").reshape(wB.shape[0], -1)
-    wV = require_device_f32(wV, "convV.weight").reshape(wV.shape[0], -1)
-    wP = require_device_f32(wP, "proj.weight").reshape(wP.shape[0], -1)
-    bA, bB, bV, bP = (require_device_f32(t, n) for t, n in ((bA, "convA.bias"), (bB, "convB.bias"),
-                                                           (bV, "convV.bias"), (bP, "proj.bias")))
+    wA = param32(wA, "convA.weight").reshape(wA.shape[0], -1)
+    wB = param32(wB, "convB.weight").reshape(wB.shape[0], -1)
+    wV = param32(wV, "convV.weight").reshape(wV.shape[0], -1)
+    wP = param32(wP, "proj.weight").reshape(wP.shape[0], -1)
+    bA, bB, bV, bP = (param32(t, n) for t, n in ((bA, "convA.bias"), (bB, "convB.bias"),
+                                                 (bV, "convV.bias"), (bP, "proj.bias")))
     cm, cn = wA.shape[0], wB.shape[0]
     Cout = wP.shape[0]
     if wV.shape[0] != cn or wP.shape[1] != cm or wA.shape[1] != C:
         raise ValueError("DoubleAttention weight shapes are inconsistent")
-    y = torch.empty(B, Cout, H, W, dtype=torch.float32, device=x.device)
+    y = torch.empty(B, Cout, H, W, dtype=x.dtype, device=x.device)
+    if io:
+        n = lib().mi355_double_attn16_ws_bytes(B, C, cm, cn, H, W, io)
+        ws = workspace(n, x.device)
+        check(lib().mi355_double_attn16_fwd(dptr(x), dptr(wA), dptr(bA), dptr(wB), dptr(bB), dptr(wV), dptr(bV),
+                                            dptr(wP), dptr(bP), dptr(y), B, C, cm, cn, H, W, io,
+                                            dptr(ws), ws.numel(), stream_ptr(x.device)), "mi355_double_attn16_fwd")
+        return y
     n = lib().mi355_double_attn_ws_bytes(B, C, cm, cn, H, W, _prec(precision))
     ws = workspace(n, x.device)
     check(lib().mi355_double_attn_fwd(dptr(x), dptr(wA), dptr(bA), dptr(wB), dptr(bB), dptr(wV), dptr(bV),

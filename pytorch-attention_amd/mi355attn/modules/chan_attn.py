@@ -83,7 +83,16 @@ class CBAM(nn.Module):
 
 
 class DoubleAttention(nn.Module):
-    """A2-Net double attention block; `precision` selects the MFMA operand format (None = package default)."""
+    """A2-Net double attention block; `precision` selects the MFMA operand format (None = package default).
+
+    x may be fp32, fp16 or bf16 (dense device tensor; channels_last and sliced views are made contiguous) and y has the type of x.
+    For a 16-bit x the operand format is the tensor's own type: fp16 runs the precision-1 arithmetic, bf16 the precision-2 arithmetic,
+    and a `precision` of None, 1, 2 or 3 is ignored.  Precision 0 (here, as the package default, or in a strict re-run) widens x, runs
+    the strict route and rounds the result once.  y is rounded to nearest even; an fp16 y beyond 65504 is inf, unreported, exactly
+    where ``m(x.float()).half()`` is.  Parameters may be fp32 (autocast) or 16-bit (``module.half()``).  An fp16 x can saturate the
+    fp16 operands A, G and M' (range code 8): the forward is range-guarded like an fp32 one and re-runs strict; bf16 cannot."""
+
+    _mi355_fp16_io_saturates = True          # functional.range_fallback_forward: arm and wait for an fp16 x too
 
     def __init__(self, in_channels, c_m, c_n, precision=None):
         super().__init__()
