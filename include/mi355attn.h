@@ -784,7 +784,9 @@ int mi355_vit_tail_fwd(const float* x, const float* ln1_w, const float* ln1_b, f
  * q (B,Nq,.) / k,v (B,Nkv,.) / out (B,Nq,.) are addressed as  ptr + (b*N + n)*ld + i*head_dim + j  (ld = row stride in elements,
  * >= heads*head_dim), so they may be slices of one fused projection or separate tensors.  bias (heads, Nq, Nkv) fp32 or NULL;
  * image b uses bias + b*bias_batch_stride (0 = shared).  io16 = 0: fp32 tensors; 1: tensors in the 16-bit operand type of
- * `precision` (1 fp16, 2 bf16).  head_dim in {32, 64}. */
+ * `precision` (1 fp16, 2 bf16).  head_dim in {32, 64, 128, 192, 256}; above 64 the value / output columns are processed in 64-wide
+ * slices, one workgroup per (query block, slice).  bias entries are finite or -inf (a masked_fill mask; mi355_topk_mask_fwd writes
+ * -1e30): -inf keys get weight 0 wherever they lie, and a row with no finite logit yields NaN, as torch.softmax does. */
 int mi355_sdpa_general_fwd(const void* q, const void* k, const void* v, const float* bias, void* out, int B, int num_heads, int Nq,
                            int Nkv, int head_dim, long ldq, long ldk, long ldv, long ldo, long bias_batch_stride, float scale,
                            int io16, int precision, mi355_stream_t stream);

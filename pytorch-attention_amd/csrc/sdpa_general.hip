@@ -229,14 +229,18 @@ __global__ __launch_bounds__(NWV * 64) void sdpa_stream_kernel(const sdpa_kargs<
         }
         mt = fmaxf(mt, __shfl_xor(mt, 16, WAVE));
         mt = fmaxf(mt, __shfl_xor(mt, 32, WAVE));
-        const float m_new = fmaxf(m_run, mt);                  // finite: every tile holds at least one valid key
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+        // m_new is -inf while every key seen so far carries a -inf bias (masked_fill masks): subtract 0 until a finite logit arrives, so
+        // that alpha and p are exp2(-inf) = 0 and not exp2(-inf - -inf) = NaN.  A row with no finite logit at all ends with l_run = 0
+        // and comes out NaN (0 * 1/0), as torch.softmax gives it.  For finite logits m_sub == m_new.
+        const float m_new = fmaxf(m_run, mt);
+        const float m_sub = (m_new == -INFINITY) ? 0.f : m_new;
+        const float alpha = __builtin_amdgcn_exp2f(m_run - m_sub);
         float ps = 0.f;
 #pragma unroll
         for (int kt = 0; kt < KTILE / 16; ++kt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float p = __builtin_amdgcn_exp2f(s[kt][r] - m_new);
+                const float p = __builtin_amdgcn_exp2f(s[kt][r] - m_sub);
                 s[kt][r] = p;
                 ps += p;
             }

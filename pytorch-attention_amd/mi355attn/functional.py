@@ -1591,7 +1591,9 @@ def sdpa_general(q, k, v, num_heads, scale, bias=None, precision=None, out=None)
     """softmax(q k^T * scale + bias) v for (B,Nq,C) queries and (B,Nkv,C) keys / values (views into fused projections welcome).
     fp32 tensors -> fp32 result; fp16 / bf16 tensors (the operand type of `precision`) -> same type.  bias: (heads,Nq,Nkv) or
     (B,heads,Nq,Nkv) fp32.  out: optional (B,Nq,C) destination view with unit channel stride and a dense batch axis (a channel
-    slice of a wider tensor: the C entry takes the row stride)."""
+    slice of a wider tensor: the C entry takes the row stride).  Head width C / num_heads in SDPA_WIDTHS = {32, 64, 128, 192, 256}.
+    bias entries are finite or -inf (masked_fill masks): a -inf key gets weight 0, a row with no finite logit comes out NaN, as
+    torch.softmax gives it."""
     p = _prec(precision)
     q, ldq = _rows3(q, "q")
     k, ldk = _rows3(k, "k")

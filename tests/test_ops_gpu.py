@@ -294,6 +294,9 @@ GENERAL = [  # B, Nq, Nkv, heads, d, bias
     (3, 1, 77, 2, 32, False),         # single query
     (2, 196, 49, 4, 32, True),        # CMT: relative-position term, N_kv % 4 != 0 -> scalar bias loads
     (1, 65, 64, 1, 64, True),         # exactly one key tile, N_kv % 4 == 0 -> vector bias loads
+    (2, 70, 90, 2, 128, True),        # wide heads (value / output columns in 64-wide slices): ragged, biased, scalar bias loads
+    (1, 70, 200, 2, 192, True),       # ViT's default 768 / 4 heads width, vector bias loads
+    (1, 17, 65, 1, 256, False),       # widest head, one key in the second tile
 ]
 
 
