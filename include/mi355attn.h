@@ -431,6 +431,28 @@ size_t mi355_attention_gate_workspace_bytes(int B, int H, int W);
 int mi355_attention_gate_fwd(const float* x, const float* w, const float* affine, float* y, int B, int C, int H, int W, int ksize,
                              void* workspace, size_t workspace_bytes, mi355_stream_t stream);
 
+/* CoordinateAttention, TripletAttention, AttentionGate and BAM on 16-bit activations (axis_attn_io16.hip): x and y are NCHW in ONE 16-bit
+ * type selected by `io` (1 = IEEE half, 2 = bfloat16).  Each entry is the fp32 prototype with `const void* x`, `void* y` and `int io` in
+ * front of the workspace; parameters stay fp32, and the workspaces are the fp32 entries' (mi355_axis_attn_workspace_bytes,
+ * mi355_attention_gate_workspace_bytes, mi355_bam_workspace_bytes): every intermediate is fp32 and keeps its size.  Only the kernels that
+ * touch x or y differ: they read packed 16-bit data (16-byte lanes when the row length is a multiple of 8 and x, y are 16-byte aligned,
+ * 2-byte lanes for any shape and any 2-byte-aligned pointer), compute in fp32 on the exactly widened values and round y once, to nearest
+ * even, at the store.  Shapes the fp32 entry refuses are refused with the same code.
+ * Triplet's and AttentionGate's gates lie in (0, 1): a finite x gives a finite y.  coordatt multiplies by two unbounded linear maps and
+ * bam's y = x (1 + sigmoid(.)) reaches 2|x|, so an fp16 y may overflow: y is +-inf exactly where the fp32 entry's result rounded to fp16
+ * is.  Outputs are not MFMA operands: these entries report nothing to mi355_range_status.
+ * Validation (io, then pointers, sizes and the workspace) precedes every launch: MI355_EINVAL with text in mi355_last_error.  Nothing is
+ * allocated.  mi355_gc_fwd, mi355_bam_gates_fwd and mi355_zpool_fwd have no 16-bit form. */
+int mi355_coordatt16_fwd(const void* x, const float* w1, const float* b1, const float* bn_scale, const float* bn_shift, const float* wh,
+                         const float* bh, const float* ww, const float* bw, void* y, int B, int C, int hidden, int H, int W, int io,
+                         void* workspace, size_t workspace_bytes, mi355_stream_t stream);
+int mi355_triplet16_fwd(const void* x, const float* w_ch, const float* w_cw, const float* w_hw, const float* affine, void* y, int B, int C,
+                        int H, int W, int ksize, int io, void* workspace, size_t workspace_bytes, mi355_stream_t stream);
+int mi355_attention_gate16_fwd(const void* x, const float* w, const float* affine, void* y, int B, int C, int H, int W, int ksize, int io,
+                               void* workspace, size_t workspace_bytes, mi355_stream_t stream);
+int mi355_bam16_fwd(const void* x, const float* const* params, void* y, int B, int C, int Cr, int H, int W, int dilation, int io,
+                    void* workspace, size_t workspace_bytes, mi355_stream_t stream);
+
 /*   sk        sk_module.py:41-56   u1 = relu(bn(conv3x3_grouped(x))), u2 = relu(bn(conv3x3_grouped_dilation2(x))), s = mean_hw(u1 + u2),
  *                                  z = relu(bn1d(fc s)), [a, b] = softmax over the two branches of [fc1 z, fc2 z], y = u1 a + u2 b.
  *                                  x (B,Cin,H,W), y (B,planes,H,W); planes / groups in {1,2,4,8,16}; parameters as an array of

@@ -9,12 +9,14 @@
 //     gate_conv_kernel     k x k convolution of a 2-plane map -> BatchNorm(eval, folded) -> ReLU -> sigmoid (Triplet's AttentionGate)
 //     small_conv_kernel    dilated 3x3 convolution on a handful of channels + folded BatchNorm + ReLU (BAM's spatial gate)
 //     apply_kernel<MODE>   the broadcast pass
+// The *16 entries at the end of each group take x and y in fp16 / bf16: the kernels above that touch x or y are replaced by their
+// 16-bit forms (axis_attn_io16.hip, mi355::axis16_*), everything in between runs on the fp32 kernels of this file unchanged.
 #include "common.h"
 #include "mma.h"
 
 namespace {
 
-enum { AP_GC = 0, AP_COORD = 1, AP_TRIPLET = 2, AP_BAM = 3, AP_SPATIAL = 4 };
+using mi355::AP_GC; using mi355::AP_COORD; using mi355::AP_TRIPLET; using mi355::AP_BAM; using mi355::AP_SPATIAL;   // common.h
 
 // ---- reductions over the channel axis ---------------------------------------------------------------------------------------
 // MODE 0: out[b, k, p] = bias[k] + sum_c w[k*C + c] * x[b, c, p]  for k < K (K <= KMAX)
@@ -767,6 +769,30 @@ int mi355_coordatt_fwd(const float* x, const float* w1, const float* b1, const f
     return MI355_OK;
 }
 
+// The same forward on 16-bit activations: x, y in the type `io` selects (1 = IEEE half, 2 = bfloat16), the pooled axes and a_h / a_w fp32.
+int mi355_coordatt16_fwd(const void* x, const float* w1, const float* b1, const float* bn_scale, const float* bn_shift, const float* wh,
+                         const float* bh, const float* ww, const float* bw, void* y, int B, int C, int hidden, int H, int W, int io,
+                         void* workspace, size_t workspace_bytes, mi355_stream_t stream) {
+    MI355_CHECK_ARG(io == 1 || io == 2);
+    MI355_CHECK_ARG(x && w1 && bn_scale && bn_shift && wh && ww && y && workspace && B > 0 && C > 0 && hidden > 0 && H > 0 && W > 0);
+    MI355_CHECK_ARG(workspace_bytes >= mi355_axis_attn_workspace_bytes(B, C, H, W) && aligned16(workspace));
+    if (hidden > 128) return mi355::fail(MI355_EUNSUPPORTED, "mi355_coordatt16_fwd: hidden width %d > 128", hidden);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t bc = (size_t)B * C;
+    float* ws = static_cast<float*>(workspace);
+    float* ph = ws;
+    float* pw = ph + fl(bc * H);
+    float* ah = pw + fl(bc * W);
+    float* aw = ah + fl(bc * H);
+    const int rc = mi355::axis16_plane_pool(x, io, false, ph, nullptr, pw, nullptr, (long)bc, H, W, st);
+    if (rc != MI355_OK) return rc;
+    coord_mlp_kernel<<<dim3(cdiv(H + W, 64), B), 256, (size_t)hidden * 64 * sizeof(float), st>>>(ph, pw, w1, b1, bn_scale, bn_shift, wh, bh, ww, bw,
+                                                                                                 ah, aw, C, hidden, H, W);
+    mi355::axis16_apply(AP_COORD, x, io, y, ah, aw, nullptr, B, C, H, W, st);
+    MI355_LAUNCH_CHECK();
+    return MI355_OK;
+}
+
 int mi355_triplet_fwd(const float* x, const float* w_ch, const float* w_cw, const float* w_hw, const float* affine, float* y, int B, int C,
                       int H, int W, int ksize, void* workspace, size_t workspace_bytes, mi355_stream_t stream) {
     MI355_CHECK_ARG(x && w_ch && w_cw && w_hw && affine && y && workspace && B > 0 && C > 0 && H > 0 && W > 0);
@@ -797,6 +823,35 @@ int mi355_triplet_fwd(const float* x, const float* w_ch, const float* w_cw, cons
     return MI355_OK;
 }
 
+int mi355_triplet16_fwd(const void* x, const float* w_ch, const float* w_cw, const float* w_hw, const float* affine, void* y, int B, int C,
+                        int H, int W, int ksize, int io, void* workspace, size_t workspace_bytes, mi355_stream_t stream) {
+    MI355_CHECK_ARG(io == 1 || io == 2);
+    MI355_CHECK_ARG(x && w_ch && w_cw && w_hw && affine && y && workspace && B > 0 && C > 0 && H > 0 && W > 0);
+    MI355_CHECK_ARG(ksize >= 1 && ksize <= 15 && (ksize & 1));
+    MI355_CHECK_ARG(workspace_bytes >= mi355_axis_attn_workspace_bytes(B, C, H, W) && aligned16(workspace));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t bc = (size_t)B * C;
+    const long HW = (long)H * W;
+    float* ws = static_cast<float*>(workspace);
+    float* h_mean = ws;                            // the layout of mi355_triplet_fwd
+    float* h_max = h_mean + fl(bc * H);
+    float* w_mean = h_max + fl(bc * H);
+    float* w_max = w_mean + fl(bc * W);
+    float* s_ch = w_max + fl(bc * W);
+    float* s_cw = s_ch + fl(bc * H);
+    float* zp = s_cw + fl(bc * W);
+    float* s_hw = zp + 2 * fl((size_t)B * HW);
+    const int rc = mi355::axis16_plane_pool(x, io, true, h_mean, h_max, w_mean, w_max, (long)bc, H, W, st);
+    if (rc != MI355_OK) return rc;
+    mi355::axis16_chan_reduce(x, io, 1, 1, nullptr, nullptr, zp, B, C, HW, 2, st);
+    launch_gate_conv(h_mean, h_max, (long)C * H, w_ch, affine + 0, s_ch, B, C, H, ksize, st);
+    launch_gate_conv(w_mean, w_max, (long)C * W, w_cw, affine + 2, s_cw, B, C, W, ksize, st);
+    launch_gate_conv(zp, zp + HW, 2 * HW, w_hw, affine + 4, s_hw, B, H, W, ksize, st);
+    mi355::axis16_apply(AP_TRIPLET, x, io, y, s_ch, s_cw, s_hw, B, C, H, W, st);
+    MI355_LAUNCH_CHECK();
+    return MI355_OK;
+}
+
 size_t mi355_bam_workspace_bytes(int B, int C, int Cr, int H, int W) {
     if (B <= 0 || C <= 0 || Cr <= 0 || H <= 0 || W <= 0) return 0;
     const size_t hw = (size_t)H * W;
@@ -805,11 +860,14 @@ size_t mi355_bam_workspace_bytes(int B, int C, int Cr, int H, int W) {
 
 // The two gates of BAM (ChannelGate.forward bam.py:28-33, SpatialGate.forward :53-59) without the broadcast: cg (B,C) and / or
 // sg (B,HW); either output may be null.  t0 / t1: (B,Cr,HW) scratch, mean: (B,C) scratch.
-static int bam_gates(const float* x, const float* const* p, float* mean, float* cg, float* t0, float* t1, float* sg, int B, int C, int Cr,
+// io = 0: x is fp32; 1 / 2: x is IEEE half / bfloat16 and its two sweeps run on the kernels of axis_attn_io16.hip.
+static int bam_gates(const void* xv, int io, const float* const* p, float* mean, float* cg, float* t0, float* t1, float* sg, int B, int C, int Cr,
                      int H, int W, int dilation, hipStream_t st) {
     const long HW = (long)H * W;
+    const float* x = static_cast<const float*>(xv);
     if (cg) {
-        launch_plane_dot(x, nullptr, mean, (long)B * C, C, HW, 1.0f / (float)HW, st);
+        if (io) mi355::axis16_plane_dot(xv, io, mean, (long)B * C, HW, 1.0f / (float)HW, st);
+        else    launch_plane_dot(x, nullptr, mean, (long)B * C, C, HW, 1.0f / (float)HW, st);
         bam_channel_kernel<<<B, 256, Cr * sizeof(float), st>>>(mean, p[MI355_BAM_FC1_W], p[MI355_BAM_FC1_B], p[MI355_BAM_FC2_W], p[MI355_BAM_FC2_B],
                                                                p[MI355_BAM_BN1D_SCALE], p[MI355_BAM_BN1D_SHIFT], cg, C, Cr);
     }
@@ -819,7 +877,8 @@ static int bam_gates(const float* x, const float* const* p, float* mean, float* 
         if (Cr <= 4) FN(4); else if (Cr <= 8) FN(8); else if (Cr <= 16) FN(16); else FN(32); \
     } while (0)
 #define RED(K_) launch_chan_reduce<0, K_>(x, p[MI355_BAM_CONV1_W], p[MI355_BAM_CONV1_B], t0, B, C, HW, Cr, st)
-    CR_DISPATCH(RED);
+    if (io) mi355::axis16_chan_reduce(xv, io, 0, Cr, p[MI355_BAM_CONV1_W], p[MI355_BAM_CONV1_B], t0, B, C, HW, Cr, st);
+    else    CR_DISPATCH(RED);
 #undef RED
     const dim3 grid(cdiv(cdiv(HW, Cr > 16 ? 2 : 4), 256), B);
     const bool quad = (W & 3) == 0 && (dilation & 3) == 0 && Cr <= 16;
@@ -844,7 +903,7 @@ static int bam_gates(const float* x, const float* const* p, float* mean, float* 
     return MI355_OK;
 }
 
-static int bam_check(const float* x, const float* const* p, int B, int C, int Cr, int H, int W, int dilation, const void* workspace,
+static int bam_check(const void* x, const float* const* p, int B, int C, int Cr, int H, int W, int dilation, const void* workspace,
                      size_t workspace_bytes) {
     MI355_CHECK_ARG(x && p && workspace && B > 0 && C > 0 && Cr > 0 && H > 0 && W > 0 && dilation > 0);
     for (int q = 0; q < MI355_BAM_NPARAMS; ++q) MI355_CHECK_ARG(p[q] != nullptr);
@@ -868,10 +927,29 @@ int mi355_bam_fwd(const float* x, const float* const* p, float* y, int B, int C,
     float* t0 = cg + fl((size_t)B * C);                  // (B,Cr,HW)  conv1: :55
     float* t1 = t0 + fl((size_t)B * Cr * HW);            // (B,Cr,HW)  conv2 stages: :56
     float* sg = t1 + fl((size_t)B * Cr * HW);            // (B,HW)     bn(conv3(.)): :57-58
-    if (int rc = bam_gates(x, p, mean, cg, t0, t1, sg, B, C, Cr, H, W, dilation, st)) return rc;
+    if (int rc = bam_gates(x, 0, p, mean, cg, t0, t1, sg, B, C, Cr, H, W, dilation, st)) return rc;
     ApplyArgs g{};
     g.x = x; g.y = y; g.a = cg; g.b = sg; g.C = C; g.H = H; g.W = W;
     launch_apply<AP_BAM>(g, B, st);
+    MI355_LAUNCH_CHECK();
+    return MI355_OK;
+}
+
+int mi355_bam16_fwd(const void* x, const float* const* p, void* y, int B, int C, int Cr, int H, int W, int dilation, int io, void* workspace,
+                    size_t workspace_bytes, mi355_stream_t stream) {
+    MI355_CHECK_ARG(io == 1 || io == 2);
+    MI355_CHECK_ARG(y != nullptr);
+    if (int rc = bam_check(x, p, B, C, Cr, H, W, dilation, workspace, workspace_bytes)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const long HW = (long)H * W;
+    float* ws = static_cast<float*>(workspace);
+    float* mean = ws;                                    // the layout of mi355_bam_fwd
+    float* cg = mean + fl((size_t)B * C);
+    float* t0 = cg + fl((size_t)B * C);
+    float* t1 = t0 + fl((size_t)B * Cr * HW);
+    float* sg = t1 + fl((size_t)B * Cr * HW);
+    if (int rc = bam_gates(x, io, p, mean, cg, t0, t1, sg, B, C, Cr, H, W, dilation, st)) return rc;
+    mi355::axis16_apply(AP_BAM, x, io, y, cg, sg, nullptr, B, C, H, W, st);
     MI355_LAUNCH_CHECK();
     return MI355_OK;
 }
@@ -888,7 +966,7 @@ int mi355_bam_gates_fwd(const float* x, const float* const* p, float* cg, float*
     float* mean = ws;
     float* t0 = mean + 2 * fl((size_t)B * C);
     float* t1 = t0 + fl((size_t)B * Cr * HW);
-    if (int rc = bam_gates(x, p, mean, cg, t0, t1, sg, B, C, Cr, H, W, dilation, st)) return rc;
+    if (int rc = bam_gates(x, 0, p, mean, cg, t0, t1, sg, B, C, Cr, H, W, dilation, st)) return rc;
     MI355_LAUNCH_CHECK();
     return MI355_OK;
 }
@@ -921,6 +999,23 @@ int mi355_attention_gate_fwd(const float* x, const float* w, const float* affine
     ApplyArgs g{};
     g.x = x; g.y = y; g.c = gate; g.C = C; g.H = H; g.W = W;
     launch_apply<AP_SPATIAL>(g, B, st);
+    MI355_LAUNCH_CHECK();
+    return MI355_OK;
+}
+
+int mi355_attention_gate16_fwd(const void* x, const float* w, const float* affine, void* y, int B, int C, int H, int W, int ksize, int io,
+                               void* workspace, size_t workspace_bytes, mi355_stream_t stream) {
+    MI355_CHECK_ARG(io == 1 || io == 2);
+    MI355_CHECK_ARG(x && w && affine && y && workspace && B > 0 && C > 0 && H > 0 && W > 0);
+    MI355_CHECK_ARG(ksize >= 1 && ksize <= 15 && (ksize & 1));
+    MI355_CHECK_ARG(workspace_bytes >= mi355_attention_gate_workspace_bytes(B, H, W) && aligned16(workspace));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const long HW = (long)H * W;
+    float* zp = static_cast<float*>(workspace);            // (B,2,HW)
+    float* gate = zp + 2 * fl((size_t)B * HW);             // (B,HW)
+    mi355::axis16_chan_reduce(x, io, 1, 1, nullptr, nullptr, zp, B, C, HW, 2, st);
+    launch_gate_conv(zp, zp + HW, 2 * HW, w, affine, gate, B, H, W, ksize, st);
+    mi355::axis16_apply(AP_SPATIAL, x, io, y, nullptr, nullptr, gate, B, C, H, W, st);
     MI355_LAUNCH_CHECK();
     return MI355_OK;
 }

@@ -109,6 +109,17 @@ int    double_attn_fused(const void* x, const float* wA, const float* bA, const 
 bool   double_attn_small_ok(int B, int C, int cm, int cn, int HW, int precision);
 int    double_attn_small(const void* x, const float* wA, const float* bA, const float* wB, const float* bB, const float* wV, const float* bV,
                          const float* wP, const float* bP, void* y, int B, int C, int HW, int precision, bool io16, hipStream_t st);
+// The sweeps over a 16-bit x of the axis gates (axis_attn_io16.hip; io = 1 IEEE half, 2 bfloat16), called by the *16 entries of
+// axis_attn.hip: fp32 results into the workspace, apply writes y in the I/O type.  mode of axis16_chan_reduce: 0 = 1x1 conv to K <= kmax
+// planes (kmax 4 / 8 / 16 / 32), 1 = mean and max; axis16_plane_pool returns what launch_plane_pool returns for the shape.
+enum { AP_GC = 0, AP_COORD = 1, AP_TRIPLET = 2, AP_BAM = 3, AP_SPATIAL = 4 };      // the broadcast passes of the axis gates
+void axis16_chan_reduce(const void* x, int io, int mode, int kmax, const float* w, const float* bias, float* out, int B, int C, long HW, int K,
+                        hipStream_t st);
+int  axis16_plane_pool(const void* x, int io, bool with_max, float* h_mean, float* h_max, float* w_mean, float* w_max, long planes, int H, int W,
+                       hipStream_t st);
+void axis16_plane_dot(const void* x, int io, float* out, long planes, long HW, float scale, hipStream_t st);
+void axis16_apply(int mode, const void* x, int io, void* y, const float* a, const float* b, const float* c, int B, int C, int H, int W,
+                  hipStream_t st);
 // GEMM engine (gemm.hip), shared by the other translation units.  NT: B is (N,K) K-contiguous; KN: B is (K,N) N-contiguous.
 int gemm_nt(const float* A, const float* B, const float* bias, const float* gamma, const float* resid, float* C, int M, int N,
             int K, int lda, int ldb, int ldc, int act, int precision, hipStream_t st);

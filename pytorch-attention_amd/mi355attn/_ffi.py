@@ -112,6 +112,10 @@ SIGNATURES = {
     "mi355_zpool_fwd": (c_int, [c_vp, c_vp] + [c_int] * 4 + [c_vp]),
     "mi355_attention_gate_workspace_bytes": (ctypes.c_size_t, [c_int] * 3),
     "mi355_attention_gate_fwd": (c_int, [c_vp] * 4 + [c_int] * 5 + [c_vp, ctypes.c_size_t, c_vp]),
+    "mi355_coordatt16_fwd": (c_int, [c_vp] * 10 + [c_int] * 6 + [c_vp, c_size, c_vp]),
+    "mi355_triplet16_fwd": (c_int, [c_vp] * 6 + [c_int] * 6 + [c_vp, c_size, c_vp]),
+    "mi355_attention_gate16_fwd": (c_int, [c_vp] * 4 + [c_int] * 6 + [c_vp, c_size, c_vp]),
+    "mi355_bam16_fwd": (c_int, [c_vp] * 3 + [c_int] * 7 + [c_vp, c_size, c_vp]),
     "mi355_ln_fold_stats_bytes": (ctypes.c_size_t, [c_int] * 2),
     "mi355_ln_center16_fwd": (c_int, [c_vp] * 4 + [c_int, c_int, c_float, c_int, c_vp]),
     "mi355_ln_finalize_fwd": (c_int, [c_vp] * 5 + [c_int, c_int, c_float, c_float, c_int, c_vp, c_vp]),
@@ -238,7 +242,7 @@ def require_device_f32(t, name):
     if t.dtype != torch.float32:
         raise TypeError(f"{name}: expected float32, got {t.dtype} (16-bit activations are accepted by SELayer, ECALayer, CBAM, "
                         "ChannelAttention, SpatialAttention, SELayerBias, SELayerBias4, SELayerHidden, SqueezeExcite, simam_module, SRM, "
-                        "GaussianGCT, LCT, GCT and DoubleAttention only)")
+                        "GaussianGCT, LCT, GCT, DoubleAttention, CoordinateAttention, TripletAttention, AttentionGate and BAM only)")
     if t.requires_grad and torch.is_grad_enabled():
         _warn_no_autograd()
     return t if t.is_contiguous() else t.contiguous()

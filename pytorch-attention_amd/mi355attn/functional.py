@@ -298,30 +298,38 @@ def bn_fold(bn, pre_bias=None):
     """(scale, shift) of an eval-mode BatchNorm, optionally absorbing the bias of the layer in front of it:
     bn(z + pre_bias) = z * scale + shift.  Cached with the BatchNorm (and the bias) like the other derived tensors."""
     def build():
-        s = bn.weight.detach() / torch.sqrt(bn.running_var.detach() + bn.eps)
-        t = bn.bias.detach() - bn.running_mean.detach() * s
+        # folded in fp32 from the widened values: a .half() / .bfloat16() module folds to the bits of its .float() copy (for fp32
+        # parameters .float() is the tensor itself)
+        s = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
+        t = bn.bias.detach().float() - bn.running_mean.detach().float() * s
         if pre_bias is not None:
-            t = t + s * pre_bias.detach().reshape(-1)
-        return s.float().contiguous(), t.float().contiguous()
+            t = t + s * pre_bias.detach().float().reshape(-1)
+        return s.contiguous(), t.contiguous()
 
     anchors = (bn,) if pre_bias is None else (bn, pre_bias)
     tag = _bn_tag(bn) + (() if pre_bias is None else (pre_bias._version, pre_bias.data_ptr()))
     return _derived_get(anchors, ("bnfold",), tag, build)
 
 
-def _axis(x):
-    x = require_device_f32(x, "x")
+def _axis(x, io16=False):
+    """Common prologue of the axis gates: (x, io, y, workspace, shape).  io16: x may be fp16 / bf16 (io = its precision code) besides fp32."""
+    x, io = _ffi.require_device_io(x, "x") if io16 else (require_device_f32(x, "x"), 0)
     B, C, H, W = x.shape
     ws = workspace(lib().mi355_axis_attn_workspace_bytes(B, C, H, W), x.device)
-    return x, torch.empty_like(x), ws, (B, C, H, W)
+    return x, io, torch.empty_like(x), ws, (B, C, H, W)
 
 
 def _flat(t, name, *shape):
     return require_device_f32(t, name).reshape(*shape) if t is not None else None
 
 
+def _flat_io(io, t, name, *shape):
+    """_flat for the gates that take 16-bit activations: on the 16-bit path the parameter may be 16-bit too (_p)."""
+    return _p(io, t, name).reshape(*shape) if t is not None else None
+
+
 def gc_forward(x, conv_w, conv_b, w1, b1, ln_w, ln_b, ln_eps, w2, b2):
-    x, y, ws, (B, C, H, W) = _axis(x)
+    x, _, y, ws, (B, C, H, W) = _axis(x)
     Cr = w1.shape[0]
     check(lib().mi355_gc_fwd(dptr(x), dptr(_flat(conv_w, "conv.weight", C)), dptr(_flat(conv_b, "conv.bias", 1)),
                              dptr(_flat(w1, "transform.0.weight", Cr, C)), dptr(_flat(b1, "transform.0.bias", Cr)),
@@ -332,37 +340,56 @@ def gc_forward(x, conv_w, conv_b, w1, b1, ln_w, ln_b, ln_eps, w2, b2):
 
 
 def coordatt_forward(x, w1, b1, bn_scale, bn_shift, wh, bh, ww, bw):
-    x, y, ws, (B, C, H, W) = _axis(x)
+    """x fp32 / fp16 / bf16 (output in the same type); on the 16-bit path the parameters may be 16-bit too (param32)."""
+    x, io, y, ws, (B, C, H, W) = _axis(x, io16=True)
     hid = w1.shape[0]
-    check(lib().mi355_coordatt_fwd(dptr(x), dptr(_flat(w1, "conv1.weight", hid, C)), dptr(_flat(b1, "conv1.bias", hid)),
-                                   dptr(_flat(bn_scale, "bn1 scale", hid)), dptr(_flat(bn_shift, "bn1 shift", hid)),
-                                   dptr(_flat(wh, "conv_h.weight", C, hid)), dptr(_flat(bh, "conv_h.bias", C)),
-                                   dptr(_flat(ww, "conv_w.weight", C, hid)), dptr(_flat(bw, "conv_w.bias", C)), dptr(y),
-                                   B, C, hid, H, W, dptr(ws), ws.numel(), stream_ptr(x.device)), "mi355_coordatt_fwd")
+    ps = [_flat_io(io, t, n, *shape) for t, n, shape in (
+        (w1, "conv1.weight", (hid, C)), (b1, "conv1.bias", (hid,)), (bn_scale, "bn1 scale", (hid,)), (bn_shift, "bn1 shift", (hid,)),
+        (wh, "conv_h.weight", (C, hid)), (bh, "conv_h.bias", (C,)), (ww, "conv_w.weight", (C, hid)), (bw, "conv_w.bias", (C,)))]
+    ptrs = [dptr(t) for t in ps]        # `ps` keeps the tensors (a contiguous copy may be a temporary) alive over the call
+    if io:
+        check(lib().mi355_coordatt16_fwd(dptr(x), *ptrs, dptr(y), B, C, hid, H, W, io, dptr(ws), ws.numel(), stream_ptr(x.device)),
+              "mi355_coordatt16_fwd")
+    else:
+        check(lib().mi355_coordatt_fwd(dptr(x), *ptrs, dptr(y), B, C, hid, H, W, dptr(ws), ws.numel(), stream_ptr(x.device)),
+              "mi355_coordatt_fwd")
     return y
 
 
 def triplet_forward(x, w_ch, w_cw, w_hw, affine, ksize):
-    x, y, ws, (B, C, H, W) = _axis(x)
+    """x fp32 / fp16 / bf16 (output in the same type); on the 16-bit path the parameters may be 16-bit too (param32)."""
+    x, io, y, ws, (B, C, H, W) = _axis(x, io16=True)
     n = 2 * ksize * ksize
-    check(lib().mi355_triplet_fwd(dptr(x), dptr(_flat(w_ch, "ch.conv.conv.weight", n)), dptr(_flat(w_cw, "cw.conv.conv.weight", n)),
-                                  dptr(_flat(w_hw, "hw.conv.conv.weight", n)), dptr(_flat(affine, "gate affine", 6)), dptr(y),
-                                  B, C, H, W, int(ksize), dptr(ws), ws.numel(), stream_ptr(x.device)), "mi355_triplet_fwd")
+    ps = [_flat_io(io, w_ch, "ch.conv.conv.weight", n), _flat_io(io, w_cw, "cw.conv.conv.weight", n),
+          _flat_io(io, w_hw, "hw.conv.conv.weight", n), _flat_io(io, affine, "gate affine", 6)]
+    ptrs = [dptr(t) for t in ps]
+    if io:
+        check(lib().mi355_triplet16_fwd(dptr(x), *ptrs, dptr(y), B, C, H, W, int(ksize), io, dptr(ws), ws.numel(), stream_ptr(x.device)),
+              "mi355_triplet16_fwd")
+    else:
+        check(lib().mi355_triplet_fwd(dptr(x), *ptrs, dptr(y), B, C, H, W, int(ksize), dptr(ws), ws.numel(), stream_ptr(x.device)),
+              "mi355_triplet_fwd")
     return y
 
 
 def bam_forward(x, params, Cr, dilation):
-    """`params`: the MI355_BAM_NPARAMS tensors in the order of the enum in include/mi355attn.h."""
-    x = require_device_f32(x, "x")
+    """`params`: the MI355_BAM_NPARAMS tensors in the order of the enum in include/mi355attn.h (fp32; on the 16-bit path
+    also 16-bit, param32).
+    x fp32 / fp16 / bf16 (output in the same type)."""
+    x, io = _ffi.require_device_io(x, "x")
     B, C, H, W = x.shape
     if len(params) != 16:
         raise ValueError("bam_forward: expected 16 parameter tensors")
-    ps = [require_device_f32(t, f"bam parameter {i}") for i, t in enumerate(params)]
+    ps = [_p(io, t, f"bam parameter {i}") for i, t in enumerate(params)]
     table = (ctypes.c_void_p * 16)(*[t.data_ptr() for t in ps])
     ws = workspace(lib().mi355_bam_workspace_bytes(B, C, Cr, H, W), x.device)
     y = torch.empty_like(x)
-    check(lib().mi355_bam_fwd(dptr(x), ctypes.cast(table, ctypes.c_void_p), dptr(y), B, C, Cr, H, W, int(dilation), dptr(ws), ws.numel(),
-                              stream_ptr(x.device)), "mi355_bam_fwd")
+    if io:
+        check(lib().mi355_bam16_fwd(dptr(x), ctypes.cast(table, ctypes.c_void_p), dptr(y), B, C, Cr, H, W, int(dilation), io, dptr(ws),
+                                    ws.numel(), stream_ptr(x.device)), "mi355_bam16_fwd")
+    else:
+        check(lib().mi355_bam_fwd(dptr(x), ctypes.cast(table, ctypes.c_void_p), dptr(y), B, C, Cr, H, W, int(dilation), dptr(ws), ws.numel(),
+                                  stream_ptr(x.device)), "mi355_bam_fwd")
     return y
 
 
@@ -392,17 +419,22 @@ def zpool(x):
 
 
 def attention_gate(x, w, affine, ksize):
-    """x * sigmoid(relu(bn(conv_kxk(zpool(x))))): w (2,k,k) conv weight, affine (2,) = folded BatchNorm scale / shift."""
-    x = require_device_f32(x, "x")
+    """x * sigmoid(relu(bn(conv_kxk(zpool(x))))): w (2,k,k) conv weight, affine (2,) = folded BatchNorm scale / shift.
+    x fp32 / fp16 / bf16 (output in the same type); on the 16-bit path the parameters may be 16-bit too (param32)."""
+    x, io = _ffi.require_device_io(x, "x")
     B, C, H, W = x.shape
-    w = require_device_f32(w, "w").reshape(-1)
-    affine = require_device_f32(affine, "affine").reshape(-1)
+    w = _p(io, w, "w").reshape(-1)
+    affine = _p(io, affine, "affine").reshape(-1)
     if w.numel() != 2 * ksize * ksize or affine.numel() != 2:
         raise ValueError("attention_gate: w must be (1,2,k,k) and affine (2,)")
     ws = workspace(lib().mi355_attention_gate_workspace_bytes(B, H, W), x.device)
     y = torch.empty_like(x)
-    check(lib().mi355_attention_gate_fwd(dptr(x), dptr(w), dptr(affine), dptr(y), B, C, H, W, int(ksize), dptr(ws), ws.numel(),
-                                         stream_ptr(x.device)), "mi355_attention_gate_fwd")
+    if io:
+        check(lib().mi355_attention_gate16_fwd(dptr(x), dptr(w), dptr(affine), dptr(y), B, C, H, W, int(ksize), io, dptr(ws), ws.numel(),
+                                               stream_ptr(x.device)), "mi355_attention_gate16_fwd")
+    else:
+        check(lib().mi355_attention_gate_fwd(dptr(x), dptr(w), dptr(affine), dptr(y), B, C, H, W, int(ksize), dptr(ws), ws.numel(),
+                                             stream_ptr(x.device)), "mi355_attention_gate_fwd")
     return y
 
 

@@ -11,6 +11,10 @@ Same constructor signatures, submodule names and state_dict keys as the referenc
 statistics); calling forward() in training mode raises.  The helper classes that only exist as parameter containers in the
 reference (BasicConv2d, ZPool, AttentionGate, ChannelGate, SpatialGate) keep their names and parameters; the fused forward lives in
 the top-level module.
+
+CoordinateAttention, TripletAttention, AttentionGate and BAM also take an fp16 / bf16 device tensor and return the same type
+(csrc/axis_attn_io16.hip: 16-bit sweeps over x and y, fp32 gates in between); their parameters may then be 16-bit too.  GCModule and the
+parameter-container helpers (ZPool, BasicConv2d, ChannelGate, SpatialGate) are fp32 only.
 """
 import torch
 from torch import nn
@@ -177,7 +181,7 @@ class SpatialGate(nn.Module):
         s, t = F.bn_fold(self.bn, self.conv3.bias)
         tag = (id(s), self.conv3.weight._version, self.conv3.weight.data_ptr())
         w3, b3 = F._derived_get((self.conv3.weight, self.bn), ("bam_conv3",), tag,
-                                lambda: ((self.conv3.weight.detach().reshape(-1) * s).contiguous(), t))
+                                lambda: ((self.conv3.weight.detach().float().reshape(-1) * s).contiguous(), t))   # fp32, as bn_fold
         return [self.conv1.weight, self.conv1.bias, self.conv2[0].weight, d1[0], d1[1], self.conv2[3].weight, d2[0], d2[1], w3, b3]
 
     def forward(self, x):
