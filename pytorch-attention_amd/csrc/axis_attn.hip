@@ -9,8 +9,10 @@
 //     gate_conv_kernel     k x k convolution of a 2-plane map -> BatchNorm(eval, folded) -> ReLU -> sigmoid (Triplet's AttentionGate)
 //     small_conv_kernel    dilated 3x3 convolution on a handful of channels + folded BatchNorm + ReLU (BAM's spatial gate)
 //     apply_kernel<MODE>   the broadcast pass
-// The *16 entries at the end of each group take x and y in fp16 / bf16: the kernels above that touch x or y are replaced by their
-// 16-bit forms (axis_attn_io16.hip, mi355::axis16_*), everything in between runs on the fp32 kernels of this file unchanged.
+// The *16 entries take x and y in fp16 / bf16.  Each gate has ONE host body (coordatt_run, triplet_run, bam_run, attention_gate_run) with
+// the workspace layout and the launch order; both of its entries call it, the fp32 entry with io = 0.  The body reaches x and y through
+// four io-switching launchers (chan_reduce, plane_pool, plane_dot, apply): io = 0 runs the kernels above, io = 1 / 2 their 16-bit forms
+// (axis_attn_io16.hip, mi355::axis16_*).  Everything in between runs on the fp32 kernels of this file in either case.
 #include "common.h"
 #include "mma.h"
 
@@ -710,7 +712,144 @@ __global__ __launch_bounds__(256) void small_conv_quad_kernel(const float* __res
         }
 }
 
+// ---- the sweeps over x (and the store of y) in either I/O type ------------------------------------------------------------------
+// io = 0: x / y are fp32 and the launchers above run; io = 1 / 2: x / y are IEEE half / bfloat16 and the 16-bit forms in
+// axis_attn_io16.hip (mi355::axis16_*) run.  Everything the sweeps write besides y is fp32 in either case.
+template <int MODE, int KMAX>
+void chan_reduce(const void* x, int io, const float* w, const float* bias, float* out, int B, int C, long HW, int K, hipStream_t st) {
+    if (io) mi355::axis16_chan_reduce(x, io, MODE, KMAX, w, bias, out, B, C, HW, K, st);
+    else    launch_chan_reduce<MODE, KMAX>(static_cast<const float*>(x), w, bias, out, B, C, HW, K, st);
+}
+
+template <bool WITH_MAX>
+int plane_pool(const void* x, int io, float* h_mean, float* h_max, float* w_mean, float* w_max, long planes, int H, int W, hipStream_t st) {
+    if (io) return mi355::axis16_plane_pool(x, io, WITH_MAX, h_mean, h_max, w_mean, w_max, planes, H, W, st);
+    return launch_plane_pool<WITH_MAX>(static_cast<const float*>(x), h_mean, h_max, w_mean, w_max, planes, H, W, st);
+}
+
+void plane_dot(const void* x, int io, const float* v, float* out, long planes, int C, long HW, float scale, hipStream_t st) {
+    if (io) mi355::axis16_plane_dot(x, io, out, planes, HW, scale, st);          // plain sums only: v is null on the 16-bit path
+    else    launch_plane_dot(static_cast<const float*>(x), v, out, planes, C, HW, scale, st);
+}
+
+template <int MODE>
+void apply(const void* x, int io, void* y, const float* a, const float* b, const float* c, int B, int C, int H, int W, hipStream_t st) {
+    if (io) { mi355::axis16_apply(MODE, x, io, y, a, b, c, B, C, H, W, st); return; }
+    ApplyArgs g{};
+    g.x = static_cast<const float*>(x); g.y = static_cast<float*>(y); g.a = a; g.b = b; g.c = c; g.C = C; g.H = H; g.W = W;
+    launch_apply<MODE>(g, B, st);
+}
+
+// BAM's dilated convolution: the reduced width Cr <= 32 picks the 4 / 8 / 16 / 32-wide instantiation, the quad form where it applies
+void launch_small_conv(const float* in, const float* w, const float* sc, const float* sh, float* out, int B, int Cr, int H, int W, int dil,
+                       hipStream_t st) {
+    const size_t wrow = (size_t)Cr * 9 * sizeof(float);          // LDS: wrow * CMAX
+    if ((W & 3) == 0 && (dil & 3) == 0 && Cr <= 16) {
+        const dim3 grid(cdiv((long)H * (W >> 2), 256), B);
+        if (Cr <= 4)      small_conv_quad_kernel<4><<<grid, 256, wrow * 4, st>>>(in, w, sc, sh, out, Cr, H, W, dil);
+        else if (Cr <= 8) small_conv_quad_kernel<8><<<grid, 256, wrow * 8, st>>>(in, w, sc, sh, out, Cr, H, W, dil);
+        else              small_conv_quad_kernel<16><<<grid, 256, wrow * 16, st>>>(in, w, sc, sh, out, Cr, H, W, dil);
+        return;
+    }
+    const dim3 grid(cdiv(cdiv((long)H * W, Cr > 16 ? 2 : 4), 256), B);
+    if (Cr <= 4)       small_conv_kernel<4><<<grid, 256, wrow * 4, st>>>(in, w, sc, sh, out, Cr, H, W, dil);
+    else if (Cr <= 8)  small_conv_kernel<8><<<grid, 256, wrow * 8, st>>>(in, w, sc, sh, out, Cr, H, W, dil);
+    else if (Cr <= 16) small_conv_kernel<16><<<grid, 256, wrow * 16, st>>>(in, w, sc, sh, out, Cr, H, W, dil);
+    else               small_conv_kernel<32><<<grid, 256, wrow * 32, st>>>(in, w, sc, sh, out, Cr, H, W, dil);
+}
+
 size_t fl(size_t n) { return (n + 63) & ~(size_t)63; }           // 256-byte aligned sub-buffers (in floats)
+
+// ---- one body per gate: the workspace layout and the launch sequence, for x / y in the type `io` selects ------------------------------
+// Both ABI entries of a gate expand its *_FWD(io) macro below: validation, the body (io = 0 from the fp32 entry) and the launch check.
+// A macro, not a function, because MI355_CHECK_ARG and MI355_LAUNCH_CHECK print __func__ and the texts name the entry.
+int coordatt_run(const void* x, int io, const float* w1, const float* b1, const float* bn_scale, const float* bn_shift, const float* wh,
+                 const float* bh, const float* ww, const float* bw, void* y, int B, int C, int hidden, int H, int W, void* workspace,
+                 hipStream_t st) {
+    const size_t bc = (size_t)B * C;
+    float* ws = static_cast<float*>(workspace);
+    float* ph = ws;                       // (B,C,H)  pool_h: coordatten.py:33
+    float* pw = ph + fl(bc * H);          // (B,C,W)  pool_w: :34
+    float* ah = pw + fl(bc * W);          // (B,C,H)  conv_h(...): :41
+    float* aw = ah + fl(bc * H);          // (B,C,W)  conv_w(...): :42
+    if (int rc = plane_pool<false>(x, io, ph, nullptr, pw, nullptr, (long)bc, H, W, st)) return rc;
+    coord_mlp_kernel<<<dim3(cdiv(H + W, 64), B), 256, (size_t)hidden * 64 * sizeof(float), st>>>(ph, pw, w1, b1, bn_scale, bn_shift, wh, bh, ww, bw,
+                                                                                                 ah, aw, C, hidden, H, W);
+    apply<AP_COORD>(x, io, y, ah, aw, nullptr, B, C, H, W, st);
+    return MI355_OK;
+}
+
+int triplet_run(const void* x, int io, const float* w_ch, const float* w_cw, const float* w_hw, const float* affine, void* y, int B, int C,
+                int H, int W, int ksize, void* workspace, hipStream_t st) {
+    const size_t bc = (size_t)B * C;
+    const long HW = (long)H * W;
+    float* ws = static_cast<float*>(workspace);
+    float* h_mean = ws;                            // ZPool over w of x.permute(0,3,1,2): (B,C,H) mean / max   (triplet_attention.py:59, :33-36)
+    float* h_max = h_mean + fl(bc * H);
+    float* w_mean = h_max + fl(bc * H);            // ZPool over h of x.permute(0,2,1,3): (B,C,W)              (:60)
+    float* w_max = w_mean + fl(bc * W);
+    float* s_ch = w_max + fl(bc * W);              // gates
+    float* s_cw = s_ch + fl(bc * H);
+    float* zp = s_cw + fl(bc * W);                 // ZPool over c: (B,2,HW)                                   (:61)
+    float* s_hw = zp + 2 * fl((size_t)B * HW);
+    if (int rc = plane_pool<true>(x, io, h_mean, h_max, w_mean, w_max, (long)bc, H, W, st)) return rc;
+    chan_reduce<1, 1>(x, io, nullptr, nullptr, zp, B, C, HW, 2, st);
+    launch_gate_conv(h_mean, h_max, (long)C * H, w_ch, affine + 0, s_ch, B, C, H, ksize, st);
+    launch_gate_conv(w_mean, w_max, (long)C * W, w_cw, affine + 2, s_cw, B, C, W, ksize, st);
+    launch_gate_conv(zp, zp + HW, 2 * HW, w_hw, affine + 4, s_hw, B, H, W, ksize, st);
+    apply<AP_TRIPLET>(x, io, y, s_ch, s_cw, s_hw, B, C, H, W, st);
+    return MI355_OK;
+}
+
+// The two gates of BAM (ChannelGate.forward bam.py:28-33, SpatialGate.forward :53-59) without the broadcast: cg (B,C) and / or
+// sg (B,HW); either output may be null.  t0 / t1: (B,Cr,HW) scratch, mean: (B,C) scratch.
+void bam_gates(const void* x, int io, const float* const* p, float* mean, float* cg, float* t0, float* t1, float* sg, int B, int C, int Cr,
+               int H, int W, int dilation, hipStream_t st) {
+    const long HW = (long)H * W;
+    if (cg) {
+        plane_dot(x, io, nullptr, mean, (long)B * C, C, HW, 1.0f / (float)HW, st);
+        bam_channel_kernel<<<B, 256, Cr * sizeof(float), st>>>(mean, p[MI355_BAM_FC1_W], p[MI355_BAM_FC1_B], p[MI355_BAM_FC2_W], p[MI355_BAM_FC2_B],
+                                                               p[MI355_BAM_BN1D_SCALE], p[MI355_BAM_BN1D_SHIFT], cg, C, Cr);
+    }
+    if (!sg) return;
+    const float *w1 = p[MI355_BAM_CONV1_W], *b1 = p[MI355_BAM_CONV1_B];
+    if (Cr <= 4)       chan_reduce<0, 4>(x, io, w1, b1, t0, B, C, HW, Cr, st);
+    else if (Cr <= 8)  chan_reduce<0, 8>(x, io, w1, b1, t0, B, C, HW, Cr, st);
+    else if (Cr <= 16) chan_reduce<0, 16>(x, io, w1, b1, t0, B, C, HW, Cr, st);
+    else               chan_reduce<0, 32>(x, io, w1, b1, t0, B, C, HW, Cr, st);
+    launch_small_conv(t0, p[MI355_BAM_DCONV1_W], p[MI355_BAM_DCONV1_SCALE], p[MI355_BAM_DCONV1_SHIFT], t1, B, Cr, H, W, dilation, st);
+    launch_small_conv(t1, p[MI355_BAM_DCONV2_W], p[MI355_BAM_DCONV2_SCALE], p[MI355_BAM_DCONV2_SHIFT], t0, B, Cr, H, W, dilation, st);
+    launch_chan_reduce<0, 1>(t0, p[MI355_BAM_CONV3_W], p[MI355_BAM_CONV3_B], sg, B, Cr, HW, 1, st);
+}
+
+struct BamWs { float *mean, *cg, *t0, *t1, *sg; };
+BamWs bam_carve(void* workspace, int B, int C, int Cr, int H, int W) {
+    const long HW = (long)H * W;
+    BamWs w;
+    w.mean = static_cast<float*>(workspace);             // (B,C)      avgpool: bam.py:30
+    w.cg = w.mean + fl((size_t)B * C);                   // (B,C)      bn(mlp(.)): :31-32
+    w.t0 = w.cg + fl((size_t)B * C);                     // (B,Cr,HW)  conv1: :55
+    w.t1 = w.t0 + fl((size_t)B * Cr * HW);               // (B,Cr,HW)  conv2 stages: :56
+    w.sg = w.t1 + fl((size_t)B * Cr * HW);               // (B,HW)     bn(conv3(.)): :57-58
+    return w;
+}
+
+void bam_run(const void* x, int io, const float* const* p, void* y, int B, int C, int Cr, int H, int W, int dilation, void* workspace,
+             hipStream_t st) {
+    const BamWs w = bam_carve(workspace, B, C, Cr, H, W);
+    bam_gates(x, io, p, w.mean, w.cg, w.t0, w.t1, w.sg, B, C, Cr, H, W, dilation, st);
+    apply<AP_BAM>(x, io, y, w.cg, w.sg, nullptr, B, C, H, W, st);
+}
+
+void attention_gate_run(const void* x, int io, const float* w, const float* affine, void* y, int B, int C, int H, int W, int ksize,
+                        void* workspace, hipStream_t st) {
+    const long HW = (long)H * W;
+    float* zp = static_cast<float*>(workspace);            // (B,2,HW)
+    float* gate = zp + 2 * fl((size_t)B * HW);             // (B,HW)
+    chan_reduce<1, 1>(x, io, nullptr, nullptr, zp, B, C, HW, 2, st);
+    launch_gate_conv(zp, zp + HW, 2 * HW, w, affine, gate, B, H, W, ksize, st);
+    apply<AP_SPATIAL>(x, io, y, nullptr, nullptr, gate, B, C, H, W, st);
+}
 
 }  // namespace
 
@@ -738,35 +877,26 @@ int mi355_gc_fwd(const float* x, const float* conv_w, const float* conv_b, const
     launch_chan_reduce<0, 1>(x, conv_w, conv_b, attn, B, C, HW, 1, st);
     launch_plane_dot(x, attn, ctx, (long)B * C, C, HW, 1.0f, st);
     gc_transform_kernel<<<B, 256, Cr * sizeof(float), st>>>(ctx, w1, b1, ln_w, ln_b, w2, b2, tvec, C, Cr, ln_eps);
-    ApplyArgs g{};
-    g.x = x; g.y = y; g.a = tvec; g.C = C; g.H = H; g.W = W;
-    launch_apply<AP_GC>(g, B, st);
+    apply<AP_GC>(x, 0, y, tvec, nullptr, nullptr, B, C, H, W, st);
     MI355_LAUNCH_CHECK();
     return MI355_OK;
 }
 
+#define COORDATT_FWD(io_)                                                                                                                    \
+    do {                                                                                                                                     \
+        MI355_CHECK_ARG(x && w1 && bn_scale && bn_shift && wh && ww && y && workspace && B > 0 && C > 0 && hidden > 0 && H > 0 && W > 0);    \
+        MI355_CHECK_ARG(workspace_bytes >= mi355_axis_attn_workspace_bytes(B, C, H, W) && aligned16(workspace));                             \
+        if (hidden > 128) return mi355::fail(MI355_EUNSUPPORTED, "%s: hidden width %d > 128", __func__, hidden);                             \
+        if (int rc_ = coordatt_run(x, io_, w1, b1, bn_scale, bn_shift, wh, bh, ww, bw, y, B, C, hidden, H, W, workspace, static_cast<hipStream_t>(stream)))\
+            return rc_;                                                                                                                      \
+        MI355_LAUNCH_CHECK();                                                                                                                \
+        return MI355_OK;                                                                                                                     \
+    } while (0)
+
 int mi355_coordatt_fwd(const float* x, const float* w1, const float* b1, const float* bn_scale, const float* bn_shift, const float* wh,
                        const float* bh, const float* ww, const float* bw, float* y, int B, int C, int hidden, int H, int W,
                        void* workspace, size_t workspace_bytes, mi355_stream_t stream) {
-    MI355_CHECK_ARG(x && w1 && bn_scale && bn_shift && wh && ww && y && workspace && B > 0 && C > 0 && hidden > 0 && H > 0 && W > 0);
-    MI355_CHECK_ARG(workspace_bytes >= mi355_axis_attn_workspace_bytes(B, C, H, W) && aligned16(workspace));
-    if (hidden > 128) return mi355::fail(MI355_EUNSUPPORTED, "mi355_coordatt_fwd: hidden width %d > 128", hidden);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t bc = (size_t)B * C;
-    float* ws = static_cast<float*>(workspace);
-    float* ph = ws;                       // (B,C,H)  pool_h: coordatten.py:33
-    float* pw = ph + fl(bc * H);          // (B,C,W)  pool_w: :34
-    float* ah = pw + fl(bc * W);          // (B,C,H)  conv_h(...): :41
-    float* aw = ah + fl(bc * H);          // (B,C,W)  conv_w(...): :42
-    const int rc = launch_plane_pool<false>(x, ph, nullptr, pw, nullptr, (long)bc, H, W, st);
-    if (rc != MI355_OK) return rc;
-    coord_mlp_kernel<<<dim3(cdiv(H + W, 64), B), 256, (size_t)hidden * 64 * sizeof(float), st>>>(ph, pw, w1, b1, bn_scale, bn_shift, wh, bh, ww, bw,
-                                                                                                 ah, aw, C, hidden, H, W);
-    ApplyArgs g{};
-    g.x = x; g.y = y; g.a = ah; g.b = aw; g.C = C; g.H = H; g.W = W;
-    launch_apply<AP_COORD>(g, B, st);
-    MI355_LAUNCH_CHECK();
-    return MI355_OK;
+    COORDATT_FWD(0);
 }
 
 // The same forward on 16-bit activations: x, y in the type `io` selects (1 = IEEE half, 2 = bfloat16), the pooled axes and a_h / a_w fp32.
@@ -774,82 +904,28 @@ int mi355_coordatt16_fwd(const void* x, const float* w1, const float* b1, const 
                          const float* bh, const float* ww, const float* bw, void* y, int B, int C, int hidden, int H, int W, int io,
                          void* workspace, size_t workspace_bytes, mi355_stream_t stream) {
     MI355_CHECK_ARG(io == 1 || io == 2);
-    MI355_CHECK_ARG(x && w1 && bn_scale && bn_shift && wh && ww && y && workspace && B > 0 && C > 0 && hidden > 0 && H > 0 && W > 0);
-    MI355_CHECK_ARG(workspace_bytes >= mi355_axis_attn_workspace_bytes(B, C, H, W) && aligned16(workspace));
-    if (hidden > 128) return mi355::fail(MI355_EUNSUPPORTED, "mi355_coordatt16_fwd: hidden width %d > 128", hidden);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t bc = (size_t)B * C;
-    float* ws = static_cast<float*>(workspace);
-    float* ph = ws;
-    float* pw = ph + fl(bc * H);
-    float* ah = pw + fl(bc * W);
-    float* aw = ah + fl(bc * H);
-    const int rc = mi355::axis16_plane_pool(x, io, false, ph, nullptr, pw, nullptr, (long)bc, H, W, st);
-    if (rc != MI355_OK) return rc;
-    coord_mlp_kernel<<<dim3(cdiv(H + W, 64), B), 256, (size_t)hidden * 64 * sizeof(float), st>>>(ph, pw, w1, b1, bn_scale, bn_shift, wh, bh, ww, bw,
-                                                                                                 ah, aw, C, hidden, H, W);
-    mi355::axis16_apply(AP_COORD, x, io, y, ah, aw, nullptr, B, C, H, W, st);
-    MI355_LAUNCH_CHECK();
-    return MI355_OK;
+    COORDATT_FWD(io);
 }
+
+#define TRIPLET_FWD(io_)                                                                                                                     \
+    do {                                                                                                                                     \
+        MI355_CHECK_ARG(x && w_ch && w_cw && w_hw && affine && y && workspace && B > 0 && C > 0 && H > 0 && W > 0);                          \
+        MI355_CHECK_ARG(ksize >= 1 && ksize <= 15 && (ksize & 1));                                                                           \
+        MI355_CHECK_ARG(workspace_bytes >= mi355_axis_attn_workspace_bytes(B, C, H, W) && aligned16(workspace));                             \
+        if (int rc_ = triplet_run(x, io_, w_ch, w_cw, w_hw, affine, y, B, C, H, W, ksize, workspace, static_cast<hipStream_t>(stream))) return rc_;\
+        MI355_LAUNCH_CHECK();                                                                                                                \
+        return MI355_OK;                                                                                                                     \
+    } while (0)
 
 int mi355_triplet_fwd(const float* x, const float* w_ch, const float* w_cw, const float* w_hw, const float* affine, float* y, int B, int C,
                       int H, int W, int ksize, void* workspace, size_t workspace_bytes, mi355_stream_t stream) {
-    MI355_CHECK_ARG(x && w_ch && w_cw && w_hw && affine && y && workspace && B > 0 && C > 0 && H > 0 && W > 0);
-    MI355_CHECK_ARG(ksize >= 1 && ksize <= 15 && (ksize & 1));
-    MI355_CHECK_ARG(workspace_bytes >= mi355_axis_attn_workspace_bytes(B, C, H, W) && aligned16(workspace));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t bc = (size_t)B * C;
-    const long HW = (long)H * W;
-    float* ws = static_cast<float*>(workspace);
-    float* h_mean = ws;                            // ZPool over w of x.permute(0,3,1,2): (B,C,H) mean / max   (triplet_attention.py:59, :33-36)
-    float* h_max = h_mean + fl(bc * H);
-    float* w_mean = h_max + fl(bc * H);            // ZPool over h of x.permute(0,2,1,3): (B,C,W)              (:60)
-    float* w_max = w_mean + fl(bc * W);
-    float* s_ch = w_max + fl(bc * W);              // gates
-    float* s_cw = s_ch + fl(bc * H);
-    float* zp = s_cw + fl(bc * W);                 // ZPool over c: (B,2,HW)                                   (:61)
-    float* s_hw = zp + 2 * fl((size_t)B * HW);
-    const int rc = launch_plane_pool<true>(x, h_mean, h_max, w_mean, w_max, (long)bc, H, W, st);
-    if (rc != MI355_OK) return rc;
-    launch_chan_reduce<1, 1>(x, nullptr, nullptr, zp, B, C, HW, 2, st);
-    launch_gate_conv(h_mean, h_max, (long)C * H, w_ch, affine + 0, s_ch, B, C, H, ksize, st);
-    launch_gate_conv(w_mean, w_max, (long)C * W, w_cw, affine + 2, s_cw, B, C, W, ksize, st);
-    launch_gate_conv(zp, zp + HW, 2 * HW, w_hw, affine + 4, s_hw, B, H, W, ksize, st);
-    ApplyArgs g{};
-    g.x = x; g.y = y; g.a = s_ch; g.b = s_cw; g.c = s_hw; g.C = C; g.H = H; g.W = W;
-    launch_apply<AP_TRIPLET>(g, B, st);
-    MI355_LAUNCH_CHECK();
-    return MI355_OK;
+    TRIPLET_FWD(0);
 }
 
 int mi355_triplet16_fwd(const void* x, const float* w_ch, const float* w_cw, const float* w_hw, const float* affine, void* y, int B, int C,
                         int H, int W, int ksize, int io, void* workspace, size_t workspace_bytes, mi355_stream_t stream) {
     MI355_CHECK_ARG(io == 1 || io == 2);
-    MI355_CHECK_ARG(x && w_ch && w_cw && w_hw && affine && y && workspace && B > 0 && C > 0 && H > 0 && W > 0);
-    MI355_CHECK_ARG(ksize >= 1 && ksize <= 15 && (ksize & 1));
-    MI355_CHECK_ARG(workspace_bytes >= mi355_axis_attn_workspace_bytes(B, C, H, W) && aligned16(workspace));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t bc = (size_t)B * C;
-    const long HW = (long)H * W;
-    float* ws = static_cast<float*>(workspace);
-    float* h_mean = ws;                            // the layout of mi355_triplet_fwd
-    float* h_max = h_mean + fl(bc * H);
-    float* w_mean = h_max + fl(bc * H);
-    float* w_max = w_mean + fl(bc * W);
-    float* s_ch = w_max + fl(bc * W);
-    float* s_cw = s_ch + fl(bc * H);
-    float* zp = s_cw + fl(bc * W);
-    float* s_hw = zp + 2 * fl((size_t)B * HW);
-    const int rc = mi355::axis16_plane_pool(x, io, true, h_mean, h_max, w_mean, w_max, (long)bc, H, W, st);
-    if (rc != MI355_OK) return rc;
-    mi355::axis16_chan_reduce(x, io, 1, 1, nullptr, nullptr, zp, B, C, HW, 2, st);
-    launch_gate_conv(h_mean, h_max, (long)C * H, w_ch, affine + 0, s_ch, B, C, H, ksize, st);
-    launch_gate_conv(w_mean, w_max, (long)C * W, w_cw, affine + 2, s_cw, B, C, W, ksize, st);
-    launch_gate_conv(zp, zp + HW, 2 * HW, w_hw, affine + 4, s_hw, B, H, W, ksize, st);
-    mi355::axis16_apply(AP_TRIPLET, x, io, y, s_ch, s_cw, s_hw, B, C, H, W, st);
-    MI355_LAUNCH_CHECK();
-    return MI355_OK;
+    TRIPLET_FWD(io);
 }
 
 size_t mi355_bam_workspace_bytes(int B, int C, int Cr, int H, int W) {
@@ -858,51 +934,7 @@ size_t mi355_bam_workspace_bytes(int B, int C, int Cr, int H, int W) {
     return 4 * (2 * fl((size_t)B * C) + 2 * fl((size_t)B * Cr * hw) + fl((size_t)B * hw)) + 256;
 }
 
-// The two gates of BAM (ChannelGate.forward bam.py:28-33, SpatialGate.forward :53-59) without the broadcast: cg (B,C) and / or
-// sg (B,HW); either output may be null.  t0 / t1: (B,Cr,HW) scratch, mean: (B,C) scratch.
-// io = 0: x is fp32; 1 / 2: x is IEEE half / bfloat16 and its two sweeps run on the kernels of axis_attn_io16.hip.
-static int bam_gates(const void* xv, int io, const float* const* p, float* mean, float* cg, float* t0, float* t1, float* sg, int B, int C, int Cr,
-                     int H, int W, int dilation, hipStream_t st) {
-    const long HW = (long)H * W;
-    const float* x = static_cast<const float*>(xv);
-    if (cg) {
-        if (io) mi355::axis16_plane_dot(xv, io, mean, (long)B * C, HW, 1.0f / (float)HW, st);
-        else    launch_plane_dot(x, nullptr, mean, (long)B * C, C, HW, 1.0f / (float)HW, st);
-        bam_channel_kernel<<<B, 256, Cr * sizeof(float), st>>>(mean, p[MI355_BAM_FC1_W], p[MI355_BAM_FC1_B], p[MI355_BAM_FC2_W], p[MI355_BAM_FC2_B],
-                                                               p[MI355_BAM_BN1D_SCALE], p[MI355_BAM_BN1D_SHIFT], cg, C, Cr);
-    }
-    if (!sg) return MI355_OK;
-#define CR_DISPATCH(FN)                                  \
-    do {                                                 \
-        if (Cr <= 4) FN(4); else if (Cr <= 8) FN(8); else if (Cr <= 16) FN(16); else FN(32); \
-    } while (0)
-#define RED(K_) launch_chan_reduce<0, K_>(x, p[MI355_BAM_CONV1_W], p[MI355_BAM_CONV1_B], t0, B, C, HW, Cr, st)
-    if (io) mi355::axis16_chan_reduce(xv, io, 0, Cr, p[MI355_BAM_CONV1_W], p[MI355_BAM_CONV1_B], t0, B, C, HW, Cr, st);
-    else    CR_DISPATCH(RED);
-#undef RED
-    const dim3 grid(cdiv(cdiv(HW, Cr > 16 ? 2 : 4), 256), B);
-    const bool quad = (W & 3) == 0 && (dilation & 3) == 0 && Cr <= 16;
-#define SCQ(IN_, W_, SC_, SH_, OUT_)                                                                                                \
-    do {                                                                                                                           \
-        const dim3 qgrid(cdiv((long)H * (W >> 2), 256), B);                                                                        \
-        if (Cr <= 4)      small_conv_quad_kernel<4><<<qgrid, 256, (size_t)Cr * 9 * 4 * sizeof(float), st>>>(IN_, W_, SC_, SH_, OUT_, Cr, H, W, dilation);  \
-        else if (Cr <= 8) small_conv_quad_kernel<8><<<qgrid, 256, (size_t)Cr * 9 * 8 * sizeof(float), st>>>(IN_, W_, SC_, SH_, OUT_, Cr, H, W, dilation);  \
-        else              small_conv_quad_kernel<16><<<qgrid, 256, (size_t)Cr * 9 * 16 * sizeof(float), st>>>(IN_, W_, SC_, SH_, OUT_, Cr, H, W, dilation); \
-    } while (0)
-#define SC1(K_) small_conv_kernel<K_><<<grid, 256, (size_t)Cr * 9 * K_ * sizeof(float), st>>>(t0, p[MI355_BAM_DCONV1_W], p[MI355_BAM_DCONV1_SCALE], p[MI355_BAM_DCONV1_SHIFT], t1, Cr, H, W, dilation)
-    if (quad) SCQ(t0, p[MI355_BAM_DCONV1_W], p[MI355_BAM_DCONV1_SCALE], p[MI355_BAM_DCONV1_SHIFT], t1);
-    else      CR_DISPATCH(SC1);
-#undef SC1
-#define SC2(K_) small_conv_kernel<K_><<<grid, 256, (size_t)Cr * 9 * K_ * sizeof(float), st>>>(t1, p[MI355_BAM_DCONV2_W], p[MI355_BAM_DCONV2_SCALE], p[MI355_BAM_DCONV2_SHIFT], t0, Cr, H, W, dilation)
-    if (quad) SCQ(t1, p[MI355_BAM_DCONV2_W], p[MI355_BAM_DCONV2_SCALE], p[MI355_BAM_DCONV2_SHIFT], t0);
-    else      CR_DISPATCH(SC2);
-#undef SC2
-#undef SCQ
-#undef CR_DISPATCH
-    launch_chan_reduce<0, 1>(t0, p[MI355_BAM_CONV3_W], p[MI355_BAM_CONV3_B], sg, B, Cr, HW, 1, st);
-    return MI355_OK;
-}
-
+// BAM's three entries share their validation as a function: its texts have always named bam_check / mi355_bam_fwd, and callers see them.
 static int bam_check(const void* x, const float* const* p, int B, int C, int Cr, int H, int W, int dilation, const void* workspace,
                      size_t workspace_bytes) {
     MI355_CHECK_ARG(x && p && workspace && B > 0 && C > 0 && Cr > 0 && H > 0 && W > 0 && dilation > 0);
@@ -915,43 +947,24 @@ static int bam_check(const void* x, const float* const* p, int B, int C, int Cr,
     return MI355_OK;
 }
 
+#define BAM_FWD(io_)                                                                                                                         \
+    do {                                                                                                                                     \
+        MI355_CHECK_ARG(y != nullptr);                                                                                                       \
+        if (int rc_ = bam_check(x, p, B, C, Cr, H, W, dilation, workspace, workspace_bytes)) return rc_;                                     \
+        bam_run(x, io_, p, y, B, C, Cr, H, W, dilation, workspace, static_cast<hipStream_t>(stream));                                        \
+        MI355_LAUNCH_CHECK();                                                                                                                \
+        return MI355_OK;                                                                                                                     \
+    } while (0)
+
 int mi355_bam_fwd(const float* x, const float* const* p, float* y, int B, int C, int Cr, int H, int W, int dilation, void* workspace,
                   size_t workspace_bytes, mi355_stream_t stream) {
-    MI355_CHECK_ARG(y != nullptr);
-    if (int rc = bam_check(x, p, B, C, Cr, H, W, dilation, workspace, workspace_bytes)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const long HW = (long)H * W;
-    float* ws = static_cast<float*>(workspace);
-    float* mean = ws;                                    // (B,C)      avgpool: bam.py:30
-    float* cg = mean + fl((size_t)B * C);                // (B,C)      bn(mlp(.)): :31-32
-    float* t0 = cg + fl((size_t)B * C);                  // (B,Cr,HW)  conv1: :55
-    float* t1 = t0 + fl((size_t)B * Cr * HW);            // (B,Cr,HW)  conv2 stages: :56
-    float* sg = t1 + fl((size_t)B * Cr * HW);            // (B,HW)     bn(conv3(.)): :57-58
-    if (int rc = bam_gates(x, 0, p, mean, cg, t0, t1, sg, B, C, Cr, H, W, dilation, st)) return rc;
-    ApplyArgs g{};
-    g.x = x; g.y = y; g.a = cg; g.b = sg; g.C = C; g.H = H; g.W = W;
-    launch_apply<AP_BAM>(g, B, st);
-    MI355_LAUNCH_CHECK();
-    return MI355_OK;
+    BAM_FWD(0);
 }
 
 int mi355_bam16_fwd(const void* x, const float* const* p, void* y, int B, int C, int Cr, int H, int W, int dilation, int io, void* workspace,
                     size_t workspace_bytes, mi355_stream_t stream) {
     MI355_CHECK_ARG(io == 1 || io == 2);
-    MI355_CHECK_ARG(y != nullptr);
-    if (int rc = bam_check(x, p, B, C, Cr, H, W, dilation, workspace, workspace_bytes)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const long HW = (long)H * W;
-    float* ws = static_cast<float*>(workspace);
-    float* mean = ws;                                    // the layout of mi355_bam_fwd
-    float* cg = mean + fl((size_t)B * C);
-    float* t0 = cg + fl((size_t)B * C);
-    float* t1 = t0 + fl((size_t)B * Cr * HW);
-    float* sg = t1 + fl((size_t)B * Cr * HW);
-    if (int rc = bam_gates(x, io, p, mean, cg, t0, t1, sg, B, C, Cr, H, W, dilation, st)) return rc;
-    mi355::axis16_apply(AP_BAM, x, io, y, cg, sg, nullptr, B, C, H, W, st);
-    MI355_LAUNCH_CHECK();
-    return MI355_OK;
+    BAM_FWD(io);
 }
 
 // Stand-alone gates of BAM: cg (B,C) = ChannelGate.forward before its expand_as (bam.py:28-33), sg (B,HW) = SpatialGate.forward before
@@ -960,13 +973,8 @@ int mi355_bam_gates_fwd(const float* x, const float* const* p, float* cg, float*
                         void* workspace, size_t workspace_bytes, mi355_stream_t stream) {
     MI355_CHECK_ARG(cg || sg);
     if (int rc = bam_check(x, p, B, C, Cr, H, W, dilation, workspace, workspace_bytes)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const long HW = (long)H * W;
-    float* ws = static_cast<float*>(workspace);
-    float* mean = ws;
-    float* t0 = mean + 2 * fl((size_t)B * C);
-    float* t1 = t0 + fl((size_t)B * Cr * HW);
-    if (int rc = bam_gates(x, 0, p, mean, cg, t0, t1, sg, B, C, Cr, H, W, dilation, st)) return rc;
+    const BamWs w = bam_carve(workspace, B, C, Cr, H, W);          // the caller's cg / sg take the place of the workspace's
+    bam_gates(x, 0, p, w.mean, cg, w.t0, w.t1, sg, B, C, Cr, H, W, dilation, static_cast<hipStream_t>(stream));
     MI355_LAUNCH_CHECK();
     return MI355_OK;
 }
@@ -985,39 +993,26 @@ size_t mi355_attention_gate_workspace_bytes(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
     return 4 * 3 * fl((size_t)B * H * W) + 256;
 }
+
+#define ATTENTION_GATE_FWD(io_)                                                                                                              \
+    do {                                                                                                                                     \
+        MI355_CHECK_ARG(x && w && affine && y && workspace && B > 0 && C > 0 && H > 0 && W > 0);                                             \
+        MI355_CHECK_ARG(ksize >= 1 && ksize <= 15 && (ksize & 1));                                                                           \
+        MI355_CHECK_ARG(workspace_bytes >= mi355_attention_gate_workspace_bytes(B, H, W) && aligned16(workspace));                           \
+        attention_gate_run(x, io_, w, affine, y, B, C, H, W, ksize, workspace, static_cast<hipStream_t>(stream));                            \
+        MI355_LAUNCH_CHECK();                                                                                                                \
+        return MI355_OK;                                                                                                                     \
+    } while (0)
+
 int mi355_attention_gate_fwd(const float* x, const float* w, const float* affine, float* y, int B, int C, int H, int W, int ksize,
                              void* workspace, size_t workspace_bytes, mi355_stream_t stream) {
-    MI355_CHECK_ARG(x && w && affine && y && workspace && B > 0 && C > 0 && H > 0 && W > 0);
-    MI355_CHECK_ARG(ksize >= 1 && ksize <= 15 && (ksize & 1));
-    MI355_CHECK_ARG(workspace_bytes >= mi355_attention_gate_workspace_bytes(B, H, W) && aligned16(workspace));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const long HW = (long)H * W;
-    float* zp = static_cast<float*>(workspace);            // (B,2,HW)
-    float* gate = zp + 2 * fl((size_t)B * HW);             // (B,HW)
-    launch_chan_reduce<1, 1>(x, nullptr, nullptr, zp, B, C, HW, 2, st);
-    launch_gate_conv(zp, zp + HW, 2 * HW, w, affine, gate, B, H, W, ksize, st);
-    ApplyArgs g{};
-    g.x = x; g.y = y; g.c = gate; g.C = C; g.H = H; g.W = W;
-    launch_apply<AP_SPATIAL>(g, B, st);
-    MI355_LAUNCH_CHECK();
-    return MI355_OK;
+    ATTENTION_GATE_FWD(0);
 }
 
 int mi355_attention_gate16_fwd(const void* x, const float* w, const float* affine, void* y, int B, int C, int H, int W, int ksize, int io,
                                void* workspace, size_t workspace_bytes, mi355_stream_t stream) {
     MI355_CHECK_ARG(io == 1 || io == 2);
-    MI355_CHECK_ARG(x && w && affine && y && workspace && B > 0 && C > 0 && H > 0 && W > 0);
-    MI355_CHECK_ARG(ksize >= 1 && ksize <= 15 && (ksize & 1));
-    MI355_CHECK_ARG(workspace_bytes >= mi355_attention_gate_workspace_bytes(B, H, W) && aligned16(workspace));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const long HW = (long)H * W;
-    float* zp = static_cast<float*>(workspace);            // (B,2,HW)
-    float* gate = zp + 2 * fl((size_t)B * HW);             // (B,HW)
-    mi355::axis16_chan_reduce(x, io, 1, 1, nullptr, nullptr, zp, B, C, HW, 2, st);
-    launch_gate_conv(zp, zp + HW, 2 * HW, w, affine, gate, B, H, W, ksize, st);
-    mi355::axis16_apply(AP_SPATIAL, x, io, y, nullptr, nullptr, gate, B, C, H, W, st);
-    MI355_LAUNCH_CHECK();
-    return MI355_OK;
+    ATTENTION_GATE_FWD(io);
 }
 
 }  // extern "C"

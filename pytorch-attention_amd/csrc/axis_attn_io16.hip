@@ -6,7 +6,8 @@
 //     apply16_kernel<MODE>      the broadcast pass: 16-bit x, fp32 gates, 16-bit y
 // Everything between them (pooled axes, the coordinate MLP, the gate convolutions, BAM's dilated stack) is fp32 in the workspace and runs
 // on the kernels of axis_attn.hip unchanged; the entries (mi355_coordatt16_fwd, mi355_triplet16_fwd, mi355_attention_gate16_fwd,
-// mi355_bam16_fwd) live there too and reach this file through the mi355::axis16_* launchers declared in common.h.
+// mi355_bam16_fwd) live there too and share one host body per gate with the fp32 entries; that body's io-switching launchers
+// (chan_reduce, plane_pool, plane_dot, apply) reach this file through the mi355::axis16_* functions declared in common.h.
 //
 // All arithmetic is fp32 on the exactly widened inputs, in fixed orders; the only rounding the path adds is the one store of y, to
 // nearest even.  Conversions go through io16.h only.
@@ -437,7 +438,7 @@ void apply16_io(int mode, const Apply16Args& g, int B, hipStream_t st) {
 
 }  // namespace
 
-// ---- what the entries in axis_attn.hip call (io = 1: IEEE half, 2: bfloat16; validated there) -------------------------------------------
+// ---- what the io-switching launchers of axis_attn.hip call (io = 1: IEEE half, 2: bfloat16; validated by the entries there) ----------------
 namespace mi355 {
 
 void axis16_chan_reduce(const void* x, int io, int mode, int kmax, const float* w, const float* bias, float* out, int B, int C, long HW, int K,

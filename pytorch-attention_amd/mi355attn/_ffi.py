@@ -170,6 +170,26 @@ SIGNATURES = {
     "mi355_layernorm_workspace_bytes": (c_size, [c_int] * 2),
 }
 
+# op -> (fp32 entry, 16-bit entry) of every drop-in gate that takes fp32, fp16 or bf16 activations.  The 16-bit prototype is the fp32
+# one with `int io` in front of (workspace, workspace_bytes, stream); double_attn's fp32 entry carries its precision in that slot.
+# functional._call_io picks the symbol from here; tests/test_io_entries_cpu.py keeps the table complete.
+IO_ENTRIES = {
+    "se": ("mi355_se_fwd", "mi355_se16_fwd"),
+    "se_ex": ("mi355_se_ex_fwd", "mi355_se16_ex_fwd"),
+    "eca": ("mi355_eca_fwd", "mi355_eca16_fwd"),
+    "cbam": ("mi355_cbam_fwd", "mi355_cbam16_fwd"),
+    "coordatt": ("mi355_coordatt_fwd", "mi355_coordatt16_fwd"),
+    "triplet": ("mi355_triplet_fwd", "mi355_triplet16_fwd"),
+    "attention_gate": ("mi355_attention_gate_fwd", "mi355_attention_gate16_fwd"),
+    "bam": ("mi355_bam_fwd", "mi355_bam16_fwd"),
+    "simam": ("mi355_simam_fwd", "mi355_simam16_fwd"),
+    "srm": ("mi355_srm_fwd", "mi355_srm16_fwd"),
+    "gct_gauss": ("mi355_gct_gauss_fwd", "mi355_gct_gauss16_fwd"),
+    "lct": ("mi355_lct_fwd", "mi355_lct16_fwd"),
+    "gct": ("mi355_gct_fwd", "mi355_gct16_fwd"),
+    "double_attn": ("mi355_double_attn_fwd", "mi355_double_attn16_fwd"),
+}
+
 
 class Mi355Error(RuntimeError):
     pass

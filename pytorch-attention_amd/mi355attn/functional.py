@@ -270,6 +270,32 @@ def param32(param, name):
     return _derived_get((param,), ("w32",), tag, lambda: param.detach().float().contiguous())
 
 
+def _param(io, t, name, shape=None, optional=False):
+    """A parameter of a gate that takes 16-bit activations, as an fp32 device tensor.  On the 16-bit path (io != 0) it may be fp32 or 16-bit
+    (param32: converted once and cached); on the fp32 path (io = 0) it is fp32 as before and anything else raises require_device_f32's
+    TypeError.  `shape`: reshape to it.  optional: None stays None (NULL).  SE, ECA, CBAM and DoubleAttention take 16-bit parameters on
+    either path and call param32 themselves."""
+    if t is None and optional:
+        return None
+    t = param32(t, name) if io else require_device_f32(t, name)
+    return t if shape is None else t.reshape(*shape)
+
+
+def _dedicated(name, io, x, nbytes):
+    """The dedicated workspace (exchange area) of op `name` for the shape of x -- one per I/O type, so that fp32 and 16-bit launches of one
+    shape never share ticket state."""
+    key = (name + "16", io) + tuple(x.shape) if io else (name,) + tuple(x.shape)
+    return _ffi.workspace_dedicated(key, nbytes, x.device)
+
+
+def _call_io(op, io, head, ws, device, slot32=()):
+    """Call the entry of `op` (_ffi.IO_ENTRIES) for the I/O type: the fp32 entry for io = 0, the 16-bit entry otherwise.  `head`: the
+    arguments in front of the `io` slot; behind it come the workspace, its size and the stream.  slot32: what the fp32 entry carries in
+    that slot (DoubleAttention: its precision; nothing for the others)."""
+    name = _ffi.IO_ENTRIES[op][1 if io else 0]
+    check(getattr(lib(), name)(*head, *((io,) if io else slot32), dptr(ws), ws.numel(), stream_ptr(device)), name)
+
+
 def se_forward(x, w1, w2):
     """SELayer forward: x (B,C,H,W) fp32 / fp16 / bf16 (output in the same type), w1 (C/r,C), w2 (C,C/r)."""
     x, io = _ffi.require_device_io(x, "x")
@@ -280,15 +306,8 @@ def se_forward(x, w1, w2):
     if tuple(w1.shape) != (Cr, C) or tuple(w2.shape) != (C, Cr):
         raise ValueError(f"SE weight shapes {tuple(w1.shape)}, {tuple(w2.shape)} do not match C={C}")
     y = torch.empty_like(x)
-    n = lib().mi355_se_workspace_bytes(B, C, H, W)
-    if io:
-        ws = _ffi.workspace_dedicated(("se16", io, B, C, H, W), n, x.device)
-        check(lib().mi355_se16_fwd(dptr(x), dptr(w1), dptr(w2), dptr(y), B, C, Cr, H, W, io, dptr(ws), ws.numel(),
-                                   stream_ptr(x.device)), "mi355_se16_fwd")
-    else:
-        ws = _ffi.workspace_dedicated(("se", B, C, H, W), n, x.device)
-        check(lib().mi355_se_fwd(dptr(x), dptr(w1), dptr(w2), dptr(y), B, C, Cr, H, W, dptr(ws), ws.numel(),
-                                 stream_ptr(x.device)), "mi355_se_fwd")
+    ws = _dedicated("se", io, x, lib().mi355_se_workspace_bytes(B, C, H, W))
+    _call_io("se", io, (dptr(x), dptr(w1), dptr(w2), dptr(y), B, C, Cr, H, W), ws, x.device)
     _sync_check()
     return y
 
@@ -319,23 +338,15 @@ def _axis(x, io16=False):
     return x, io, torch.empty_like(x), ws, (B, C, H, W)
 
 
-def _flat(t, name, *shape):
-    return require_device_f32(t, name).reshape(*shape) if t is not None else None
-
-
-def _flat_io(io, t, name, *shape):
-    """_flat for the gates that take 16-bit activations: on the 16-bit path the parameter may be 16-bit too (_p)."""
-    return _p(io, t, name).reshape(*shape) if t is not None else None
-
-
 def gc_forward(x, conv_w, conv_b, w1, b1, ln_w, ln_b, ln_eps, w2, b2):
     x, _, y, ws, (B, C, H, W) = _axis(x)
     Cr = w1.shape[0]
-    check(lib().mi355_gc_fwd(dptr(x), dptr(_flat(conv_w, "conv.weight", C)), dptr(_flat(conv_b, "conv.bias", 1)),
-                             dptr(_flat(w1, "transform.0.weight", Cr, C)), dptr(_flat(b1, "transform.0.bias", Cr)),
-                             dptr(_flat(ln_w, "transform.1.weight", Cr)), dptr(_flat(ln_b, "transform.1.bias", Cr)),
-                             dptr(_flat(w2, "transform.3.weight", C, Cr)), dptr(_flat(b2, "transform.3.bias", C)), dptr(y),
-                             B, C, Cr, H, W, float(ln_eps), dptr(ws), ws.numel(), stream_ptr(x.device)), "mi355_gc_fwd")
+    ps = [_param(0, t, n, shape, optional=True) for t, n, shape in (
+        (conv_w, "conv.weight", (C,)), (conv_b, "conv.bias", (1,)), (w1, "transform.0.weight", (Cr, C)), (b1, "transform.0.bias", (Cr,)),
+        (ln_w, "transform.1.weight", (Cr,)), (ln_b, "transform.1.bias", (Cr,)), (w2, "transform.3.weight", (C, Cr)),
+        (b2, "transform.3.bias", (C,)))]
+    check(lib().mi355_gc_fwd(dptr(x), *[dptr(t) for t in ps], dptr(y), B, C, Cr, H, W, float(ln_eps), dptr(ws), ws.numel(),
+                             stream_ptr(x.device)), "mi355_gc_fwd")
     return y
 
 
@@ -343,16 +354,11 @@ def coordatt_forward(x, w1, b1, bn_scale, bn_shift, wh, bh, ww, bw):
     """x fp32 / fp16 / bf16 (output in the same type); on the 16-bit path the parameters may be 16-bit too (param32)."""
     x, io, y, ws, (B, C, H, W) = _axis(x, io16=True)
     hid = w1.shape[0]
-    ps = [_flat_io(io, t, n, *shape) for t, n, shape in (
+    ps = [_param(io, t, n, shape, optional=True) for t, n, shape in (
         (w1, "conv1.weight", (hid, C)), (b1, "conv1.bias", (hid,)), (bn_scale, "bn1 scale", (hid,)), (bn_shift, "bn1 shift", (hid,)),
         (wh, "conv_h.weight", (C, hid)), (bh, "conv_h.bias", (C,)), (ww, "conv_w.weight", (C, hid)), (bw, "conv_w.bias", (C,)))]
     ptrs = [dptr(t) for t in ps]        # `ps` keeps the tensors (a contiguous copy may be a temporary) alive over the call
-    if io:
-        check(lib().mi355_coordatt16_fwd(dptr(x), *ptrs, dptr(y), B, C, hid, H, W, io, dptr(ws), ws.numel(), stream_ptr(x.device)),
-              "mi355_coordatt16_fwd")
-    else:
-        check(lib().mi355_coordatt_fwd(dptr(x), *ptrs, dptr(y), B, C, hid, H, W, dptr(ws), ws.numel(), stream_ptr(x.device)),
-              "mi355_coordatt_fwd")
+    _call_io("coordatt", io, (dptr(x), *ptrs, dptr(y), B, C, hid, H, W), ws, x.device)
     return y
 
 
@@ -360,15 +366,10 @@ def triplet_forward(x, w_ch, w_cw, w_hw, affine, ksize):
     """x fp32 / fp16 / bf16 (output in the same type); on the 16-bit path the parameters may be 16-bit too (param32)."""
     x, io, y, ws, (B, C, H, W) = _axis(x, io16=True)
     n = 2 * ksize * ksize
-    ps = [_flat_io(io, w_ch, "ch.conv.conv.weight", n), _flat_io(io, w_cw, "cw.conv.conv.weight", n),
-          _flat_io(io, w_hw, "hw.conv.conv.weight", n), _flat_io(io, affine, "gate affine", 6)]
+    ps = [_param(io, t, name, (size,), optional=True) for t, name, size in (
+        (w_ch, "ch.conv.conv.weight", n), (w_cw, "cw.conv.conv.weight", n), (w_hw, "hw.conv.conv.weight", n), (affine, "gate affine", 6))]
     ptrs = [dptr(t) for t in ps]
-    if io:
-        check(lib().mi355_triplet16_fwd(dptr(x), *ptrs, dptr(y), B, C, H, W, int(ksize), io, dptr(ws), ws.numel(), stream_ptr(x.device)),
-              "mi355_triplet16_fwd")
-    else:
-        check(lib().mi355_triplet_fwd(dptr(x), *ptrs, dptr(y), B, C, H, W, int(ksize), dptr(ws), ws.numel(), stream_ptr(x.device)),
-              "mi355_triplet_fwd")
+    _call_io("triplet", io, (dptr(x), *ptrs, dptr(y), B, C, H, W, int(ksize)), ws, x.device)
     return y
 
 
@@ -380,16 +381,11 @@ def bam_forward(x, params, Cr, dilation):
     B, C, H, W = x.shape
     if len(params) != 16:
         raise ValueError("bam_forward: expected 16 parameter tensors")
-    ps = [_p(io, t, f"bam parameter {i}") for i, t in enumerate(params)]
+    ps = [_param(io, t, f"bam parameter {i}") for i, t in enumerate(params)]
     table = (ctypes.c_void_p * 16)(*[t.data_ptr() for t in ps])
     ws = workspace(lib().mi355_bam_workspace_bytes(B, C, Cr, H, W), x.device)
     y = torch.empty_like(x)
-    if io:
-        check(lib().mi355_bam16_fwd(dptr(x), ctypes.cast(table, ctypes.c_void_p), dptr(y), B, C, Cr, H, W, int(dilation), io, dptr(ws),
-                                    ws.numel(), stream_ptr(x.device)), "mi355_bam16_fwd")
-    else:
-        check(lib().mi355_bam_fwd(dptr(x), ctypes.cast(table, ctypes.c_void_p), dptr(y), B, C, Cr, H, W, int(dilation), dptr(ws), ws.numel(),
-                                  stream_ptr(x.device)), "mi355_bam_fwd")
+    _call_io("bam", io, (dptr(x), ctypes.cast(table, ctypes.c_void_p), dptr(y), B, C, Cr, H, W, int(dilation)), ws, x.device)
     return y
 
 
@@ -423,18 +419,13 @@ def attention_gate(x, w, affine, ksize):
     x fp32 / fp16 / bf16 (output in the same type); on the 16-bit path the parameters may be 16-bit too (param32)."""
     x, io = _ffi.require_device_io(x, "x")
     B, C, H, W = x.shape
-    w = _p(io, w, "w").reshape(-1)
-    affine = _p(io, affine, "affine").reshape(-1)
+    w = _param(io, w, "w", (-1,))
+    affine = _param(io, affine, "affine", (-1,))
     if w.numel() != 2 * ksize * ksize or affine.numel() != 2:
         raise ValueError("attention_gate: w must be (1,2,k,k) and affine (2,)")
     ws = workspace(lib().mi355_attention_gate_workspace_bytes(B, H, W), x.device)
     y = torch.empty_like(x)
-    if io:
-        check(lib().mi355_attention_gate16_fwd(dptr(x), dptr(w), dptr(affine), dptr(y), B, C, H, W, int(ksize), io, dptr(ws), ws.numel(),
-                                               stream_ptr(x.device)), "mi355_attention_gate16_fwd")
-    else:
-        check(lib().mi355_attention_gate_fwd(dptr(x), dptr(w), dptr(affine), dptr(y), B, C, H, W, int(ksize), dptr(ws), ws.numel(),
-                                             stream_ptr(x.device)), "mi355_attention_gate_fwd")
+    _call_io("attention_gate", io, (dptr(x), dptr(w), dptr(affine), dptr(y), B, C, H, W, int(ksize)), ws, x.device)
     return y
 
 
@@ -478,11 +469,6 @@ def tokens_to_nchw_axpy(tokens, x, alpha):
     return y
 
 
-def _opt32(t, name):
-    """Optional parameter of the channel-attention family (None -> NULL), fp32 or 16-bit (param32)."""
-    return None if t is None else param32(t, name)
-
-
 def se_ex_forward(x, w1, b1, w2, b2, gate="sigmoid"):
     """SE with optional excitation biases and a choice of gate ("sigmoid" | "hard_sigmoid"): the variants inside the reference's CNNs.
     x fp32 / fp16 / bf16 (output in the same type)."""
@@ -490,23 +476,16 @@ def se_ex_forward(x, w1, b1, w2, b2, gate="sigmoid"):
     B, C, H, W = x.shape
     w1 = param32(w1, "w1").reshape(w1.shape[0], -1)
     w2 = param32(w2, "w2").reshape(w2.shape[0], -1)
-    b1, b2 = (_opt32(b1, "b1"), _opt32(b2, "b2")) if io else (_opt(b1, "b1"), _opt(b2, "b2"))
+    b1, b2 = _param(io, b1, "b1", optional=True), _param(io, b2, "b2", optional=True)
     Cr = w1.shape[0]
     if tuple(w1.shape) != (Cr, C) or tuple(w2.shape) != (C, Cr):
         raise ValueError(f"SE weight shapes {tuple(w1.shape)}, {tuple(w2.shape)} do not match C={C}")
     if gate not in ("sigmoid", "hard_sigmoid"):
         raise ValueError("gate must be 'sigmoid' or 'hard_sigmoid'")
     y = torch.empty_like(x)
-    n = lib().mi355_se_workspace_bytes(B, C, H, W)
+    ws = _dedicated("se", io, x, lib().mi355_se_workspace_bytes(B, C, H, W))      # the key of se_forward: the same kernels
     code = 1 if gate == "hard_sigmoid" else 0
-    if io:
-        ws = _ffi.workspace_dedicated(("se16", io, B, C, H, W), n, x.device)
-        check(lib().mi355_se16_ex_fwd(dptr(x), dptr(w1), dptr(b1), dptr(w2), dptr(b2), dptr(y), B, C, Cr, H, W, code, io, dptr(ws),
-                                      ws.numel(), stream_ptr(x.device)), "mi355_se16_ex_fwd")
-    else:
-        ws = _ffi.workspace_dedicated(("se", B, C, H, W), n, x.device)
-        check(lib().mi355_se_ex_fwd(dptr(x), dptr(w1), dptr(b1), dptr(w2), dptr(b2), dptr(y), B, C, Cr, H, W, code, dptr(ws), ws.numel(),
-                                    stream_ptr(x.device)), "mi355_se_ex_fwd")
+    _call_io("se_ex", io, (dptr(x), dptr(w1), dptr(b1), dptr(w2), dptr(b2), dptr(y), B, C, Cr, H, W, code), ws, x.device)
     _sync_check()
     return y
 
@@ -518,14 +497,8 @@ def eca_forward(x, wconv):
     B, C, H, W = x.shape
     k = wconv.numel()
     y = torch.empty_like(x)
-    n = lib().mi355_eca_workspace_bytes(B, C, H, W)
-    ws = workspace(n, x.device)
-    if io:
-        check(lib().mi355_eca16_fwd(dptr(x), dptr(wconv), dptr(y), B, C, k, H, W, io, dptr(ws), ws.numel(),
-                                    stream_ptr(x.device)), "mi355_eca16_fwd")
-    else:
-        check(lib().mi355_eca_fwd(dptr(x), dptr(wconv), dptr(y), B, C, k, H, W, dptr(ws), ws.numel(),
-                                  stream_ptr(x.device)), "mi355_eca_fwd")
+    ws = workspace(lib().mi355_eca_workspace_bytes(B, C, H, W), x.device)
+    _call_io("eca", io, (dptr(x), dptr(wconv), dptr(y), B, C, k, H, W), ws, x.device)
     return y
 
 
@@ -547,16 +520,9 @@ def cbam_forward(x, w1=None, w2=None, wconv=None, stage=0):
             raise ValueError(f"CBAM spatial conv weight must be (1,2,k,k), got {tuple(wconv.shape)}")
     y = torch.empty_like(x)
     ptrs = (dptr(w1 if stage != 2 else None), dptr(w2 if stage != 2 else None), dptr(wconv if stage != 1 else None))
-    if io:
-        n = lib().mi355_cbam16_workspace_bytes(B, C, H, W)
-        ws = _ffi.workspace_dedicated(("cbam16", io, B, C, H, W), n, x.device) if stage == 0 else workspace(n, x.device)
-        check(lib().mi355_cbam16_fwd(dptr(x), *ptrs, dptr(y), B, C, Cr, ks, H, W, stage, io, dptr(ws), ws.numel(),
-                                     stream_ptr(x.device)), "mi355_cbam16_fwd")
-    else:
-        n = lib().mi355_cbam_workspace_bytes(B, C, H, W)
-        ws = _ffi.workspace_dedicated(("cbam", B, C, H, W), n, x.device) if stage == 0 else workspace(n, x.device)
-        check(lib().mi355_cbam_fwd(dptr(x), *ptrs, dptr(y), B, C, Cr, ks, H, W, stage, dptr(ws), ws.numel(),
-                                   stream_ptr(x.device)), "mi355_cbam_fwd")
+    n = (lib().mi355_cbam16_workspace_bytes if io else lib().mi355_cbam_workspace_bytes)(B, C, H, W)
+    ws = _dedicated("cbam", io, x, n) if stage == 0 else workspace(n, x.device)
+    _call_io("cbam", io, (dptr(x), *ptrs, dptr(y), B, C, Cr, ks, H, W, stage), ws, x.device)
     if stage == 0:
         _sync_check()
     return y
@@ -564,65 +530,40 @@ def cbam_forward(x, w1=None, w2=None, wconv=None, stage=0):
 
 def _zoo(kind, x):
     """Common prologue of the channel-statistics gates: dense device x in fp32, fp16 or bf16, output of the same type, dedicated workspace
-    (exchange area) -- one per I/O type, so that fp32 and 16-bit launches of one shape never share ticket state."""
+    (_dedicated)."""
     x, io = _ffi.require_device_io(x, "x")
     B, C, H, W = x.shape
-    n = lib().mi355_chan_stat_workspace_bytes(B, C)
-    key = (kind + "16", io, B, C, H, W) if io else (kind, B, C, H, W)
-    return x, io, torch.empty_like(x), _ffi.workspace_dedicated(key, n, x.device), (B, C, H, W)
-
-
-def _p(io, t, name):
-    """A parameter of these gates: fp32 as before on the fp32 path, fp32 or 16-bit (converted once and cached) on the 16-bit path."""
-    return param32(t, name) if io else require_device_f32(t, name)
+    ws = _dedicated(kind, io, x, lib().mi355_chan_stat_workspace_bytes(B, C))
+    return x, io, torch.empty_like(x), ws, (B, C, H, W)
 
 
 def simam_forward(x, e_lambda=1e-4):
     x, io, y, ws, (B, C, H, W) = _zoo("simam", x)
-    if io:
-        check(lib().mi355_simam16_fwd(dptr(x), dptr(y), B, C, H, W, float(e_lambda), io, dptr(ws), ws.numel(), stream_ptr(x.device)),
-              "mi355_simam16_fwd")
-    else:
-        check(lib().mi355_simam_fwd(dptr(x), dptr(y), B, C, H, W, float(e_lambda), dptr(ws), ws.numel(), stream_ptr(x.device)),
-              "mi355_simam_fwd")
+    _call_io("simam", io, (dptr(x), dptr(y), B, C, H, W, float(e_lambda)), ws, x.device)
     return y
 
 
 def srm_forward(x, cfc, bn_weight, bn_bias, bn_mean, bn_var, bn_eps):
     x, io, y, ws, (B, C, H, W) = _zoo("srm", x)
-    cfc = _p(io, cfc, "cfc.weight").reshape(C, 2)
-    ps = [_p(io, t, n) for t, n in ((bn_weight, "bn.weight"), (bn_bias, "bn.bias"), (bn_mean, "bn.running_mean"),
+    cfc = _param(io, cfc, "cfc.weight", (C, 2))
+    ps = [_param(io, t, n) for t, n in ((bn_weight, "bn.weight"), (bn_bias, "bn.bias"), (bn_mean, "bn.running_mean"),
                                     (bn_var, "bn.running_var"))]
-    if io:
-        check(lib().mi355_srm16_fwd(dptr(x), dptr(cfc), dptr(ps[0]), dptr(ps[1]), dptr(ps[2]), dptr(ps[3]), float(bn_eps), dptr(y),
-                                    B, C, H, W, io, dptr(ws), ws.numel(), stream_ptr(x.device)), "mi355_srm16_fwd")
-    else:
-        check(lib().mi355_srm_fwd(dptr(x), dptr(cfc), dptr(ps[0]), dptr(ps[1]), dptr(ps[2]), dptr(ps[3]), float(bn_eps), dptr(y),
-                                  B, C, H, W, dptr(ws), ws.numel(), stream_ptr(x.device)), "mi355_srm_fwd")
+    _call_io("srm", io, (dptr(x), dptr(cfc), dptr(ps[0]), dptr(ps[1]), dptr(ps[2]), dptr(ps[3]), float(bn_eps), dptr(y), B, C, H, W),
+             ws, x.device)
     return y
 
 
 def gct_gauss_forward(x, c=2, eps=1e-5):
     x, io, y, ws, (B, C, H, W) = _zoo("gct_gauss", x)
-    if io:
-        check(lib().mi355_gct_gauss16_fwd(dptr(x), dptr(y), B, C, H, W, float(c), float(eps), io, dptr(ws), ws.numel(),
-                                          stream_ptr(x.device)), "mi355_gct_gauss16_fwd")
-    else:
-        check(lib().mi355_gct_gauss_fwd(dptr(x), dptr(y), B, C, H, W, float(c), float(eps), dptr(ws), ws.numel(), stream_ptr(x.device)),
-              "mi355_gct_gauss_fwd")
+    _call_io("gct_gauss", io, (dptr(x), dptr(y), B, C, H, W, float(c), float(eps)), ws, x.device)
     _sync_check()
     return y
 
 
 def lct_forward(x, w, b, groups, eps=1e-5):
     x, io, y, ws, (B, C, H, W) = _zoo("lct", x)
-    w, b = _p(io, w, "w"), _p(io, b, "b")
-    if io:
-        check(lib().mi355_lct16_fwd(dptr(x), dptr(w), dptr(b), dptr(y), B, C, int(groups), H, W, float(eps), io, dptr(ws), ws.numel(),
-                                    stream_ptr(x.device)), "mi355_lct16_fwd")
-    else:
-        check(lib().mi355_lct_fwd(dptr(x), dptr(w), dptr(b), dptr(y), B, C, int(groups), H, W, float(eps), dptr(ws), ws.numel(),
-                                  stream_ptr(x.device)), "mi355_lct_fwd")
+    w, b = _param(io, w, "w"), _param(io, b, "b")
+    _call_io("lct", io, (dptr(x), dptr(w), dptr(b), dptr(y), B, C, int(groups), H, W, float(eps)), ws, x.device)
     _sync_check()
     return y
 
@@ -631,14 +572,9 @@ def gct_forward(x, alpha, gamma, beta, epsilon=1e-5, mode="l2", after_relu=False
     if mode not in ("l2", "l1"):
         raise ValueError("GCT mode must be 'l2' or 'l1'")
     x, io, y, ws, (B, C, H, W) = _zoo("gct", x)
-    alpha, gamma, beta = (_p(io, t, n).reshape(-1) for t, n in ((alpha, "alpha"), (gamma, "gamma"), (beta, "beta")))
+    alpha, gamma, beta = (_param(io, t, n, (-1,)) for t, n in ((alpha, "alpha"), (gamma, "gamma"), (beta, "beta")))
     l1, relu = 1 if mode == "l1" else 0, 1 if after_relu else 0
-    if io:
-        check(lib().mi355_gct16_fwd(dptr(x), dptr(alpha), dptr(gamma), dptr(beta), dptr(y), B, C, H, W, float(epsilon), l1, relu, io,
-                                    dptr(ws), ws.numel(), stream_ptr(x.device)), "mi355_gct16_fwd")
-    else:
-        check(lib().mi355_gct_fwd(dptr(x), dptr(alpha), dptr(gamma), dptr(beta), dptr(y), B, C, H, W, float(epsilon), l1, relu,
-                                  dptr(ws), ws.numel(), stream_ptr(x.device)), "mi355_gct_fwd")
+    _call_io("gct", io, (dptr(x), dptr(alpha), dptr(gamma), dptr(beta), dptr(y), B, C, H, W, float(epsilon), l1, relu), ws, x.device)
     _sync_check()
     return y
 
@@ -667,18 +603,12 @@ def double_attention_forward(x, wA, bA, wB, bB, wV, bV, wP, bP, precision=None):
     if wV.shape[0] != cn or wP.shape[1] != cm or wA.shape[1] != C:
         raise ValueError("DoubleAttention weight shapes are inconsistent")
     y = torch.empty(B, Cout, H, W, dtype=x.dtype, device=x.device)
-    if io:
-        n = lib().mi355_double_attn16_ws_bytes(B, C, cm, cn, H, W, io)
-        ws = workspace(n, x.device)
-        check(lib().mi355_double_attn16_fwd(dptr(x), dptr(wA), dptr(bA), dptr(wB), dptr(bB), dptr(wV), dptr(bV),
-                                            dptr(wP), dptr(bP), dptr(y), B, C, cm, cn, H, W, io,
-                                            dptr(ws), ws.numel(), stream_ptr(x.device)), "mi355_double_attn16_fwd")
-        return y
-    n = lib().mi355_double_attn_ws_bytes(B, C, cm, cn, H, W, _prec(precision))
+    # the fp32 entry and its workspace query carry the precision where the 16-bit ones carry io
+    n = (lib().mi355_double_attn16_ws_bytes(B, C, cm, cn, H, W, io) if io
+         else lib().mi355_double_attn_ws_bytes(B, C, cm, cn, H, W, _prec(precision)))
     ws = workspace(n, x.device)
-    check(lib().mi355_double_attn_fwd(dptr(x), dptr(wA), dptr(bA), dptr(wB), dptr(bB), dptr(wV), dptr(bV),
-                                      dptr(wP), dptr(bP), dptr(y), B, C, cm, cn, H, W, _prec(precision),
-                                      dptr(ws), ws.numel(), stream_ptr(x.device)), "mi355_double_attn_fwd")
+    _call_io("double_attn", io, (dptr(x), dptr(wA), dptr(bA), dptr(wB), dptr(bB), dptr(wV), dptr(bV), dptr(wP), dptr(bP), dptr(y),
+                                 B, C, cm, cn, H, W), ws, x.device, slot32=(_prec(precision),))
     return y
 
 

@@ -5,7 +5,7 @@ Reference: oracle.axis_attn.{coordatt,triplet,bam}_forward in fp64 on x16.double
 in fp32 on the exactly widened input and round once, so for every element, none excluded,
     |y - ref64| <= u * |ref64| + 3e-5 * max|ref64| (+ 2^-25 for fp16 results below the normal range),
 u = 2^-11 (fp16) / 2^-8 (bf16): half an ulp, relative; 3e-5 is what tests/test_gpu_parity.py allows these modules in fp32
-(VECTOR_CHAINS).  _check below is test_io16_gpu._check with that fp32 allowance in place of the channel gates' 1e-5; it prints
+(VECTOR_CHAINS).  _check below is io16_common._check_chan with that fp32 allowance in place of the channel gates' 1e-5; it prints
 max err / bound before it asserts.  tests/test_axis_io16_cpu.py shows on the CPU that the fp32 oracle, rounded once, keeps the bound.
 
 Modules are seeded (axis_io16_arena_rows.build): the default BatchNorm is the identity.  Each shape is the smallest that reaches one
@@ -16,12 +16,11 @@ import pytest
 import torch
 
 from axis_io16_arena_rows import build, reference
-from test_io16_gpu import DTYPES, U, _input, _ulps
+from io16_common import DTYPES, IO, U, _input, _run, _status, _ulps
 
 pytestmark = pytest.mark.gpu
 
 T32 = 3e-5
-IO = {torch.float16: 1, torch.bfloat16: 2}
 
 
 def _check(got, ref, dtype, what, only=None):
@@ -40,21 +39,6 @@ def _check(got, ref, dtype, what, only=None):
     worst = float((err[fin] / bound[fin]).max()) if fin.any() else 0.0
     print(f"[axis16] {what}: max err / bound = {worst:.3f}, max abs err = {float(err[fin].max()) if fin.any() else 0.0:.3e}, t32 = {t32:.3e}")
     assert worst <= 1.0, f"{what}: error is {worst:.3f} x the bound"
-
-
-def _status():
-    import mi355attn
-    mi355attn.sync_status(wait=True)
-    mi355attn.range_status(wait=True)
-
-
-def _run(m, xd):
-    """(output, kernel tags) of one forward."""
-    import mi355attn
-    outs = []
-    with torch.no_grad():
-        rows = mi355attn.kernel_trace(lambda: outs.append(m(xd)))
-    return outs[0], [r[0] for r in rows]
 
 
 @functools.lru_cache(maxsize=None)

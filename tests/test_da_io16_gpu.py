@@ -17,13 +17,11 @@ import torch
 
 import oracle.chan_attn as OC
 from conftest import assert_parity, no_range_fallback, rel_fro
+from io16_common import DTYPES, IO, U, _input, _status
 
 pytestmark = pytest.mark.gpu
 
-DTYPES = [torch.float16, torch.bfloat16]
-IO = {torch.float16: 1, torch.bfloat16: 2}
 TOL = {torch.float16: 1e-3, torch.bfloat16: 1.2e-2}
-U = {torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
 
 # (shape, c_m, c_n)
 SMALL = [((2, 64, 32, 32), 32, 32),
@@ -56,19 +54,8 @@ def _params(m):
                                                m.proj.weight, m.proj.bias)]
 
 
-def _input(shape, dtype, seed=4321):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    return torch.randn(*shape, generator=g).to(dtype)
-
-
 def _ref(x16, m):
     return OC.double_attention_forward(x16.double().cpu(), *_params(m), dtype=torch.float64)
-
-
-def _status():
-    import mi355attn
-    mi355attn.sync_status(wait=True)
-    mi355attn.range_status(wait=True)
 
 
 def _trace(fn):

@@ -10,11 +10,10 @@ import pytest
 import torch
 
 import oracle.chan_attn as OC
+from io16_common import DTYPES, _check_chan as _check, _input, _status as _common_status, _ulps
 
 pytestmark = pytest.mark.gpu
 
-DTYPES = [torch.float16, torch.bfloat16]
-U = {torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
 NEW_TAGS = ("se16_", "eca16_", "cbam16_", "pool16_", "scale16_", "chan_gates16_")
 
 
@@ -22,11 +21,6 @@ def _mods(C, red=16, ks=7):
     from mi355attn.modules import CBAM, ECALayer, SELayer
     torch.manual_seed(1234)
     return SELayer(C, red).eval(), ECALayer(C).eval(), CBAM(C, red, ks).eval()
-
-
-def _input(shape, dtype, seed=4321):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    return torch.randn(*shape, generator=g).to(dtype)
 
 
 def _blocks(C, red=16, ks=7):
@@ -44,36 +38,8 @@ def _blocks(C, red=16, ks=7):
             ("sa", cbam.sa, lambda x: OC.cbam_spatial_forward(x.double(), wc, dtype=f64))]
 
 
-def _check(got, ref, dtype, what):
-    """The derived bound, every element; prints the figures before it asserts."""
-    assert got.dtype == dtype and tuple(got.shape) == tuple(ref.shape), what
-    got, ref = got.detach().cpu().double(), ref.double()
-    fin = torch.isfinite(ref)
-    assert torch.equal(torch.isnan(got), torch.isnan(ref)), f"{what}: NaN pattern differs from the reference"
-    assert torch.equal(torch.isinf(got), torch.isinf(ref)) and torch.equal(got[torch.isinf(ref)], ref[torch.isinf(ref)]), f"{what}: inf pattern"
-    t32 = 1e-5 * float(ref[fin].abs().max()) if fin.any() else 0.0
-    bound = U[dtype] * ref.abs() + t32
-    if dtype == torch.float16:
-        bound = bound + (ref.abs() < 2.0 ** -14).double() * 2.0 ** -25
-    err = (got - ref).abs()
-    worst = float((err[fin] / bound[fin]).max()) if fin.any() else 0.0
-    print(f"[io16] {what}: max err / bound = {worst:.3f}, max abs err = {float(err[fin].max()) if fin.any() else 0.0:.3e}, t32 = {t32:.3e}")
-    assert worst <= 1.0, f"{what}: error is {worst:.3f} x the bound"
-
-
-def _ord(t):
-    """16-bit floats as integers that count representable values (sign-magnitude -> monotonic)."""
-    i = t.detach().cpu().view(torch.int16).to(torch.int32)
-    return torch.where(i < 0, -(i & 0x7fff), i)
-
-
-def _ulps(a, b):
-    return int((_ord(a) - _ord(b)).abs().max())
-
-
 def _status():
-    import mi355attn
-    mi355attn.sync_status(wait=True)
+    _common_status(range_word=False)                                   # these tests have always read the sync word alone
 
 
 def _red_ks(shape):

@@ -5,14 +5,14 @@ Reference: the oracle functions in fp64 on x16.double() and the fp32 parameters.
 every element, none excluded,
     |got - ref64| <= u * |ref64| + 1e-5 * max|ref64| (+ 2^-25 for fp16 results below the normal range),
 u = 2^-11 (fp16) / 2^-8 (bf16): half an ulp, relative; 1e-5 is what the fp32 GPU tests of these modules allow
-(tests/test_chan_attn_gpu.py, assert_parity(..., 1e-5, ...)).  test_io16_gpu._check is that bound; it prints max err / bound first.
+(tests/test_chan_attn_gpu.py, assert_parity(..., 1e-5, ...)).  io16_common._check_chan is that bound; it prints max err / bound first.
 
 Parameters are seeded with O(1) values: the defaults make GCT (gamma = beta = 0) and SRM's BatchNorm the identity."""
 import pytest
 import torch
 
 import oracle.chan_attn as OC
-from test_io16_gpu import DTYPES, U, _check, _input, _ulps
+from io16_common import DTYPES, U, _check_chan as _check, _input, _run, _status, _ulps
 
 pytestmark = pytest.mark.gpu
 
@@ -23,12 +23,6 @@ SINGLE = [(2, 64, 32, 32),        # two full chunks per lane
           (3, 8, 64, 64)]         # 8 chunks per lane, the row limit
 GENERAL = [(3, 72, 7, 7), (2, 48, 13, 17), (2, 100, 5, 9), (1, 8, 1, 2), (1, 8, 1, 1)]
 SMALL = SINGLE[0]
-
-
-def _status():
-    import mi355attn
-    mi355attn.sync_status(wait=True)
-    mi355attn.range_status(wait=True)
 
 
 def _zoo(C, hw):
@@ -93,15 +87,6 @@ def _se(C):
     w = [hid.fc[0].weight.detach().clone(), hid.fc[2].weight.detach().clone()]
     out.append(("se_hidden", hid, lambda x, w=w: OC.se_forward(x.double(), *w, dtype=F64)))
     return [(n, m.eval().cuda(), r) for n, m, r in out], p
-
-
-def _run(m, xd):
-    """(output, kernel tags) of one forward."""
-    import mi355attn
-    outs = []
-    with torch.no_grad():
-        rows = mi355attn.kernel_trace(lambda: outs.append(m(xd)))
-    return outs[0], [r[0] for r in rows]
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
