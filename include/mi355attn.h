@@ -599,7 +599,8 @@ int mi355_mixer_token_fwd(const float* x, const float* ln_w, const float* ln_b, 
  * normalised on their way into LDS, so the 16-bit LayerNorm output never exists in HBM.  N % 8 == 0. */
 int mi355_ln_linear16_fwd(const float* X, const void* W16, const float* bias, void* Y, int M, int N, int K, int ldx, int ldy, float eps,
                           int act, int out16, int precision, mi355_stream_t stream);
-/* mi355_sdpa_fwd / mi355_cswin_lepe_attn_fwd with 16-bit qkv and out buffers (same layouts). */
+/* mi355_sdpa_fwd / mi355_cswin_lepe_attn_fwd with 16-bit qkv and out buffers (same layouts).  The LePE entry takes stripe windows
+ * of up to 512 tokens, as mi355_cswin_lepe_attn_fwd does (above 224 on the key-blocked kernel; above 512: MI355_EUNSUPPORTED). */
 int mi355_sdpa16_fwd(const void* qkv16, void* out16, int B, int N, int heads, int d, float scale, int precision,
                      mi355_stream_t stream);
 int mi355_cswin_lepe_attn16_fwd(const void* qkv16, const float* getv_w, const float* getv_b, void* out16,
@@ -628,7 +629,8 @@ int mi355_qkv_split16_fwd(const float* x, const void* w_hi, const void* w_lo, co
 int mi355_sdpa16_split_fwd(const void* qkv5, void* out16, int B, int N, int heads, int d, float scale, mi355_stream_t stream);
 /* Both stripe branches of a CSWinBlock in ONE launch (cswin.py:155-165, 186-192): branch 0 = vertical stripes (H_sp = reso, W_sp =
  * split) on channels [0, Ctot/2) with get_v weights w0/b0, branch 1 = horizontal stripes on [Ctot/2, Ctot) with w1/b1; `heads` per branch.
- * Same arithmetic as two mi355_cswin_lepe_attn16_fwd calls. */
+ * Same arithmetic as two mi355_cswin_lepe_attn16_fwd calls.  reso * split <= 512 tokens per stripe window (else MI355_EUNSUPPORTED,
+ * nothing launched); windows above 224 tokens run on the key-blocked kernel, both branches still in one grid. */
 int mi355_cswin_lepe_attn16_pair_fwd(const void* qkv16, const float* getv_w0, const float* getv_b0, const float* getv_w1,
                                      const float* getv_b1, void* out16, int B, int reso, int Ctot, int heads, int split, float scale,
                                      int precision, mi355_stream_t stream);
@@ -682,7 +684,11 @@ int mi355_sdpa_fwd(const float* qkv, float* out, int B, int N, int heads, int d,
  *   qkv: token-major (B,L,3,Ctot) buffer of the block's qkv Linear; this call handles the channel slice
  *   [c0, c0+Cb) with `heads` heads of width Cb/heads, stripe window (Hsp x Wsp) on a (reso x reso) token
  *   grid; writes out[b,l,c0+...] of a (B,L,Ctot) buffer.  getv_w (Cb,3,3), getv_b (Cb): depth-wise 3x3
- *   LePE conv, zero padded at the WINDOW border. */
+ *   LePE conv, zero padded at the WINDOW border.
+ *   Envelope: head width Cb / heads == 32 and Hsp * Wsp <= 512 tokens per stripe window, in all three precisions; anything else is
+ *   MI355_EUNSUPPORTED before any launch.  Windows of up to 224 tokens keep their whole score row in registers; longer ones (CSWin at
+ *   384 - 512 px: 288, 392, 512 tokens in stage 3) run on a key-blocked kernel with an online softmax (K and V resident in LDS; same
+ *   rounding points, so the results follow the same bars).  In precision 1 both report a saturating q / k / v with range code 7. */
 int mi355_cswin_lepe_attn_fwd(const float* qkv, const float* getv_w, const float* getv_b, float* out,
                               int B, int reso, int Ctot, int c0, int Cb, int heads, int Hsp, int Wsp,
                               float scale, int precision, mi355_stream_t stream);

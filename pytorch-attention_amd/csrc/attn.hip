@@ -459,6 +459,385 @@ __global__ __launch_bounds__(NW * 64, OCC) void win_attn_kernel(const attn_kargs
     if constexpr (RG) rg_report(rgm, pr.ovf, 7u);
 }
 
+// ---- long stripe windows: 224 < T <= 512 tokens, head width 32, LePE (CSWin stage 3 / 4 at 384 - 512 px) ------------------------------
+// win_attn_kernel keeps the whole score row of a query tile in registers (f4 s[KT], KT <= 14).  Here the keys are consumed in blocks of
+// LONG_KB tiles with an online softmax: per query tile a running maximum m, a running sum and the O accumulators, all rescaled by
+// 2^(m_old - m_new) when a block raises the maximum, so the score registers are bounded by the block and not by T.  Everything outside the
+// score loop is the short kernel's: one workgroup per (image, window, head), tok() index math, q pre-scaled, K and V^T (all of them: K/V stay
+// RESIDENT in every precision) in LDS, LePE taps read from V^T with a zero column for taps outside the window, per-wave output slab, whole-row
+// stores, XCD-contiguous block order.
+//   * LDS at KT = 32 (512 keys): one operand plane is 512 * 80 B (K, pitch 40) + 32 * 516 * 2 B (V^T) = 73,984 B; strict needs two (hi / lo)
+//     = 147,968 B, + 9,216 B slab (4 waves, fp32) + 1,280 B LePE weights = 158,464 B of the 163,840 B.  The tap table of the short kernel
+//     (9 * TK * 2 B) does not fit beside that, so the nine tap offsets of a query slot are computed per query tile instead (a divide by
+//     magic and nine compare / select pairs per lane, once per 16 queries x 512 keys of score work) -- in all precisions, one code path.
+//     They live in 32-bit registers: the largest is the zero column at byte 2 * TK = 1,024 of a V^T row.
+//   * m starts at -inf and the first block always holds live keys (T > 224 > one block), so the first rescale factor is 2^(-inf) = 0 on
+//     zero accumulators; the select on m == -inf keeps (-inf) - (-inf) out even for a row whose scores so far were all -inf.
+//   * padded keys (>= T) exist only in the last block that runs (the block loop stops at T), and that block holds at least one live key.
+//   * strict keeps s * post rounded before the maximum is subtracted (row maximum -> exactly 2^0; a block whose maximum is 127 or more
+//     log2 units below the final one is wiped by a rescale factor of exactly 0: v_exp_f32 flushes), the 16-bit modes keep the normaliser
+//     on the matrix pipe (all-ones A tile over the rounded P of the block, folded into the running sum with the block's factor).
+constexpr int LONG_KB = 8;         // key tiles per block: 32 score registers per lane
+constexpr int LONG_TMAX = 512;     // envelope of the long kernel (tokens per window)
+template <int PREC, int KT, bool IO16, int NW>
+__global__ __launch_bounds__(NW * 64, 1) void win_attn_long_kernel(const attn_kargs<IO16> pr) {
+    constexpr int D = 32, KB = LONG_KB;
+    static_assert(!IO16 || PREC != 0, "16-bit I/O exists for the fp16 / bf16 operand modes only");
+    static_assert(KT % 2 == 0 && KB % 2 == 0 && KT * 16 <= LONG_TMAX, "P.V consumes key tiles in pairs");
+    const int lid = xcd_contiguous_block();
+    const bool second = lid >= pr.split;
+    const AttnArgs a = second ? pr.a1 : pr.a0;
+    constexpr int NTHR = NW * 64;
+    using M_ = Mma<PREC>;
+    using v8 = typename M_::v8;
+    using v4 = typename M_::v4;
+    using el = typename M_::e;
+    constexpr int NS = M_::NSPLIT;
+    constexpr int TK = KT * 16;               // padded key count
+    constexpr int KP = D + 8;                 // K row pitch (elements)
+    constexpr int VP = TK + 4;                // V^T row pitch (elements); column TK is the zero column of the LePE taps
+    static_assert((TK + 1) * 2 <= VP * 2 && VP * 2 < 65536, "tap byte offsets stay inside a V^T row");
+    constexpr bool RG = !IO16 && PREC == 1;   // fp32 q / k / v staged to fp16: range code 7, as win_attn_kernel
+    float rgm = 0.f;
+    constexpr int OP = IO16 ? D + 8 : D + 4;
+    constexpr int K_EL = TK * KP, V_EL = D * VP;
+    using slab_t = typename std::conditional<IO16, unsigned short, float>::type;
+    __shared__ __attribute__((aligned(16))) unsigned short s_k[NS * K_EL];
+    __shared__ __attribute__((aligned(16))) unsigned short s_v[NS * V_EL];
+    __shared__ __attribute__((aligned(16))) slab_t s_o[NW * 16 * OP];
+    __shared__ float s_lw[D * 10];
+    static_assert(sizeof(unsigned short) * NS * (K_EL + V_EL) + sizeof(slab_t) * NW * 16 * OP + sizeof(float) * D * 10 <= 163840,
+                  "K, V^T, the output slab and the LePE weights share one workgroup's LDS");
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    int bid = lid - (second ? pr.split : 0);
+    const int head = bid % a.heads; bid /= a.heads;
+    const int win = bid % a.nwin;
+    const int b = bid / a.nwin;
+    const int T = a.T;                                                // host: 224 < T <= TK
+    const int wy0 = (win / a.nWx) * a.Hsp, wx0 = (win % a.nWx) * a.Wsp;
+    const int ch0 = a.c0 + head * D;
+    const int och0 = a.oc0 + head * D;
+    const long row3 = 3L * a.Ctot;
+    using gel = typename std::conditional<IO16, el, float>::type;
+    const gel* base = static_cast<const gel*>(a.qkv) + (long)b * a.L * row3 + ch0;
+    auto srow = [&](int s) { return a.Wsp == 1 ? s : (int)__umulhi((unsigned)s, a.wsp_magic); };
+    auto tok = [&](int s) { const int r = srow(s); return (wy0 + r) * a.reso + wx0 + (s - r * a.Wsp); };
+
+    const int l15 = lane & 15, g = lane >> 4;
+    const int nqt = (T + 15) >> 4;
+    // 16-bit I/O: one raw buffer descriptor per image (host: the image's qkv rows span < 2^31 bytes); dead slots read zeros
+    const rsrc_t img_rs = make_rsrc(IO16 ? static_cast<const void*>(base) : nullptr, IO16 ? (bufops_u32)((long)a.L * row3 * sizeof(gel)) : 0u);
+    auto ld16 = [&](bool live, int token, int el_off) -> v8 {
+        const bufops_u32 off = live ? (bufops_u32)((token * (int)row3 + el_off) * 2) : OOB;
+        return __builtin_bit_cast(v8, __builtin_amdgcn_raw_buffer_load_b128(img_rs, off, 0, 0));
+    };
+    const f4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    // the q fragment of one query tile as it comes from HBM (column q = l15, d = g*8 + [0,8)); the next tile's is requested before this
+    // tile's score loop starts
+    struct QF32 { f4 lo, hi; };
+    using qraw_t = typename std::conditional<IO16, v8, QF32>::type;
+    auto ldq = [&](int qt_) -> qraw_t {
+        const int qs = qt_ * 16 + l15;
+        const bool live = qs < T;
+        const int tq = tok(live ? qs : 0);
+        if constexpr (IO16) {
+            return ld16(live, tq, g * 8);
+        } else {
+            QF32 r{zero4, zero4};
+            if (live) {
+                const float* qrow = base + (long)tq * row3 + g * 8;
+                r.lo = *reinterpret_cast<const f4*>(qrow);
+                r.hi = *reinterpret_cast<const f4*>(qrow + 4);
+            }
+            return r;
+        }
+    };
+    qraw_t qnext = ldq(wave);
+    for (int q = t; q < D * 10; q += NTHR) {
+        const int c = q / 10, i = q - c * 10;
+        s_lw[q] = i < 9 ? a.lepe_w[(long)(head * D + c) * 9 + i] : a.lepe_b[head * D + c];
+    }
+
+    // ---- phase A: K -> LDS [key][d],  V -> LDS transposed [d][key]; keys in [T, TK) are zeros ----------------------------
+    constexpr int D4 = D / 4;
+    if constexpr (IO16) {
+        constexpr int D8 = D / 8;
+        constexpr int NKI = (TK * D8 + NTHR - 1) / NTHR, NVI = ((TK / 4) * D8 + NTHR - 1) / NTHR;
+        v8 kreg[NKI];
+        v8 vreg[NVI][4];
+#pragma unroll
+        for (int it = 0; it < NKI; ++it) {
+            const int idx = t + it * NTHR, key = idx / D8, d8 = idx % D8;
+            const bool live = idx < TK * D8 && key < T;
+            kreg[it] = ld16(live, tok(live ? key : 0), a.koff + d8 * 8);
+        }
+#pragma unroll
+        for (int it = 0; it < NVI; ++it) {
+            const int idx = t + it * NTHR, kg = idx / D8, d8 = idx % D8;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int key = kg * 4 + j;
+                const bool live = idx < (TK / 4) * D8 && key < T;
+                vreg[it][j] = ld16(live, tok(live ? key : 0), a.voff + d8 * 8);
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < NKI; ++it) {
+            const int idx = t + it * NTHR, key = idx / D8, d8 = idx % D8;
+            if (idx < TK * D8) *reinterpret_cast<v8*>(s_k + key * KP + d8 * 8) = kreg[it];
+        }
+#pragma unroll
+        for (int it = 0; it < NVI; ++it) {
+            const int idx = t + it * NTHR, kg = idx / D8, d8 = idx % D8;
+            if (idx < (TK / 4) * D8) {
+#pragma unroll
+                for (int q = 0; q < 8; ++q)
+                    *reinterpret_cast<v4*>(s_v + (d8 * 8 + q) * VP + kg * 4) =
+                        v4{vreg[it][0][q], vreg[it][1][q], vreg[it][2][q], vreg[it][3][q]};
+            }
+        }
+    } else {
+        for (int idx = t; idx < TK * D4; idx += NTHR) {
+            const int key = idx / D4, d4 = idx % D4;
+            f4 v = zero4;
+            if (key < T) v = *reinterpret_cast<const f4*>(base + (long)tok(key) * row3 + a.koff + d4 * 4);
+            if constexpr (RG) rgm = rg_absmax4(rgm, v);
+            const v4 h = M_::cvt(v);
+            *reinterpret_cast<v4*>(s_k + key * KP + d4 * 4) = h;
+            if constexpr (NS == 2) *reinterpret_cast<v4*>(s_k + K_EL + key * KP + d4 * 4) = M_::cvt_lo(v, h);
+        }
+        for (int idx = t; idx < (TK / 4) * D4; idx += NTHR) {
+            const int kg = idx / D4, d4 = idx % D4;
+            f4 r[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int key = kg * 4 + j;
+                r[j] = zero4;
+                if (key < T) r[j] = *reinterpret_cast<const f4*>(base + (long)tok(key) * row3 + a.voff + d4 * 4);
+                if constexpr (RG) rgm = rg_absmax4(rgm, r[j]);
+            }
+            const f4 c[4] = {{r[0].x, r[1].x, r[2].x, r[3].x}, {r[0].y, r[1].y, r[2].y, r[3].y},
+                             {r[0].z, r[1].z, r[2].z, r[3].z}, {r[0].w, r[1].w, r[2].w, r[3].w}};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const v4 h = M_::cvt(c[q]);
+                *reinterpret_cast<v4*>(s_v + (d4 * 4 + q) * VP + kg * 4) = h;
+                if constexpr (NS == 2) *reinterpret_cast<v4*>(s_v + V_EL + (d4 * 4 + q) * VP + kg * 4) = M_::cvt_lo(c[q], h);
+            }
+        }
+    }
+    for (int q = t; q < NS * D; q += NTHR) s_v[(q / D) * V_EL + (q % D) * VP + TK] = 0;      // the zero column of the LePE taps
+    __syncthreads();
+
+    // ---- phase B: each wave owns 16-query tiles; keys in blocks of KB tiles ------------------------------------------------
+    slab_t* slab = s_o + wave * 16 * OP;
+    const float post = (a.pre_scale ? 1.0f : a.scale) * 1.44269504088896340736f;
+    for (int qt = wave; qt < nqt; qt += NW) {
+        const qraw_t qr = qnext;
+        qnext = ldq(qt + NW);                                         // slots past T: nothing is read
+        v8 qf[NS];
+        {
+            f4 lo4, hi4;
+            if constexpr (IO16) {
+                lo4 = f4{(float)qr[0], (float)qr[1], (float)qr[2], (float)qr[3]};
+                hi4 = f4{(float)qr[4], (float)qr[5], (float)qr[6], (float)qr[7]};
+            } else {
+                lo4 = qr.lo; hi4 = qr.hi;
+            }
+            if (a.pre_scale) { lo4 = lo4 * a.scale; hi4 = hi4 * a.scale; }
+            if constexpr (RG) rgm = rg_absmax4(rg_absmax4(rgm, lo4), hi4);
+            const v4 h0 = M_::cvt(lo4), h1 = M_::cvt(hi4);
+            qf[0] = v8{h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+            if constexpr (NS == 2) {
+                const v4 e0 = M_::cvt_lo(lo4, h0), e1 = M_::cvt_lo(hi4, h1);
+                qf[1] = v8{e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};
+            }
+        }
+        f4 o[D / 16] = {zero4, zero4};
+        float m = -INFINITY, sum = 0.f;                                // strict: sum is this lane's part (its 4 keys of every tile)
+        typedef typename M_::e el1_t;
+        const v8 ones = v8{(el1_t)1.0f, (el1_t)1.0f, (el1_t)1.0f, (el1_t)1.0f, (el1_t)1.0f, (el1_t)1.0f, (el1_t)1.0f, (el1_t)1.0f};
+        for (int kb0 = 0; kb0 * 16 < T; kb0 += KB) {
+            // S^T tiles of the block: lane holds S^T[key = (kb0 + kt)*16 + g*4 + r][q = l15]
+            f4 s[KB];
+#pragma unroll
+            for (int kt = 0; kt < KB; ++kt) {
+                f4 acc = zero4;
+                if ((kb0 + kt) * 16 < T) {
+                    v8 kf[NS];
+#pragma unroll
+                    for (int sp = 0; sp < NS; ++sp)
+                        kf[sp] = *reinterpret_cast<const v8*>(s_k + sp * K_EL + ((kb0 + kt) * 16 + l15) * KP + g * 8);
+                    acc = mma_step<PREC>(kf, qf, acc);
+                }
+                s[kt] = acc;
+            }
+            // block maximum (masked beyond T): raw scores in the 16-bit modes, rounded s * post in strict
+            float mb = -INFINITY;
+#pragma unroll
+            for (int kt = 0; kt < KB; ++kt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int key = (kb0 + kt) * 16 + g * 4 + r;
+                    const float sc = PREC != 0 ? s[kt][r] : s[kt][r] * post;
+                    const float v = key < T ? sc : -INFINITY;
+                    s[kt][r] = v;
+                    mb = fmaxf(mb, v);
+                }
+            mb = fmaxf(mb, __shfl_xor(mb, 16, WAVE));
+            mb = fmaxf(mb, __shfl_xor(mb, 32, WAVE));
+            const float mn = fmaxf(m, mb);
+            // factor that carries the earlier blocks to the new maximum (the same in the four lanes of a query); 0 for the first block
+            float alpha, bsum = 0.f;
+            if constexpr (PREC != 0) {
+                const float mneg = -(mn * post);
+                alpha = m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(__builtin_fmaf(m, post, mneg));
+#pragma unroll
+                for (int kt = 0; kt < KB; ++kt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) s[kt][r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt][r], post, mneg));
+            } else {
+                alpha = m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m - mn);
+#pragma unroll
+                for (int kt = 0; kt < KB; ++kt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float p = __builtin_amdgcn_exp2f(s[kt][r] - mn);      // the row maximum: exactly 2^0
+                        s[kt][r] = p;
+                        bsum += p;
+                    }
+            }
+            m = mn;
+#pragma unroll
+            for (int nt = 0; nt < D / 16; ++nt) o[nt] = o[nt] * alpha;
+            // O^T += V^T . P^T over the block (P re-packed in-lane, as win_attn_kernel); 16-bit modes: the block's sum of the rounded P
+            // from the all-ones A tile
+            f4 osum = zero4;
+#pragma unroll
+            for (int kb = 0; kb < KB / 2; ++kb) {
+                if ((kb0 + 2 * kb) * 16 < T) {
+                    v8 pf[NS];
+                    {
+                        const f4 p0 = s[2 * kb], p1 = s[2 * kb + 1];
+                        const v4 h0 = M_::cvt(p0), h1 = M_::cvt(p1);
+                        pf[0] = v8{h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+                        if constexpr (NS == 2) {
+                            const v4 e0 = M_::cvt_lo(p0, h0), e1 = M_::cvt_lo(p1, h1);
+                            pf[1] = v8{e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};
+                        }
+                    }
+#pragma unroll
+                    for (int nt = 0; nt < D / 16; ++nt) {
+                        v8 vf[NS];
+#pragma unroll
+                        for (int sp = 0; sp < NS; ++sp) {
+                            const unsigned short* vr = s_v + sp * V_EL + (nt * 16 + l15) * VP + (kb0 + 2 * kb) * 16 + g * 4;
+                            const v4 a0 = *reinterpret_cast<const v4*>(vr);
+                            const v4 a1 = *reinterpret_cast<const v4*>(vr + 16);
+                            vf[sp] = v8{a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+                        }
+                        o[nt] = mma_step<PREC>(vf, pf, o[nt]);
+                    }
+                    if constexpr (PREC != 0) osum = M_::mma(ones, pf[0], osum);
+                }
+            }
+            if constexpr (PREC != 0) bsum = osum.x;
+            sum = sum * alpha + bsum;
+        }
+        if constexpr (PREC == 0) {
+            sum += __shfl_xor(sum, 16, WAVE);
+            sum += __shfl_xor(sum, 32, WAVE);
+        }
+        const float inv = __builtin_amdgcn_rcpf(sum);
+        // LePE: dw 3x3 over the (Hsp x Wsp) window image of V, zero halo; byte offsets of the nine taps inside a V^T row, computed here
+        const int qslot = qt * 16 + l15;
+        const bool qlive = qslot < T;
+        int off[9];
+        {
+            const int ty = srow(qlive ? qslot : 0), tx = (qlive ? qslot : 0) - ty * a.Wsp;
+#pragma unroll
+            for (int i = 0; i < 9; ++i) {
+                const int yy = ty + i / 3 - 1, xx = tx + i % 3 - 1;
+                off[i] = ((yy >= 0 && yy < a.Hsp && xx >= 0 && xx < a.Wsp) ? yy * a.Wsp + xx : TK) * 2;
+            }
+        }
+#pragma unroll
+        for (int nt = 0; nt < D / 16; ++nt) {
+            f4 val = o[nt] * inv;
+            if (qlive) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int d = nt * 16 + g * 4 + r;
+                    const float* lwp = s_lw + d * 10;
+                    const char* vrow = reinterpret_cast<const char*>(s_v + d * VP);
+                    float acc = lwp[9];
+#pragma unroll
+                    for (int i = 0; i < 9; ++i) {
+                        float vv = (float)(*reinterpret_cast<const el*>(vrow + off[i]));
+                        if constexpr (NS == 2) vv += (float)(*reinterpret_cast<const el*>(vrow + V_EL * 2 + off[i]));
+                        acc = __builtin_fmaf(lwp[i], vv, acc);
+                    }
+                    val[r] += acc;
+                }
+            }
+            if constexpr (IO16) *reinterpret_cast<v4*>(slab + l15 * OP + nt * 16 + g * 4) = M_::cvt(val);
+            else *reinterpret_cast<f4*>(slab + l15 * OP + nt * 16 + g * 4) = val;
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        if constexpr (IO16) {
+            constexpr int LPR = D / 8, RPI = 64 / LPR;
+#pragma unroll
+            for (int it = 0; it < 16 / RPI; ++it) {
+                const int r = it * RPI + lane / LPR, c8 = (lane % LPR) * 8;
+                const int qs = qt * 16 + r;
+                if (qs < T)
+                    *reinterpret_cast<v8*>(static_cast<gel*>(a.out) + ((long)b * a.L + tok(qs)) * a.Ctot + och0 + c8) =
+                        *reinterpret_cast<const v8*>(slab + r * OP + c8);
+            }
+        } else {
+            constexpr int LPR = D / 4, RPI = 64 / LPR;
+#pragma unroll
+            for (int it = 0; it < 16 / RPI; ++it) {
+                const int r = it * RPI + lane / LPR, c4 = (lane % LPR) * 4;
+                const int qs = qt * 16 + r;
+                if (qs < T)
+                    *reinterpret_cast<f4*>(static_cast<gel*>(a.out) + ((long)b * a.L + tok(qs)) * a.Ctot + och0 + c4) =
+                        *reinterpret_cast<const f4*>(slab + r * OP + c4);
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    }
+    if constexpr (RG) rg_report(rgm, pr.ovf, 7u);
+}
+
+// Launches the long kernel for a (pair of) LePE argument set(s) with 224 < T <= LONG_TMAX.  Two key-plane sizes are built: 20 tiles (T <= 320:
+// the 384 px stage-3 stripes, 288 tokens) and 32 tiles.  Eight waves share a head's K / V except in strict mode at 32 tiles, where the two
+// operand planes leave LDS room for the output slabs of four.
+template <bool IO16>
+int launch_attn_long(const AttnPairRg& pr, int grid, int B, int precision, hipStream_t st) {
+    const AttnArgs& a = pr.a0;
+    const int Tmax = pr.split < grid && pr.a1.T > a.T ? pr.a1.T : a.T;
+    if (Tmax > LONG_TMAX) return mi355::fail(MI355_EUNSUPPORTED, "LePE attention: %d tokens per stripe window > %d", Tmax, LONG_TMAX);
+    // 16-bit I/O addresses an image's qkv rows through one buffer descriptor with 32-bit byte offsets (dead lanes: offset 2^31)
+    if (IO16 && (long)a.L * 3L * a.Ctot * 2L >= (1L << 31))
+        return mi355::fail(MI355_EUNSUPPORTED, "LePE attention, 16-bit I/O: the qkv rows of one image span %ld bytes (limit 2^31)", (long)a.L * 3L * a.Ctot * 2L);
+    MI355_TRACE(st, "win_attn_long_kernel<d=32,lepe%s> B=%d windows=%d heads=%d tokens=%d", IO16 ? ",io16" : "", B, a.nwin, a.heads, a.T);
+#define GOL(P, KT_, NW_) win_attn_long_kernel<P, KT_, (IO16 && P != 0), NW_><<<grid, NW_ * 64, 0, st>>>(attn_pick<(IO16 && P != 0)>(pr))
+#define BYT(P) do { if (Tmax <= 320) GOL(P, 20, 8); else GOL(P, 32, (P == 0 ? 4 : 8)); } while (0)
+    switch (precision) {
+        case MI355_PREC_STRICT: BYT(0); break;
+        case MI355_PREC_FP16:   BYT(1); break;
+        case MI355_PREC_BF16:   BYT(2); break;
+        default: return mi355::fail(MI355_EINVAL, "precision must be 0, 1 or 2 (got %d)", precision);
+    }
+#undef BYT
+#undef GOL
+    return MI355_OK;
+}
+
 template <int D, bool LEPE, bool IO16>
 int launch_attn(const AttnArgs& a, int B, int precision, hipStream_t st, const AttnArgs* other = nullptr) {
     AttnPairRg pr{};
@@ -472,6 +851,9 @@ int launch_attn(const AttnArgs& a, int B, int precision, hipStream_t st, const A
     if (IO16 && precision == MI355_PREC_STRICT)
         return mi355::fail(MI355_EINVAL, "16-bit activation I/O needs precision 1 (fp16) or 2 (bf16)");
     if (!IO16 && precision == MI355_PREC_FP16) pr.ovf = mi355::range_word(st);       // fp32 q / k / v staged to fp16: a producer
+    if constexpr (LEPE && D == 32) {
+        if (a.T > 224 || (other && other->T > 224)) return launch_attn_long<IO16>(pr, grid, B, precision, st);
+    }
     MI355_TRACE(st, "win_attn_kernel<d=%d%s%s> B=%d windows=%d heads=%d tokens=%d", D, LEPE ? ",lepe" : "", IO16 ? ",io16" : "", B, a.nwin, a.heads, a.T);
 #define GO(P, KT_, NW_) win_attn_kernel<P, D, KT_, LEPE, (IO16 && P != 0), NW_><<<grid, NW_ * 64, 0, st>>>(attn_pick<(IO16 && P != 0)>(pr))
 #define GO_OCC(P, KT_, NW_, OCC_) win_attn_kernel<P, D, KT_, LEPE, (IO16 && P != 0), NW_, ((IO16 && P != 0 && D == 32) ? OCC_ : 1)><<<grid, NW_ * 64, 0, st>>>(attn_pick<(IO16 && P != 0)>(pr))
@@ -570,7 +952,7 @@ static int lepe_common(const void* qkv, const float* getv_w, const float* getv_b
     MI355_CHECK_ARG(B > 0 && reso > 0 && Ctot > 0 && c0 >= 0 && Cb > 0 && c0 + Cb <= Ctot && heads > 0 && Cb % heads == 0); \
     MI355_CHECK_ARG(Hsp > 0 && Wsp > 0 && reso % Hsp == 0 && reso % Wsp == 0);                                             \
     if (Cb / heads != 32) return mi355::fail(MI355_EUNSUPPORTED, fn ": head dim %d (built: 32)", Cb / heads);             \
-    if (Hsp * Wsp > 224) return mi355::fail(MI355_EUNSUPPORTED, fn ": %d tokens per stripe window > 224", Hsp * Wsp);     \
+    if (Hsp * Wsp > 512) return mi355::fail(MI355_EUNSUPPORTED, fn ": %d tokens per stripe window > 512", Hsp * Wsp);     \
     MI355_CHECK_ARG((Ctot & 7) == 0 && (c0 & 7) == 0 && aligned16(qkv) && aligned16(out))
 
 extern "C" {
@@ -622,7 +1004,7 @@ int mi355_cswin_lepe_attn16_pair_fwd(const void* qkv, const float* getv_w0, cons
     MI355_CHECK_ARG(qkv && getv_w0 && getv_b0 && getv_w1 && getv_b1 && out);
     MI355_CHECK_ARG(B > 0 && reso > 0 && Ctot > 0 && heads > 0 && (Ctot / 2) % heads == 0 && split > 0 && reso % split == 0);
     if (Ctot / 2 / heads != 32) return mi355::fail(MI355_EUNSUPPORTED, "mi355_cswin_lepe_attn16_pair_fwd: head dim %d (built: 32)", Ctot / 2 / heads);
-    if (reso * split > 224) return mi355::fail(MI355_EUNSUPPORTED, "mi355_cswin_lepe_attn16_pair_fwd: %d tokens per stripe window > 224", reso * split);
+    if (reso * split > 512) return mi355::fail(MI355_EUNSUPPORTED, "mi355_cswin_lepe_attn16_pair_fwd: %d tokens per stripe window > 512", reso * split);
     MI355_CHECK_ARG((Ctot & 15) == 0 && aligned16(qkv) && aligned16(out));
     // branch 0: idx 0 of cswin.py:62-67 (H_sp = resolution, W_sp = split) on channels [0, C/2); branch 1: idx 1 on [C/2, C)
     const AttnArgs a0 = lepe_args(qkv, getv_w0, getv_b0, out, reso, Ctot, 0, heads, reso, split, scale);
