@@ -254,14 +254,15 @@ def _heads_attention(q, k, v, scale, topk=None):
     return torch.softmax(attn, dim=-1) @ v
 
 
-def global_attention_forward(x, p, num_heads, dtype=torch.float32):
-    """GlobalAttention.forward -- vision_transformers/dilateformer.py:152-164: plain MHSA on a channels-last (B,H,W,C) grid."""
+def global_attention_forward(x, p, num_heads, dtype=torch.float32, scale=None):
+    """GlobalAttention.forward -- vision_transformers/dilateformer.py:152-164: plain MHSA on a channels-last (B,H,W,C) grid.
+    `scale`: the constructor's qk_scale (dilateformer.py:143, `qk_scale or head_dim ** -0.5`); None = the default."""
     x = _t(x, dtype)
     B, H, W, C = x.shape
     d = C // num_heads
     qkv = linear(x.reshape(B, H * W, C), _t(p["qkv.weight"], dtype), _t(p["qkv.bias"], dtype) if "qkv.bias" in p else None)
     qkv = qkv.reshape(B, H * W, 3, num_heads, d).permute(2, 0, 3, 1, 4)
-    o = _heads_attention(qkv[0], qkv[1], qkv[2], d ** -0.5).transpose(1, 2).reshape(B, H, W, C)
+    o = _heads_attention(qkv[0], qkv[1], qkv[2], scale or d ** -0.5).transpose(1, 2).reshape(B, H, W, C)
     return linear(o, _t(p["proj.weight"], dtype), _t(p["proj.bias"], dtype))
 
 
@@ -317,9 +318,11 @@ def conv_attention_forward(x, p, num_heads, dtype=torch.float32, bn_eps=1e-5):
     return TF.conv2d(o, g("proj.weight"), g("proj.bias"))
 
 
-def pooling_attention_forward(x, p, H, W, d_convs, num_heads, pool_ratios, dtype=torch.float32):
+def pooling_attention_forward(x, p, H, W, d_convs, num_heads, pool_ratios, dtype=torch.float32, scale=None, sizes=None):
     """PoolingAttention.forward -- vision_transformers/p2t.py:71-95.  `d_convs`: the depth-wise 3x3 Conv2d modules the enclosing block
-    passes in (p2t.py:127-128), one per pool ratio."""
+    passes in (p2t.py:127-128), one per pool ratio.  `scale`: the constructor's qk_scale (p2t.py:58), None = the default.  `sizes`:
+    pooled (oh, ow) per ratio in place of p2t.py:78's round(H / ratio), round(W / ratio) -- Python rounds half to even -- for tests
+    that measure what another rounding would change."""
     import torch.nn.functional as TF
     x = _t(x, dtype)
     B, N, C = x.shape
@@ -328,12 +331,12 @@ def pooling_attention_forward(x, p, H, W, d_convs, num_heads, pool_ratios, dtype
     q = linear(x, _t(p["q.0.weight"], dtype), opt("q.0.bias")).reshape(B, N, num_heads, d).permute(0, 2, 1, 3)
     grid = x.permute(0, 2, 1).reshape(B, C, H, W)
     pools = []
-    for ratio, conv in zip(pool_ratios, d_convs):
-        pool = TF.adaptive_avg_pool2d(grid, (round(H / ratio), round(W / ratio)))
+    for i, (ratio, conv) in enumerate(zip(pool_ratios, d_convs)):
+        pool = TF.adaptive_avg_pool2d(grid, (round(H / ratio), round(W / ratio)) if sizes is None else tuple(sizes[i]))
         pool = pool + TF.conv2d(pool, _t(conv.weight, dtype), _t(conv.bias, dtype), padding=1, groups=C)
         pools.append(pool.reshape(B, C, -1))
     pools = torch.cat(pools, dim=2).permute(0, 2, 1)
     pools = layernorm(pools, _t(p["norm.weight"], dtype), _t(p["norm.bias"], dtype))
     kv = linear(pools, _t(p["kv.0.weight"], dtype), opt("kv.0.bias")).reshape(B, -1, 2, num_heads, d).permute(2, 0, 3, 1, 4)
-    o = _heads_attention(q, kv[0], kv[1], d ** -0.5).transpose(1, 2).reshape(B, N, C)
+    o = _heads_attention(q, kv[0], kv[1], scale or d ** -0.5).transpose(1, 2).reshape(B, N, C)
     return linear(o, _t(p["proj.weight"], dtype), _t(p["proj.bias"], dtype))

@@ -1553,7 +1553,10 @@ def sdpa_general(q, k, v, num_heads, scale, bias=None, precision=None, out=None)
     """softmax(q k^T * scale + bias) v for (B,Nq,C) queries and (B,Nkv,C) keys / values (views into fused projections welcome).
     fp32 tensors -> fp32 result; fp16 / bf16 tensors (the operand type of `precision`) -> same type.  bias: (heads,Nq,Nkv) or
     (B,heads,Nq,Nkv) fp32.  out: optional (B,Nq,C) destination view with unit channel stride and a dense batch axis (a channel
-    slice of a wider tensor: the C entry takes the row stride).  Head width C / num_heads in SDPA_WIDTHS = {32, 64, 128, 192, 256}.
+    slice of a wider tensor: the C entry takes the row stride).  Head width C / num_heads in SDPA_WIDTHS = {32, 64, 128, 192, 256}:
+    this entry pads nothing.  All ten classes of modules/mhsa.py (Attention, SRAttention, SRAttentionRelPos, SRConvAttention,
+    GlobalAttention, Broad_Attention, QKVSplitAttention, KNNAttention, ConvAttention, PoolingAttention) and ViT's Attention zero-pad
+    any other width up to 256 onto the next of these (attn_head_width, head_padded) before they call it.
     bias entries are finite or -inf (masked_fill masks): a -inf key gets weight 0, a row with no finite logit comes out NaN, as
     torch.softmax gives it."""
     p = _prec(precision)
@@ -1669,7 +1672,7 @@ def topk_mask_(logits, k):
 def head_padded(weight, bias, groups, d, dp, axis):
     """Linear parameters with every head's slice of width d padded to dp with zeros -- along the output features (axis 0: weight rows
     and bias, `groups` = number of head slices) or the input features (axis 1: weight columns).  Lets head widths outside the
-    attention kernel's {32, 64} run on it: zero q/k columns add nothing to the logits, zero v columns produce zero outputs that the
+    attention kernel's SDPA_WIDTHS run on it: zero q/k columns add nothing to the logits, zero v columns produce zero outputs that the
     padded projection ignores.  Cached with the parameters."""
     def build():
         w = weight.detach()

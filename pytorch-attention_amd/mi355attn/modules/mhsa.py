@@ -6,6 +6,10 @@ attention core (csrc/sdpa_general.hip).  Module level only: the surrounding mode
                                                          conv (kernel == stride == sr_ratio) + BatchNorm2d
   SRAttentionRelPos    cmt.py:75-111                     the same with an additive relative-position term (heads, N, N')
   SRConvAttention      segformer.py:17-50                q Linear, fused kv Linear; K, V from a dense conv (kernel == stride == sr_ratio)
+
+Every class runs any head width up to 256: a width outside functional.SDPA_WIDTHS is zero padded onto the next kernel width
+(functional.head_padded: output features of the q / k / v projections, input features of proj); a wider head is a ValueError
+(functional.attn_head_width).  At a kernel width no padded tensor is built.
 """
 import torch
 from torch import nn
@@ -41,15 +45,16 @@ class Attention(nn.Module):
 
     def forward(self, x):
         _dropout_is_identity(self)
-        C = x.shape[-1]
-        qkv = F.linear(x, self.qkv.weight, self.qkv.bias, precision=self.precision)
-        ctx = F.sdpa_general(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], self.num_heads, self.scale, precision=self.precision)
-        return F.linear(ctx, self.proj.weight, self.proj.bias, precision=self.precision)
+        out, _, _ = _fused_qkv_attention(x, self.qkv, self.proj, self.num_heads, x.shape[-1] // self.num_heads, self.scale, self.precision)
+        return out
 
 
 class SRAttention(nn.Module):
     """pvt.py:53-54 / cmt.py:73-74: `sr_ratio` is the THIRD positional parameter (both files call `Attention(dim, num_heads,
-    sr_ratio, ...)` positionally, pvt.py:98, cmt.py:119); segformer.py:18 has it last (SRConvAttention below)."""
+    sr_ratio, ...)` positionally, pvt.py:98, cmt.py:119); segformer.py:18 has it last (SRConvAttention below).
+
+    With sr_ratio > 1, H and W must be multiples of sr_ratio: the reduction kernel (mi355_dwconv_patch_tokens_fwd) states that
+    envelope and raises Mi355Error outside it, where the reference's strided conv floors (drops the last rows / columns)."""
 
     def __init__(self, dim, num_heads=8, sr_ratio=1, qkv_bias=False, attn_drop=0, proj_drop=0, precision=None):
         super().__init__()
@@ -76,17 +81,25 @@ class SRAttention(nn.Module):
 
     def forward(self, x, H, W, relative_pos=None):
         _dropout_is_identity(self)
-        p = self.precision
-        q = F.linear(x, self.q.weight, self.q.bias, precision=p)
+        p, h = self.precision, self.num_heads
+        d = x.shape[-1] // h
+        dp = F.attn_head_width(d)
+        (wq, bq), (wk, bk), (wv, bv) = ((l.weight, l.bias) for l in (self.q, self.k, self.v))
+        wp = self.proj.weight
+        if dp != d:
+            (wq, bq), (wk, bk), (wv, bv) = (F.head_padded(l.weight, l.bias, h, d, dp, 0) for l in (self.q, self.k, self.v))
+            wp = F.head_padded(self.proj.weight, None, h, d, dp, 1)[0]
+        q = F.linear(x, wq, bq, precision=p)
         src = self._kv_source(x, H, W)
-        k = F.linear(src, self.k.weight, self.k.bias, precision=p)
-        v = F.linear(src, self.v.weight, self.v.bias, precision=p)
-        ctx = F.sdpa_general(q, k, v, self.num_heads, self.scale, bias=relative_pos, precision=p)
-        return F.linear(ctx, self.proj.weight, self.proj.bias, precision=p)
+        k = F.linear(src, wk, bk, precision=p)
+        v = F.linear(src, wv, bv, precision=p)
+        ctx = F.sdpa_general(q, k, v, h, self.scale, bias=relative_pos, precision=p)
+        return F.linear(ctx, wp, self.proj.bias, precision=p)
 
 
 class SRAttentionRelPos(SRAttention):
-    """cmt.py:75-111: `relative_pos` (heads, N, N') is a required forward argument, added to the scaled logits."""
+    """cmt.py:75-111: `relative_pos` (heads, N, N') is a required forward argument, added to the scaled logits.  H and W must be
+    multiples of sr_ratio, as for SRAttention (Mi355Error otherwise; the reference floors)."""
 
     def forward(self, x, H, W, relative_pos):
         _dropout_is_identity(self)
@@ -94,6 +107,9 @@ class SRAttentionRelPos(SRAttention):
 
 
 class SRConvAttention(nn.Module):
+    """segformer.py:17-50.  The reduction is a dense strided conv on the GEMM engine (functional.conv2d_tokens), which floors
+    H / sr_ratio and W / sr_ratio as the reference does: unlike SRAttention there is no `H % sr_ratio` limit here."""
+
     def __init__(self, dim, num_heads=8, qkv_bias=False, attn_drop=0, proj_drop=0, sr_ratio=1, precision=None):
         super().__init__()
         assert dim % num_heads == 0
@@ -112,21 +128,29 @@ class SRConvAttention(nn.Module):
 
     def forward(self, x, H, W):
         _dropout_is_identity(self)
-        p = self.precision
-        C = x.shape[-1]
-        q = F.linear(x, self.q.weight, self.q.bias, precision=p)
+        p, h = self.precision, self.num_heads
+        d = x.shape[-1] // h
+        dp = F.attn_head_width(d)
+        wq, bq, wkv, bkv, wp = self.q.weight, self.q.bias, self.kv.weight, self.kv.bias, self.proj.weight
+        if dp != d:
+            wq, bq = F.head_padded(self.q.weight, self.q.bias, h, d, dp, 0)
+            wkv, bkv = F.head_padded(self.kv.weight, self.kv.bias, 2 * h, d, dp, 0)
+            wp = F.head_padded(self.proj.weight, None, h, d, dp, 1)[0]
+        Cp = h * dp
+        q = F.linear(x, wq, bq, precision=p)
         src = x
         if self.sr_ratio > 1:
             src, _ = F.conv2d_tokens(x, self.sr.weight, self.sr.bias, self.sr_ratio, self.sr_ratio, 0, 1, hw=(H, W), precision=p)
-        kv = F.linear(src, self.kv.weight, self.kv.bias, precision=p)
-        ctx = F.sdpa_general(q, kv[..., :C], kv[..., C:], self.num_heads, self.scale, precision=p)
-        return F.linear(ctx, self.proj.weight, self.proj.bias, precision=p)
+        kv = F.linear(src, wkv, bkv, precision=p)
+        ctx = F.sdpa_general(q, kv[..., :Cp], kv[..., Cp:], h, self.scale, precision=p)
+        return F.linear(ctx, wp, self.proj.bias, precision=p)
 
 
 # ---- the remaining copies (dilateformer, bvit, efficientformer, kvt, cvt) -------------------------------------------------------------
 def _fused_qkv_attention(x, qkv, proj, heads, d, scale, precision, bias_fn=None, qkv_precision=None):
-    """x (B,N,C) -> proj(softmax(q k^T scale [+ bias]) v) for a fused qkv Linear laid out [3][heads][d]; head widths other than 32 / 64
-    run zero padded (functional.head_padded).  Returns (out, qkv tensor, padded width) so that callers can expose q / k / v."""
+    """x (B,N,C) -> proj(softmax(q k^T scale [+ bias]) v) for a fused qkv Linear laid out [3][heads][d]; head widths outside
+    functional.SDPA_WIDTHS run zero padded (functional.head_padded), the kernel widths on the parameters themselves.  Returns
+    (out, qkv tensor, padded width) so that callers can expose q / k / v."""
     dp = F.attn_head_width(d)
     if dp == d:
         wq, bq, wp = qkv.weight, qkv.bias, (proj.weight if proj is not None else None)

@@ -17,6 +17,10 @@ Writes, under tests/golden/live/:
                       it holds at most 257 values, else 257 strided samples), its sum and absolute sum, fp64 checksums of the state_dict
                       and of the input, and for `error` rows the name of the exception the reference raises (tests/test_models_cpu.py);
                       --models-only rewrites this file alone;
+  mhsa.npz            per row of tests/mhsa_cases.py (the multi-head copies of modules/mhsa.py, non-trivial parameters): the routes.npz
+                      record of the reference's own class (Broad_Attention: of the concatenation cases.flat_out makes), and for the
+                      error rows the name of the exception the reference raises ("" where it runs) (tests/test_mhsa_cases_cpu.py);
+                      --mhsa-only rewrites this file alone;
 and tests/golden/reference_names.json: the public names of every reference module a drop-in shim mirrors (tests/test_signatures.py).
 """
 import argparse
@@ -74,11 +78,36 @@ def _model_records(model_cases, ref_cls, sample_index):
     return rec
 
 
+def _mhsa_records(mhsa_cases, ref_cls, sample_index, flat_out):
+    """mhsa.npz: per row of tests/mhsa_cases.py, built from the reference's class by mhsa_cases.build_row."""
+    rec = {"ids": np.array([r["id"] for r in mhsa_cases.ALL_ROWS])}
+    for r in mhsa_cases.ALL_ROWS:
+        m, x = mhsa_cases.build_row(r, ref_cls(r["mod"], r["cls"]))
+        rid = r["id"] + "__"
+        if "error" in r:
+            try:
+                m(x, *mhsa_cases.fwd_args(r))
+                rec[rid + "error"] = np.array("")
+            except Exception as e:               # the type is what the record keeps
+                rec[rid + "error"] = np.array(type(e).__name__)
+            continue
+        y = flat_out(m(x, *mhsa_cases.fwd_args(r)))
+        sd = m.state_dict()
+        yf = y.reshape(-1)
+        rec.update({rid + "y_samples": yf[sample_index(yf.numel())].numpy(), rid + "y_shape": np.array(list(y.shape)),
+                    rid + "y_sum": np.array(float(yf.double().sum())), rid + "y_abs": np.array(float(yf.double().abs().sum())),
+                    rid + "x_sum": np.array(float(x.double().sum())), rid + "p_keys": np.array(list(sd)),
+                    rid + "p_sum": np.array([float(v.double().sum()) for v in sd.values()]),
+                    rid + "p_abs": np.array([float(v.double().abs().sum()) for v in sd.values()])})
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", required=True, help="the reference checkout")
     ap.add_argument("--routes-only", action="store_true", help="write tests/golden/live/routes.npz only")
     ap.add_argument("--models-only", action="store_true", help="write tests/golden/live/models.npz only")
+    ap.add_argument("--mhsa-only", action="store_true", help="write tests/golden/live/mhsa.npz only")
     args = ap.parse_args()
     ref_root = os.path.abspath(args.ref)
     sys.dont_write_bytecode = True
@@ -89,7 +118,8 @@ def main():
     from test_aten_seq_cpu import CASES                      # shapes of the cases (drop-in side; imported before the reference is)
     from route_cases import ROWS, prep_nontrivial
     import model_cases
-    from cases import sample_index
+    import mhsa_cases
+    from cases import flat_out, sample_index
     shapes = {c[0]: c[2] for c in CASES}
     # the drop-in package exports the same import paths: forget its modules, then import the reference's
     sys.path.insert(0, os.path.join(ROOT, "pytorch-attention_amd"))
@@ -109,6 +139,12 @@ def main():
 
     files = {}
     with torch.no_grad():
+        files["mhsa"] = _mhsa_records(mhsa_cases, ref_cls, sample_index, flat_out)
+        if args.mhsa_only:
+            os.makedirs(os.path.join(HERE, "live"), exist_ok=True)
+            np.savez_compressed(os.path.join(HERE, "live", "mhsa.npz"), **files["mhsa"])
+            print("wrote mhsa.npz (%d rows)" % len(mhsa_cases.ALL_ROWS))
+            return
         files["models"] = _model_records(model_cases, ref_cls, sample_index)
         if args.models_only:
             os.makedirs(os.path.join(HERE, "live"), exist_ok=True)
