@@ -294,7 +294,13 @@ int    mi355_cbam16_fwd(const void* x, const float* w1, const float* w2, const f
 size_t mi355_double_attn_workspace_bytes(int B, int C, int cm, int cn, int H, int W);
 /* The same for one precision mode (any mode fits in the size above): the 16-bit modes at c_m = c_n = 128, C in {128, 256} run in two
  * passes over the image (x read once, y written once, a 16-bit softmax(V) in between) and need a fraction of it.  Option "da_fused" = 0
- * selects the seven-launch pipeline for every shape. */
+ * selects the seven-launch pipeline for every shape.
+ * Routes of mi355_double_attn_fwd: the one-kernel and two-pass routes listed at mi355_double_attn16_fwd (16-bit modes only); the general
+ * seven-launch route where H*W, C, c_m and c_n are multiples of 4 (x, y and the workspace 16-byte aligned, else MI355_EUNSUPPORTED);
+ * the ragged route for every other shape -- a 7 x 7 or 65 x 65 map, odd channel counts: x is staged once, by scalar loads, into a
+ * zero-padded (round_up(C, 4) x round_up(H*W, 4)) image in the workspace, the parameters are padded likewise, both softmaxes run
+ * over the valid entries only, and y is stored element by element; x and y may sit at any alignment.  The workspace queries name a
+ * larger size for such shapes and the size they always named for every other. */
 size_t mi355_double_attn_ws_bytes(int B, int C, int cm, int cn, int H, int W, int precision);
 int    mi355_double_attn_fwd(const float* x, const float* wA, const float* bA, const float* wB, const float* bB,
                              const float* wV, const float* bV, const float* wP, const float* bP, float* y,
@@ -310,9 +316,11 @@ int    mi355_double_attn_fwd(const float* x, const float* wA, const float* bA, c
  *                  shapes, as mi355_double_attn_ws_bytes does: parameters off 16-byte alignment take that route);
  *   two passes     c_m = c_n = 128, C in {128, 256}, H*W a multiple of 4 (the fp32 entry's envelope): pass 1 stages 8-byte row pieces of
  *                  x into the X^T operand image, pass 2 stores y in 16 bit; the 16-bit V tensor in between as in the fp32 entry;
- *   general        everything else mi355_double_attn_fwd takes (H*W, C, c_m, c_n multiples of 4, else MI355_EUNSUPPORTED): x is transposed
- *                  to 16-bit tokens directly where C % 64 == 0 and widened to fp32 in the workspace otherwise; the fp32 result of the
- *                  last product is rounded into y.
+ *   general        everything else with H*W, C, c_m and c_n multiples of 4 (x, y and the workspace 16-byte aligned, else
+ *                  MI355_EUNSUPPORTED): x is transposed to 16-bit tokens directly where C % 64 == 0 and widened to fp32 in the workspace
+ *                  otherwise; the fp32 result of the last product is rounded into y;
+ *   ragged         every other shape, as in mi355_double_attn_fwd: the staging kernel widens x into the zero-padded fp32 image, and
+ *                  the fp32 result of the last product is rounded into y element by element (x and y at any alignment).
  * From the operand tile onwards the fused routes keep the tile size, tile order and wave ownership of the fp32-I/O kernels: y equals
  * mi355_double_attn_fwd(precision = io) on the widened x, rounded once.  Precision 0 on 16-bit tensors is the caller's: widen, call
  * mi355_double_attn_fwd, round.  Validation (io, sizes, pointers, workspace size) precedes every HIP call: MI355_EINVAL. */
@@ -479,13 +487,18 @@ int mi355_sk_fwd(const float* x, const float* const* params, float* y, int B, in
                  void* workspace, size_t workspace_bytes, mi355_stream_t stream);
 
 /* DANet dual attention (dual_attention.py).  CAM :35-42: y = beta * softmax(X X^T) X + x with X = x viewed as (C, HW) per image; beta is
- * a 1-element device array; H*W and C multiples of 4; workspace of mi355_cam_workspace_bytes (the Gram matrices).  The logits are
+ * a 1-element device array; workspace of mi355_cam_ws_bytes.  The logits are
  * unscaled sums over HW, so X X^T always runs in the fp32-class split-bf16 mode; `precision` selects the operand format of attn . X.
+ * Routes: H*W and C multiples of 4 (x and y 16-byte aligned, else MI355_EUNSUPPORTED) -- x is the engine's operand as it lies, and the
+ * workspace holds the Gram matrices: mi355_cam_ws_bytes equals mi355_cam_workspace_bytes(B, C); any other shape -- x is staged once
+ * into a zero-padded (round_up(C, 4) x round_up(H*W, 4)) image behind the Gram matrices (mi355_cam_ws_bytes is larger), the softmax
+ * runs over the C valid columns, y is stored element by element, and x and y may sit at any alignment.  fp32 x only.
  * PAM :20-28 is composed by the caller from mi355_conv2d_tokens_fwd (the three 1x1 convs as one token-major GEMM),
  * mi355_sdpa_general_fwd (one head of width C, scale 1) and mi355_tokens_to_nchw_axpy_fwd:
  *   y[b,c,p] = alpha[0] * tokens[b,p,c] + x[b,c,p]      tokens (B,HW,C), x / y (B,C,HW), alpha a 1-element device array;
  *   alpha == NULL means 1, x == NULL means 0 (a plain token-major -> NCHW transpose). */
 size_t mi355_cam_workspace_bytes(int B, int C);
+size_t mi355_cam_ws_bytes(int B, int C, int H, int W);
 int mi355_cam_fwd(const float* x, const float* beta, float* y, int B, int C, int H, int W, int precision, void* workspace,
                   size_t workspace_bytes, mi355_stream_t stream);
 int mi355_tokens_to_nchw_axpy_fwd(const float* tokens, const float* x, const float* alpha, float* y, int B, int HW, int C,

@@ -109,6 +109,12 @@ int    double_attn_fused(const void* x, const float* wA, const float* bA, const 
 bool   double_attn_small_ok(int B, int C, int cm, int cn, int HW, int precision);
 int    double_attn_small(const void* x, const float* wA, const float* bA, const float* wB, const float* bB, const float* wV, const float* bV,
                          const float* wP, const float* bP, void* y, int B, int C, int HW, int precision, bool io16, hipStream_t st);
+// Maps whose H*W or channel counts are no multiples of 4 (ragged_maps.hip; DoubleAttention and CAM): x (B, C, HW) in fp32 (io 0) or the
+// 16-bit type of io -> the GEMM engine's K-major operand xp (B, round_up(C, 4), round_up(HW, 4)) fp32 with zero pads (report16: an fp32 x
+// staged for fp16 operands reports range code 8), and the in-place softmax over the first `cols` entries of rows of pitch `ld` that
+// writes 0 behind them (scale: a 1-element device array or null).
+int  ragged_stage(const void* x, int io, float* xp, int B, int C, int HW, bool report16, hipStream_t st);
+void ragged_softmax_rows(float* p, int imgs, int rows_per_img, int cols, int ld, long img_stride, const float* scale, hipStream_t st);
 // The sweeps over a 16-bit x of the axis gates (axis_attn_io16.hip; io = 1 IEEE half, 2 bfloat16), called by the *16 entries of
 // axis_attn.hip: fp32 results into the workspace, apply writes y in the I/O type.  mode of axis16_chan_reduce: 0 = 1x1 conv to K <= kmax
 // planes (kmax 4 / 8 / 16 / 32), 1 = mean and max; axis16_plane_pool returns what launch_plane_pool returns for the shape.

@@ -173,6 +173,53 @@ __global__ __launch_bounds__(256) void da_round16_kernel(const float* __restrict
     reinterpret_cast<t4*>(y)[i] = t4{(T)v.x, (T)v.y, (T)v.z, (T)v.w};
 }
 
+// ---- the ragged route: H*W, C, c_m or c_n no multiple of 4 -------------------------------------------------------------------------
+// The parameters in the padded layout the engine wants, in one launch: Wcat (M3p x Cp) = [WA; WB; WV] with c_m and c_n each rounded up
+// to 4 (M3p = cmp + 2 cnp), bcat (M3p) and WP (C x cmp); pad rows and pad columns are zero.
+__global__ __launch_bounds__(256) void da_pack_ragged_kernel(const float* __restrict__ wA, const float* __restrict__ bA, const float* __restrict__ wB,
+                                                            const float* __restrict__ bB, const float* __restrict__ wV, const float* __restrict__ bV,
+                                                            const float* __restrict__ wP, float* __restrict__ Wcat, float* __restrict__ bcat,
+                                                            float* __restrict__ WPp, int C, int Cp, int cm, int cmp, int cn, int cnp) {
+    const int M3p = cmp + 2 * cnp;
+    const long nW = (long)M3p * Cp, i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < nW + M3p) {
+        const bool bias = i >= nW;
+        const int r = bias ? (int)(i - nW) : (int)(i / Cp), c = bias ? 0 : (int)(i % Cp);
+        const int seg = r < cmp ? 0 : (r < cmp + cnp ? 1 : 2), rr = r - (seg == 0 ? 0 : (seg == 1 ? cmp : cmp + cnp));
+        const float* w = seg == 0 ? wA : (seg == 1 ? wB : wV);
+        const float* b = seg == 0 ? bA : (seg == 1 ? bB : bV);
+        const bool live = rr < (seg == 0 ? cm : cn) && c < C;
+        if (bias) bcat[r] = live ? b[rr] : 0.f;
+        else      Wcat[i] = live ? w[(long)rr * C + c] : 0.f;
+    } else if (i < nW + M3p + (long)C * cmp) {
+        const long j = i - nW - M3p;
+        const int o = (int)(j / cmp), k = (int)(j % cmp);
+        WPp[j] = k < cm ? wP[(long)o * cm + k] : 0.f;
+    }
+}
+
+// da_round16_kernel for any element count and any alignment of y: B*C*H*W need not be a multiple of 4 here.
+template <typename T>
+__global__ __launch_bounds__(256) void da_round16_ragged_kernel(const float* __restrict__ s, T* __restrict__ y, long n) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) y[i] = (T)s[i];
+}
+
+inline int up4(int v) { return (v + 3) & ~3; }
+inline bool ragged_shape(int C, int cm, int cn, int HW) { return ((C | cm | cn | HW) & 3) != 0; }
+
+// workspace of the ragged route: xp (B, Cp, HWp) | Wcat (M3p x Cp) | bcat (M3p) | WP (C x cmp) | ABV (B, M3p, HWp) | G (B, cmp, cnp) | M' (B, C, cnp)
+size_t ragged_workspace(int B, int C, int cm, int cn, int HW) {
+    const size_t Cp = up4(C), cmp = up4(cm), cnp = up4(cn), HWp = up4(HW), M3p = cmp + 2 * cnp;
+    return r16((size_t)B * Cp * HWp * 4) + r16(M3p * Cp * 4) + r16(M3p * 4) + r16((size_t)C * cmp * 4) + r16((size_t)B * M3p * HWp * 4) +
+           r16((size_t)B * cmp * cnp * 4) + r16((size_t)B * C * cnp * 4);
+}
+
+// The seven launches behind both entries for such shapes.  x is fp32 (io 0) or in the 16-bit type of io; y is fp32 at leading dimension HW.
+int ragged_route(const void* x, int io, const float* wA, const float* bA, const float* wB, const float* bB, const float* wV,
+                 const float* bV, const float* wP, const float* bP, float* y, int B, int C, int cm, int cn, int HW, int precision, void* ws,
+                 mi355_stream_t stream);
+
 // The seven-launch pipeline behind both entries.  Exactly one of x (fp32) and x16 (the operand type of `precision`, C % 64 == 0) is set.
 int general_route(const float* x, const void* x16, const float* wA, const float* bA, const float* wB, const float* bB,
                   const float* wV, const float* bV, const float* wP, const float* bP, float* y, int B, int C, int cm, int cn, int HW,
@@ -194,6 +241,7 @@ size_t mi355_double_attn_workspace_bytes(int B, int C, int cm, int cn, int H, in
 size_t mi355_double_attn_ws_bytes(int B, int C, int cm, int cn, int H, int W, int precision) {
     if (B > 0 && C > 0 && H > 0 && W > 0 && mi355::opt(mi355::O_DA_FUSED) != 0 && mi355::double_attn_fused_ok(B, C, cm, cn, H * W, precision))
         return mi355::double_attn_fused_workspace(B, C, H * W);
+    if (B > 0 && C > 0 && cm > 0 && cn > 0 && H > 0 && W > 0 && ragged_shape(C, cm, cn, H * W)) return ragged_workspace(B, C, cm, cn, H * W);
     return mi355_double_attn_workspace_bytes(B, C, cm, cn, H, W);
 }
 
@@ -209,9 +257,13 @@ int mi355_double_attn_fwd(const float* x, const float* wA, const float* bA, cons
         return mi355::double_attn_small(x, wA, bA, wB, bB, wV, bV, wP, bP, y, B, C, HW, precision, false, static_cast<hipStream_t>(stream));
     if (mi355::double_attn_fused_ok(B, C, cm, cn, HW, precision) && aligned16(x) && aligned16(y) && aligned16(ws) && mi355::opt(mi355::O_DA_FUSED) != 0)
         return mi355::double_attn_fused(x, wA, bA, wB, bB, wV, bV, wP, bP, y, B, C, HW, precision, false, ws, static_cast<hipStream_t>(stream));
-    if ((HW & 3) || (C & 3) || (cm & 3) || (cn & 3) || !aligned16(x) || !aligned16(y) || !aligned16(ws))
-        return mi355::fail(MI355_EUNSUPPORTED, "mi355_double_attn_fwd: H*W, C, c_m, c_n must be multiples of 4 (HW=%d C=%d cm=%d cn=%d)",
-                           HW, C, cm, cn);
+    if (ragged_shape(C, cm, cn, HW)) {                          // x and y at any alignment: staged by scalar loads, stored by scalar stores
+        if (!aligned16(ws)) return mi355::fail(MI355_EUNSUPPORTED, "mi355_double_attn_fwd: the workspace must be 16-byte aligned");
+        return ragged_route(x, 0, wA, bA, wB, bB, wV, bV, wP, bP, y, B, C, cm, cn, HW, precision, ws, stream);
+    }
+    if (!aligned16(x) || !aligned16(y) || !aligned16(ws))
+        return mi355::fail(MI355_EUNSUPPORTED, "mi355_double_attn_fwd: x, y and the workspace must be 16-byte aligned when H*W, C, c_m and c_n "
+                                               "are multiples of 4 (HW=%d C=%d cm=%d cn=%d)", HW, C, cm, cn);
     return general_route(x, nullptr, wA, bA, wB, bB, wV, bV, wP, bP, y, B, C, cm, cn, HW, precision, ws, stream);
 }
 
@@ -223,6 +275,7 @@ size_t mi355_double_attn16_ws_bytes(int B, int C, int cm, int cn, int H, int W, 
     if (mi355::opt(mi355::O_DA_FUSED) != 0 && mi355::double_attn_fused_ok(B, C, cm, cn, H * W, io))
         return mi355::double_attn_fused_workspace(B, C, H * W);
     const size_t n = (size_t)B * C * H * W;
+    if (ragged_shape(C, cm, cn, H * W)) return r16(n * 4) + ragged_workspace(B, C, cm, cn, H * W);      // the fp32 result | the ragged route's
     return r16(n * 4) + ((C & 63) ? r16(n * 4) : 0) + mi355_double_attn_workspace_bytes(B, C, cm, cn, H, W);
 }
 
@@ -240,11 +293,22 @@ int mi355_double_attn16_fwd(const void* x, const float* wA, const float* bA, con
         return mi355::double_attn_small(x, wA, bA, wB, bB, wV, bV, wP, bP, y, B, C, HW, io, true, st);
     if (mi355::double_attn_fused_ok(B, C, cm, cn, HW, io) && aligned16(x) && aligned16(y) && aligned16(ws) && mi355::opt(mi355::O_DA_FUSED) != 0)
         return mi355::double_attn_fused(x, wA, bA, wB, bB, wV, bV, wP, bP, y, B, C, HW, io, true, ws, st);
-    // the general route refuses exactly what mi355_double_attn_fwd refuses
-    if ((HW & 3) || (C & 3) || (cm & 3) || (cn & 3) || !aligned16(x) || !aligned16(y) || !aligned16(ws))
-        return mi355::fail(MI355_EUNSUPPORTED, "mi355_double_attn16_fwd: H*W, C, c_m, c_n must be multiples of 4 (HW=%d C=%d cm=%d cn=%d)",
-                           HW, C, cm, cn);
     const size_t n = (size_t)B * C * HW;
+    if (ragged_shape(C, cm, cn, HW)) {                          // the staging kernel widens x; the fp32 result is rounded element by element
+        if (!aligned16(ws)) return mi355::fail(MI355_EUNSUPPORTED, "mi355_double_attn16_fwd: the workspace must be 16-byte aligned");
+        float* y32 = static_cast<float*>(ws);
+        int rc = ragged_route(x, io, wA, bA, wB, bB, wV, bV, wP, bP, y32, B, C, cm, cn, HW, io, static_cast<char*>(ws) + r16(n * 4), stream);
+        if (rc) return rc;
+        MI355_TRACE(st, "da_round16_ragged_kernel io=%d n=%ld", io, (long)n);
+        if (io == 1) da_round16_ragged_kernel<_Float16><<<cdiv((long)n, 256), 256, 0, st>>>(y32, static_cast<_Float16*>(y), (long)n);
+        else         da_round16_ragged_kernel<__bf16><<<cdiv((long)n, 256), 256, 0, st>>>(y32, static_cast<__bf16*>(y), (long)n);
+        MI355_LAUNCH_CHECK();
+        return MI355_OK;
+    }
+    // the general route refuses exactly what mi355_double_attn_fwd refuses
+    if (!aligned16(x) || !aligned16(y) || !aligned16(ws))
+        return mi355::fail(MI355_EUNSUPPORTED, "mi355_double_attn16_fwd: x, y and the workspace must be 16-byte aligned when H*W, C, c_m and c_n "
+                                               "are multiples of 4 (HW=%d C=%d cm=%d cn=%d)", HW, C, cm, cn);
     const long n4 = (long)(n / 4);
     // (the size of the query for every shape that can get here; checked again because this route writes all of it)
     MI355_CHECK_ARG(ws_bytes >= r16(n * 4) + ((C & 63) ? r16(n * 4) : 0) + mi355_double_attn_workspace_bytes(B, C, cm, cn, H, W));
@@ -340,6 +404,58 @@ int general_route(const float* x, const void* x16, const float* wA, const float*
                                 precision, st);
     if (rc) return rc;
     rc = mi355::gemm_kn_batched(Mp, ABV + (long)(cm + cn) * HW, bP, nullptr, y, B, C, HW, cn, cn, HW, HW, (long)C * cn, sABV,
+                                (long)C * HW, MI355_ACT_NONE, precision, st);
+    if (rc) return rc;
+    MI355_LAUNCH_CHECK();
+    return MI355_OK;
+}
+
+int ragged_route(const void* x, int io, const float* wA, const float* bA, const float* wB, const float* bB, const float* wV,
+                 const float* bV, const float* wP, const float* bP, float* y, int B, int C, int cm, int cn, int HW, int precision, void* ws,
+                 mi355_stream_t stream) {
+    const int Cp = up4(C), cmp = up4(cm), cnp = up4(cn), HWp = up4(HW), M3p = cmp + 2 * cnp;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* p = static_cast<char*>(ws);
+    float* xp = reinterpret_cast<float*>(p);   p += r16((size_t)B * Cp * HWp * 4);
+    float* Wcat = reinterpret_cast<float*>(p); p += r16((size_t)M3p * Cp * 4);
+    float* bcat = reinterpret_cast<float*>(p); p += r16((size_t)M3p * 4);
+    float* WPp = reinterpret_cast<float*>(p);  p += r16((size_t)C * cmp * 4);
+    float* ABV = reinterpret_cast<float*>(p);  p += r16((size_t)B * M3p * HWp * 4);
+    float* G = reinterpret_cast<float*>(p);    p += r16((size_t)B * cmp * cnp * 4);
+    float* Mp = reinterpret_cast<float*>(p);
+    // the one read of x: scalar guarded loads (an image plane starts at any 4-byte -- 2-byte for 16-bit x -- address), zero pads
+    int rc = mi355::ragged_stage(x, io, xp, B, C, HW, io == 0 && precision == MI355_PREC_FP16, st);
+    if (rc) return rc;
+    {
+        const long n = (long)M3p * Cp + M3p + (long)C * cmp;
+        MI355_TRACE(st, "da_pack_ragged_kernel C=%d cm=%d cn=%d", C, cm, cn);
+        da_pack_ragged_kernel<<<cdiv(n, 256), 256, 0, st>>>(wA, bA, wB, bB, wV, bV, wP, Wcat, bcat, WPp, C, Cp, cm, cmp, cn, cnp);
+    }
+    // [A; Bm; V] (M3p x HWp) = Wcat xp + bcat: pad ROWS come out zero (zero weights, zero bias), pad COLUMNS hold the bias
+    const long sABV = (long)M3p * HWp;
+    rc = mi355::gemm_kn_batched(Wcat, xp, bcat, nullptr, ABV, B, M3p, HWp, Cp, Cp, HWp, HWp, 0, (long)Cp * HWp, sABV, MI355_ACT_NONE, precision, st);
+    if (rc) return rc;
+    // softmax over the HW valid positions of the c_n valid rows of Bm, zero into its pad columns: G = A Bm^T over K = HWp is then exact
+    // (A's pad columns meet zeros) and the pad rows and columns of G are zero (A's and Bm's pad rows are)
+    mi355::ragged_softmax_rows(ABV + (long)cmp * HWp, B, cn, HW, HWp, sABV, nullptr, st);
+    {
+        // softmax over the c_n valid channels of V at every position of the padded row; the pad rows stay zero, which makes M' V over
+        // K = cnp exact, and the pad positions (a softmax of the biases) lie beyond the N = HW columns of the last product
+        const long total = (long)B * HWp;
+        float* Vp = ABV + (long)(cmp + cnp) * HWp;
+        if (cn <= 64)       softmax_cols_reg_kernel<16><<<cdiv(total, 64), 256, 0, st>>>(Vp, cn, HWp, sABV, total);
+        else if (cn <= 128) softmax_cols_reg_kernel<32><<<cdiv(total, 64), 256, 0, st>>>(Vp, cn, HWp, sABV, total);
+        else if (cn <= 256) softmax_cols_reg_kernel<64><<<cdiv(total, 64), 256, 0, st>>>(Vp, cn, HWp, sABV, total);
+        else                softmax_cols_kernel<<<cdiv(total, 256), 256, 0, st>>>(Vp, cn, HWp, sABV, total);
+    }
+    rc = mi355::gemm_nt_batched(ABV, ABV + (long)cmp * HWp, G, B, cmp, cnp, HWp, HWp, HWp, cnp, sABV, sABV, (long)cmp * cnp, precision, st);
+    if (rc) return rc;
+    rc = mi355::gemm_kn_batched(WPp, G, nullptr, nullptr, Mp, B, C, cnp, cmp, cmp, cnp, cnp, 0, (long)cmp * cnp, (long)C * cnp, MI355_ACT_NONE,
+                                precision, st);                 // M' = WP G (C x cnp), as in general_route
+    if (rc) return rc;
+    // y = M' V + bP at leading dimension HW: the engine stores element by element where ldc or the image base is off 16 bytes, and its
+    // 16-byte loads of V at columns up to HWp stay inside the padded row
+    rc = mi355::gemm_kn_batched(Mp, ABV + (long)(cmp + cnp) * HWp, bP, nullptr, y, B, C, HW, cnp, cnp, HWp, HW, (long)C * cnp, sABV,
                                 (long)C * HW, MI355_ACT_NONE, precision, st);
     if (rc) return rc;
     MI355_LAUNCH_CHECK();

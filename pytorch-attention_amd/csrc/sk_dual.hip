@@ -359,20 +359,47 @@ int mi355_sk_fwd(const float* x, const float* const* p, float* y, int B, int Cin
 
 size_t mi355_cam_workspace_bytes(int B, int C) { return (B <= 0 || C <= 0) ? 0 : 4 * fl((size_t)B * C * C) + 256; }
 
+// The same with the map size: H*W or C off a multiple of 4 adds the padded image (B, Cp, HWp) behind the (Cp x Cp) Gram matrices.
+size_t mi355_cam_ws_bytes(int B, int C, int H, int W) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
+    const size_t HW = (size_t)H * W, Cp = ((size_t)C + 3) & ~(size_t)3, HWp = (HW + 3) & ~(size_t)3;
+    if (((HW | (size_t)C) & 3) == 0) return mi355_cam_workspace_bytes(B, C);
+    return 4 * (fl((size_t)B * Cp * Cp) + fl((size_t)B * Cp * HWp)) + 256;
+}
+
 int mi355_cam_fwd(const float* x, const float* beta, float* y, int B, int C, int H, int W, int precision, void* workspace,
                   size_t workspace_bytes, mi355_stream_t stream) {
     MI355_CHECK_ARG(x && beta && y && workspace && B > 0 && C > 0 && H > 0 && W > 0);
     MI355_CHECK_ARG(precision >= MI355_PREC_STRICT && precision <= MI355_PREC_BF16);
-    MI355_CHECK_ARG(workspace_bytes >= mi355_cam_workspace_bytes(B, C) && aligned16(workspace));
+    MI355_CHECK_ARG(workspace_bytes >= mi355_cam_ws_bytes(B, C, H, W) && aligned16(workspace));
     const long HW = (long)H * W;
-    if ((HW & 3) || (C & 3) || !aligned16(x) || !aligned16(y))
-        return mi355::fail(MI355_EUNSUPPORTED, "mi355_cam_fwd: H*W and C must be multiples of 4 (HW=%ld C=%d)", HW, C);
     hipStream_t st = static_cast<hipStream_t>(stream);
     float* G = static_cast<float*>(workspace);                  // x_ x_^T: dual_attention.py:38
+    int rc;
+    if ((HW & 3) || (C & 3)) {
+        MI355_CHECK_ARG(HW <= 0x7ffffffc);                     // round_up(HW, 4) is an int leading dimension
+        // Ragged map: x staged into the zero-padded (Cp x HWp) operand (x and y at any alignment), the Gram product over K = HWp (the
+        // pad columns add zeros), the softmax over the C valid columns of a Cp-wide G with zeros behind them, and attn @ x_ + x over
+        // K = Cp into y at leading dimension HW, which the engine stores element by element; the residual is read from x itself.
+        const int Cp = (C + 3) & ~3, HWp = (int)((HW + 3) & ~3l);
+        float* xp = G + fl((size_t)B * Cp * Cp);
+        rc = mi355::ragged_stage(x, 0, xp, B, C, (int)HW, false, st);
+        if (rc) return rc;
+        rc = mi355::gemm_nt_batched(xp, xp, G, B, Cp, Cp, HWp, HWp, HWp, Cp, (long)Cp * HWp, (long)Cp * HWp, (long)Cp * Cp, MI355_PREC_STRICT, st);
+        if (rc) return rc;
+        mi355::ragged_softmax_rows(G, B, Cp, C, Cp, (long)Cp * Cp, beta, st);
+        rc = mi355::gemm_kn_batched(G, xp, nullptr, x, y, B, C, (int)HW, Cp, Cp, HWp, (int)HW, (long)Cp * Cp, (long)Cp * HWp, (long)C * HW,
+                                    MI355_ACT_NONE, precision, st);
+        if (rc) return rc;
+        MI355_LAUNCH_CHECK();
+        return MI355_OK;
+    }
+    if (!aligned16(x) || !aligned16(y))
+        return mi355::fail(MI355_EUNSUPPORTED, "mi355_cam_fwd: x and y must be 16-byte aligned when H*W and C are multiples of 4 (HW=%ld C=%d)", HW, C);
     // the logits are unscaled sums over HW (O(HW) on the diagonal): always the fp32-class split-bf16 mode; `precision` selects the
     // operand format of the second product only (softmax weights in [0, 1], residual added in fp32)
-    int rc = mi355::gemm_nt_batched(x, x, G, B, C, C, (int)HW, (int)HW, (int)HW, C, (long)C * HW, (long)C * HW, (long)C * C,
-                                    MI355_PREC_STRICT, st);
+    rc = mi355::gemm_nt_batched(x, x, G, B, C, C, (int)HW, (int)HW, (int)HW, C, (long)C * HW, (long)C * HW, (long)C * C,
+                                MI355_PREC_STRICT, st);
     if (rc) return rc;
     softmax_rows_scaled_kernel<<<cdiv((long)B * C, 4), 256, 0, st>>>(G, C, (long)B * C, beta);      // softmax: :39, beta: :41
     rc = mi355::gemm_kn_batched(G, x, nullptr, x, y, B, C, (int)HW, C, C, (int)HW, (int)HW, (long)C * C, (long)C * HW, (long)C * HW,

@@ -129,6 +129,7 @@ SIGNATURES = {
     "mi355_sk_workspace_bytes": (ctypes.c_size_t, [c_int] * 4),
     "mi355_sk_fwd": (c_int, [c_vp] * 3 + [c_int] * 7 + [c_vp, ctypes.c_size_t, c_vp]),
     "mi355_cam_workspace_bytes": (ctypes.c_size_t, [c_int] * 2),
+    "mi355_cam_ws_bytes": (ctypes.c_size_t, [c_int] * 4),
     "mi355_cam_fwd": (c_int, [c_vp] * 3 + [c_int] * 5 + [c_vp, ctypes.c_size_t, c_vp]),
     "mi355_tokens_to_nchw_axpy_fwd": (c_int, [c_vp] * 4 + [c_int] * 3 + [c_vp]),
     "mi355_dwconv_nchw_tokens_fwd": (c_int, [c_vp] * 4 + [c_int] * 5 + [c_vp]),

@@ -448,7 +448,7 @@ def cam_forward(x, beta, precision=None):
     x = require_device_f32(x, "x")
     B, C, H, W = x.shape
     beta = require_device_f32(beta, "beta").reshape(1)
-    ws = workspace(lib().mi355_cam_workspace_bytes(B, C), x.device)
+    ws = workspace(lib().mi355_cam_ws_bytes(B, C, H, W), x.device)
     y = torch.empty_like(x)
     check(lib().mi355_cam_fwd(dptr(x), dptr(beta), dptr(y), B, C, H, W, _prec(precision), dptr(ws), ws.numel(), stream_ptr(x.device)),
           "mi355_cam_fwd")

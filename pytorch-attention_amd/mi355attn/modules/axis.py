@@ -296,7 +296,8 @@ class PAM(nn.Module):
 
 
 class CAM(nn.Module):
-    """Channel attention of DANet (dual_attention.py:30-42)."""
+    """Channel attention of DANet (dual_attention.py:30-42).  fp32 x of any map size and channel count: where H*W or C is no multiple
+    of 4 (DANet's 65 x 65 map) x is staged once into a zero-padded image in the workspace and y is stored element by element."""
 
     def __init__(self):
         super().__init__()

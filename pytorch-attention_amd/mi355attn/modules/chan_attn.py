@@ -90,7 +90,10 @@ class DoubleAttention(nn.Module):
     and a `precision` of None, 1, 2 or 3 is ignored.  Precision 0 (here, as the package default, or in a strict re-run) widens x, runs
     the strict route and rounds the result once.  y is rounded to nearest even; an fp16 y beyond 65504 is inf, unreported, exactly
     where ``m(x.float()).half()`` is.  Parameters may be fp32 (autocast) or 16-bit (``module.half()``).  An fp16 x can saturate the
-    fp16 operands A, G and M' (range code 8): the forward is range-guarded like an fp32 one and re-runs strict; bf16 cannot."""
+    fp16 operands A, G and M' (range code 8): the forward is range-guarded like an fp32 one and re-runs strict; bf16 cannot.
+
+    Any map size and any channel counts: where H*W, in_channels, c_m or c_n is no multiple of 4 (a 7 x 7 or 65 x 65 map) the ragged
+    route stages x once into a zero-padded image, runs both softmaxes over the valid entries and stores y element by element."""
 
     _mi355_fp16_io_saturates = True          # functional.range_fallback_forward: arm and wait for an fp16 x too
 
