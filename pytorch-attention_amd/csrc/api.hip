@@ -82,7 +82,7 @@ bool stream_is_capturing(hipStream_t st) {
 // Workspaces of the kernels that keep their launch tag in device memory (se_single_kernel, cbam_single_kernel): the host only has to know whether the
 // region was zeroed for this shape.  Under stream capture an unknown region stays unknown (the memset the caller records runs at
 // replay time, not now); a known one needs nothing.
-bool ws_known(const void* region, unsigned long long key, hipStream_t st) {
+static bool ws_known(const void* region, unsigned long long key, hipStream_t st) {
     if (!opt(O_WS_PERSISTENT)) return false;
     std::lock_guard<std::mutex> lk(g_ws_mu);
     auto it = g_ws.find(region);
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void ws_zero_kernel(unsigned* p, size_t words)
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (size_t)gridDim.x * 256) p[i] = 0u;
 }
 }  // namespace
-hipError_t ws_zero_async(void* p, size_t bytes, hipStream_t st) {
+static hipError_t ws_zero_async(void* p, size_t bytes, hipStream_t st) {
     const size_t words = bytes / 4;                                    // callers pass multiples of 4 bytes, 4-byte aligned
     if (!words) return hipSuccess;
     size_t blocks = (words + 1023) / 1024;
@@ -175,7 +175,8 @@ unsigned* sync_err_word() {
     });
     return thread_words();
 }
-unsigned* sync_err_word_on(hipStream_t st) {
+// sync_err_word(), but never allocates inside a stream capture (may return null there)
+static unsigned* sync_err_word_on(hipStream_t st) {
     if (!g_sync_block && stream_is_capturing(st)) return nullptr;         // never allocate pinned memory inside a capture
     return sync_err_word();
 }
@@ -303,6 +304,25 @@ int sync_pending(const char* who) {
     return fail(MI355_ESYNC, "%s: an inter-workgroup exchange of an EARLIER launch of %s ran out of its poll budget (%u sweeps): that launch's "
                 "output is invalid.  Typical cause: fewer workgroups resident than one image needs (partitioned / masked device)",
                 who, names[code < 5 ? code : 0], spin_limit());
+}
+// ---- host half of the granule-exchange protocol (common.h): the one place where a failed zeroing or launch forgets the region ----
+int xch_begin(const char* who, hipStream_t st, unsigned** herr, unsigned* spin) {
+    *herr = sync_err_word_on(st);
+    *spin = spin_limit();
+    return sync_pending(who);
+}
+int xch_zero(const char* who, void* region, unsigned long long key, size_t bytes, hipStream_t st) {
+    if (ws_known(region, key, st)) return MI355_OK;      // unknown history: first use, another layout key, "ws_persistent" off
+    const hipError_t e = ws_zero_async(region, bytes, st);
+    if (e == hipSuccess) return MI355_OK;
+    ws_forget(region);
+    return fail(MI355_EHIP, "%s: zeroing -> %s", who, hipGetErrorString(e));
+}
+int xch_launched(const char* who, const void* region) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return MI355_OK;
+    if (region) ws_forget(region);
+    return fail(MI355_EHIP, "%s: launch -> %s", who, hipGetErrorString(e));
 }
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the CURRENT device and is a LIMIT: remember the largest byte count set per
 // (kernel, device ordinal) and raise it when a later launch asks for more (a kernel whose dynamic LDS depends on the shape --

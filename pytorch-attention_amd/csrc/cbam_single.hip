@@ -19,62 +19,13 @@
 // workgroup) zeroes the ticket word and advances the epoch.  Slots written by earlier launches never look valid, the region is
 // only zeroed when its history is unknown, and because nothing about a launch lives on the host, eager launches and hipGraph
 // replays can share a workspace.  Polls are bounded and raise the workspace error word instead of hanging.
-#include "common.h"
-#include "bufops.h"
+#include "cbam_band.h"
 
 namespace {
 
 using v4f = float __attribute__((ext_vector_type(4)));
-typedef unsigned int u32;
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 
-#define AGENT_RLX __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
-__device__ __forceinline__ void gran_put(rsrc_t g, u32 idx, float v0, float v1, u32 TAG) {
-    const u32x4 v = {__float_as_uint(v0), TAG, __float_as_uint(v1), TAG};
-    __builtin_amdgcn_raw_buffer_store_b128(v, g, idx * 16u, 0, AUX_SC1);      // one write-through 16-byte store
-}
-__device__ __forceinline__ bool gran_get(rsrc_t g, u32 idx, float& v0, float& v1, u32 TAG) {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(g, idx * 16u, 0, AUX_SC1);
-    v0 = __uint_as_float(v.x);
-    v1 = __uint_as_float(v.z);
-    return v.y == TAG && v.w == TAG;
-}
-
-// Cross-lane steps as DPP modifiers (one VALU op each, no LDS round trip like ds_bpermute): quad_perm for xor 1 / xor 2,
-// row_ror for the rotations inside a row of 16 lanes.
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v) {
-    // old = the source itself and bound_ctrl set: every lane of these permutations has a valid source, so no "old" value has to be
-    // materialised and the compiler can fold the permutation into the consuming add / max as a DPP modifier
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float rdlane(float v, int lane) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
-}
-// Sum / max over the SEG (16 or 32) lanes of a segment; the result is only guaranteed in the segment's lane 0 (fixed order).
-template <int SEG>
-__device__ __forceinline__ void seg_reduce(float& s, float& m, int lane) {
-    s += dpp<0xB1>(s);  m = fmaxf(m, dpp<0xB1>(m));                   // xor 1
-    s += dpp<0x4E>(s);  m = fmaxf(m, dpp<0x4E>(m));                   // xor 2
-    s += dpp<0x124>(s); m = fmaxf(m, dpp<0x124>(m));                  // row_ror 4
-    s += dpp<0x128>(s); m = fmaxf(m, dpp<0x128>(m));                  // row_ror 8: every lane of the row holds the row total
-    if (SEG == 32) {                                                  // rows 0+1 -> lane 0, rows 2+3 -> lane 32 (only those two lanes are used)
-        const float s1 = rdlane(s, 16), s3 = rdlane(s, 48), m1 = rdlane(m, 16), m3 = rdlane(m, 48);
-        s += (lane < 32) ? s1 : s3;
-        m = fmaxf(m, (lane < 32) ? m1 : m3);
-    }
-}
-
-struct CbamSingleArgs {
-    const float* x; float* y; const float* w1; const float* w2; const float* wconv;
-    u32x4* g1; u32x4* g2; u32x4* g3; u32* ticket; u32* epoch; u32* err; u32* herr;   // herr: pinned host word every later call checks (api.hip)
-    u32 spin;
-    int C, Cr, H, W, ks, R, Q, NB, cpb, total, nts, wlds;
-#ifdef CBAM_TIMING
-    unsigned long long* dbg;                                          // [gridDim][16 slices][10 stamps] of wall_clock64 (tools/cbam_timing.hip)
-#endif
-};
+struct CbamSingleArgs : CbamArgsT<float> {};       // a type of its own, not an alias: the kernels' symbols keep their names
 
 #ifdef CBAM_TIMING
 #define STAMP(k)                                                                                                  \
@@ -365,48 +316,9 @@ __global__ __launch_bounds__(NT, 4) void cbam_single_kernel(const CbamSingleArgs
     }
 }
 
-struct Geo {
-    int NT, R, Q, NB, SEG, CL, NV, cpb;
-    size_t smem_base, smem_w;
-};
-
-// Rows per band: the most pixels per band with R | H, (R*W) % 4 == 0 and R*W <= NT/4 (four conv lanes per pixel); 0 if none.
-int band_rows(int H, int W, int nt) {
-    int best = 0;
-    for (int R = 1; R <= H; ++R) {
-        if (H % R || (R * W) % 4 || R * W > nt / 4) continue;
-        best = R;
-    }
-    return best;
-}
-
-bool geometry(int nt, int C, int Cr, int H, int W, int ks, Geo& g) {
-    if (!(ks & 1) || ks > 15) return false;
-    const int best = band_rows(H, W, nt);
-    if (!best) return false;
-    g.NT = nt;
-    g.R = best;
-    g.Q = best * W / 4;
-    g.NB = H / best;
-    g.SEG = g.Q > 16 ? 32 : 16;
-    g.CL = nt / g.SEG;
-    const int nv = (C + g.CL - 1) / g.CL;
-    if (nv > 16) return false;
-    g.NV = nv <= 4 ? 4 : (nv <= 8 ? 8 : 16);
-    g.cpb = (C + g.NB - 1) / g.NB;
-    const int pad = (ks - 1) / 2, TW = W + 2 * pad, TH = best + 2 * pad, npx = best * W;
-    auto r4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
-    const size_t Cp = (size_t)g.CL * g.NV > (size_t)C ? (size_t)g.CL * g.NV : r4(C);
-    g.smem_base = (3 * Cp + 2 * r4(Cr) + 2 * r4((size_t)g.NB * g.cpb) + 2 * (size_t)g.CL * g.SEG * 4 +
-                   r4(2 * (size_t)TH * TW) + (size_t)g.SEG * 4 + r4(2 * (size_t)ks * ks)) * 4;
-    (void)npx;
-    g.smem_w = 2 * (size_t)C * Cr * 4;
-    return g.smem_base <= 40 * 1024;
-}
-
 // 512-thread workgroups, two per CU.  (256-thread workgroups with half-size bands -- four exchange chains per CU instead of two -- were
 // measured at 0.72 ms against 0.49 ms at the C2 shape: every phase got slower.  DESIGN.md 6.1.)
-bool pick_geometry(int C, int Cr, int H, int W, int ks, Geo& g) { return geometry(512, C, Cr, H, W, ks, g); }
+bool pick_geometry(int C, int Cr, int H, int W, int ks, Geo& g) { return geometry(512, C, Cr, H, W, ks, false, g); }
 
 }  // namespace
 
@@ -440,8 +352,7 @@ int cbam_single(const float* x, const float* w1, const float* w2, const float* w
     a.ticket = reinterpret_cast<u32*>(a.g3 + (size_t)B * H * W);
     a.err = a.ticket + 1;
     a.epoch = a.ticket + 2;
-    a.herr = sync_err_word_on(st); a.spin = spin_limit();
-    if (int rc = sync_pending("cbam_single")) return rc;
+    if (int rc = xch_begin("cbam_single", st, &a.herr, &a.spin)) return rc;
     a.C = C; a.Cr = Cr; a.H = H; a.W = W; a.ks = ks; a.R = g.R; a.Q = g.Q; a.NB = g.NB; a.cpb = g.cpb;
     const long total_l = (long)B * g.NB;
     if (total_l > (1L << 30)) return fail(MI355_EUNSUPPORTED, "cbam_single: too many slices");
@@ -458,10 +369,7 @@ int cbam_single(const float* x, const float* w1, const float* w2, const float* w
     if (g.NB > grid) return fail(MI355_EUNSUPPORTED, "cbam_single: an image needs %d resident workgroups, the device holds %ld", g.NB, grid);
     if (grid > a.total) grid = a.total;
     const unsigned long long key = ((unsigned long long)B << 48) ^ ((unsigned long long)C << 32) ^ ((unsigned long long)H << 16) ^ (unsigned long long)W ^ ((unsigned long long)g.NT << 40) ^ 0xCBA0000000000000ull;
-    if (!ws_known(extra, key, st)) {                                            // unknown history: granules, ticket, epoch
-        hipError_t e = ws_zero_async(extra, cbam_single_extra_bytes(B, C, H, W), st);
-        if (e != hipSuccess) { ws_forget(extra); return fail(MI355_EHIP, "cbam_single: zeroing -> %s", hipGetErrorString(e)); }
-    }
+    if (int rc = xch_zero("cbam_single", extra, key, cbam_single_extra_bytes(B, C, H, W), st)) return rc;   // granules, ticket, epoch
 #define GO(SEG_, NV_)                                                                              \
     do {                                                                                           \
         if (full) cbam_single_kernel<512, SEG_, NV_, true><<<(int)grid, 512, smem, st>>>(a);       \
@@ -477,9 +385,7 @@ int cbam_single(const float* x, const float* w1, const float* w2, const float* w
         else GO(16, 16);
     }
 #undef GO
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { ws_forget(extra); return fail(MI355_EHIP, "cbam_single: launch -> %s", hipGetErrorString(e)); }
-    return MI355_OK;
+    return xch_launched("cbam_single", extra);
 }
 
 }  // namespace mi355

@@ -447,11 +447,10 @@ inline Tune resolve_tune(int B, long bytes_per_image) {
 extern "C" {
 
 // workspace: pooled means [B*C] (rounded to 16 B) | single-pass sync state (arrive[B], ticket, err)
-static inline size_t pooled_bytes(int B, int C) { return (((size_t)B * C * sizeof(float)) + 15) & ~(size_t)15; }
 size_t mi355_se_workspace_bytes(int B, int C, int, int) {
-    return pooled_bytes(B, C) + mi355::fused_state_bytes(B) + mi355::se_single_extra_bytes(B, C);
+    return mi355::pooled_bytes(B, C) + mi355::fused_state_bytes(B) + mi355::se_single_extra_bytes(B, C);
 }
-size_t mi355_eca_workspace_bytes(int B, int C, int, int) { return pooled_bytes(B, C) + mi355::fused_state_bytes(B); }
+size_t mi355_eca_workspace_bytes(int B, int C, int, int) { return mi355::pooled_bytes(B, C) + mi355::fused_state_bytes(B); }
 
 static int se_eca_common(int mode, const float* x, const float* wa, const float* wb, float* y, int B, int C, int Cr,
                          int H, int W, void* ws, size_t ws_bytes, hipStream_t st, mi355::SeExtra ex = mi355::SeExtra{nullptr, nullptr, 0}) {
@@ -462,7 +461,7 @@ static int se_eca_common(int mode, const float* x, const float* wa, const float*
     const size_t smem = (size_t)(C + (mode == 0 ? Cr : 0) + RPB) * sizeof(float);
     if (smem > 64 * 1024) return mi355::fail(MI355_EUNSUPPORTED, "channel count %d too large for the gate stage", C);
     if (mode == 0 && vec && mi355::se_single_applicable(C, Cr, H, W)) {       // SE: x read once, means exchanged as tagged granules
-        char* state = static_cast<char*>(ws) + pooled_bytes(B, C);
+        char* state = static_cast<char*>(ws) + mi355::pooled_bytes(B, C);
         return mi355::se_single(x, wa, wb, y, B, C, Cr, H, W, state, state + mi355::fused_state_bytes(B), ex, st);
     }
     if (mode == 1 && vec && mi355::eca_single_applicable(C, Cr, H, W))         // ECA: x read once, no exchange between workgroups
@@ -519,12 +518,8 @@ int mi355_eca_fwd(const float* x, const float* wconv, float* y, int B, int C, in
 }
 
 // workspace: avg[B*C] | max[B*C] | smap[B*2*HW]   (each region rounded to 16 B)
-static inline size_t r16(size_t n) { return (n + 15) & ~(size_t)15; }
-static inline size_t cbam_multipass_bytes(int B, int C, int H, int W) {
-    return 2 * r16((size_t)B * C * 4) + r16((size_t)B * 2 * H * W * 4);
-}
 size_t mi355_cbam_workspace_bytes(int B, int C, int H, int W) {
-    return cbam_multipass_bytes(B, C, H, W) + mi355::cbam_single_extra_bytes(B, C, H, W);
+    return mi355::cbam_multipass_bytes(B, C, H, W) + mi355::cbam_single_extra_bytes(B, C, H, W);
 }
 
 int mi355_cbam_fwd(const float* x, const float* w1, const float* w2, const float* wconv, float* y, int B, int C, int Cr,
@@ -538,14 +533,14 @@ int mi355_cbam_fwd(const float* x, const float* w1, const float* w2, const float
     MI355_CHECK_ARG(ws_bytes >= mi355_cbam_workspace_bytes(B, C, H, W));
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (stage == 0 && aligned16(x) && aligned16(y) && mi355::cbam_single_applicable(C, Cr, H, W, ks))                                                   // x read once
-        return mi355::cbam_single(x, w1, w2, wconv, y, B, C, Cr, H, W, ks, static_cast<char*>(ws) + cbam_multipass_bytes(B, C, H, W), st);
+        return mi355::cbam_single(x, w1, w2, wconv, y, B, C, Cr, H, W, ks, static_cast<char*>(ws) + mi355::cbam_multipass_bytes(B, C, H, W), st);
     if (!do_c) Cr = 0;
     if (!do_s) ks = 1;
     const int HW = H * W;
     const bool vec_pix = (HW % 4 == 0) && aligned16(x) && aligned16(y);          // whole-image rows
     const bool vec_band = vec_pix && (W % 4 == 0);                               // row bands start 16-byte aligned
     char* wsp = static_cast<char*>(ws);
-    const size_t bc = r16((size_t)B * C * 4);
+    const size_t bc = mi355::r16((size_t)B * C * 4);
     float* avg = reinterpret_cast<float*>(wsp);
     float* mx = reinterpret_cast<float*>(wsp + bc);
     float* smap = reinterpret_cast<float*>(wsp + 2 * bc);

@@ -362,8 +362,7 @@ int se_single(const float* x, const float* w1, const float* w2, float* y, int B,
     a.ticket = static_cast<u32*>(state) + B;
     a.epoch = static_cast<u32*>(state);
     a.err = a.ticket + 1;
-    a.herr = sync_err_word_on(st); a.spin = spin_limit();
-    if (int rc = sync_pending("se_single")) return rc;
+    if (int rc = xch_begin("se_single", st, &a.herr, &a.spin)) return rc;
     a.C = C; a.Cr = Cr; a.HW = H * W; a.n4 = a.HW / 4; a.gpi = C / ECW;
     a.inv = 1.0f / (float)a.HW;
     const long total_l = (long)B * a.gpi;
@@ -378,19 +377,14 @@ int se_single(const float* x, const float* w1, const float* w2, float* y, int B,
     if (a.gpi > grid) return fail(MI355_EUNSUPPORTED, "se_single: an image needs %d resident workgroups, the device holds %ld", a.gpi, grid);
     if (grid > a.total) grid = a.total;
     const unsigned long long key = ((unsigned long long)B << 32) ^ (unsigned long long)C ^ ((unsigned long long)grid << 44) ^ 0x5E00000000000000ull;
-    hipError_t e = hipSuccess;
-    if (!ws_known(state, key, st)) {                      // unknown history (first use, other shape, "ws_persistent" off): epoch, ticket, granules
-        e = ws_zero_async(state, fused_state_bytes(B) + se_single_extra_bytes(B, C), st);     // state | granules are contiguous (chan_attn.hip)
-        if (e != hipSuccess) { ws_forget(state); return fail(MI355_EHIP, "se_single: zeroing -> %s", hipGetErrorString(e)); }
-    }
+    // epoch, ticket, granules: state | granules are contiguous (chan_attn.hip)
+    if (int rc = xch_zero("se_single", state, key, fused_state_bytes(B) + se_single_extra_bytes(B, C), st)) return rc;
     const size_t smem = (size_t)(C + Cr + (wlds ? 2 * C * Cr : 0)) * sizeof(float);
     const bool nts = (opt(O_NT) & 2) != 0;
     const bool extra = ex.b1 || ex.b2 || ex.gate;
     if (extra) se_launch_nv<true>(nv, occ, nts, wlds, (int)grid, smem, st, a);
     else       se_launch_nv<false>(nv, occ, nts, wlds, (int)grid, smem, st, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) { ws_forget(state); return fail(MI355_EHIP, "se_single: launch -> %s", hipGetErrorString(e)); }
-    return MI355_OK;
+    return xch_launched("se_single", state);
 }
 
 }  // namespace mi355

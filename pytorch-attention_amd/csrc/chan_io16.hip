@@ -17,12 +17,15 @@
 #include "common.h"
 #include "bufops.h"
 #include "io16.h"
+#include "cbam_band.h"
 
 namespace {
 
-#define AGENT_RLX __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
 constexpr int ECW = 8;          // channel rows per workgroup of the single-read SE / ECA kernels (chan_fused.hip)
+// 16-byte chunks per lane a row needs -> the instantiation that holds it (the NV of the kernel): one table per kernel family, read by
+// the dispatch chain, the occupancy rule and (static_assert) the kernel its launch bounds are computed for
+constexpr int se16_nv(int nv) { return nv <= 1 ? 1 : (nv <= 2 ? 2 : (nv <= 4 ? 4 : (nv <= 7 ? 7 : 8))); }
+constexpr int eca16_nv(int nv) { return nv <= 1 ? 1 : (nv <= 2 ? 2 : (nv <= 4 ? 4 : (nv <= 7 ? 7 : 8))); }
 // Waves per SIMD the single-read kernels are compiled for (512 threads = 2 waves per SIMD and workgroup: 8 / 6 / 4 = four / three / two
 // workgroups per CU at <= 64 / 80 / 128 VGPRs), by 16-byte chunks per lane: the largest that compiles without scratch.  The packed row
 // of a 56 x 56 image (7 chunks) is 28 registers, but the SE kernel's scalar state sits at the SGPR limit and overflows into VGPRs, so
@@ -36,6 +39,7 @@ constexpr int eca16_waves(int nv) { return nv <= 4 ? 8 : (nv <= 7 ? 6 : 4); }
 template <int IO, int NV>
 __global__ __launch_bounds__(512, eca16_waves(NV)) void eca16_halo_kernel(const u16* __restrict__ x, const float* __restrict__ taps, u16* __restrict__ y,
                                                            int C, int k, int HW, int gpi, int total, int per_xcd, int nts) {
+    static_assert(eca16_nv(NV) == NV, "NV is a bucket of eca16_nv");
     __shared__ float s_mean[ECW + 8];                        // means of channels c0-pad .. c0+ECW+pad-1
     const int s = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
     if (s >= total) return;
@@ -103,6 +107,7 @@ struct Se16Args {
 // SELayer instantiation carries none of their pointers and selects and keeps its code.
 template <int IO, int NV, bool WLDS, bool EXTRA>
 __global__ __launch_bounds__(512, se16_waves(NV)) void se16_single_kernel(const Se16Args a) {
+    static_assert(se16_nv(NV) == NV, "NV is a bucket of se16_nv");
     extern __shared__ __attribute__((aligned(16))) float smem[];      // p[C] | h[Cr] | (WLDS: W1[Cr*C] | W2[C*Cr])
     __shared__ u32 s_tk[2];
     __shared__ u32 s_ep;
@@ -235,53 +240,20 @@ static void se16_go(bool wlds, int grid, size_t smem, hipStream_t st, const Se16
 }
 template <int IO, bool EXTRA>
 static void se16_go_nv(int nv, bool wlds, int grid, size_t smem, hipStream_t st, const Se16Args& a) {
-    if (nv <= 1) se16_go<IO, 1, EXTRA>(wlds, grid, smem, st, a);
-    else if (nv <= 2) se16_go<IO, 2, EXTRA>(wlds, grid, smem, st, a);
-    else if (nv <= 4) se16_go<IO, 4, EXTRA>(wlds, grid, smem, st, a);
-    else if (nv <= 7) se16_go<IO, 7, EXTRA>(wlds, grid, smem, st, a);
-    else se16_go<IO, 8, EXTRA>(wlds, grid, smem, st, a);
+    switch (se16_nv(nv)) {
+        case 1: se16_go<IO, 1, EXTRA>(wlds, grid, smem, st, a); break;
+        case 2: se16_go<IO, 2, EXTRA>(wlds, grid, smem, st, a); break;
+        case 4: se16_go<IO, 4, EXTRA>(wlds, grid, smem, st, a); break;
+        case 7: se16_go<IO, 7, EXTRA>(wlds, grid, smem, st, a); break;
+        default: se16_go<IO, 8, EXTRA>(wlds, grid, smem, st, a);
+    }
 }
 
 // =====================================================================================================================================
 // single read: CBAM (cbam_single_kernel of cbam_single.hip; a lane holds 4 pixels of a channel's band as ONE 8-byte register pair)
 // =====================================================================================================================================
-__device__ __forceinline__ void gran_put(rsrc_t g, u32 idx, float v0, float v1, u32 TAG) {
-    const u32x4 v = {__float_as_uint(v0), TAG, __float_as_uint(v1), TAG};
-    __builtin_amdgcn_raw_buffer_store_b128(v, g, idx * 16u, 0, AUX_SC1);      // one write-through 16-byte store
-}
-__device__ __forceinline__ bool gran_get(rsrc_t g, u32 idx, float& v0, float& v1, u32 TAG) {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(g, idx * 16u, 0, AUX_SC1);
-    v0 = __uint_as_float(v.x);
-    v1 = __uint_as_float(v.z);
-    return v.y == TAG && v.w == TAG;
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float rdlane(float v, int lane) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
-}
-// sum / max over the SEG (16 or 32) lanes of a segment; the result is only guaranteed in the segment's lane 0 (fixed order)
-template <int SEG>
-__device__ __forceinline__ void seg_reduce(float& s, float& m, int lane) {
-    s += dpp<0xB1>(s);  m = fmaxf(m, dpp<0xB1>(m));                   // xor 1
-    s += dpp<0x4E>(s);  m = fmaxf(m, dpp<0x4E>(m));                   // xor 2
-    s += dpp<0x124>(s); m = fmaxf(m, dpp<0x124>(m));                  // row_ror 4
-    s += dpp<0x128>(s); m = fmaxf(m, dpp<0x128>(m));                  // row_ror 8
-    if (SEG == 32) {
-        const float s1 = rdlane(s, 16), s3 = rdlane(s, 48), m1 = rdlane(m, 16), m3 = rdlane(m, 48);
-        s += (lane < 32) ? s1 : s3;
-        m = fmaxf(m, (lane < 32) ? m1 : m3);
-    }
-}
-
-struct Cbam16Args {
-    const u16* x; u16* y; const float* w1; const float* w2; const float* wconv;
-    u32x4* g1; u32x4* g2; u32x4* g3; u32* ticket; u32* epoch; u32* err; u32* herr;
-    u32 spin;
-    int C, Cr, H, W, ks, R, Q, NB, cpb, total, nts, wlds;
-};
+// granules, DPP reductions and band geometry: cbam_band.h
+struct Cbam16Args : CbamArgsT<u16> {};            // a type of its own, not an alias: the kernels' symbols keep their names
 
 template <int IO, int SEG, int NV, bool FULL>
 __global__ __launch_bounds__(512, 4) void cbam16_single_kernel(const Cbam16Args a) {
@@ -536,44 +508,6 @@ __global__ __launch_bounds__(512, 4) void cbam16_single_kernel(const Cbam16Args 
     }
 }
 
-struct Geo {
-    int R, Q, NB, SEG, CL, NV, cpb;
-    size_t smem_base, smem_w;
-};
-
-// rows per band: the most pixels per band with R | H, (R*W) % 4 == 0 (8-byte lanes) and R*W <= 128 (four conv lanes per pixel)
-int band_rows(int H, int W) {
-    int best = 0;
-    for (int R = 1; R <= H; ++R) {
-        if (H % R || (R * W) % 4 || R * W > 128) continue;
-        best = R;
-    }
-    return best;
-}
-
-bool geometry(int C, int Cr, int H, int W, int ks, Geo& g) {
-    if (!(ks & 1) || ks > 15) return false;
-    const int best = band_rows(H, W);
-    if (!best) return false;
-    g.R = best;
-    g.Q = best * W / 4;
-    g.NB = H / best;
-    g.SEG = g.Q > 16 ? 32 : 16;
-    g.CL = 512 / g.SEG;
-    const int nv = (C + g.CL - 1) / g.CL;
-    if (nv > 16) return false;
-    g.NV = nv <= 4 ? 4 : (nv <= 8 ? 8 : 16);
-    g.cpb = (C + g.NB - 1) / g.NB;
-    const int pad = (ks - 1) / 2, TW = W + 2 * pad, TH = best + 2 * pad;
-    auto r4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
-    const size_t Cp = (size_t)g.CL * g.NV > (size_t)C ? (size_t)g.CL * g.NV : r4(C);
-    g.smem_base = (3 * Cp + 2 * r4(Cr) + 2 * r4((size_t)g.NB * g.cpb) + 2 * (size_t)g.CL * g.SEG * 4 +
-                   r4(2 * (size_t)TH * TW) + (size_t)g.SEG * 4 + r4(2 * (size_t)ks * ks)) * 4;
-    g.smem_w = 2 * (size_t)C * Cr * 4;
-    if (g.NV == 16 && C != g.CL * g.NV) return false;   // 16 partly filled register pairs per lane spill at 128 VGPRs: the general form takes these
-    return g.smem_base <= 40 * 1024;
-}
-
 // =====================================================================================================================================
 // general form: pool pass -> gate kernel(s) -> scale pass
 // =====================================================================================================================================
@@ -747,10 +681,6 @@ __global__ __launch_bounds__(256) void scale16_kernel(const u16* __restrict__ x,
     }
 }
 
-inline size_t r16(size_t n) { return (n + 15) & ~(size_t)15; }
-inline size_t pooled_bytes(int B, int C) { return r16((size_t)B * C * sizeof(float)); }
-inline size_t cbam_multipass_bytes(int B, int C, int H, int W) { return 2 * r16((size_t)B * C * 4) + r16((size_t)B * 2 * H * W * 4); }
-
 #define BY_IO(io, CALL) do { if ((io) == 1) { CALL(1); } else { CALL(2); } } while (0)
 
 // ---- single-read launchers ------------------------------------------------------------------------------------------------------------
@@ -769,13 +699,13 @@ int eca16_single(const u16* x, const float* taps, u16* y, int B, int C, int k, i
     MI355_TRACE(st, "eca16_halo_kernel io=%d C=%d HW=%d", io, C, HW);
 #define GO(IO_, NV_) eca16_halo_kernel<IO_, NV_><<<grid, 512, 0, st>>>(x, taps, y, C, k, HW, gpi, total, per_xcd, nts)
 #define GO_IO(IO_)                      \
-    do {                                \
-        if (nv <= 1) GO(IO_, 1);        \
-        else if (nv <= 2) GO(IO_, 2);   \
-        else if (nv <= 4) GO(IO_, 4);   \
-        else if (nv <= 7) GO(IO_, 7);   \
-        else GO(IO_, 8);                \
-    } while (0)
+    switch (eca16_nv(nv)) {             \
+        case 1: GO(IO_, 1); break;      \
+        case 2: GO(IO_, 2); break;      \
+        case 4: GO(IO_, 4); break;      \
+        case 7: GO(IO_, 7); break;      \
+        default: GO(IO_, 8);            \
+    }
     BY_IO(io, GO_IO);
 #undef GO_IO
 #undef GO
@@ -801,8 +731,7 @@ int se16_single(const u16* x, const float* w1, const float* w2, u16* y, int B, i
     a.ticket = static_cast<u32*>(state) + B;
     a.epoch = static_cast<u32*>(state);
     a.err = a.ticket + 1;
-    a.herr = mi355::sync_err_word_on(st); a.spin = mi355::spin_limit();
-    if (int rc = mi355::sync_pending("se16_single")) return rc;
+    if (int rc = mi355::xch_begin("se16_single", st, &a.herr, &a.spin)) return rc;
     a.C = C; a.Cr = Cr; a.HW = H * W; a.gpi = C / ECW;
     a.inv = 1.0f / (float)a.HW;
     a.nts = (mi355::opt(mi355::O_NT) & 2) ? 1 : 0;
@@ -813,18 +742,15 @@ int se16_single(const u16* x, const float* w1, const float* w2, u16* y, int B, i
     const size_t smem = ((size_t)C + Cr + (wlds ? 2 * (size_t)C * Cr : 0)) * sizeof(float);
     const int nv = (a.HW / 8 + 63) / 64;
     int occ = (int)mi355::opt(mi355::O_IO16_OCC);                 // workgroups per CU the grid is sized for: 2 .. 4, as far as registers and LDS allow
-    if (occ > se16_waves(nv <= 1 ? 1 : nv <= 2 ? 2 : nv <= 4 ? 4 : nv <= 7 ? 7 : 8) / 2) occ = se16_waves(nv <= 1 ? 1 : nv <= 2 ? 2 : nv <= 4 ? 4 : nv <= 7 ? 7 : 8) / 2;
+    if (occ > se16_waves(se16_nv(nv)) / 2) occ = se16_waves(se16_nv(nv)) / 2;
     while (occ > 2 && smem * occ > 150 * 1024) --occ;
     long grid = (long)mi355::resident_slots(occ);
     if (a.gpi > (long)mi355::resident_slots(2))
         return mi355::fail(MI355_EUNSUPPORTED, "se16_single: an image needs %d resident workgroups, the device holds %d", a.gpi, mi355::resident_slots(2));
     if (grid > a.total) grid = a.total;
     const unsigned long long key = ((unsigned long long)B << 32) ^ (unsigned long long)C ^ ((unsigned long long)grid << 44) ^ 0x5E16000000000000ull;
-    hipError_t e = hipSuccess;
-    if (!mi355::ws_known(state, key, st)) {               // unknown history: epoch, ticket, granules (contiguous)
-        e = mi355::ws_zero_async(state, mi355::fused_state_bytes(B) + mi355::se_single_extra_bytes(B, C), st);
-        if (e != hipSuccess) { mi355::ws_forget(state); return mi355::fail(MI355_EHIP, "se16_single: zeroing -> %s", hipGetErrorString(e)); }
-    }
+    // epoch, ticket, granules (contiguous)
+    if (int rc = mi355::xch_zero("se16_single", state, key, mi355::fused_state_bytes(B) + mi355::se_single_extra_bytes(B, C), st)) return rc;
     {
         MI355_TRACE(st, "se16_single_kernel io=%d C=%d HW=%d", io, C, a.HW);
         const bool extra = ex.b1 || ex.b2 || ex.gate;
@@ -836,22 +762,20 @@ int se16_single(const u16* x, const float* w1, const float* w2, u16* y, int B, i
             else         se16_go_nv<2, false>(nv, wlds, (int)grid, smem, st, a);
         }
     }
-    e = hipGetLastError();
-    if (e != hipSuccess) { mi355::ws_forget(state); return mi355::fail(MI355_EHIP, "se16_single: launch -> %s", hipGetErrorString(e)); }
-    return MI355_OK;
+    return mi355::xch_launched("se16_single", state);
 }
 
 bool cbam16_single_ok(int C, int Cr, int H, int W, int ks) {
     Geo g;
     // all NB bands of an image must be resident together (two workgroups per CU); the exchange area is the fp32 kernel's
-    return mi355::opt(mi355::O_CBAM_SINGLE) && geometry(C, Cr, H, W, ks, g) && g.NB <= mi355::resident_slots(2) &&
+    return mi355::opt(mi355::O_CBAM_SINGLE) && geometry(512, C, Cr, H, W, ks, true, g) && g.NB <= mi355::resident_slots(2) &&
            mi355::cbam_single_extra_bytes(1, C, H, W) != 0;
 }
 
 int cbam16_single(const u16* x, const float* w1, const float* w2, const float* wconv, u16* y, int B, int C, int Cr, int H, int W, int ks, int io,
                   void* extra, hipStream_t st) {
     Geo g;
-    if (!geometry(C, Cr, H, W, ks, g)) return mi355::fail(MI355_EUNSUPPORTED, "cbam16_single: unsupported shape");
+    if (!geometry(512, C, Cr, H, W, ks, true, g)) return mi355::fail(MI355_EUNSUPPORTED, "cbam16_single: unsupported shape");
     Cbam16Args a{};
     a.x = x; a.y = y; a.w1 = w1; a.w2 = w2; a.wconv = wconv;
     a.g1 = static_cast<u32x4*>(extra);
@@ -860,8 +784,7 @@ int cbam16_single(const u16* x, const float* w1, const float* w2, const float* w
     a.ticket = reinterpret_cast<u32*>(a.g3 + (size_t)B * H * W);
     a.err = a.ticket + 1;
     a.epoch = a.ticket + 2;
-    a.herr = mi355::sync_err_word_on(st); a.spin = mi355::spin_limit();
-    if (int rc = mi355::sync_pending("cbam16_single")) return rc;
+    if (int rc = mi355::xch_begin("cbam16_single", st, &a.herr, &a.spin)) return rc;
     a.C = C; a.Cr = Cr; a.H = H; a.W = W; a.ks = ks; a.R = g.R; a.Q = g.Q; a.NB = g.NB; a.cpb = g.cpb;
     const long total_l = (long)B * g.NB;
     if (total_l > (1L << 30)) return mi355::fail(MI355_EUNSUPPORTED, "cbam16_single: too many slices");
@@ -873,12 +796,8 @@ int cbam16_single(const u16* x, const float* w1, const float* w2, const float* w
     long grid = (long)mi355::resident_slots(2);
     if (g.NB > grid) return mi355::fail(MI355_EUNSUPPORTED, "cbam16_single: an image needs %d resident workgroups, the device holds %ld", g.NB, grid);
     if (grid > a.total) grid = a.total;
-    const size_t extra_bytes = ((size_t)B * g.NB * C + (size_t)B * C + (size_t)B * H * W) * 16 + 16;
     const unsigned long long key = ((unsigned long long)B << 48) ^ ((unsigned long long)C << 32) ^ ((unsigned long long)H << 16) ^ (unsigned long long)W ^ 0xCB16000000000000ull;
-    if (!mi355::ws_known(extra, key, st)) {
-        hipError_t e = mi355::ws_zero_async(extra, extra_bytes, st);
-        if (e != hipSuccess) { mi355::ws_forget(extra); return mi355::fail(MI355_EHIP, "cbam16_single: zeroing -> %s", hipGetErrorString(e)); }
-    }
+    if (int rc = mi355::xch_zero("cbam16_single", extra, key, mi355::cbam_single_extra_bytes(B, C, H, W), st)) return rc;
     {
         MI355_TRACE(st, "cbam16_single_kernel io=%d C=%d H=%d W=%d", io, C, H, W);
 #define GO(IO_, SEG_, NV_)                                                                         \
@@ -902,9 +821,7 @@ int cbam16_single(const u16* x, const float* w1, const float* w2, const float* w
 #undef GO_IO
 #undef GO
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { mi355::ws_forget(extra); return mi355::fail(MI355_EHIP, "cbam16_single: launch -> %s", hipGetErrorString(e)); }
-    return MI355_OK;
+    return mi355::xch_launched("cbam16_single", extra);
 }
 
 // ---- general-form launchers ------------------------------------------------------------------------------------------------------------
@@ -942,7 +859,7 @@ bool check_io16(int io, long B, long C, long H, long W) {
 extern "C" {
 
 size_t mi355_cbam16_workspace_bytes(int B, int C, int H, int W) {
-    return mi355_cbam_workspace_bytes(B, C, H, W) + r16((size_t)B * H * W * sizeof(float));
+    return mi355_cbam_workspace_bytes(B, C, H, W) + mi355::r16((size_t)B * H * W * sizeof(float));
 }
 
 // mode 0: SE (wa = w1, wb = w2, Cr), mode 1: ECA (wa = taps, Cr = k)
@@ -955,7 +872,7 @@ static int se_eca16(int mode, const void* xv, const float* wa, const float* wb, 
     const size_t smem = (size_t)(2 * (size_t)C + (mode == 0 ? Cr : 0)) * sizeof(float);
     if (smem > 64 * 1024) return mi355::fail(MI355_EUNSUPPORTED, "channel count %d too large for the gate stage", C);
     if (mode == 0 && vec && se16_single_ok(C, Cr, H, W)) {
-        char* state = static_cast<char*>(ws) + pooled_bytes(B, C);
+        char* state = static_cast<char*>(ws) + mi355::pooled_bytes(B, C);
         return se16_single(x, wa, wb, y, B, C, Cr, H, W, io, state, state + mi355::fused_state_bytes(B), ex, st);
     }
     if (mode == 1 && vec && eca16_single_ok(C, Cr, H, W)) return eca16_single(x, wa, y, B, C, Cr, H, W, io, st);
@@ -1024,10 +941,10 @@ int mi355_cbam16_fwd(const void* xv, const float* w1, const float* w2, const flo
     u16* y = static_cast<u16*>(yv);
     char* wsp = static_cast<char*>(ws);
     if (stage == 0 && aligned16(x) && aligned16(y) && cbam16_single_ok(C, Cr, H, W, ks))                  // x read once
-        return cbam16_single(x, w1, w2, wconv, y, B, C, Cr, H, W, ks, io, wsp + cbam_multipass_bytes(B, C, H, W), st);
+        return cbam16_single(x, w1, w2, wconv, y, B, C, Cr, H, W, ks, io, wsp + mi355::cbam_multipass_bytes(B, C, H, W), st);
     const int HW = H * W;
     const bool vec = (HW % 8 == 0) && aligned16(x) && aligned16(y);
-    const size_t bc = r16((size_t)B * C * 4);
+    const size_t bc = mi355::r16((size_t)B * C * 4);
     float* avg = reinterpret_cast<float*>(wsp);                           // becomes the channel gates in place
     float* mx = reinterpret_cast<float*>(wsp + bc);
     float* smap = reinterpret_cast<float*>(wsp + 2 * bc);

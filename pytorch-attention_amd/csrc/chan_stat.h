@@ -1,5 +1,6 @@
 // chan_stat.h -- what the fp32 and the 16-bit channel-statistics gates share (chan_stat.hip, chan_stat_io16.hip): the mode codes, the
-// kernel argument block, the gate of a channel and the reductions over the values an image's workgroups exchange.  All of it is fp32.
+// kernel argument block, the gate of a channel and the reductions over the values an image's workgroups exchange (all of it fp32), and
+// the host body that picks single read or two passes and sets up the exchange (stat_run).
 #pragma once
 #include "common.h"
 
@@ -93,6 +94,60 @@ __device__ __forceinline__ void group_reduce(const float* s_p, int c, int cpg, f
     w = wave_sum_sw(w);
     red0 = u / (float)cpg;
     red1 = w / (float)cpg - red0 * red0;
+}
+
+// ---- host: the one launcher body of both files ----------------------------------------------------------------------------------------
+// Single read when the rows fit the register layout, two passes otherwise.  TR (statics only, one struct per file) holds what depends
+// on the width of x and y:
+//   Args, who              StatArgsT<float> / StatArgsT<u16>; the prefix of every error text
+//   EPC, MAX_NV            elements per 16-byte chunk (4 / 8); chunks per lane of the largest instantiation (16 / 8)
+//   IO_IN_KEY              the I/O type is part of the exchange area's layout key
+//   vec(a)                 rows are whole 16-byte chunks and both pointers are 16-byte aligned
+//   occ<MODE>(nv, smem)    workgroups per CU the grid is sized for: what the instantiation's launch bounds guarantee
+//   single<MODE>(..)       the bucket table: picks the instantiation for nv chunks per lane and launches it
+//   general<MODE>(..)      the two passes; MI355_OK, or the error of a step in front of the launches
+// io is 0 for the fp32 entries.
+template <int MODE, class TR>
+int stat_run(typename TR::Args a, int io, int H, int W, void* ws, size_t ws_bytes, hipStream_t st) {
+    const int B = a.B, C = a.C;
+    a.HW = H * W;
+    constexpr bool XCH = MODE >= M_GCTG;
+    const bool vec = TR::vec(a);
+    const bool nts = (mi355::opt(mi355::O_NT) & 2) != 0;
+    const bool single = mi355::opt(mi355::O_ZOO_SINGLE) && vec && (a.HW / TR::EPC <= TR::MAX_NV * 64) && (C % ECW == 0) &&
+                        (size_t)C * 4 <= 48 * 1024 && (MODE != M_LCT || a.i0 <= C) &&
+                        (!XCH || C / ECW <= mi355::resident_slots(2));     // an image's slices must all be resident to exchange granules
+    if (single) {
+        a.nchunk = a.HW / TR::EPC; a.gpi = C / ECW;
+        const long total_l = (long)B * a.gpi;
+        if (total_l > (1L << 30)) return mi355::fail(MI355_EUNSUPPORTED, "%s: too many slices", TR::who);
+        a.total = (int)total_l;
+        const int nv = (a.nchunk + 63) / 64;
+        const size_t smem = XCH ? (size_t)C * 4 : 0;
+        long grid = (long)mi355::resident_slots(TR::template occ<MODE>(nv, smem));
+        if (grid > a.total) grid = a.total;
+        if (XCH) {
+            if (ws_bytes < mi355::zoo_workspace_bytes(B, C)) return mi355::fail(MI355_EINVAL, "%s: workspace too small", TR::who);
+            char* base = static_cast<char*>(ws);
+            a.ticket = reinterpret_cast<u32*>(base);
+            a.err = a.ticket + 1;
+            a.epoch = a.ticket + 2;
+            if (int rc = mi355::xch_begin(TR::who, st, &a.herr, &a.spin)) return rc;
+            a.gran = reinterpret_cast<u64*>(base + 16);
+            // mode and grid size (and the I/O type) are part of the key: the ticket protocol counts total + grid draws per launch
+            const unsigned long long key = ((unsigned long long)B << 32) ^ (unsigned long long)C ^ ((unsigned long long)grid << 44) ^
+                                           ((unsigned long long)MODE << 56) ^ (TR::IO_IN_KEY ? (unsigned long long)io << 60 : 0ull);
+            if (int rc = mi355::xch_zero(TR::who, ws, key, 16 + (size_t)B * C * 8, st)) return rc;       // ticket, epoch, granules
+        }
+        TR::template single<MODE>(nv, (int)grid, smem, st, a, io, nts);
+    } else {
+        if (ws_bytes < mi355::zoo_workspace_bytes(B, C)) return mi355::fail(MI355_EINVAL, "%s: workspace too small", TR::who);
+        if ((size_t)C * 4 > 64 * 1024) return mi355::fail(MI355_EUNSUPPORTED, "%s: C = %d too large", TR::who, C);
+        a.stats = reinterpret_cast<float*>(static_cast<char*>(ws) + 16 + (size_t)B * C * 8);
+        if (XCH) mi355::ws_forget(ws);
+        if (int rc = TR::template general<MODE>(vec, a, io, st, nts)) return rc;
+    }
+    return mi355::xch_launched(TR::who, XCH ? ws : nullptr);
 }
 
 }  // namespace

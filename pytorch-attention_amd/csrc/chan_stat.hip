@@ -233,46 +233,21 @@ __global__ __launch_bounds__(256) void stat_apply_kernel(const StatArgs a, int g
     }
 }
 
-template <int MODE>
-int run(StatArgs a, int H, int W, void* ws, size_t ws_bytes, hipStream_t st) {
-    const int B = a.B, C = a.C;
-    a.HW = H * W;
-    constexpr bool XCH = MODE >= M_GCTG;
-    const bool single = mi355::opt(mi355::O_ZOO_SINGLE) && (a.HW % 4 == 0) && (a.HW / 4 <= 16 * 64) && (C % ECW == 0) && aligned16(a.x) &&
-                        aligned16(a.y) && (size_t)C * 4 <= 48 * 1024 && (MODE != M_LCT || a.i0 <= C) &&
-                        (!XCH || C / ECW <= mi355::resident_slots(2));     // an image's slices must all be resident to exchange granules
-    if (single) {
-        a.nchunk = a.HW / 4; a.gpi = C / ECW;
-        const long total_l = (long)B * a.gpi;
-        if (total_l > (1L << 30)) return mi355::fail(MI355_EUNSUPPORTED, "channel-statistics gate: too many slices");
-        a.total = (int)total_l;
-        const int nv = (a.nchunk + 63) / 64;
-        // workgroups per CU = what the kernel's launch bounds allow: three (<= 80 VGPRs) up to 13 float4 per lane, two beyond; SimAM's
-        // per-element gate needs 120 registers (two per CU), 141 at 16 float4 per lane (one per CU)
-        long grid = (long)mi355::resident_slots(MODE == M_SIMAM ? (nv > 13 ? 1 : 2) : (nv > 13 ? 2 : 3));
-        if (grid > a.total) grid = a.total;
-        if (XCH) {
-            if (ws_bytes < mi355::zoo_workspace_bytes(B, C)) return mi355::fail(MI355_EINVAL, "channel-statistics gate: workspace too small");
-            char* base = static_cast<char*>(ws);
-            a.ticket = reinterpret_cast<u32*>(base);
-            a.err = a.ticket + 1;
-            a.epoch = a.ticket + 2;
-            a.herr = mi355::sync_err_word_on(st); a.spin = mi355::spin_limit();
-            if (int rc = mi355::sync_pending("channel-statistics gate")) return rc;
-            a.gran = reinterpret_cast<u64*>(base + 16);
-            // the grid size is part of the key: the ticket protocol counts total + grid draws per launch
-            const unsigned long long key = ((unsigned long long)B << 32) ^ (unsigned long long)C ^ ((unsigned long long)grid << 44) ^ ((unsigned long long)MODE << 56);
-            if (!mi355::ws_known(ws, key, st)) {          // unknown history: ticket, epoch, granules (a kernel, not a memset node: api.hip ws_zero_async)
-                hipError_t e = mi355::ws_zero_async(ws, 16 + (size_t)B * C * 8, st);
-                if (e != hipSuccess) { mi355::ws_forget(ws); return mi355::fail(MI355_EHIP, "channel-statistics gate: zeroing -> %s", hipGetErrorString(e)); }
-            }
-        }
-        const size_t smem = XCH ? (size_t)C * 4 : 0;
-        const bool nts = (mi355::opt(mi355::O_NT) & 2) != 0;
-#define GO(NV_)                                                                                        \
-        do {                                                                                           \
-            if (nts) stat_single_kernel<MODE, NV_, true><<<(int)grid, 512, smem, st>>>(a);             \
-            else     stat_single_kernel<MODE, NV_, false><<<(int)grid, 512, smem, st>>>(a);            \
+// what stat_run (chan_stat.h) needs to know about fp32 rows
+struct Stat32 {
+    typedef StatArgs Args;
+    static constexpr const char* who = "channel-statistics gate";
+    static constexpr int EPC = 4, MAX_NV = 16;
+    static constexpr bool IO_IN_KEY = false;
+    static bool vec(const Args& a) { return (a.HW % 4 == 0) && aligned16(a.x) && aligned16(a.y); }
+    // workgroups per CU = what the kernel's launch bounds allow: three (<= 80 VGPRs) up to 13 float4 per lane, two beyond; SimAM's
+    // per-element gate needs 120 registers (two per CU), 141 at 16 float4 per lane (one per CU)
+    template <int MODE> static int occ(int nv, size_t) { return MODE == M_SIMAM ? (nv > 13 ? 1 : 2) : (nv > 13 ? 2 : 3); }
+    template <int MODE> static void single(int nv, int grid, size_t smem, hipStream_t st, const Args& a, int, bool nts) {
+#define GO(NV_)                                                                                    \
+        do {                                                                                       \
+            if (nts) stat_single_kernel<MODE, NV_, true><<<grid, 512, smem, st>>>(a);              \
+            else     stat_single_kernel<MODE, NV_, false><<<grid, 512, smem, st>>>(a);             \
         } while (0)
         if (nv <= 2) GO(2);
         else if (nv <= 4) GO(4);
@@ -280,19 +255,19 @@ int run(StatArgs a, int H, int W, void* ws, size_t ws_bytes, hipStream_t st) {
         else if (nv <= 13) GO(13);
         else GO(16);
 #undef GO
-    } else {
-        if (ws_bytes < mi355::zoo_workspace_bytes(B, C)) return mi355::fail(MI355_EINVAL, "channel-statistics gate: workspace too small");
-        if ((size_t)C * 4 > 64 * 1024) return mi355::fail(MI355_EUNSUPPORTED, "channel-statistics gate: C = %d too large", C);
-        a.stats = reinterpret_cast<float*>(static_cast<char*>(ws) + 16 + (size_t)B * C * 8);
-        if (XCH) mi355::ws_forget(ws);
-        const long rows = (long)B * C;
-        row_stats_kernel<<<(int)((rows + 3) / 4), 256, 0, st>>>(a.x, a.stats, rows, a.HW);
-        const int groups = (C + 3) / 4;
-        stat_apply_kernel<MODE><<<B * groups, 256, XCH ? (size_t)C * 4 : 0, st>>>(a, groups);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { if (XCH) mi355::ws_forget(ws); return mi355::fail(MI355_EHIP, "channel-statistics gate: launch -> %s", hipGetErrorString(e)); }
-    return MI355_OK;
+    template <int MODE> static int general(bool, const Args& a, int, hipStream_t st, bool) {
+        const long rows = (long)a.B * a.C;
+        row_stats_kernel<<<(int)((rows + 3) / 4), 256, 0, st>>>(a.x, a.stats, rows, a.HW);
+        const int groups = (a.C + 3) / 4;
+        stat_apply_kernel<MODE><<<a.B * groups, 256, MODE >= M_GCTG ? (size_t)a.C * 4 : 0, st>>>(a, groups);
+        return MI355_OK;
+    }
+};
+
+template <int MODE>
+int run(const StatArgs& a, int H, int W, void* ws, size_t ws_bytes, hipStream_t st) {
+    return stat_run<MODE, Stat32>(a, 0, H, W, ws, ws_bytes, st);
 }
 
 }  // namespace

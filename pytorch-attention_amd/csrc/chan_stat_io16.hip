@@ -295,11 +295,13 @@ __global__ __launch_bounds__(256) void stat_apply16_kernel(const Stat16Args a, i
 
 template <int IO, int MODE>
 void go_single(int nv, int grid, size_t smem, hipStream_t st, const Stat16Args& a, int nts) {
-    if (nv <= 1) stat16_single_kernel<IO, MODE, 1><<<grid, 512, smem, st>>>(a, nts);
-    else if (nv <= 2) stat16_single_kernel<IO, MODE, 2><<<grid, 512, smem, st>>>(a, nts);
-    else if (nv <= 4) stat16_single_kernel<IO, MODE, 4><<<grid, 512, smem, st>>>(a, nts);
-    else if (nv <= 7) stat16_single_kernel<IO, MODE, 7><<<grid, 512, smem, st>>>(a, nts);
-    else stat16_single_kernel<IO, MODE, 8><<<grid, 512, smem, st>>>(a, nts);
+    switch (stat16_nv(nv)) {
+        case 1: stat16_single_kernel<IO, MODE, 1><<<grid, 512, smem, st>>>(a, nts); break;
+        case 2: stat16_single_kernel<IO, MODE, 2><<<grid, 512, smem, st>>>(a, nts); break;
+        case 4: stat16_single_kernel<IO, MODE, 4><<<grid, 512, smem, st>>>(a, nts); break;
+        case 7: stat16_single_kernel<IO, MODE, 7><<<grid, 512, smem, st>>>(a, nts); break;
+        default: stat16_single_kernel<IO, MODE, 8><<<grid, 512, smem, st>>>(a, nts);
+    }
 }
 
 template <int IO, int MODE>
@@ -328,63 +330,40 @@ void go_general(bool vec, const Stat16Args& a, hipStream_t st, int nts) {
         MI355_CHECK_ARG(ws_bytes >= mi355::zoo_workspace_bytes(B, C));                                                     \
     } while (0)
 
-template <int MODE>
-int run16(Stat16Args a, int io, int H, int W, void* ws, hipStream_t st) {
-    const int B = a.B, C = a.C;
-    a.HW = H * W;
-    constexpr bool XCH = MODE >= M_GCTG;
-    const bool vec = (a.HW % 8 == 0) && aligned16(a.x) && aligned16(a.y);
-    const int nts = (mi355::opt(mi355::O_NT) & 2) ? 1 : 0;
-    // an image's slices must all be resident to exchange granules: every instantiation runs at least two workgroups per CU (<= 128
-    // VGPRs by its launch bounds, <= 48 KB of LDS)
-    const bool single = mi355::opt(mi355::O_ZOO_SINGLE) && vec && (a.HW / 8 <= 8 * 64) && (C % ECW == 0) && (size_t)C * 4 <= 48 * 1024 &&
-                        (!XCH || C / ECW <= mi355::resident_slots(2));
-    if (single) {
-        a.nchunk = a.HW / 8; a.gpi = C / ECW;
-        const long total_l = (long)B * a.gpi;
-        if (total_l > (1L << 30)) return mi355::fail(MI355_EUNSUPPORTED, "channel-statistics gate (16-bit): too many slices");
-        a.total = (int)total_l;
-        const int nv = (a.nchunk + 63) / 64;
-        const size_t smem = XCH ? (size_t)C * 4 : 0;
-        // workgroups per CU the grid counts on: what the launch bounds of the instantiation guarantee, as far as the LDS allows
-        int occ = stat16_waves(MODE, stat16_nv(nv)) / 2;
-        while (occ > 2 && (smem + 256) * occ > 150 * 1024) --occ;
-        long grid = (long)mi355::resident_slots(occ);
-        if (grid > a.total) grid = a.total;
-        if (XCH) {
-            char* base = static_cast<char*>(ws);
-            a.ticket = reinterpret_cast<u32*>(base);
-            a.err = a.ticket + 1;
-            a.epoch = a.ticket + 2;
-            a.herr = mi355::sync_err_word_on(st); a.spin = mi355::spin_limit();
-            if (int rc = mi355::sync_pending("channel-statistics gate (16-bit)")) return rc;
-            a.gran = reinterpret_cast<u64*>(base + 16);
-            // I/O type, mode and grid size are part of the key: the ticket protocol counts total + grid draws per launch
-            const unsigned long long key = ((unsigned long long)B << 32) ^ (unsigned long long)C ^ ((unsigned long long)grid << 44) ^
-                                           ((unsigned long long)MODE << 56) ^ ((unsigned long long)io << 60);
-            if (!mi355::ws_known(ws, key, st)) {
-                hipError_t e = mi355::ws_zero_async(ws, 16 + (size_t)B * C * 8, st);
-                if (e != hipSuccess) { mi355::ws_forget(ws); return mi355::fail(MI355_EHIP, "channel-statistics gate (16-bit): zeroing -> %s", hipGetErrorString(e)); }
-            }
-        }
-        MI355_TRACE(st, "stat16_single_kernel io=%d mode=%d C=%d HW=%d", io, MODE, C, a.HW);
-        if (io == 1) go_single<1, MODE>(nv, (int)grid, smem, st, a, nts);
-        else         go_single<2, MODE>(nv, (int)grid, smem, st, a, nts);
-    } else {
-        if ((size_t)C * 4 > 64 * 1024) return mi355::fail(MI355_EUNSUPPORTED, "channel-statistics gate (16-bit): C = %d too large", C);
-        a.stats = reinterpret_cast<float*>(static_cast<char*>(ws) + 16 + (size_t)B * C * 8);
-        if (XCH) mi355::ws_forget(ws);
-        if (XCH && (size_t)C * 4 > 48 * 1024) {
+// what stat_run (chan_stat.h) needs to know about packed 16-bit rows
+struct Stat16 {
+    typedef Stat16Args Args;
+    static constexpr const char* who = "channel-statistics gate (16-bit)";
+    static constexpr int EPC = 8, MAX_NV = 8;
+    static constexpr bool IO_IN_KEY = true;
+    static bool vec(const Args& a) { return (a.HW % 8 == 0) && aligned16(a.x) && aligned16(a.y); }
+    // workgroups per CU the grid counts on: what the launch bounds of the instantiation guarantee (every one runs at least two: <= 128
+    // VGPRs, <= 48 KB of LDS), as far as the LDS allows
+    template <int MODE> static int occ(int nv, size_t smem) {
+        int n = stat16_waves(MODE, stat16_nv(nv)) / 2;
+        while (n > 2 && (smem + 256) * n > 150 * 1024) --n;
+        return n;
+    }
+    template <int MODE> static void single(int nv, int grid, size_t smem, hipStream_t st, const Args& a, int io, bool nts) {
+        MI355_TRACE(st, "stat16_single_kernel io=%d mode=%d C=%d HW=%d", io, MODE, a.C, a.HW);
+        if (io == 1) go_single<1, MODE>(nv, grid, smem, st, a, nts ? 1 : 0);
+        else         go_single<2, MODE>(nv, grid, smem, st, a, nts ? 1 : 0);
+    }
+    template <int MODE> static int general(bool vec, const Args& a, int io, hipStream_t st, bool nts) {
+        if (MODE >= M_GCTG && (size_t)a.C * 4 > 48 * 1024) {
             const void* fn = io == 1 ? (vec ? (const void*)stat_apply16_kernel<1, MODE, true> : (const void*)stat_apply16_kernel<1, MODE, false>)
                                      : (vec ? (const void*)stat_apply16_kernel<2, MODE, true> : (const void*)stat_apply16_kernel<2, MODE, false>);
-            if (int rc = mi355::func_dynamic_lds(fn, C * 4)) return rc;
+            if (int rc = mi355::func_dynamic_lds(fn, a.C * 4)) return rc;
         }
-        if (io == 1) go_general<1, MODE>(vec, a, st, nts);
-        else         go_general<2, MODE>(vec, a, st, nts);
+        if (io == 1) go_general<1, MODE>(vec, a, st, nts ? 1 : 0);
+        else         go_general<2, MODE>(vec, a, st, nts ? 1 : 0);
+        return MI355_OK;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { if (XCH) mi355::ws_forget(ws); return mi355::fail(MI355_EHIP, "channel-statistics gate (16-bit): launch -> %s", hipGetErrorString(e)); }
-    return MI355_OK;
+};
+
+template <int MODE>
+int run16(const Stat16Args& a, int io, int H, int W, void* ws, size_t ws_bytes, hipStream_t st) {
+    return stat_run<MODE, Stat16>(a, io, H, W, ws, ws_bytes, st);
 }
 
 }  // namespace
@@ -396,7 +375,7 @@ int mi355_simam16_fwd(const void* x, void* y, int B, int C, int H, int W, float 
     CHECK_IO16(2);
     Stat16Args a{};
     a.x = static_cast<const u16*>(x); a.y = static_cast<u16*>(y); a.B = B; a.C = C; a.f0 = e_lambda;
-    return run16<M_SIMAM>(a, io, H, W, ws, static_cast<hipStream_t>(stream));
+    return run16<M_SIMAM>(a, io, H, W, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 int mi355_srm16_fwd(const void* x, const float* cfc, const float* bn_weight, const float* bn_bias, const float* bn_mean, const float* bn_var,
@@ -406,7 +385,7 @@ int mi355_srm16_fwd(const void* x, const float* cfc, const float* bn_weight, con
     Stat16Args a{};
     a.x = static_cast<const u16*>(x); a.y = static_cast<u16*>(y); a.B = B; a.C = C;
     a.p0 = cfc; a.p1 = bn_weight; a.p2 = bn_bias; a.p3 = bn_mean; a.p4 = bn_var; a.f0 = bn_eps;
-    return run16<M_SRM>(a, io, H, W, ws, static_cast<hipStream_t>(stream));
+    return run16<M_SRM>(a, io, H, W, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 int mi355_gct_gauss16_fwd(const void* x, void* y, int B, int C, int H, int W, float c, float eps, int io, void* ws, size_t ws_bytes,
@@ -414,7 +393,7 @@ int mi355_gct_gauss16_fwd(const void* x, void* y, int B, int C, int H, int W, fl
     CHECK_IO16(1);
     Stat16Args a{};
     a.x = static_cast<const u16*>(x); a.y = static_cast<u16*>(y); a.B = B; a.C = C; a.f0 = eps; a.f1 = c;
-    return run16<M_GCTG>(a, io, H, W, ws, static_cast<hipStream_t>(stream));
+    return run16<M_GCTG>(a, io, H, W, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 int mi355_lct16_fwd(const void* x, const float* w, const float* b, void* y, int B, int C, int groups, int H, int W, float eps, int io,
@@ -425,7 +404,7 @@ int mi355_lct16_fwd(const void* x, const float* w, const float* b, void* y, int 
     MI355_CHECK_ARG(w && b);
     Stat16Args a{};
     a.x = static_cast<const u16*>(x); a.y = static_cast<u16*>(y); a.B = B; a.C = C; a.p0 = w; a.p1 = b; a.f0 = eps; a.i0 = C / groups;
-    return run16<M_LCT>(a, io, H, W, ws, static_cast<hipStream_t>(stream));
+    return run16<M_LCT>(a, io, H, W, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 int mi355_gct16_fwd(const void* x, const float* alpha, const float* gamma, const float* beta, void* y, int B, int C, int H, int W,
@@ -435,8 +414,8 @@ int mi355_gct16_fwd(const void* x, const float* alpha, const float* gamma, const
     Stat16Args a{};
     a.x = static_cast<const u16*>(x); a.y = static_cast<u16*>(y); a.B = B; a.C = C;
     a.p0 = alpha; a.p1 = gamma; a.p2 = beta; a.f0 = epsilon; a.i0 = after_relu ? 1 : 0;
-    return mode_l1 ? run16<M_GCT1>(a, io, H, W, ws, static_cast<hipStream_t>(stream))
-                   : run16<M_GCT2>(a, io, H, W, ws, static_cast<hipStream_t>(stream));
+    return mode_l1 ? run16<M_GCT1>(a, io, H, W, ws, ws_bytes, static_cast<hipStream_t>(stream))
+                   : run16<M_GCT2>(a, io, H, W, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

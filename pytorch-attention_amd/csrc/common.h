@@ -32,11 +32,22 @@ int   mlp_wide(const float* x, const void* w1_16, const float* b1, const void* w
 int   gemm_small_nt(const float* A, const float* B, const float* bias, float* C, int M, int N, int K, int lda, int ldb, int ldc, int precision,
                     hipStream_t st);
 void  ws_forget(const void* region);
-bool  ws_known(const void* region, unsigned long long key, hipStream_t st);   // api.hip: was this workspace zeroed for this shape? (device-resident launch tags)
-hipError_t ws_zero_async(void* p, size_t bytes, hipStream_t st);   // zero an exchange area with a kernel (capture-safe ordering)
-unsigned* sync_err_word_on(hipStream_t st);     // sync_err_word(), but never allocates inside a stream capture (may return null there)
+// ---- host half of the granule-exchange protocol (api.hip), in the order a launcher calls it; `who` prefixes every error text ----
+//   xch_begin     hands out the argument block's pinned error word (null under a capture that would have to allocate it) and poll budget,
+//                 then reports a poll time-out of an EARLIER launch on this thread: sync_pending(who)
+//   xch_zero      zeroes the region (with a kernel: capture-safe ordering) unless it is known to have been zeroed for `key`
+//   xch_launched  the launch check; `region` is forgotten when the launch failed (null: nothing to forget)
+// A region whose zeroing or launch failed is never left "known": both failure paths forget it here, once, for every user.
+int   xch_begin(const char* who, hipStream_t st, unsigned** herr, unsigned* spin);
+int   xch_zero(const char* who, void* region, unsigned long long key, size_t bytes, hipStream_t st);
+int   xch_launched(const char* who, const void* region);
 bool  stream_is_capturing(hipStream_t st);      // hipGraph capture in progress on this stream
 void  ws_forget_range(const void* base, size_t bytes);
+// 16-byte-aligned regions at the head of the SE / ECA / CBAM workspaces (fp32 and 16-bit entries): pooled means [B*C], and CBAM's
+// avg[B*C] | max[B*C] | smap[B*2*HW] in front of the single-read kernel's exchange area
+inline size_t r16(size_t n) { return (n + 15) & ~(size_t)15; }
+inline size_t pooled_bytes(int B, int C) { return r16((size_t)B * C * sizeof(float)); }
+inline size_t cbam_multipass_bytes(int B, int C, int H, int W) { return 2 * r16((size_t)B * C * 4) + r16((size_t)B * 2 * H * W * 4); }
 // ---- exchange-kernel failure reporting (api.hip) ----------------------------------------------------------------------------
 // The single-read kernels bound their inter-workgroup polls.  A poll that runs out stores a non-zero code into a pinned,
 // device-visible host word of the LAUNCHING thread (system-scope store, no synchronisation needed to read it); every later library entry

@@ -39,9 +39,9 @@ EXEMPT = {
     "mi355_stream_read": "measurement tool of bench.py: read-only sweep into a 4-byte sink",
     # aliases of the legacy names block: the cited line of csrc/api.hip is the one forwarding call that is the whole body
     # (tests/test_abi_memory_cpu.py checks the body and the line number)
-    "mi355_sdpa_core_fwd": "alias: csrc/api.hip:478 forwards to mi355_sdpa_fwd in one call",
-    "mi355_gemm_bias_act_fwd": "alias: csrc/api.hip:483 forwards to mi355_linear_fwd in one call",
-    "mi355_mixer_token_mlp_fwd": "alias: csrc/api.hip:489 forwards to mi355_mixer_token_fwd in one call",
+    "mi355_sdpa_core_fwd": "alias: csrc/api.hip:498 forwards to mi355_sdpa_fwd in one call",
+    "mi355_gemm_bias_act_fwd": "alias: csrc/api.hip:503 forwards to mi355_linear_fwd in one call",
+    "mi355_mixer_token_mlp_fwd": "alias: csrc/api.hip:509 forwards to mi355_mixer_token_fwd in one call",
 }
 
 # options that do not select a kernel (tests/test_abi_memory_cpu.py: every OTHER key of csrc/options.h must appear in some row)

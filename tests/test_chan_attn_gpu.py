@@ -108,7 +108,8 @@ def test_se_single_granule_protocol_under_repetition(monkeypatch):
 
 
 CBAM_SINGLE_SHAPES = [(2, 64, 32, 32), (3, 256, 56, 56), (1, 8, 4, 4), (2, 16, 2, 2), (2, 256, 14, 14), (2, 24, 112, 112), (5, 40, 12, 12),
-                      (1, 512, 8, 8), (40, 64, 28, 28), (2, 100, 10, 10), (1, 32, 64, 128), (3, 48, 16, 20)]
+                      (1, 512, 8, 8), (40, 64, 28, 28), (2, 100, 10, 10), (1, 32, 64, 128), (3, 48, 16, 20),
+                      (2, 400, 8, 8)]                 # 16 register slots per lane, the last one partly filled
 
 
 @pytest.mark.parametrize("shape", CBAM_SINGLE_SHAPES)

@@ -50,10 +50,13 @@ def _red_ks(shape):
 SMALL = (2, 64, 32, 32)
 # general form: rows that are not a multiple of 16 bytes, C not a multiple of 8, 1 x 1 maps
 GENERAL = [(3, 72, 7, 7), (2, 48, 13, 17), (1, 8, 1, 1), (2, 100, 5, 9)]
+# 16 register slots per lane with the last one partly filled: the fp32 CBAM reads x once here, the 16-bit CBAM refuses the single-read
+# kernel and takes its general form (SE and ECA read once)
+CBAM_NV16_PARTIAL = (2, 400, 8, 8)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("shape", [SMALL] + GENERAL)
+@pytest.mark.parametrize("shape", [SMALL] + GENERAL + [CBAM_NV16_PARTIAL])
 def test_blocks_vs_fp64_oracle(shape, dtype):
     red, ks = _red_ks(shape)
     x = _input(shape, dtype)
