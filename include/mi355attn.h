@@ -159,8 +159,10 @@ const char* mi355_last_error(void);         /* thread-local message of the last 
  *                   2 = GELU epilogues too).  A row's K halves are added as two chains: results differ from the tile kernels by at most one unit
  *                   of the 16-bit output.  3 / 4 = the same products (N % 256 == 0, M % 32 == 0) on the one-wave-per-SIMD kernel that keeps W in
  *                   AGPRs as MFMA operands: one chain per row, bit-identical to the tile kernels (3 = without activation, 4 = GELU too).
- *                   0 (default): both measured slower than the tile kernels (profiles/r06_gemm_wst.md: qkv 200-219 vs 174-180 us, fc1 281-337
- *                   vs 275-288).
+ *                   1 .. 4 force their kernel whatever the row count (1 / 2 from eight row tiles per workgroup up, 3 / 4 from M = 32).
+ *                   5 (default) = the dispatch hands GELU products (ViT fc1) of at least 32 768 rows to the 3 / 4 kernel, where its
+ *                   software-pipelined form measured faster than gemm16_pa (profiles/gemm_wst_pipe.md); 6 = products without activation too (a
+ *                   tie with gemm16_w4).  0 = the tile kernels always.  The modes exclude each other: 1 .. 4 also turn the default route off.
  *   "gemm_wslab"    1 (default) = 16-bit outputs with K = 256 / 384 / 512 and N a multiple of the slab width (256 / 192 / 256 columns) keep a column slab
  *                   of W in the registers of a persistent workgroup and stream 32-row tiles of X (gemm16_wslab.hip) when the epilogue is a GELU or M is
  *                   not a multiple of 256 -- the products it measured faster on (5-12 % / 88-96 -> 65-69 us; profiles/r06_gemm_wslab.md); 2 = every

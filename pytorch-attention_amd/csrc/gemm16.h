@@ -53,7 +53,7 @@ size_t gemm16_p8_workspace_bytes(int M, int N, int K);
 int gemm16_pa(const g16::G16Args& g, int out16, int precision, hipStream_t st, int abl = 0);        // g.lnc_a != null: emitting variant                                 // gemm16_pa.hip
 int gemm16_w4(const g16::G16Args& g, int out16, int precision, hipStream_t st);                        // gemm16_w4.hip
 int gemm16_wreg(const g16::G16Args& g, int out16, int precision, hipStream_t st);                      // gemm16_wreg.hip
-int gemm16_wst(const g16::G16Args& g, int out16, int precision, hipStream_t st);                       // gemm16_wst.hip
+int gemm16_wst(const g16::G16Args& g, int out16, int precision, hipStream_t st, bool one_wave = false);                       // gemm16_wst.hip
 int gemm16_wslab(const g16::G16Args& g, int out16, int precision, hipStream_t st);                     // gemm16_wslab.hip
 int gemm16_wslab_check(const g16::G16Args& g, int precision);                                            // would gemm16_wslab take it? (nothing launched)
 int gemm16_rows(const g16::G16Args& g, int out16, int precision, hipStream_t st);                      // gemm16.hip: few rows, 32 x 64 ring tiles

@@ -574,6 +574,10 @@ int mi355_linear16_ln16_fwd(const void* X16, const void* W16, const float* bias,
 
 }  // extern "C"
 
+// Fewest rows at which the default route below hands a K = 768 product to the weight-stationary kernel: the smallest row count of the sweep
+// in profiles/gemm_wst_pipe.md at which it beat gemm16_pa on fc1 (16 384: slower, 24 576: a tie)
+static constexpr int WST_AUTO_MIN_ROWS = 32768;
+
 // Kernel choice of mi355_linear16_ws_fwd on a checked argument block (also the product of the patch embedding, gemm.hip, which
 // brings a periodic residual table: only the persistent and the plain tile kernels read one).  The policy reads top to bottom: each
 // step is a condition and a kernel to try; a kernel that refuses the call (MI355_EUNSUPPORTED, nothing launched) leaves it to the next
@@ -598,9 +602,15 @@ int mi355::linear16_dispatch(const G16Args& g, int out16, int precision, void* w
     }
     if (variant == 0) {
         int rc;
-        // ViT qkv / fc1, opt-in: a 192-column slab of W stays in the registers of a workgroup, X streams through LDS once per slab (gemm16_wst.hip)
-        if ((opt.wst == 2 || opt.wst == 4 || ((opt.wst & 1) && g.act == MI355_ACT_NONE)) &&
+        // ViT qkv / fc1, forced (gemm_wst = 1 .. 4): a 192-column slab of W stays in the registers of a workgroup, X streams through LDS once per slab (gemm16_wst.hip)
+        if ((opt.wst == 2 || opt.wst == 4 || ((opt.wst == 1 || opt.wst == 3) && g.act == MI355_ACT_NONE)) &&
             (rc = checked(mi355::gemm16_wst(g, out16, precision, st))) != MI355_EUNSUPPORTED)
+            return rc;
+        // ViT qkv / fc1 / the k, v product of the pooled-token tail, by default (gemm_wst = 5: GELU products, 6: all): the software-pipelined one-wave-per-SIMD form of the same
+        // kernel (bit-identical to the tile kernels; it checks K = 768, N % 256, M % 32 itself).  The row floor is policy and lives here: the
+        // weight prologue and the ramp of a stream make it lose on few rows (profiles/gemm_wst_pipe.md).
+        if (out16 && K == 768 && M >= WST_AUTO_MIN_ROWS && (opt.wst == 6 || (opt.wst == 5 && gelu)) &&
+            (rc = checked(mi355::gemm16_wst(g, out16, precision, st, true))) != MI355_EUNSUPPORTED)
             return rc;
         if ((K == 64 || K == 128) && M >= 2048 && (!out16 || (N & 7) == 0)) {       // short-K, HBM-bound: weight-stationary streaming kernel
             MI355_TRACE(st, "gemm16_ws_kernel<%s> M=%d N=%d K=%d", out16 ? "out16" : "out32", M, N, K);

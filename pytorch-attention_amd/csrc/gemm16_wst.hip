@@ -1,5 +1,6 @@
 // gemm16_wst.hip -- Y16 (M x N, 16 bit) = act(X16 (M x 768) . W16^T (N x 768) + bias) with the WEIGHTS STATIONARY in registers: the qkv and fc1
-// products of a ViT-Base encoder layer (ViT.py:81 and :59-61; N = 2304 / 3072, K = 768, M = 50 432 at B = 256), gfx950.  Round 6, OPT-IN.
+// products of a ViT-Base encoder layer (ViT.py:81 and :59-61; N = 2304 / 3072, K = 768, M = 50 432 at B = 256), gfx950.  The 8-wave form is
+// opt-in; the software-pipelined one-wave-per-SIMD form is the default for fc1 (GELU) from 32 768 rows up (option "gemm_wst" = 5).
 //
 // The tile kernels of the engine (gemm16_p8 / gemm16_w4 / gemm16_pa) stream BOTH operands through LDS for every 256 x 256 output tile:
 // 1.39 GB cross the L2 -> CU path for the qkv product, half of it the same 3.5 MB of weights over and over, and the MFMA pipes sit 0.44-0.53
@@ -21,8 +22,10 @@
 // MEASURED (profiles/r06_gemm_wst.md): qkv 208-219 us against 174-180 us on gemm16_w4, fc1 306-383 against 275-288 on gemm16_pa; a tie only on
 // row counts the one-wave-per-SIMD kernel below does not take (M % 32 != 0: 192-200 vs 192-204 us).  Two barriers, the K-half exchange and the
 // per-tile DMA address arithmetic leave the matrix pipes 0.43 busy -- below the tile kernels' 0.53.  Option "gemm_wst" = 1 / 2 (default 0).
-// gemm16_wst1_kernel further down ("gemm_wst" = 3 / 4) is the one-wave-per-SIMD form with W in AGPRs: bit-identical to the tile kernels, qkv
-// 200-217 us, fc1 318-337 (281 with undeferred stores): a tie at best, also opt-in.
+// gemm16_wst1_kernel further down ("gemm_wst" = 3 / 4, and the default route 5 / 6) is the one-wave-per-SIMD form with W in AGPRs,
+// bit-identical to the tile kernels.  Compiler-ordered it tied them at best (qkv 200-217 us, fc1 281-337).  With the epilogue of row block
+// r - 1, the fragment reads, the DMA pieces and the stores placed by hand between the MFMAs of row block r (profiles/gemm_wst_pipe.md): fc1
+// 245-254 us against 272-309 on gemm16_pa, qkv 162-183 against 173-187 on gemm16_w4.
 #include "gemm16.h"
 #include "bufops.h"
 #include <type_traits>
@@ -154,7 +157,7 @@ __global__ __launch_bounds__(512, 1) void gemm16_wst_kernel(const G16Args g, int
 // v_accvgpr moves: 545 us, profiles/r06_gemm_wst.md), so the MFMAs are inline assembly whose A-operand constraint is "a": the fragments are
 // written to their accumulation registers once and read there by the matrix pipe for the rest of the kernel.  No K split (a row's K steps form one
 // ascending chain: the bit pattern of the tile kernels), no exchange, ONE barrier per 32-row tile, a ring of three X tiles, stores deferred by one
-// tile.  A tile takes 3.6-3.8 us of which the MFMAs are 1.6: one wave per SIMD has nobody to hide its serial work behind (profiles/r06_gemm_wst.md).
+// row block.  With one wave per SIMD nobody else hides the wave's serial work, so the wave hides it itself: see the schedule below.
 template <typename T>
 __device__ __forceinline__ void wst_mfma_a(f4& c, const typename Vec8<T>::t& w, const typename Vec8<T>::t& x) {
     if constexpr (std::is_same<T, _Float16>::value) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "a"(w), "v"(x));
@@ -174,16 +177,66 @@ __device__ __forceinline__ void wst_dma_so(const void* base, unsigned off, unsig
                  : "memory");
 }
 
+template <int I> struct WstI { static constexpr int v = I; };
+template <int B, int N>
+struct WstUnroll {
+    template <class F>
+    static __device__ __forceinline__ void run(F& f) {
+        f(WstI<B>{});
+        WstUnroll<B + 1, N>::run(f);
+    }
+};
+template <int N>
+struct WstUnroll<N, N> {
+    template <class F>
+    static __device__ __forceinline__ void run(F&) {}
+};
+// the first k-step of a row block multiplies into a zero C operand: no accumulator clearing
+template <typename T>
+__device__ __forceinline__ void wst_mfma_a0(f4& c, const typename Vec8<T>::t& w, const typename Vec8<T>::t& x) {
+    if constexpr (std::is_same<T, _Float16>::value) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(c) : "a"(w), "v"(x));
+    else                                            asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(c) : "a"(w), "v"(x));
+}
+
+// SOFTWARE PIPELINE INSIDE THE ONE WAVE (profiles/gemm_wst_pipe.md).  The unit is one 16-row block = 96 MFMAs (24 k-steps x 4 column tiles) =
+// 1 536 matrix-pipe cycles; the two row blocks of a 32-row tile own disjoint accumulators acc[0][*] / acc[1][*], so while block r accumulates
+// into one set the epilogue of block r - 1 drains the other.  The block body is 96 SLOTS, one MFMA each, and the ORDER of the statements is the
+// schedule (the MFMAs and DMA pieces are `asm volatile`, a scheduling barrier closes every slot).  Behind the MFMA of slot m = 4 ks + ct ride:
+//   m = 0 .. 3        the four deferred row stores of the SAME row block of the tile before (pend[rt], converted one row block ago);
+//   m % 4 == 1        the ds_read_b128 of the X fragment of k-step ks + 3 (ring of four; past the end of row block 0: of row block 1; the
+//                     first three of a tile are read behind the barrier);
+//   m % 16 == 7       one of the tile's twelve LDS-DMA pieces (six per row block) of the tile TWO ahead (its lane offset read from LDS at m - 4);
+//   m >= 4, m % 4 != 3   one PIECE of the epilogue of the previous row block: per output bias add, min, FMA | 3 FMA | FMA, v_exp_f32, multiply,
+//                     FMA | FMA (+ the conversion of a finished group of four); per four outputs one range-maximum piece.  68 pieces of at
+//                     most four VALU instructions.  The first reads an accumulator five MFMAs (>= 64 cycles) after the MFMA that wrote it
+//                     last: no s_nop.
+// Per tile ONE counted wait and ONE barrier, in front of row block 0.  Issue order of an iteration: [4 stores][6 DMA][4 stores][6 DMA], the DMA
+// pieces those of the tile two ahead.  INVARIANT of `s_waitcnt vmcnt(12)`: all pieces of the tile this iteration reads were issued BEFORE the
+// twelve pieces of the next tile (in the iteration before, or in the prologue, which issues the whole first tile ahead of the second).  Loads
+// return in order among themselves, so if one piece of this tile were still out, all twelve later pieces would be out too: thirteen operations,
+// more than the wait leaves.  That holds whatever order stores complete in against loads -- no assumption about a common retirement order.
+// With an in-order counter the wait also covers the four stores and four pieces that opened the previous iteration, one tile old; waiting
+// at vmcnt(20), which needs that assumption, measured the same (profiles/gemm_wst_pipe.md).  Where no next tile was requested (the last tile of
+// a stream) the wait is vmcnt(0).
+// The kernel waits for no other workgroup (capture-safe); a row's K steps form one ascending chain and the epilogue expressions are those of the
+// tile kernels: the output is bit-identical to theirs wherever the row sits.
+// TOOLCHAIN: the placement rests on the compiler leaving the plain C++ pieces between the `asm volatile` statements where the scheduling
+// barriers put them, and the first epilogue piece reads an accumulator with no s_nop and no dependency the hazard recogniser can see (the MFMAs
+// are opaque to it).  Another compiler version may order this differently without a diagnostic: re-run tests/test_gemm16_wst_pipe_gpu.py
+// (bit identity with the tile kernels) and tests/test_gemm16_wst_pipe_cpu.py (no scratch) on every toolchain change.
 template <typename T, bool GELU>
 __global__ __launch_bounds__(256, 1) void gemm16_wst1_kernel(const G16Args g, int nslab) {
     using v8 = typename Vec8<T>::t;
     typedef T t4 __attribute__((ext_vector_type(4)));
+    constexpr bool F16 = std::is_same<T, _Float16>::value;
     constexpr int K = 768, KS = 24, KSA = 16, RT = 2, ROWS = 16 * RT, CPR = K / 8;
     constexpr int TILE_EL = ROWS * K;                                 // 48 KB
     constexpr int NDMA = TILE_EL * 2 / 1024 / 4;                      // 12 pieces per wave and tile
     constexpr int NB = 3;
+    constexpr int NPIECE = 4 * 17;                                    // epilogue pieces per row block
     __shared__ __attribute__((aligned(1024))) unsigned short s_x[NB][TILE_EL];
     __shared__ __attribute__((aligned(16))) float s_bias[256];
+    __shared__ unsigned s_doff[NDMA][256];                            // the lanes' DMA source offsets: twelve registers the pipelined body has no room for
     const int t = threadIdx.x, lane = t & 63, l15 = lane & 15, gq = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int lid = xcd_contiguous_block();
@@ -193,6 +246,26 @@ __global__ __launch_bounds__(256, 1) void gemm16_wst1_kernel(const G16Args g, in
     const T* __restrict__ A = static_cast<const T*>(g.A);
     const T* __restrict__ W = static_cast<const T*>(g.B);
     T* __restrict__ C = static_cast<T*>(g.C);
+    // ---- DMA: piece j = wave + 4 m moves LDS chunks 64 j .. 64 j + 63; LDS chunk q = (row q / 96, slot q % 96) holds the row's chunk slot ^ (row & 15).
+    // The first two tiles are on their way before the weight fragments are asked for. ----
+    const unsigned lds0 = wst_lds_addr(&s_x[0][0]);
+    const int ntile = __builtin_amdgcn_readfirstlane(g.M / ROWS);    // launcher: M % 32 == 0
+    int tile = stream;
+#pragma unroll
+    for (int m = 0; m < NDMA; ++m) {
+        const unsigned q = (unsigned)((wave + 4 * m) * 64 + lane);
+        const unsigned r = (q * 43691u) >> 22;                        // q / 96 for q < 4096
+        const unsigned c = (q - r * 96u) ^ (r & 15u);
+        const unsigned off = (r * (unsigned)g.lda + c * 8u) * 2u;
+        s_doff[m][t] = off;                                           // read back by the lane that wrote it
+        if (tile < ntile) wst_dma_so(reinterpret_cast<const char*>(A + (long)tile * ROWS * g.lda), off, lds0 + (unsigned)(wave + 4 * m) * 1024u);
+    }
+    if (tile + nstream < ntile) {                                     // all of the second tile BEHIND all of the first: the counted wait relies on it
+#pragma unroll
+        for (int m = 0; m < NDMA; ++m)
+            wst_dma_so(reinterpret_cast<const char*>(A + (long)(tile + nstream) * ROWS * g.lda), s_doff[m][t],
+                       lds0 + (unsigned)(TILE_EL * 2) + (unsigned)(wave + 4 * m) * 1024u);
+    }
     // ---- W fragments: k-steps 0 .. 15 -> AGPRs (through the "a" constraint of their consumers), 16 .. 23 -> VGPRs -----------------------------
     v8 wa[4][KSA], wv[4][KS - KSA];
 #pragma unroll
@@ -204,111 +277,168 @@ __global__ __launch_bounds__(256, 1) void gemm16_wst1_kernel(const G16Args g, in
         for (int ks = KSA; ks < KS; ++ks) wv[ct][ks - KSA] = *reinterpret_cast<const v8*>(wr + ks * 32);
     }
     s_bias[t] = g.bias ? g.bias[slab * 256 + t] : 0.f;
-    // ---- DMA: piece j = wave + 4 m moves LDS chunks 64 j .. 64 j + 63; LDS chunk q = (row q / 96, slot q % 96) holds the row's chunk slot ^ (row & 15) ----
-    unsigned doff[NDMA];
+    // ---- fragment reads: k-step ks = 4 kh + kl of row block rt sits at chunk (16 kh + ((4 kl + gq) ^ l15)) of row rt * 16 + l15: four lane
+    // offsets (kl), everything else is an immediate ----
+    const unsigned short* xp[4];                                      // into ring buffer 0; they move on with the ring
 #pragma unroll
-    for (int m = 0; m < NDMA; ++m) {
-        const unsigned q = (unsigned)((wave + 4 * m) * 64 + lane);
-        const unsigned r = (q * 43691u) >> 22;                        // q / 96 for q < 4096
-        const unsigned c = (q - r * 96u) ^ (r & 15u);
-        doff[m] = (r * (unsigned)g.lda + c * 8u) * 2u;
-    }
-    const unsigned lds0 = wst_lds_addr(&s_x[0][0]);
-    const long ntile = (long)g.M / ROWS;                              // launcher: M % 32 == 0
-    auto dma_tile = [&](long tile, int buf) {
-        const char* base = reinterpret_cast<const char*>(A + tile * ROWS * (long)g.lda);
+    for (int kl = 0; kl < 4; ++kl) xp[kl] = &s_x[0][0] + (l15 * CPR + ((kl * 4 + gq) ^ l15)) * 8;
+    auto xfrag = [&](int rt, int ks) { return *reinterpret_cast<const v8*>(xp[ks & 3] + rt * 16 * K + (ks >> 2) * 128); };
+    auto bias4 = [&](int ct) { return *reinterpret_cast<const f4*>(&s_bias[wave * 64 + ct * 16 + gq * 4]); };
+
+    const unsigned coff = ((unsigned)l15 * (unsigned)g.ldc + (unsigned)(n0 + gq * 4)) * 2u;     // the lane's byte offset in a 16-row block of C
+    f4 acc[RT][4];
 #pragma unroll
-        for (int m = 0; m < NDMA; ++m) wst_dma_so(base, doff[m], lds0 + (unsigned)buf * (TILE_EL * 2) + (unsigned)(wave + 4 * m) * 1024u);
-    };
-    float rgmax = 0.f;
-    long tile = stream;
-#pragma unroll
-    for (int pre = 0; pre < NB - 1; ++pre)
-        if (tile + (long)pre * nstream < ntile) dma_tile(tile + (long)pre * nstream, pre);
-    int buf = 0;
-    // The 16-bit results of a tile wait in registers and are stored one tile LATER, right behind the next DMA issue.  The counted wait at the
-    // top of an iteration then sees, besides the tile it needs (two tiles old), only operations that are one whole tile old -- twelve DMA pieces
-    // and eight stores: vmcnt(12) is met without waiting for anything fresh, and it is SAFE whatever order stores and loads complete in
-    // (loads return in order: with at most twelve operations out, the pieces of the tile before the newest have all landed).  With the stores
-    // issued at the end of the iteration the same wait stalled on them every tile (213-229 us for the qkv product).
+    for (int ct = 0; ct < 4; ++ct) acc[1][ct] = f4{0.f, 0.f, 0.f, 0.f};   // the first row block drains this set before anything is in it
+    v8 xq[4];
     t4 pend[RT][4];
-    long prow = -1;
-    auto flush = [&]() {
-        if (prow >= 0) {
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-                for (int ct = 0; ct < 4; ++ct) *reinterpret_cast<t4*>(C + (prow + rt * 16) * g.ldc + n0 + ct * 16 + gq * 4) = pend[rt][ct];
+    f4 bv;
+    unsigned dq = 0;
+    float rgmax = 0.f, ex = 0.f, ea = 0.f, ep = 0.f, ev[4] = {0.f, 0.f, 0.f, 0.f};
+
+    // piece q of the epilogue of accumulator set `pv` (see the schedule above).  Every piece hands its values on through an empty `asm volatile`:
+    // that keeps it in its slot (left alone, the vectoriser pairs the pieces of two outputs and moves both into one slot).  bv holds the bias of
+    // column tile ct and is re-read for ct + 1 right behind its last use.
+    auto piece = [&](auto pvc, auto qc) {
+        constexpr int pv = decltype(pvc)::v, q = decltype(qc)::v, ct = q / 17, r = q % 17;
+        if constexpr (r < 16) {
+            constexpr int e = r >> 2, sub = r & 3;
+            if constexpr (sub == 0) {
+                ex = acc[pv][ct][e] + bv[e];
+                if constexpr (GELU) {
+                    ea = fminf(fabsf(ex), MI355_GELU_CLAMP);
+                    ep = __builtin_fmaf(MI355_GELU16_H5, ea, MI355_GELU16_H4);
+                    asm volatile("" : "+v"(ex), "+v"(ea), "+v"(ep));
+                } else {
+                    asm volatile("" : "+v"(ex));
+                }
+            } else if constexpr (sub == 1) {
+                if constexpr (e == 3 && ct < 3) bv = bias4(ct + 1);
+                if constexpr (GELU) {
+                    ep = __builtin_fmaf(ep, ea, MI355_GELU16_H3);
+                    ep = __builtin_fmaf(ep, ea, MI355_GELU16_H2);
+                    ep = __builtin_fmaf(ep, ea, MI355_GELU16_H1);
+                    asm volatile("" : "+v"(ep));
+                }
+            } else if constexpr (sub == 2) {
+                if constexpr (GELU) {
+                    ep = __builtin_fmaf(ep, ea, MI355_GELU16_H0);
+                    ep = __builtin_amdgcn_exp2f(ep);
+                    ex = __builtin_fmaf(0.5f, fabsf(ex), 0.5f * ex);
+                    asm volatile("" : "+v"(ep), "+v"(ex));
+                }
+            } else {
+                if constexpr (GELU) ev[e] = __builtin_fmaf(-ea, ep, ex);
+                else                ev[e] = ex;
+                asm volatile("" : "+v"(ev[e]));
+                if constexpr (e == 3) pend[pv][ct] = t4{(T)ev[0], (T)ev[1], (T)ev[2], (T)ev[3]};
+            }
+        } else {
+            if constexpr (F16) rgmax = rg_absmax4_f(rgmax, f4{ev[0], ev[1], ev[2], ev[3]});
         }
     };
-    for (; tile < ntile; tile += nstream) {
-        asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-        WST_BAR();                                                     // the tile is complete in LDS; everybody is done with the previous one
-        const long ahead = tile + (long)(NB - 1) * nstream;
-        if (ahead < ntile) dma_tile(ahead, (buf + NB - 1) % NB);      // into the buffer the previous tile has just left
-        flush();
-        f4 acc[RT][4];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = f4{0.f, 0.f, 0.f, 0.f};
-        const unsigned short* xb = &s_x[buf][0];
-        auto xfrag = [&](int idx) {                                   // flat order over (ks, rt)
-            const int ks = idx / RT, rt = idx % RT;
-            return *reinterpret_cast<const v8*>(xb + ((rt * 16 + l15) * CPR + ((ks * 4 + gq) ^ l15)) * 8);
+
+    // one row block: 96 slots.  st: the deferred stores of this row block of the tile before exist (C row pointer crow);
+    // DMA: six pieces of the tile two ahead (source dbase, LDS byte address ddst)
+    auto block = [&](auto rtc, auto dmac, bool st, char* crow, const char* dbase, unsigned ddst) {
+        constexpr int rt = decltype(rtc)::v;
+        constexpr bool DMA = decltype(dmac)::v != 0;
+        auto slot = [&](auto mc) {
+            constexpr int m = decltype(mc)::v, ks = m >> 2, ct = m & 3;
+            if constexpr (ks == 0)       wst_mfma_a0<T>(acc[rt][ct], wa[ct][0], xq[0]);
+            else if constexpr (ks < KSA) wst_mfma_a<T>(acc[rt][ct], wa[ct][ks < KSA ? ks : 0], xq[ks & 3]);
+            else                         wst_mfma_v<T>(acc[rt][ct], wv[ct][ks >= KSA ? ks - KSA : 0], xq[ks & 3]);
+            if constexpr (m < 4) {
+                if (st) *reinterpret_cast<t4*>(crow + coff + m * 32) = pend[rt][m];
+            }
+            if constexpr (m == 1) bv = bias4(0);
+            if constexpr (ct == 1) {                                   // into the ring slot the k-step before has left
+                constexpr int f = ks + 3;
+                if constexpr (f < KS)       xq[f & 3] = xfrag(rt, f);
+                else if constexpr (rt == 0) xq[f & 3] = xfrag(1, f - KS);
+            }
+            if constexpr (DMA && (m & 15) == 3) dq = s_doff[rt * 6 + (m >> 4)][t];
+            if constexpr (DMA && (m & 15) == 7) {
+                constexpr int pi = rt * 6 + (m >> 4);
+                wst_dma_so(dbase, dq, ddst + (unsigned)(wave + 4 * pi) * 1024u);
+            }
+            if constexpr (m >= 4 && (m & 3) != 3) {
+                constexpr int q = (m - 4) - (m - 4) / 4;
+                if constexpr (q < NPIECE) piece(WstI<rt ^ 1>{}, WstI<q>{});
+            }
+            __builtin_amdgcn_sched_barrier(0);
         };
-        v8 xq[5];
+        WstUnroll<0, 96>::run(slot);
+    };
+
+    int buf = 0;
+    bool first = true;
+    for (; tile < ntile; tile += nstream) {
+        if (tile + nstream < ntile) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");      // twelve pieces of the next tile were issued behind this one's
+        else                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the last tile of the stream: nothing was
+        WST_BAR();                                                     // the tile is complete in LDS; everybody is done with the previous one
 #pragma unroll
-        for (int pre = 0; pre < 4; ++pre) xq[pre] = xfrag(pre);
-#pragma unroll
-        for (int idx = 0; idx < KS * RT; ++idx) {
-            if (idx + 4 < KS * RT) xq[(idx + 4) % 5] = xfrag(idx + 4);
-            const int ks = idx / RT, rt = idx % RT;
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) {
-                if (ks < KSA) wst_mfma_a<T>(acc[rt][ct], wa[ct][ks < KSA ? ks : 0], xq[idx % 5]);
-                else          wst_mfma_v<T>(acc[rt][ct], wv[ct][ks >= KSA ? ks - KSA : 0], xq[idx % 5]);
-            }
+        for (int f = 0; f < 3; ++f) xq[f] = xfrag(0, f);
+        const int ahead = tile + (NB - 1) * nstream;
+        const char* dbase = reinterpret_cast<const char*>(A + (long)ahead * ROWS * g.lda);
+        const unsigned ddst = lds0 + (unsigned)((buf + NB - 1) % NB) * (TILE_EL * 2);      // the buffer the previous tile has just left
+        char* crow = reinterpret_cast<char*>(C + (long)(tile - nstream) * ROWS * g.ldc);      // wave-uniform: the stores add one 32-bit lane offset
+        const bool st = !first;
+        const bool dma = ahead < ntile;
+        __builtin_amdgcn_sched_barrier(0);
+        if (dma) {
+            block(WstI<0>{}, WstI<1>{}, st, crow, dbase, ddst);
+            if (first) rgmax = 0.f;                                    // row block 0 of the first tile drained an empty set
+            block(WstI<1>{}, WstI<1>{}, st, crow + 32 * (long)g.ldc, dbase, ddst);
+        } else {
+            block(WstI<0>{}, WstI<0>{}, st, crow, dbase, ddst);
+            if (first) rgmax = 0.f;
+            block(WstI<1>{}, WstI<0>{}, st, crow + 32 * (long)g.ldc, dbase, ddst);
         }
-        asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");             // the last MFMAs retire before the VALU reads their accumulators
+        first = false;
+        const int step = buf == NB - 1 ? -(NB - 1) * TILE_EL : TILE_EL;
 #pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) {
-                f4 v = acc[rt][ct] + *reinterpret_cast<const f4*>(&s_bias[wave * 64 + ct * 16 + gq * 4]);
-                if constexpr (GELU) v = gelu16_fast4(v);
-                if constexpr (std::is_same<T, _Float16>::value) rgmax = rg_absmax4_f(rgmax, v);
-                pend[rt][ct] = t4{(T)v.x, (T)v.y, (T)v.z, (T)v.w};
-            }
-        }
-        prow = tile * ROWS + l15;
+        for (int kl = 0; kl < 4; ++kl) xp[kl] += step;
         buf = (buf + 1) % NB;
     }
-    flush();
-    if constexpr (std::is_same<T, _Float16>::value) rg_report_f(rgmax, g.ovf, 3u);
+    if (!first) {                                                      // drain: row block 0 of the last tile waits in pend[0], row block 1 in acc[1]
+        char* crow = reinterpret_cast<char*>(C + (long)(tile - nstream) * ROWS * g.ldc);
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) *reinterpret_cast<t4*>(crow + coff + ct * 32) = pend[0][ct];
+        asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");             // the last MFMAs retire before the VALU reads their accumulators
+        bv = bias4(0);
+        auto tail = [&](auto qc) { piece(WstI<1>{}, qc); };
+        WstUnroll<0, NPIECE>::run(tail);
+        crow += 32 * (long)g.ldc;
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) *reinterpret_cast<t4*>(crow + coff + ct * 32) = pend[1][ct];
+    }
+    if constexpr (F16) rg_report_f(rgmax, g.ovf, 3u);
 }
 
 }  // namespace
 
 namespace mi355 {
 
-// MI355_EUNSUPPORTED (nothing launched) unless the product is one this schedule is built for: 16-bit output, K = 768, N a multiple of 192 (options
-// 3 / 4: of 256, and M of 32), at least eight row tiles per workgroup of a slab.
-int gemm16_wst(const G16Args& g, int out16, int precision, hipStream_t st) {
-    if (!out16 || g.K != 768 || (g.N % 192) || g.resid || g.gamma || g.resid_period || g.rowtau || g.lnc_a || g.row_stats || g.ln16_out)
+// MI355_EUNSUPPORTED (nothing launched) unless the product is one this schedule is built for: 16-bit output, K = 768 and
+//   one_wave (the default route of linear16_dispatch, and options 3 / 4): N a multiple of 256, M of 32 -- any number of row tiles, streams of
+//            0, 1, 2 ... tiles included: how many rows make the kernel worth its weight prologue is the dispatch's business;
+//   otherwise (options 1 / 2): N a multiple of 192, at least eight row tiles per workgroup of a slab.
+int gemm16_wst(const G16Args& g, int out16, int precision, hipStream_t st, bool one_wave) {
+    one_wave = one_wave || opt(O_GEMM_WST) == 3 || opt(O_GEMM_WST) == 4;
+    if (!out16 || g.K != 768 || (g.N % (one_wave ? 256 : 192)) || g.resid || g.gamma || g.resid_period || g.rowtau || g.lnc_a || g.row_stats || g.ln16_out)
         return MI355_EUNSUPPORTED;
     if (g.act != MI355_ACT_NONE && g.act != MI355_ACT_GELU) return MI355_EUNSUPPORTED;
     if ((g.lda & 7) || (g.ldb & 7) || (g.ldc & 3) || !aligned16(g.A) || !aligned16(g.B) || !aligned16(g.C) || (g.bias && !aligned16(g.bias)))
         return MI355_EUNSUPPORTED;
     if (precision != MI355_PREC_FP16 && precision != MI355_PREC_BF16) return MI355_EUNSUPPORTED;
     const int ncu = resident_slots(1);
-    const int nslab = g.N / 192;
-    if (nslab > ncu || (long)g.M < 32L * 8 * (ncu / nslab)) return MI355_EUNSUPPORTED;     // too few rows to amortise the resident weights
+    const int nslab = g.N / (one_wave ? 256 : 192);
+    if (nslab > ncu) return MI355_EUNSUPPORTED;
+    if (one_wave ? ((g.M & 31) || (long)g.lda * 32 * 2 >= (1L << 31) || (long)g.ldc * 32 * 2 >= (1L << 31)) : (long)g.M < 32L * 8 * (ncu / nslab)) return MI355_EUNSUPPORTED;
     MI355_TRACE(st, "gemm16_wst_kernel<%s,out16> M=%d N=%d K=%d%s", precision == MI355_PREC_FP16 ? "f16" : "bf16", g.M, g.N, g.K,
                 g.act == MI355_ACT_GELU ? " gelu" : "");
-    if (opt(O_GEMM_WST) >= 3) {                                         // one wave per SIMD, weight fragments in AGPRs (256-column slabs, M % 32 == 0)
-        if ((g.N & 255) || (g.M & 31) || (long)g.lda * 32 * 2 >= (1L << 31)) return MI355_EUNSUPPORTED;
-        const int ns = g.N / 256;
+    if (one_wave) {                                                     // one wave per SIMD, weight fragments in AGPRs (256-column slabs, M % 32 == 0)
+        const int ns = nslab;
         if (g.act == MI355_ACT_GELU) {
             if (precision == MI355_PREC_FP16) gemm16_wst1_kernel<_Float16, true><<<ncu, 256, 0, st>>>(g, ns);
             else                              gemm16_wst1_kernel<__bf16, true><<<ncu, 256, 0, st>>>(g, ns);

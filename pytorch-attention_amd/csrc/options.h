@@ -37,8 +37,13 @@ MI355_OPT(GEMM_WREG, "gemm_wreg", 1, 0, 1)                 // fp32 (+ residual) 
 MI355_OPT(XCA_TR, "xca_tr", 1, 0, 1)                       // XCA core with 16-bit q / k / v and N <= 224: covariance on the 16-bit matrix pipe from one transposed LDS image (xcit.hip xca_tr_kernel)
 MI355_OPT(MLP_WIDE, "mlp_wide", 0, 0, 1)                   // 1 = mi355_mlp_fused_fwd takes C = 256 / 384 (hidden 4C) on the weight-split kernel (mlp_wide.hip); measured SLOWER than LayerNorm + two GEMMs
                                                            // (profiles/r06_mlp_wide.md), hence opt-in; 0 (default) = those shapes are MI355_EUNSUPPORTED
-MI355_OPT(GEMM_WST, "gemm_wst", 0, 0, 4)                   // 16-bit outputs with K = 768, N % 192 == 0 (ViT qkv / fc1): weights stationary in registers (gemm16_wst.hip); 1 = products without
-                                                           // activation, 2 = GELU epilogues too; 3 / 4 = the same on the one-wave-per-SIMD kernel with W in AGPRs.  Measured slower than the tile kernels (profiles/r06_gemm_wst.md): opt-in
+MI355_OPT(GEMM_WST, "gemm_wst", 5, 0, 6)                   // 16-bit outputs with K = 768 (ViT qkv / fc1): weights stationary in registers (gemm16_wst.hip).  0 = never.  Forced, whatever the row
+                                                           // count: 1 = products without activation, 2 = GELU epilogues too, on the 8-wave K-split kernel (N % 192 == 0; measured slower,
+                                                           // profiles/r06_gemm_wst.md); 3 / 4 = the same on the software-pipelined one-wave-per-SIMD kernel with W in AGPRs (N % 256 == 0,
+                                                           // M % 32 == 0).  Default route to that kernel from the dispatch's row floor up: 5 (default) = GELU epilogues (ViT fc1), where it
+                                                           // measured faster; 6 = every such product (qkv, the k / v product of the pooled-token tail too: a tie, profiles/gemm_wst_pipe.md).
+                                                           // ONE value, so the modes exclude each other: forcing a kernel (1 .. 4) also turns the default route (5 / 6) off for the
+                                                           // products the forced kernel does not take
 MI355_OPT(GEMM_WSLAB, "gemm_wslab", 1, 0, 2)               // 16-bit outputs with K = 256 / 384 / 512 (XCiT / CSWin stage 3-4 / Mixer qkv and fc1): a column slab of W stationary in
                                                            // registers (gemm16_wslab.hip); 1 = GELU epilogues and M % 256 != 0 (where it measured faster), 2 = every product it takes
 MI355_OPT(IO16_OCC, "io16_occ", 4, 2, 4)                   // single-read SE on 16-bit activations (chan_io16.hip): workgroups per CU the grid is sized for, capped by the kernel's register budget
