@@ -498,13 +498,15 @@ int mi355_sk_fwd(const float* x, const float* const* params, float* y, int B, in
  * PAM :20-28 is composed by the caller from mi355_conv2d_tokens_fwd (the three 1x1 convs as one token-major GEMM),
  * mi355_sdpa_general_fwd (one head of width C, scale 1) and mi355_tokens_to_nchw_axpy_fwd:
  *   y[b,c,p] = alpha[0] * tokens[b,p,c] + x[b,c,p]      tokens (B,HW,C), x / y (B,C,HW), alpha a 1-element device array;
- *   alpha == NULL means 1, x == NULL means 0 (a plain token-major -> NCHW transpose). */
+ *   alpha == NULL means 1, x == NULL means 0 (a plain token-major -> NCHW transpose).  Token row p of image b starts at
+ *   tokens + (b*HW + p)*ld_tokens (ld_tokens >= C, in elements): the rows may be wider than C, as PAM's attention output is when the
+ *   channel count was zero-padded onto a head width of the attention kernel; the columns beyond C are not read. */
 size_t mi355_cam_workspace_bytes(int B, int C);
 size_t mi355_cam_ws_bytes(int B, int C, int H, int W);
 int mi355_cam_fwd(const float* x, const float* beta, float* y, int B, int C, int H, int W, int precision, void* workspace,
                   size_t workspace_bytes, mi355_stream_t stream);
 int mi355_tokens_to_nchw_axpy_fwd(const float* tokens, const float* x, const float* alpha, float* y, int B, int HW, int C,
-                                  mi355_stream_t stream);
+                                  long ld_tokens, mi355_stream_t stream);
 
 /* ---- glue of the remaining multi-head-attention copies ------------------------------------------------------------
  * mi355_dwconv_nchw_tokens_fwd: depth-wise ks x ks convolution (stride 1, zero padding (ks-1)/2) of an NCHW map, written token-major:
@@ -828,7 +830,9 @@ int mi355_vit_tail_fwd(const float* x, const float* ln1_w, const float* ln1_b, f
  * >= heads*head_dim), so they may be slices of one fused projection or separate tensors.  bias (heads, Nq, Nkv) fp32 or NULL;
  * image b uses bias + b*bias_batch_stride (0 = shared).  io16 = 0: fp32 tensors; 1: tensors in the 16-bit operand type of
  * `precision` (1 fp16, 2 bf16).  head_dim in {32, 64, 128, 192, 256}; above 64 the value / output columns are processed in 64-wide
- * slices, one workgroup per (query block, slice).  bias entries are finite or -inf (a masked_fill mask; mi355_topk_mask_fwd writes
+ * slices, one workgroup per (query block, slice).  head_dim a multiple of 64 in [320, 2048] runs on the wide-head kernel (the logits
+ * contracted over 64-channel chunks, ceil(head_dim / 256) value / output slices): io16 = 0 and bias == NULL only, otherwise
+ * MI355_EUNSUPPORTED.  Every other head_dim: MI355_EUNSUPPORTED, nothing launched.  bias entries are finite or -inf (a masked_fill mask; mi355_topk_mask_fwd writes
  * -1e30): -inf keys get weight 0 wherever they lie, and a row with no finite logit yields NaN, as torch.softmax does. */
 int mi355_sdpa_general_fwd(const void* q, const void* k, const void* v, const float* bias, void* out, int B, int num_heads, int Nq,
                            int Nkv, int head_dim, long ldq, long ldk, long ldv, long ldo, long bias_batch_stride, float scale,

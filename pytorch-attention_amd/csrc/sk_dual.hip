@@ -252,17 +252,17 @@ __global__ __launch_bounds__(256) void softmax_rows_scaled_kernel(float* __restr
 
 // ---- PAM epilogue: y[b, c, p] = alpha[0] * tok[b, p, c] + x[b, c, p]; 32 x 32 tiles through LDS ----------------------------------
 __global__ __launch_bounds__(256) void tokens_to_nchw_axpy_kernel(const float* __restrict__ tok, const float* __restrict__ x, const float* __restrict__ alpha,
-                                                                 float* __restrict__ y, long HW, int C) {
+                                                                 float* __restrict__ y, long HW, int C, long ldt) {
     __shared__ float tile[32][33];
     const int b = blockIdx.z, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;       // 32 x 8
     const long p0 = (long)blockIdx.x * 32;
     const int c0 = blockIdx.y * 32;
-    const float* tb = tok + (long)b * HW * C;
+    const float* tb = tok + (long)b * HW * ldt;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const long p = p0 + ty + r * 8;
         const int c = c0 + tx;
-        tile[ty + r * 8][tx] = (p < HW && c < C) ? tb[p * C + c] : 0.f;
+        tile[ty + r * 8][tx] = (p < HW && c < C) ? tb[p * ldt + c] : 0.f;
     }
     __syncthreads();
     const float a = alpha ? alpha[0] : 1.0f;
@@ -410,9 +410,10 @@ int mi355_cam_fwd(const float* x, const float* beta, float* y, int B, int C, int
 }
 
 int mi355_tokens_to_nchw_axpy_fwd(const float* tokens, const float* x, const float* alpha, float* y, int B, int HW, int C,
-                                  mi355_stream_t stream) {
-    MI355_CHECK_ARG(tokens && y && B > 0 && HW > 0 && C > 0 && B <= 65535);
-    tokens_to_nchw_axpy_kernel<<<dim3(cdiv(HW, 32), cdiv(C, 32), B), 256, 0, static_cast<hipStream_t>(stream)>>>(tokens, x, alpha, y, HW, C);
+                                  long ld_tokens, mi355_stream_t stream) {
+    MI355_CHECK_ARG(tokens && y && B > 0 && HW > 0 && C > 0 && B <= 65535 && ld_tokens >= C);
+    tokens_to_nchw_axpy_kernel<<<dim3(cdiv(HW, 32), cdiv(C, 32), B), 256, 0, static_cast<hipStream_t>(stream)>>>(tokens, x, alpha, y, HW, C,
+                                                                                                                   ld_tokens);
     MI355_LAUNCH_CHECK();
     return MI355_OK;
 }

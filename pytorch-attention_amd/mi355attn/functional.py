@@ -456,15 +456,19 @@ def cam_forward(x, beta, precision=None):
 
 
 def tokens_to_nchw_axpy(tokens, x, alpha):
-    """y[b,c,h,w] = alpha * tokens[b, h*W + w, c] + x[b,c,h,w]."""
+    """y[b,c,h,w] = alpha * tokens[b, h*W + w, c] + x[b,c,h,w].  tokens may be the first C columns of wider rows (a (B, H*W, C) view with
+    unit channel stride and a dense batch axis, as PAM's attention output on a zero-padded head width): the C entry takes the row stride."""
     x = require_device_f32(x, "x")
-    tokens = require_device_f32(tokens, "tokens")
     B, C, H, W = x.shape
-    if tuple(tokens.shape) != (B, H * W, C):
+    if not isinstance(tokens, torch.Tensor) or tuple(tokens.shape) != (B, H * W, C):
         raise ValueError("tokens_to_nchw_axpy: tokens must be (B, H*W, C)")
+    if tokens.is_cuda and tokens.dtype == torch.float32 and not tokens.is_contiguous():
+        tokens, ldt = _rows3(tokens, "tokens")
+    else:
+        tokens, ldt = require_device_f32(tokens, "tokens"), C
     alpha = require_device_f32(alpha, "alpha").reshape(1)
     y = torch.empty_like(x)
-    check(lib().mi355_tokens_to_nchw_axpy_fwd(dptr(tokens), dptr(x), dptr(alpha), dptr(y), B, H * W, C, stream_ptr(x.device)),
+    check(lib().mi355_tokens_to_nchw_axpy_fwd(dptr(tokens), dptr(x), dptr(alpha), dptr(y), B, H * W, C, ldt, stream_ptr(x.device)),
           "mi355_tokens_to_nchw_axpy_fwd")
     return y
 
@@ -1557,6 +1561,8 @@ def sdpa_general(q, k, v, num_heads, scale, bias=None, precision=None, out=None)
     this entry pads nothing.  All ten classes of modules/mhsa.py (Attention, SRAttention, SRAttentionRelPos, SRConvAttention,
     GlobalAttention, Broad_Attention, QKVSplitAttention, KNNAttention, ConvAttention, PoolingAttention) and ViT's Attention zero-pad
     any other width up to 256 onto the next of these (attn_head_width, head_padded) before they call it.
+    Wide heads (sdpa_wide_ok: a multiple of 64 from 320 to SDPA_WIDE_MAX = 2048) run on the channel-chunked kernel with fp32 tensors
+    and no bias only -- PAM's single head as wide as its map has channels; the entry refuses them in 16 bits or with a bias.
     bias entries are finite or -inf (masked_fill masks): a -inf key gets weight 0, a row with no finite logit comes out NaN, as
     torch.softmax gives it."""
     p = _prec(precision)
@@ -1597,7 +1603,7 @@ def tokens_to_nchw(tokens, H, W):
     if L != H * W:
         raise ValueError("tokens_to_nchw: token count does not match (H, W)")
     y = torch.empty(B, C, H, W, dtype=torch.float32, device=tokens.device)
-    check(lib().mi355_tokens_to_nchw_axpy_fwd(dptr(tokens), dptr(None), dptr(None), dptr(y), B, L, C, stream_ptr(tokens.device)),
+    check(lib().mi355_tokens_to_nchw_axpy_fwd(dptr(tokens), dptr(None), dptr(None), dptr(y), B, L, C, C, stream_ptr(tokens.device)),
           "mi355_tokens_to_nchw_axpy_fwd")
     return y
 
@@ -1694,6 +1700,12 @@ def head_padded(weight, bias, groups, d, dp, axis):
 
 
 SDPA_WIDTHS = (32, 64, 128, 192, 256)      # head widths mi355_sdpa_general_fwd is built for
+SDPA_WIDE_MAX = 2048                       # widest head of its channel-chunked kernel (fp32 tensors, no bias)
+
+
+def sdpa_wide_ok(d):
+    """True for the head widths mi355_sdpa_general_fwd runs on the wide-head kernel: multiples of 64 from 320 to SDPA_WIDE_MAX."""
+    return d % 64 == 0 and 320 <= d <= SDPA_WIDE_MAX
 
 
 def attn_head_width(d):

@@ -248,8 +248,11 @@ class SKLayer(nn.Module):
 class PAM(nn.Module):
     """Position attention of DANet (dual_attention.py:10-28): the three 1x1 convs as ONE token-major GEMM, the streaming attention
     kernel with a single head of width `dim` and scale 1, and a transposing alpha * y + x epilogue.  The logits are unscaled dot
-    products, so the default is the fp32-class precision mode (0).  dim <= 256 is one head; wider maps (DANet itself: 512) run as
-    two channel halves whose logits are added through the kernel's bias input."""
+    products, so the default is the fp32-class precision mode (0).  Any dim from 1 to 2048 on any map size, fp32 activations
+    (_route): a head width of the streaming kernel is one head as it is; any other dim <= 256 runs zero-padded onto the next of them;
+    320 / 384 / 448 / 512 (DANet itself: 512) run as two channel halves whose logits are added through the kernel's bias input;
+    every other dim up to 2048 (ResNet's 2048, ViT's 768) runs zero-padded onto a multiple of 64 on the wide-head kernel, which
+    contracts the logits over channel chunks and writes no hw x hw matrix."""
 
     def __init__(self, dim):
         super().__init__()
@@ -259,7 +262,23 @@ class PAM(nn.Module):
         self.alpha = nn.Parameter(torch.zeros(1))
         self.precision = F.PREC_STRICT
 
-    def _fused(self):
+    @staticmethod
+    def _route(c):
+        """(kind, cp): how a map of c channels runs and the head width it runs on."""
+        if c in F.SDPA_WIDTHS:
+            return "one", c
+        if c <= F.SDPA_WIDTHS[-1]:
+            return "padded", F.attn_head_width(c)
+        if any(c - c0 in F.SDPA_WIDTHS for c0 in F.SDPA_WIDTHS):
+            return "pair", c
+        if c <= F.SDPA_WIDE_MAX:
+            return "wide", (c + 63) // 64 * 64
+        raise NotImplementedError(f"PAM: dim {c} is above the widest head of the attention kernels ({F.SDPA_WIDE_MAX})")
+
+    def _fused(self, cp=None):
+        """The b | c | d weights as the rows of one GEMM and their biases, built once per parameter version.  With cp, each of the three
+        blocks is zero-padded to cp rows (and bias entries): the GEMM then emits (n, hw, 3 * cp) with 16-byte aligned q / k / v slices
+        for any dim; zero q / k columns add nothing to the logits, zero v columns give output columns nobody reads."""
         ws = (self.b.weight, self.c.weight, self.d.weight, self.b.bias, self.c.bias, self.d.bias)
         tag = tuple((t._version, t.data_ptr()) for t in ws)
 
@@ -267,14 +286,31 @@ class PAM(nn.Module):
             w = torch.cat([t.detach() for t in ws[:3]], dim=0).contiguous()
             return F._gemm_rows(w, 0), torch.cat([t.detach() for t in ws[3:]]).contiguous()
 
-        return F._derived_get(ws, ("pam_bcd",), tag, build)
+        def build_padded():
+            c = ws[0].shape[0]
+            w = torch.zeros(3, cp, c, dtype=torch.float32, device=ws[0].device)
+            bias = torch.zeros(3, cp, dtype=torch.float32, device=ws[0].device)
+            for i in range(3):
+                w[i, :c] = ws[i].detach().reshape(c, c)
+                bias[i, :c] = ws[3 + i].detach()
+            return F._gemm_rows(w.reshape(3 * cp, c, 1, 1), 0), bias.reshape(3 * cp)
+
+        if cp is None:
+            return F._derived_get(ws, ("pam_bcd",), tag, build)
+        return F._derived_get(ws, ("pam_bcd_padded", cp), tag, build_padded)
 
     def forward(self, x):
         n, c, h, w = x.shape
+        kind, cp = self._route(c)
+        if kind in ("padded", "wide"):
+            rows, bias = self._fused(cp)
+            bcd, _ = F.conv2d_tokens(x, None, bias, 1, 1, 0, 0, precision=self.precision, wrows=rows)    # (n, hw, 3 cp)
+            y = F.sdpa_general(bcd[:, :, :cp], bcd[:, :, cp:2 * cp], bcd[:, :, 2 * cp:], 1, 1.0, precision=self.precision)
+            return F.tokens_to_nchw_axpy(y[:, :, :c], x, self.alpha)                                      # rows of cp, the first c read
         rows, bias = self._fused()
         bcd, _ = F.conv2d_tokens(x, None, bias, 1, 1, 0, 0, precision=self.precision, wrows=rows)        # (n, hw, 3c)
         q, k, v = bcd[:, :, :c], bcd[:, :, c:2 * c], bcd[:, :, 2 * c:]
-        if c <= F.SDPA_WIDTHS[-1]:
+        if kind == "one":
             y = F.sdpa_general(q, k, v, 1, 1.0, precision=self.precision)
         else:
             # dim above the kernel's widest head (DANet's own PAM is 512 wide): cut the channel axis in two, c = c0 + c1.  The logits
