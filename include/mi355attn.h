@@ -465,8 +465,15 @@ int mi355_bam16_fwd(const void* x, const float* const* params, void* y, int B, i
 
 /*   sk        sk_module.py:41-56   u1 = relu(bn(conv3x3_grouped(x))), u2 = relu(bn(conv3x3_grouped_dilation2(x))), s = mean_hw(u1 + u2),
  *                                  z = relu(bn1d(fc s)), [a, b] = softmax over the two branches of [fc1 z, fc2 z], y = u1 a + u2 b.
- *                                  x (B,Cin,H,W), y (B,planes,H,W); planes / groups in {1,2,4,8,16}; parameters as an array of
- *                                  MI355_SK_NPARAMS device pointers. */
+ *                                  x (B,Cin,H,W), y (B,planes,H,W); parameters as an array of MI355_SK_NPARAMS device pointers.
+ *                                  Any groups that divides Cin and planes, any H, W >= 1; d + planes <= 12288 (else
+ *                                  MI355_EUNSUPPORTED).  planes / groups in {1,2,4,8,16}: fp32 FMA branch kernels, workspace
+ *                                  mi355_sk_workspace_bytes.  Every other width -- and every shape while option "sk_wide" is 1 --
+ *                                  runs the two branches as a grouped implicit GEMM on the matrix cores in the fp32-class
+ *                                  split-bf16 operand format (no 16-bit rounding of results, nothing reported to the range word)
+ *                                  and needs the workspace of mi355_sk_ws_bytes (the planes above plus the packed weights and
+ *                                  the band-wise pooled sums); below it: MI355_EINVAL, nothing launched.  mi355_sk_ws_bytes is
+ *                                  >= mi355_sk_workspace_bytes and valid for both routes. */
 enum {
     MI355_SK_CONV3_W = 0,      /* (planes, Cin/groups, 3, 3)  split_3x3[0].weight */
     MI355_SK_CONV3_SCALE,      /* (planes)   split_3x3[1] folded */
@@ -485,6 +492,7 @@ enum {
     MI355_SK_NPARAMS
 };
 size_t mi355_sk_workspace_bytes(int B, int planes, int H, int W);
+size_t mi355_sk_ws_bytes(int B, int Cin, int planes, int groups, int H, int W);
 int mi355_sk_fwd(const float* x, const float* const* params, float* y, int B, int Cin, int planes, int groups, int d, int H, int W,
                  void* workspace, size_t workspace_bytes, mi355_stream_t stream);
 

@@ -137,6 +137,11 @@ int  axis16_plane_pool(const void* x, int io, bool with_max, float* h_mean, floa
 void axis16_plane_dot(const void* x, int io, float* out, long planes, long HW, float scale, hipStream_t st);
 void axis16_apply(int mode, const void* x, int io, void* y, const float* a, const float* b, const float* c, int B, int C, int H, int W,
                   hipStream_t st);
+// SKLayer's two grouped 3x3 branches on the matrix cores (sk_wide.hip): u1 / u2 and band-wise pooled sums; `extra` is the
+// 16-byte-aligned region of sk_wide_extra_floats() floats behind the planes of mi355_sk_workspace_bytes
+size_t sk_wide_extra_floats(int B, int Cin, int planes, int groups, int H, int W);
+int  sk_wide(const float* x, const float* const* p, float* u1, float* u2, float* extra, float** pooled_out, int* nb_out, int B, int Cin,
+             int planes, int groups, int H, int W, hipStream_t st);
 // GEMM engine (gemm.hip), shared by the other translation units.  NT: B is (N,K) K-contiguous; KN: B is (K,N) N-contiguous.
 int gemm_nt(const float* A, const float* B, const float* bias, const float* gamma, const float* resid, float* C, int M, int N,
             int K, int lda, int ldb, int ldc, int act, int precision, hipStream_t st);

@@ -49,3 +49,5 @@ MI355_OPT(GEMM_WSLAB, "gemm_wslab", 1, 0, 2)               // 16-bit outputs wit
 MI355_OPT(IO16_OCC, "io16_occ", 4, 2, 4)                   // single-read SE on 16-bit activations (chan_io16.hip): workgroups per CU the grid is sized for, capped by the kernel's register budget
 MI355_OPT(VIT_TAIL, "vit_tail", 1, 0, 1)                   // host policy (read by the binding): 1 = a ViT that pools token 0 runs its LAST encoder block through mi355_vit_tail_fwd
                                                            // (only the rows that token needs: vit_tail.hip); 0 = the full block
+MI355_OPT(SK_WIDE, "sk_wide", 0, 0, 1)                     // SKLayer branches: 1 = every shape on the matrix-core grouped implicit GEMM (sk_wide.hip); 0 (default) = only where
+                                                           // the fp32 FMA kernels do not apply (planes / groups outside {1, 2, 4, 8, 16})

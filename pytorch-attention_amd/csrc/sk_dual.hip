@@ -5,7 +5,8 @@
 //   folded BatchNorm + ReLU, writes u1 / u2 and leaves the pooled sum of u1 + u2 per (image, channel) -- a workgroup owns one
 //   (image, group) and therefore every pixel of its output channels, which makes the pooled sum a plain deterministic block
 //   reduction.  A tiny per-image kernel evaluates fc -> BN1d -> ReLU -> fc1 / fc2 -> softmax over the two branches, and the
-//   apply pass blends u1 and u2.
+//   apply pass blends u1 and u2.  planes / groups outside {1, 2, 4, 8, 16} (and every shape under option sk_wide) runs the two
+//   branches on the matrix cores instead: sk_wide.hip.
 // CAM: softmax(X X^T) X on the GEMM engine (x is a (C x HW) matrix per image, HW contiguous -- never transposed in memory), the
 //   row softmax scaled by beta in between, the residual in the second product's epilogue.
 // PAM: host side composes the three 1x1 convs (one token-major GEMM), the streaming attention kernel and tokens_to_nchw_axpy_kernel
@@ -288,15 +289,24 @@ size_t mi355_sk_workspace_bytes(int B, int planes, int H, int W) {
     return 4 * (2 * fl((size_t)B * planes * H * W) + fl((size_t)B * planes * H) + fl((size_t)B * 2 * planes)) + 256;
 }
 
+// The same for any planes / groups: the planes above, then what the matrix-core branch kernel (sk_wide.hip) adds -- its band-wise pooled
+// sums and the packed split-bf16 weights.  mi355_sk_fwd asks for this size only when it takes that kernel.
+size_t mi355_sk_ws_bytes(int B, int Cin, int planes, int groups, int H, int W) {
+    if (B <= 0 || Cin <= 0 || planes <= 0 || groups <= 0 || H <= 0 || W <= 0 || Cin % groups || planes % groups) return 0;
+    return mi355_sk_workspace_bytes(B, planes, H, W) + 4 * mi355::sk_wide_extra_floats(B, Cin, planes, groups, H, W);
+}
+
 int mi355_sk_fwd(const float* x, const float* const* p, float* y, int B, int Cin, int planes, int groups, int d, int H, int W,
                  void* workspace, size_t workspace_bytes, mi355_stream_t stream) {
     MI355_CHECK_ARG(x && p && y && workspace && B > 0 && Cin > 0 && planes > 0 && groups > 0 && d > 0 && H > 0 && W > 0);
     MI355_CHECK_ARG(Cin % groups == 0 && planes % groups == 0);
     for (int q = 0; q < MI355_SK_NPARAMS; ++q) MI355_CHECK_ARG(p[q] != nullptr);
-    MI355_CHECK_ARG(workspace_bytes >= mi355_sk_workspace_bytes(B, planes, H, W) && aligned16(workspace));
     const int cog = planes / groups, cin_g = Cin / groups;
-    if (cog != 1 && cog != 2 && cog != 4 && cog != 8 && cog != 16)
-        return mi355::fail(MI355_EUNSUPPORTED, "mi355_sk_fwd: planes / groups = %d not in {1,2,4,8,16}", cog);
+    // the FMA kernels take planes / groups in {1, 2, 4, 8, 16}; every other width, and every shape under sk_wide = 1, runs its branches
+    // on the matrix cores (sk_wide.hip), which needs the larger workspace of mi355_sk_ws_bytes
+    const bool wide = mi355::opt(mi355::O_SK_WIDE) != 0 || (cog != 1 && cog != 2 && cog != 4 && cog != 8 && cog != 16);
+    if (wide) MI355_CHECK_ARG(workspace_bytes >= mi355_sk_ws_bytes(B, Cin, planes, groups, H, W) && aligned16(workspace));
+    else      MI355_CHECK_ARG(workspace_bytes >= mi355_sk_workspace_bytes(B, planes, H, W) && aligned16(workspace));
     if (d + planes > 12288) return mi355::fail(MI355_EUNSUPPORTED, "mi355_sk_fwd: d + planes = %d > 12288", d + planes);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long HW = (long)H * W;
@@ -312,7 +322,10 @@ int mi355_sk_fwd(const float* x, const float* const* p, float* y, int B, int Cin
     const size_t row_bytes = (size_t)cin_g * PW * sizeof(float);
     const long max_rows = ((long)49152 - (long)wbytes) / (long)row_bytes - 4;
     const bool tiled = (W & 3) == 0 && aligned16(x) && aligned16(u1) && max_rows >= 1 && cog <= 8 && B <= 65535;
-    if (tiled) {
+    if (wide) {
+        const int rc = mi355::sk_wide(x, p, u1, u2, att + fl((size_t)B * 2 * planes), &pooled, &nb, B, Cin, planes, groups, H, W, st);
+        if (rc) return rc;
+    } else if (tiled) {
         int brmax = max_rows < H ? (int)max_rows : H;
         const int fill = 256 / (W >> 2);                          // rows that one pass of the 256 threads covers (a thread = 4 pixels)
         if (fill >= 1 && brmax > fill) brmax = fill;
@@ -321,6 +334,7 @@ int mi355_sk_fwd(const float* x, const float* const* p, float* y, int B, int Cin
         nb = cdiv(H, BR);
         const size_t lds = (size_t)cin_g * (BR + 4) * PW * sizeof(float) + wbytes;
         const dim3 tgrid(groups, nb, B);
+        MI355_TRACE(st, "sk_branch_lds_kernel<%d> cin=%d bands=%d H=%d W=%d", cog, cin_g, nb, H, W);
 #define SKT(COG_)                                                                                                                    \
     sk_branch_lds_kernel<COG_><<<tgrid, 256, lds, st>>>(x, p[MI355_SK_CONV3_W], p[MI355_SK_CONV3_SCALE], p[MI355_SK_CONV3_SHIFT],    \
                                                         p[MI355_SK_CONV5_W], p[MI355_SK_CONV5_SCALE], p[MI355_SK_CONV5_SHIFT], u1, u2, \
@@ -334,6 +348,7 @@ int mi355_sk_fwd(const float* x, const float* const* p, float* y, int B, int Cin
 #undef SKT
     } else {
         const dim3 grid(groups, B);
+        MI355_TRACE(st, "sk_branch_kernel<%d> cin=%d H=%d W=%d", cog, cin_g, H, W);
 #define SKB(COG_, PIX_)                                                                                                             \
     sk_branch_kernel<COG_, PIX_><<<grid, 256, 0, st>>>(x, p[MI355_SK_CONV3_W], p[MI355_SK_CONV3_SCALE], p[MI355_SK_CONV3_SHIFT],   \
                                                        p[MI355_SK_CONV5_W], p[MI355_SK_CONV5_SCALE], p[MI355_SK_CONV5_SHIFT], u1, u2, \
@@ -347,12 +362,17 @@ int mi355_sk_fwd(const float* x, const float* const* p, float* y, int B, int Cin
         }
 #undef SKB
     }
-    sk_select_kernel<<<B, 256, (size_t)(d + planes) * sizeof(float), st>>>(pooled, p[MI355_SK_FC_W], p[MI355_SK_FC_B], p[MI355_SK_FC_BN_SCALE],
-                                                                          p[MI355_SK_FC_BN_SHIFT], p[MI355_SK_FC1_W], p[MI355_SK_FC1_B], p[MI355_SK_FC2_W],
-                                                                          p[MI355_SK_FC2_B], att, planes, d, 1.0f / (float)HW, nb);
+    {
+        MI355_TRACE(st, "sk_select_kernel planes=%d d=%d bands=%d", planes, d, nb);
+        sk_select_kernel<<<B, 256, (size_t)(d + planes) * sizeof(float), st>>>(pooled, p[MI355_SK_FC_W], p[MI355_SK_FC_B], p[MI355_SK_FC_BN_SCALE],
+                                                                              p[MI355_SK_FC_BN_SHIFT], p[MI355_SK_FC1_W], p[MI355_SK_FC1_B],
+                                                                              p[MI355_SK_FC2_W], p[MI355_SK_FC2_B], att, planes, d, 1.0f / (float)HW, nb);
+    }
     const long n = (long)B * planes * HW;
-    if ((HW & 3) == 0 && aligned16(y)) sk_apply_kernel<4><<<cdiv(n / 4, 256), 256, 0, st>>>(u1, u2, att, y, n / 4, HW, planes);
-    else                               sk_apply_kernel<1><<<cdiv(n, 256), 256, 0, st>>>(u1, u2, att, y, n, HW, planes);
+    const bool vec4 = (HW & 3) == 0 && aligned16(y);
+    MI355_TRACE(st, "sk_apply_kernel<%d> planes=%d HW=%ld", vec4 ? 4 : 1, planes, HW);
+    if (vec4) sk_apply_kernel<4><<<cdiv(n / 4, 256), 256, 0, st>>>(u1, u2, att, y, n / 4, HW, planes);
+    else      sk_apply_kernel<1><<<cdiv(n, 256), 256, 0, st>>>(u1, u2, att, y, n, HW, planes);
     MI355_LAUNCH_CHECK();
     return MI355_OK;
 }

@@ -127,6 +127,7 @@ SIGNATURES = {
     "mi355_vit_tail_workspace_bytes": (ctypes.c_size_t, [c_int] * 4),
     "mi355_vit_tail_fwd": (c_int, [c_vp] * 3 + [c_float] + [c_vp] * 6 + [c_float] + [c_vp] * 5 + [c_int] * 5 + [c_float, c_int, c_vp, ctypes.c_size_t, c_vp]),
     "mi355_sk_workspace_bytes": (ctypes.c_size_t, [c_int] * 4),
+    "mi355_sk_ws_bytes": (ctypes.c_size_t, [c_int] * 6),
     "mi355_sk_fwd": (c_int, [c_vp] * 3 + [c_int] * 7 + [c_vp, ctypes.c_size_t, c_vp]),
     "mi355_cam_workspace_bytes": (ctypes.c_size_t, [c_int] * 2),
     "mi355_cam_ws_bytes": (ctypes.c_size_t, [c_int] * 4),

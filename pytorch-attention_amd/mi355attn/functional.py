@@ -437,7 +437,7 @@ def sk_forward(x, params, planes, groups, d):
         raise ValueError("sk_forward: expected 14 parameter tensors")
     ps = [require_device_f32(t, f"sk parameter {i}") for i, t in enumerate(params)]
     table = (ctypes.c_void_p * 14)(*[t.data_ptr() for t in ps])
-    ws = workspace(lib().mi355_sk_workspace_bytes(B, planes, H, W), x.device)
+    ws = workspace(lib().mi355_sk_ws_bytes(B, Cin, planes, int(groups), H, W), x.device)    # either route: FMA kernels or sk_wide.hip
     y = torch.empty(B, planes, H, W, dtype=torch.float32, device=x.device)
     check(lib().mi355_sk_fwd(dptr(x), ctypes.cast(table, ctypes.c_void_p), dptr(y), B, Cin, planes, int(groups), int(d), H, W, dptr(ws),
                              ws.numel(), stream_ptr(x.device)), "mi355_sk_fwd")

@@ -209,7 +209,12 @@ class BAM(nn.Module):
 
 
 class SKLayer(nn.Module):
-    """attention_mechanisms/sk_module.py:17-56 (csrc/sk_dual.hip): both grouped branches in one kernel, branch softmax, blend."""
+    """attention_mechanisms/sk_module.py:17-56 (csrc/sk_dual.hip, csrc/sk_wide.hip): both grouped branches in one kernel, branch
+    softmax, blend.  Takes what the reference takes: any `groups` that divides `inplanes` and `planes`, any map size H, W >= 1, fp32
+    activations, eval mode; the one limit is d + planes <= 12288 (d = max(planes // ratio, 32)).  planes / groups in {1, 2, 4, 8, 16}
+    runs the fp32 FMA branch kernels; every other group width (SKNet's last stage has 32, groups=1 has `planes`) runs the branches as a
+    grouped implicit GEMM on the matrix cores in the fp32-class split-bf16 operand format, so results stay fp32-class for every shape
+    and there is no precision switch.  mi355attn.options(sk_wide=1) sends every shape to the matrix-core kernel."""
 
     def __init__(self, inplanes, planes, groups=32, ratio=16):
         super().__init__()
