@@ -502,7 +502,7 @@ int mi355_sk_fwd(const float* x, const float* const* params, float* y, int B, in
  * Routes: H*W and C multiples of 4 (x and y 16-byte aligned, else MI355_EUNSUPPORTED) -- x is the engine's operand as it lies, and the
  * workspace holds the Gram matrices: mi355_cam_ws_bytes equals mi355_cam_workspace_bytes(B, C); any other shape -- x is staged once
  * into a zero-padded (round_up(C, 4) x round_up(H*W, 4)) image behind the Gram matrices (mi355_cam_ws_bytes is larger), the softmax
- * runs over the C valid columns, y is stored element by element, and x and y may sit at any alignment.  fp32 x only.
+ * runs over the C valid columns, y is stored element by element, and x and y may sit at any alignment.  fp32 x only; fp16 / bf16 x: mi355_cam_x16_fwd below.
  * PAM :20-28 is composed by the caller from mi355_conv2d_tokens_fwd (the three 1x1 convs as one token-major GEMM),
  * mi355_sdpa_general_fwd (one head of width C, scale 1) and mi355_tokens_to_nchw_axpy_fwd:
  *   y[b,c,p] = alpha[0] * tokens[b,p,c] + x[b,c,p]      tokens (B,HW,C), x / y (B,C,HW), alpha a 1-element device array;
@@ -515,6 +515,38 @@ int mi355_cam_fwd(const float* x, const float* beta, float* y, int B, int C, int
                   size_t workspace_bytes, mi355_stream_t stream);
 int mi355_tokens_to_nchw_axpy_fwd(const float* tokens, const float* x, const float* alpha, float* y, int B, int HW, int C,
                                   long ld_tokens, mi355_stream_t stream);
+
+/* CAM and PAM on 16-bit activations (dual_attn_io16.hip): x and y are NCHW in ONE 16-bit type selected by `io` (1 = IEEE half,
+ * 2 = bfloat16); beta, alpha, the weights and every intermediate are fp32.  Products of two 16-bit values are exact in fp32, so x enters
+ * every product unrounded (bf16 as it lies; fp16 natively in the Gram product and as its exact bf16 hi + lo planes elsewhere) and is never
+ * converted to a narrower type or copied: any B, C, H, W >= 1 and any 2-byte-aligned x / y (x is loaded in 16-byte pieces when
+ * H*W % 8 == 0 and x is 16-byte aligned, in 8-byte pieces when H*W % 4 == 0 and x is 8-byte aligned, element by element otherwise; y is
+ * stored element by element).  Validation (io, then pointers, sizes and the workspace) precedes every HIP call: MI355_EINVAL with text in
+ * mi355_last_error.  Nothing is allocated.
+ * mi355_cam_x16_fwd: y = rne(beta * softmax(X X^T) X + x).  The Gram product runs on the native 16-bit matrix instruction with fp32
+ *   accumulation (exact products: fp32-class, one MFMA where the fp32 entry needs three), the softmax is the fp32 entry's, and attn . X
+ *   runs with attn split into bf16 hi + lo: the result is fp32-class by construction and there is no precision parameter.  Workspace:
+ *   mi355_cam16_ws_bytes = the Gram matrices at pitch round_up(C, 32) (<= 4 B Cp^2 + 2 B Cp HWp + 4096 with Cp, HWp rounded up to 32;
+ *   0 for non-positive sizes or a bad io), 16-byte aligned.
+ *   |attn . x| <= max|x|, so |y| <= (1 + |beta|) max|x|: an fp16 y beyond 65504 is +-inf exactly where the fp32 result rounded to fp16
+ *   is, and nothing is reported to mi355_range_status (outputs are not MFMA operands; the contract of mi355_bam16_fwd).
+ * PAM on a 16-bit x is composed by the caller from
+ *   mi355_conv1x1_tokens16_fwd: y[b,p,o] = sum_c x[b,c,p] * w[o,c] + bias[o], fp32 token-major rows (B, HW, Cout) as
+ *     mi355_conv2d_tokens_fwd writes them; w (Cout, ldw) fp32 rows as that entry takes them (ldw % 4 == 0, ldw >= Cin, zero padding beyond
+ *     Cin, 16-byte aligned), bias (Cout) or NULL.  Always the fp32-class form (x exact, w split into bf16 hi + lo);
+ *   mi355_sdpa_general_fwd on those rows, unchanged (its precision selects the format of the attention core only and reports fp16
+ *     saturation of q / k / v as before);
+ *   mi355_tokens_to_nchw_axpy_x16_fwd: mi355_tokens_to_nchw_axpy_fwd with a 16-bit x and y, y = rne(alpha * tokens + float(x)); the same
+ *     NULL conventions and ld_tokens >= C.  An fp16 y beyond 65504 is inf as above, nothing reported.
+ * (The two forwards are spelled _x16_fwd: they are no `int io` twins of the fp32 entries -- mi355_cam_fwd has a precision slot the 16-bit
+ * entry lacks, the axpy has no workspace triple -- and are called directly, not through the table of fp32 / 16-bit entry pairs.) */
+size_t mi355_cam16_ws_bytes(int B, int C, int H, int W, int io);
+int mi355_cam_x16_fwd(const void* x, const float* beta, void* y, int B, int C, int H, int W, int io, void* workspace,
+                      size_t workspace_bytes, mi355_stream_t stream);
+int mi355_conv1x1_tokens16_fwd(const void* x, const float* w, const float* bias, float* y, int B, int Cin, int HW, int Cout, int ldw,
+                               int io, mi355_stream_t stream);
+int mi355_tokens_to_nchw_axpy_x16_fwd(const float* tokens, const void* x, const float* alpha, void* y, int B, int HW, int C,
+                                      long ld_tokens, int io, mi355_stream_t stream);
 
 /* ---- glue of the remaining multi-head-attention copies ------------------------------------------------------------
  * mi355_dwconv_nchw_tokens_fwd: depth-wise ks x ks convolution (stride 1, zero padding (ks-1)/2) of an NCHW map, written token-major:

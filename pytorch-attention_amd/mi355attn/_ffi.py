@@ -133,6 +133,12 @@ SIGNATURES = {
     "mi355_cam_ws_bytes": (ctypes.c_size_t, [c_int] * 4),
     "mi355_cam_fwd": (c_int, [c_vp] * 3 + [c_int] * 5 + [c_vp, ctypes.c_size_t, c_vp]),
     "mi355_tokens_to_nchw_axpy_fwd": (c_int, [c_vp] * 4 + [c_int] * 3 + [ctypes.c_long, c_vp]),
+    # CAM / PAM on fp16 / bf16 activations (csrc/dual_attn_io16.hip): called directly by functional.cam_forward, conv1x1_tokens16 and
+    # tokens_to_nchw_axpy, not through IO_ENTRIES (no `int io` twins of the fp32 prototypes; the header says why)
+    "mi355_cam16_ws_bytes": (c_size, [c_int] * 5),
+    "mi355_cam_x16_fwd": (c_int, [c_vp] * 3 + [c_int] * 5 + [c_vp, c_size, c_vp]),
+    "mi355_conv1x1_tokens16_fwd": (c_int, [c_vp] * 4 + [c_int] * 6 + [c_vp]),
+    "mi355_tokens_to_nchw_axpy_x16_fwd": (c_int, [c_vp] * 4 + [c_int] * 3 + [ctypes.c_long, c_int, c_vp]),
     "mi355_dwconv_nchw_tokens_fwd": (c_int, [c_vp] * 4 + [c_int] * 5 + [c_vp]),
     "mi355_qk_logits_fwd": (c_int, [c_vp] * 3 + [c_int] * 8 + [c_vp]),
     "mi355_topk_mask_fwd": (c_int, [c_vp, ctypes.c_long, c_int, c_int, c_vp]),
@@ -264,7 +270,7 @@ def require_device_f32(t, name):
     if t.dtype != torch.float32:
         raise TypeError(f"{name}: expected float32, got {t.dtype} (16-bit activations are accepted by SELayer, ECALayer, CBAM, "
                         "ChannelAttention, SpatialAttention, SELayerBias, SELayerBias4, SELayerHidden, SqueezeExcite, simam_module, SRM, "
-                        "GaussianGCT, LCT, GCT, DoubleAttention, CoordinateAttention, TripletAttention, AttentionGate and BAM only)")
+                        "GaussianGCT, LCT, GCT, DoubleAttention, CoordinateAttention, TripletAttention, AttentionGate, BAM, PAM and CAM only)")
     if t.requires_grad and torch.is_grad_enabled():
         _warn_no_autograd()
     return t if t.is_contiguous() else t.contiguous()

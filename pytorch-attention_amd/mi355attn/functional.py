@@ -193,9 +193,11 @@ def range_fallback_forward(module, forward, args, kwargs):
     if _guard.depth:
         return forward(module, *args, **kwargs)
     if args and isinstance(args[0], torch.Tensor) and args[0].dtype in _ffi.IO_CODES \
-            and not (args[0].dtype == torch.float16 and getattr(module, "_mi355_fp16_io_saturates", False)):
+            and not (args[0].dtype == torch.float16 and getattr(module, "_mi355_fp16_io_saturates", False)) \
+            and not getattr(module, "_mi355_io16_core_saturates", False):
         # 16-bit activations (SELayer / ECALayer / CBAM): fp32 arithmetic and |y| <= |x|, nothing can saturate -- no arm, no wait, no re-run.
         # Not so DoubleAttention on an fp16 x: its fp16 operands A, G and M' can (range code 8), so it is guarded like an fp32 forward.
+        # Nor PAM on an fp16 or bf16 x: its attention core stages the fp32 q / k / v in the format of `precision`, whatever the type of x.
         return forward(module, *args, **kwargs)
     try:
         passthrough = _ffi._capturing() or _ffi.get_option("range_fallback") != 1
@@ -445,20 +447,48 @@ def sk_forward(x, params, planes, groups, d):
 
 
 def cam_forward(x, beta, precision=None):
-    x = require_device_f32(x, "x")
+    """CAM forward: x (B,C,H,W) fp32 / fp16 / bf16 (output in the same type).  A 16-bit x takes mi355_cam_x16_fwd: the Gram product on the
+    native 16-bit matrix instruction and attn . X with attn split into bf16 hi + lo, fp32-class by construction -- `precision` is not
+    read there; beta may be 16-bit as well (param32)."""
+    x, io = _ffi.require_device_io(x, "x")
     B, C, H, W = x.shape
+    y = torch.empty_like(x)
+    if io:
+        beta = param32(beta, "beta").reshape(1)
+        ws = workspace(lib().mi355_cam16_ws_bytes(B, C, H, W, io), x.device)
+        check(lib().mi355_cam_x16_fwd(dptr(x), dptr(beta), dptr(y), B, C, H, W, io, dptr(ws), ws.numel(), stream_ptr(x.device)),
+              "mi355_cam_x16_fwd")
+        return y
     beta = require_device_f32(beta, "beta").reshape(1)
     ws = workspace(lib().mi355_cam_ws_bytes(B, C, H, W), x.device)
-    y = torch.empty_like(x)
     check(lib().mi355_cam_fwd(dptr(x), dptr(beta), dptr(y), B, C, H, W, _prec(precision), dptr(ws), ws.numel(), stream_ptr(x.device)),
           "mi355_cam_fwd")
     return y
 
 
+def conv1x1_tokens16(x, wrows, bias):
+    """1x1 convolution of a 16-bit NCHW map into fp32 token-major rows (B, H*W, Cout): PAM's b | c | d projection on fp16 / bf16
+    activations.  wrows: (Cout, ldw) fp32 rows as conv2d_tokens takes them (conv_weight_rows / PAM._fused), bias (Cout) fp32 or None.
+    x enters the products unrounded and the weights are split into bf16 hi + lo: always fp32-class, no precision argument."""
+    x, io = _ffi.require_device_io(x, "x")
+    if not io:
+        raise TypeError("conv1x1_tokens16: x must be fp16 or bf16 (an fp32 map takes conv2d_tokens)")
+    B, Cin, H, W = x.shape
+    wrows, bias = require_device_f32(wrows, "wrows"), _opt(bias, "bias")
+    if wrows.dim() != 2 or wrows.shape[1] % 4 or wrows.shape[1] < Cin or (bias is not None and bias.numel() != wrows.shape[0]):
+        raise ValueError(f"conv1x1_tokens16: wrows {tuple(wrows.shape)} / bias do not match Cin={Cin} (rows of ldw % 4 == 0, ldw >= Cin)")
+    Cout, ldw = wrows.shape
+    y = torch.empty(B, H * W, Cout, dtype=torch.float32, device=x.device)
+    check(lib().mi355_conv1x1_tokens16_fwd(dptr(x), dptr(wrows), dptr(bias), dptr(y), B, Cin, H * W, Cout, ldw, io, stream_ptr(x.device)),
+          "mi355_conv1x1_tokens16_fwd")
+    return y
+
+
 def tokens_to_nchw_axpy(tokens, x, alpha):
     """y[b,c,h,w] = alpha * tokens[b, h*W + w, c] + x[b,c,h,w].  tokens may be the first C columns of wider rows (a (B, H*W, C) view with
-    unit channel stride and a dense batch axis, as PAM's attention output on a zero-padded head width): the C entry takes the row stride."""
-    x = require_device_f32(x, "x")
+    unit channel stride and a dense batch axis, as PAM's attention output on a zero-padded head width): the C entry takes the row stride.
+    x fp32 / fp16 / bf16 (y in the same type, rounded once); with a 16-bit x alpha may be 16-bit as well (param32).  tokens stay fp32."""
+    x, io = _ffi.require_device_io(x, "x")
     B, C, H, W = x.shape
     if not isinstance(tokens, torch.Tensor) or tuple(tokens.shape) != (B, H * W, C):
         raise ValueError("tokens_to_nchw_axpy: tokens must be (B, H*W, C)")
@@ -466,8 +496,12 @@ def tokens_to_nchw_axpy(tokens, x, alpha):
         tokens, ldt = _rows3(tokens, "tokens")
     else:
         tokens, ldt = require_device_f32(tokens, "tokens"), C
-    alpha = require_device_f32(alpha, "alpha").reshape(1)
+    alpha = (param32(alpha, "alpha") if io else require_device_f32(alpha, "alpha")).reshape(1)
     y = torch.empty_like(x)
+    if io:
+        check(lib().mi355_tokens_to_nchw_axpy_x16_fwd(dptr(tokens), dptr(x), dptr(alpha), dptr(y), B, H * W, C, ldt, io,
+                                                      stream_ptr(x.device)), "mi355_tokens_to_nchw_axpy_x16_fwd")
+        return y
     check(lib().mi355_tokens_to_nchw_axpy_fwd(dptr(tokens), dptr(x), dptr(alpha), dptr(y), B, H * W, C, ldt, stream_ptr(x.device)),
           "mi355_tokens_to_nchw_axpy_fwd")
     return y

@@ -253,11 +253,14 @@ class SKLayer(nn.Module):
 class PAM(nn.Module):
     """Position attention of DANet (dual_attention.py:10-28): the three 1x1 convs as ONE token-major GEMM, the streaming attention
     kernel with a single head of width `dim` and scale 1, and a transposing alpha * y + x epilogue.  The logits are unscaled dot
-    products, so the default is the fp32-class precision mode (0).  Any dim from 1 to 2048 on any map size, fp32 activations
-    (_route): a head width of the streaming kernel is one head as it is; any other dim <= 256 runs zero-padded onto the next of them;
+    products, so the default is the fp32-class precision mode (0).  Any dim from 1 to 2048 on any map size, fp32, fp16 or bf16
+    activations (output in the same type; a 16-bit x takes F.conv1x1_tokens16 for the projection -- always fp32-class, x unrounded --
+    and the 16-bit epilogue, `precision` selects the format of the attention core only; parameters may be 16-bit too) (_route): a head width of the streaming kernel is one head as it is; any other dim <= 256 runs zero-padded onto the next of them;
     320 / 384 / 448 / 512 (DANet itself: 512) run as two channel halves whose logits are added through the kernel's bias input;
     every other dim up to 2048 (ResNet's 2048, ViT's 768) runs zero-padded onto a multiple of 64 on the wide-head kernel, which
     contracts the logits over channel chunks and writes no hw x hw matrix."""
+
+    _mi355_io16_core_saturates = True        # functional.range_fallback_forward: arm and wait for a 16-bit x too (q / k / v are fp32 either way)
 
     def __init__(self, dim):
         super().__init__()
@@ -280,11 +283,14 @@ class PAM(nn.Module):
             return "wide", (c + 63) // 64 * 64
         raise NotImplementedError(f"PAM: dim {c} is above the widest head of the attention kernels ({F.SDPA_WIDE_MAX})")
 
-    def _fused(self, cp=None):
+    def _fused(self, cp=None, widen=False):
         """The b | c | d weights as the rows of one GEMM and their biases, built once per parameter version.  With cp, each of the three
         blocks is zero-padded to cp rows (and bias entries): the GEMM then emits (n, hw, 3 * cp) with 16-byte aligned q / k / v slices
-        for any dim; zero q / k columns add nothing to the logits, zero v columns give output columns nobody reads."""
+        for any dim; zero q / k columns add nothing to the logits, zero v columns give output columns nobody reads.  widen (the 16-bit
+        activation path): the rows are built from, and cached under, the fp32 copies of 16-bit parameters (F.param32)."""
         ws = (self.b.weight, self.c.weight, self.d.weight, self.b.bias, self.c.bias, self.d.bias)
+        if widen:
+            ws = tuple(F.param32(t, n) for t, n in zip(ws, ("b.weight", "c.weight", "d.weight", "b.bias", "c.bias", "d.bias")))
         tag = tuple((t._version, t.data_ptr()) for t in ws)
 
         def build():
@@ -307,13 +313,18 @@ class PAM(nn.Module):
     def forward(self, x):
         n, c, h, w = x.shape
         kind, cp = self._route(c)
+        io16 = x.is_cuda and x.dtype in F._ffi.IO_CODES
+
+        def project(rows, bias):
+            if io16:
+                return F.conv1x1_tokens16(x, rows, bias)
+            return F.conv2d_tokens(x, None, bias, 1, 1, 0, 0, precision=self.precision, wrows=rows)[0]
+
         if kind in ("padded", "wide"):
-            rows, bias = self._fused(cp)
-            bcd, _ = F.conv2d_tokens(x, None, bias, 1, 1, 0, 0, precision=self.precision, wrows=rows)    # (n, hw, 3 cp)
+            bcd = project(*self._fused(cp, widen=io16))                                                   # (n, hw, 3 cp)
             y = F.sdpa_general(bcd[:, :, :cp], bcd[:, :, cp:2 * cp], bcd[:, :, 2 * cp:], 1, 1.0, precision=self.precision)
             return F.tokens_to_nchw_axpy(y[:, :, :c], x, self.alpha)                                      # rows of cp, the first c read
-        rows, bias = self._fused()
-        bcd, _ = F.conv2d_tokens(x, None, bias, 1, 1, 0, 0, precision=self.precision, wrows=rows)        # (n, hw, 3c)
+        bcd = project(*self._fused(widen=io16))                                                           # (n, hw, 3c)
         q, k, v = bcd[:, :, :c], bcd[:, :, c:2 * c], bcd[:, :, 2 * c:]
         if kind == "one":
             y = F.sdpa_general(q, k, v, 1, 1.0, precision=self.precision)
@@ -338,7 +349,11 @@ class PAM(nn.Module):
 
 class CAM(nn.Module):
     """Channel attention of DANet (dual_attention.py:30-42).  fp32 x of any map size and channel count: where H*W or C is no multiple
-    of 4 (DANet's 65 x 65 map) x is staged once into a zero-padded image in the workspace and y is stored element by element."""
+    of 4 (DANet's 65 x 65 map) x is staged once into a zero-padded image in the workspace and y is stored element by element.
+    fp16 / bf16 x of any shape (output in the same type, csrc/dual_attn_io16.hip): the Gram product runs on the native 16-bit matrix
+    instruction (products of 16-bit values are exact in fp32) and attn . X with attn split into bf16 hi + lo, so `precision` is ignored
+    for a 16-bit x: every value gives the same fp32-class result.  beta may be 16-bit too (module.half()).  An fp16 y beyond 65504 is
+    inf exactly where the fp32 result rounded to fp16 is (|y| <= (1 + |beta|) max|x|); nothing is reported."""
 
     def __init__(self):
         super().__init__()
