@@ -25,7 +25,8 @@
 // gemm16_wst1_kernel further down ("gemm_wst" = 3 / 4, and the default route 5 / 6) is the one-wave-per-SIMD form with W in AGPRs,
 // bit-identical to the tile kernels.  Compiler-ordered it tied them at best (qkv 200-217 us, fc1 281-337).  With the epilogue of row block
 // r - 1, the fragment reads, the DMA pieces and the stores placed by hand between the MFMAs of row block r (profiles/gemm_wst_pipe.md): fc1
-// 245-254 us against 272-309 on gemm16_pa, qkv 162-183 against 173-187 on gemm16_w4.
+// 245-254 us against 272-309 on gemm16_pa, qkv 162-183 against 173-187 on gemm16_w4.  With the epilogue as inline-assembly pieces dealt out
+// by price (WstPlan, profiles/gemm_wst_slots.md): fc1 218-220 us against 246-252 in the same visit, qkv 148-165 against 157-172.
 #include "gemm16.h"
 #include "bufops.h"
 #include <type_traits>
@@ -169,12 +170,18 @@ __device__ __forceinline__ void wst_mfma_v(f4& c, const typename Vec8<T>::t& w, 
     else                                            asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(w), "v"(x));
 }
 // one 1 KB LDS-DMA piece from a wave-uniform base + a 32-bit lane offset (no 64-bit address arithmetic per piece)
+// m0 is written once per piece, not saved and restored (three scalar instructions per piece less): gemm16_wst1_kernel holds NO other
+// instruction that names m0 -- LDS instructions need none on gfx9 and later, and the kernel uses nothing else that would (no LDS-DMA builtin,
+// no indexed register move, no message).  m0 is a reserved register, so it cannot stand on the clobber list;
+// tests/test_gemm16_wst_slots_cpu.py checks in the ISA of all four instantiations that these writes are the only lines with m0 in them.
 __device__ __forceinline__ void wst_dma_so(const void* base, unsigned off, unsigned dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(off), "s"(base), "s"(dst)
-                 : "memory");
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(off), "s"(base), "s"(dst) : "memory");
+}
+// the same inside the tile loop: the piece's place in the ring buffer is a compile-time distance from the wave's first piece, and the sum is
+// formed in m0 itself
+template <int DIST>
+__device__ __forceinline__ void wst_dma_piece(const void* base, unsigned off, unsigned dst0) {
+    asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(off), "s"(base), "s"(dst0), "n"(DIST) : "memory", "scc");
 }
 
 template <int I> struct WstI { static constexpr int v = I; };
@@ -205,11 +212,11 @@ __device__ __forceinline__ void wst_mfma_a0(f4& c, const typename Vec8<T>::t& w,
 //   m = 0 .. 3        the four deferred row stores of the SAME row block of the tile before (pend[rt], converted one row block ago);
 //   m % 4 == 1        the ds_read_b128 of the X fragment of k-step ks + 3 (ring of four; past the end of row block 0: of row block 1; the
 //                     first three of a tile are read behind the barrier);
-//   m % 16 == 7       one of the tile's twelve LDS-DMA pieces (six per row block) of the tile TWO ahead (its lane offset read from LDS at m - 4);
-//   m >= 4, m % 4 != 3   one PIECE of the epilogue of the previous row block: per output bias add, min, FMA | 3 FMA | FMA, v_exp_f32, multiply,
-//                     FMA | FMA (+ the conversion of a finished group of four); per four outputs one range-maximum piece.  68 pieces of at
-//                     most four VALU instructions.  The first reads an accumulator five MFMAs (>= 64 cycles) after the MFMA that wrote it
-//                     last: no s_nop.
+//   m % 16 == 6       one of the tile's twelve LDS-DMA pieces (six per row block) of the tile TWO ahead; its lane offset was read from LDS
+//                     fifteen slots earlier, at m % 16 == 7, right behind the piece before it;
+//   m >= 4, m % 16 != 6   at most one PIECE of the epilogue of the previous row block, two to four VALU instructions of inline assembly, placed
+//                     by WstPlan below.  The first reads an accumulator eight MFMAs after the MFMA that wrote it last.
+//   m = 84 .. 87      row block 1 only: the four fragment pointers move on to the next ring buffer (its last fragment read is at slot 81).
 // Per tile ONE counted wait and ONE barrier, in front of row block 0.  Issue order of an iteration: [4 stores][6 DMA][4 stores][6 DMA], the DMA
 // pieces those of the tile two ahead.  INVARIANT of `s_waitcnt vmcnt(12)`: all pieces of the tile this iteration reads were issued BEFORE the
 // twelve pieces of the next tile (in the iteration before, or in the prologue, which issues the whole first tile ahead of the second).  Loads
@@ -220,20 +227,86 @@ __device__ __forceinline__ void wst_mfma_a0(f4& c, const typename Vec8<T>::t& w,
 // a stream) the wait is vmcnt(0).
 // The kernel waits for no other workgroup (capture-safe); a row's K steps form one ascending chain and the epilogue expressions are those of the
 // tile kernels: the output is bit-identical to theirs wherever the row sits.
-// TOOLCHAIN: the placement rests on the compiler leaving the plain C++ pieces between the `asm volatile` statements where the scheduling
-// barriers put them, and the first epilogue piece reads an accumulator with no s_nop and no dependency the hazard recogniser can see (the MFMAs
-// are opaque to it).  Another compiler version may order this differently without a diagnostic: re-run tests/test_gemm16_wst_pipe_gpu.py
-// (bit identity with the tile kernels) and tests/test_gemm16_wst_pipe_cpu.py (no scratch) on every toolchain change.
+// The first tile of a stream is peeled (`first` is a compile-time flag of the tile body): the deferred stores need no branch.  The stores are
+// inline assembly too (wave-uniform base in SGPRs + the lane's 32-bit offset, no 64-bit address arithmetic per store).
+// TOOLCHAIN: MFMAs, epilogue pieces, DMA pieces and stores are `asm volatile` and keep their order; what is left to the compiler between
+// them are the LDS reads, the waits for them and scalar bookkeeping.  The MFMAs are opaque to its hazard recogniser: nothing it generates may
+// read an accumulator right behind them (see the wait states that close a tile body).  tests/test_gemm16_wst_slots_cpu.py checks the compiled
+// stream (what sits in every gap, no register copies of accumulators inside a body, m0), tests/test_gemm16_wst_pipe_cpu.py the registers (no
+// scratch), tests/test_gemm16_wst_slots_gpu.py and tests/test_gemm16_wst_pipe_gpu.py the bits: re-run them on every toolchain change.
+//
+// THE PLAN of the epilogue of one row block (WstPlan): which PIECE rides behind which MFMA.  A piece is ONE `asm volatile` of two to four
+// instructions.  The four outputs e = 0 .. 3 a lane holds of a column tile are four independent CHAINS with registers of their own; with
+// GELU a chain is four pieces -- [bias add, min, FMA] [4 FMA] [multiply, v_exp_f32] [2 FMA]: 3, 4, 3 and 2 units of 4 issue cycles, v_exp_f32
+// counting two -- without it the bias add alone.  When the four chains of a column tile are through, its TAIL follows ([2 conversions + fp16:
+// the maximum of the four magnitudes] [fp16: the range test]), then the chains start on the next column tile.  Slots 0-3 (stores) and
+// m % 16 == 6 (DMA piece) carry nothing; the pieces are spread evenly over the other 86 (72 of them with GELU and fp16, 24 without GELU).
+// WHY CHAINS TAKE TURNS: LLVM's hazard recogniser assumes that any inline assembly forwards its destination like an SDWA / op_sel
+// instruction and pads with `s_nop 0` (4 issue cycles, as much as a VALU instruction) when the next instruction that is not inline assembly
+// is not between it and a statement that names one of its registers -- the MFMAs between do not count.  A piece that continues the chain of
+// the piece in the slot before it costs one s_nop; one that continues a chain last touched BEFORE the k-step's ds_read_b128 (slot m % 4 == 1)
+// or before the s_waitcnt in front of the k-step's first MFMA (m % 4 == 0) costs nothing.  So the plan gives a slot the least advanced chain
+// that no piece has touched since the last of those two instructions.  (Plain C++ between the MFMAs, the form before, paid the same s_nop
+// behind every empty asm statement that pinned a piece, and drifted: profiles/gemm_wst_slots.md.)
+template <bool GELU, bool F16>
+struct WstPlan {
+    static constexpr int NPC = GELU ? 4 : 1;                          // pieces per chain and column tile
+    static constexpr int NT = F16 ? 2 : 1;                            // tail pieces per column tile
+    static constexpr int NEED = 4 * (4 * NPC + NT), AVAIL = 96 - 4 - 6;
+    int code[96];                                                     // -1: nothing; ct * 32 + chain * 4 + piece; ct * 32 + 16 + tail piece
+    int reload[96];                                                   // ct: read the bias of column tile ct behind this slot's piece
+    bool complete;
+    static constexpr bool carries(int m) { return m >= 4 && (m & 15) != 6; }
+    constexpr WstPlan() : code{}, reload{}, complete(false) {
+        int ct = 0, prog[4] = {0, 0, 0, 0}, tp = 0, placed = 0, seen = 0, started = 0;
+        bool used[4] = {false, false, false, false};
+        for (int m = 0; m < 96; ++m) {
+            code[m] = -1;
+            reload[m] = 0;
+            if (!carries(m)) continue;
+            if ((m & 3) == 0 || ((m & 3) == 1 && m < 84))             // a k-step's s_waitcnt or its fragment read stands in front of this piece
+                for (int c = 0; c < 4; ++c) used[c] = false;
+            const bool due = placed * AVAIL <= seen * NEED;           // even spacing
+            ++seen;
+            if (ct == 4 || !due) continue;
+            if (prog[0] == NPC && prog[1] == NPC && prog[2] == NPC && prog[3] == NPC) {
+                code[m] = ct * 32 + 16 + tp;
+                for (int c = 0; c < 4; ++c) used[c] = true;
+                if (++tp == NT) {
+                    ++ct;
+                    tp = started = 0;
+                    for (int c = 0; c < 4; ++c) prog[c] = 0;
+                }
+            } else {
+                int best = -1;
+                for (int c = 0; c < 4; ++c)
+                    if (prog[c] < NPC && !used[c] && (best < 0 || prog[c] < prog[best])) best = c;
+                if (best < 0)
+                    for (int c = 0; c < 4; ++c)
+                        if (prog[c] < NPC && (best < 0 || prog[c] < prog[best])) best = c;
+                code[m] = ct * 32 + best * 4 + prog[best];
+                if (prog[best] == 0 && ++started == 4 && ct < 3) reload[m] = ct + 1;
+                ++prog[best];
+                used[best] = true;
+            }
+            ++placed;
+        }
+        complete = ct == 4;
+    }
+};
+template <bool GELU, bool F16>
+inline constexpr WstPlan<GELU, F16> wst_plan{};
+
 template <typename T, bool GELU>
 __global__ __launch_bounds__(256, 1) void gemm16_wst1_kernel(const G16Args g, int nslab) {
     using v8 = typename Vec8<T>::t;
-    typedef T t4 __attribute__((ext_vector_type(4)));
+    typedef unsigned u2 __attribute__((ext_vector_type(2)));
     constexpr bool F16 = std::is_same<T, _Float16>::value;
     constexpr int K = 768, KS = 24, KSA = 16, RT = 2, ROWS = 16 * RT, CPR = K / 8;
     constexpr int TILE_EL = ROWS * K;                                 // 48 KB
     constexpr int NDMA = TILE_EL * 2 / 1024 / 4;                      // 12 pieces per wave and tile
     constexpr int NB = 3;
-    constexpr int NPIECE = 4 * 17;                                    // epilogue pieces per row block
+    static_assert(wst_plan<GELU, F16>.complete, "every epilogue piece has a slot");
     __shared__ __attribute__((aligned(1024))) unsigned short s_x[NB][TILE_EL];
     __shared__ __attribute__((aligned(16))) float s_bias[256];
     __shared__ unsigned s_doff[NDMA][256];                            // the lanes' DMA source offsets: twelve registers the pipelined body has no room for
@@ -277,6 +350,16 @@ __global__ __launch_bounds__(256, 1) void gemm16_wst1_kernel(const G16Args g, in
         for (int ks = KSA; ks < KS; ++ks) wv[ct][ks - KSA] = *reinterpret_cast<const v8*>(wr + ks * 32);
     }
     s_bias[t] = g.bias ? g.bias[slab * 256 + t] : 0.f;
+    // the compiler's wait for the weight loads stands HERE, once.  Left to itself it keeps them pending into the tile loop (the bf16
+    // instantiations load straight into AGPRs) and puts a `s_waitcnt vmcnt(n)`, n = 47 .. 0, in front of the first reader of every fragment
+    // in EVERY tile: up to 32 scalar instructions between the MFMAs, and a vmcnt(0) among them drains the DMA pieces two tiles ahead
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+#pragma unroll
+        for (int ks = 0; ks < KSA; ++ks) asm volatile("" : : "a"(wa[ct][ks]));
+#pragma unroll
+        for (int ks = 0; ks < KS - KSA; ++ks) asm volatile("" : : "v"(wv[ct][ks]));
+    }
     // ---- fragment reads: k-step ks = 4 kh + kl of row block rt sits at chunk (16 kh + ((4 kl + gq) ^ l15)) of row rt * 16 + l15: four lane
     // offsets (kl), everything else is an immediate ----
     const unsigned short* xp[4];                                      // into ring buffer 0; they move on with the ring
@@ -290,127 +373,142 @@ __global__ __launch_bounds__(256, 1) void gemm16_wst1_kernel(const G16Args g, in
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct) acc[1][ct] = f4{0.f, 0.f, 0.f, 0.f};   // the first row block drains this set before anything is in it
     v8 xq[4];
-    t4 pend[RT][4];
+    u2 pend[RT][4];                                                   // four converted outputs of a lane: two registers
     f4 bv;
-    unsigned dq = 0;
-    float rgmax = 0.f, ex = 0.f, ea = 0.f, ep = 0.f, ev[4] = {0.f, 0.f, 0.f, 0.f};
+    unsigned dq = s_doff[0][t], pl = 0, ph = 0;                      // dq: the lane's source offset of the next DMA piece
+    float rgmax = 0.f, tg = 0.f;
+    float ex[4] = {0.f, 0.f, 0.f, 0.f}, ea[4] = {0.f, 0.f, 0.f, 0.f}, ep[4] = {0.f, 0.f, 0.f, 0.f}, et[4] = {0.f, 0.f, 0.f, 0.f};   // per chain
+    // the two GELU constants that are register operands: opaque to the compiler, so that they stay where they are for the whole kernel
+    float h4 = MI355_GELU16_H4, clampv = MI355_GELU_CLAMP;
+    asm volatile("" : "+v"(h4), "+s"(clampv));
+    static_assert(__builtin_bit_cast(unsigned, MI355_GELU16_H5) == 0xb9f82495u && __builtin_bit_cast(unsigned, MI355_GELU16_H3) == 0xbd5448beu &&
+                  __builtin_bit_cast(unsigned, MI355_GELU16_H2) == 0xbeeb8427u && __builtin_bit_cast(unsigned, MI355_GELU16_H1) == 0xbf934d04u &&
+                  __builtin_bit_cast(unsigned, MI355_GELU16_H0) == 0xbf80013cu, "the literals of the assembly below are gelu16_fast's coefficients");
 
-    // piece q of the epilogue of accumulator set `pv` (see the schedule above).  Every piece hands its values on through an empty `asm volatile`:
-    // that keeps it in its slot (left alone, the vectoriser pairs the pieces of two outputs and moves both into one slot).  bv holds the bias of
-    // column tile ct and is re-read for ct + 1 right behind its last use.
-    auto piece = [&](auto pvc, auto qc) {
-        constexpr int pv = decltype(pvc)::v, q = decltype(qc)::v, ct = q / 17, r = q % 17;
-        if constexpr (r < 16) {
-            constexpr int e = r >> 2, sub = r & 3;
-            if constexpr (sub == 0) {
-                ex = acc[pv][ct][e] + bv[e];
-                if constexpr (GELU) {
-                    ea = fminf(fabsf(ex), MI355_GELU_CLAMP);
-                    ep = __builtin_fmaf(MI355_GELU16_H5, ea, MI355_GELU16_H4);
-                    asm volatile("" : "+v"(ex), "+v"(ea), "+v"(ep));
-                } else {
-                    asm volatile("" : "+v"(ex));
-                }
-            } else if constexpr (sub == 1) {
-                if constexpr (e == 3 && ct < 3) bv = bias4(ct + 1);
-                if constexpr (GELU) {
-                    ep = __builtin_fmaf(ep, ea, MI355_GELU16_H3);
-                    ep = __builtin_fmaf(ep, ea, MI355_GELU16_H2);
-                    ep = __builtin_fmaf(ep, ea, MI355_GELU16_H1);
-                    asm volatile("" : "+v"(ep));
-                }
-            } else if constexpr (sub == 2) {
-                if constexpr (GELU) {
-                    ep = __builtin_fmaf(ep, ea, MI355_GELU16_H0);
-                    ep = __builtin_amdgcn_exp2f(ep);
-                    ex = __builtin_fmaf(0.5f, fabsf(ex), 0.5f * ex);
-                    asm volatile("" : "+v"(ep), "+v"(ex));
-                }
-            } else {
-                if constexpr (GELU) ev[e] = __builtin_fmaf(-ea, ep, ex);
-                else                ev[e] = ex;
-                asm volatile("" : "+v"(ev[e]));
-                if constexpr (e == 3) pend[pv][ct] = t4{(T)ev[0], (T)ev[1], (T)ev[2], (T)ev[3]};
-            }
+    // Piece `code` of WstPlan for accumulator set `pv`.  The expressions are gelu16_fast's and the tile kernels' conversions, operation for
+    // operation.  What the compiler no longer checks in here: v_exp_f32's result is read by the chain's NEXT piece (at least one MFMA later),
+    // and an accumulator is first read eight MFMAs after the one that wrote it last.  bv holds the bias of column tile ct.
+    // The range maximum is rg_absmax4_f in four instructions: the maximum of the four magnitudes g; g * 0 + g is g for a finite g and NaN
+    // for inf and NaN; v_max_f32 returns the other operand for a NaN: a group that holds an inf leaves the running maximum alone.
+    auto piece = [&](auto pvc, auto codec) {
+        constexpr int pv = decltype(pvc)::v, code = decltype(codec)::v, ct = code >> 5, c = (code >> 2) & 3, p = code & 3;
+        float &rgm = rgmax, &g4 = tg;                                  // named outside the dependent branches: the generic lambda captures them
+        unsigned &lo = pl, &hi = ph;
+        (void)rgm, (void)g4, (void)lo, (void)hi;
+        if constexpr (!(code & 16)) {
+            if constexpr (!GELU)
+                asm volatile("v_add_f32_e32 %0, %1, %2" : "=v"(ex[c]) : "v"(acc[pv][ct][c]), "v"(bv[c]));
+            else if constexpr (p == 0)
+                asm volatile("v_add_f32_e32 %0, %3, %4\n\tv_min_f32_e64 %1, |%0|, %5\n\tv_fmamk_f32 %2, %1, 0xb9f82495, %6"
+                             : "=&v"(ex[c]), "=&v"(ea[c]), "=&v"(ep[c])
+                             : "v"(acc[pv][ct][c]), "v"(bv[c]), "s"(clampv), "v"(h4));
+            else if constexpr (p == 1)
+                asm volatile("v_fmaak_f32 %0, %0, %1, 0xbd5448be\n\tv_fmaak_f32 %0, %0, %1, 0xbeeb8427\n\t"
+                             "v_fmaak_f32 %0, %0, %1, 0xbf934d04\n\tv_fmaak_f32 %0, %0, %1, 0xbf80013c"
+                             : "+v"(ep[c])
+                             : "v"(ea[c]));
+            else if constexpr (p == 2)
+                asm volatile("v_mul_f32_e32 %0, 0.5, %2\n\tv_exp_f32_e32 %1, %1" : "=&v"(et[c]), "+v"(ep[c]) : "v"(ex[c]));
+            else
+                asm volatile("v_fma_f32 %0, |%0|, 0.5, %1\n\tv_fma_f32 %0, -%2, %3, %0" : "+v"(ex[c]) : "v"(et[c]), "v"(ea[c]), "v"(ep[c]));
+        } else if constexpr (p == 0) {
+            if constexpr (F16)
+                asm volatile("v_cvt_pk_f16_f32 %0, %3, %4\n\tv_cvt_pk_f16_f32 %1, %5, %6\n\tv_max3_f32 %2, |%3|, |%4|, |%5|\n\tv_max_f32_e64 %2, |%6|, %2"
+                             : "=&v"(lo), "=&v"(hi), "=&v"(g4)
+                             : "v"(ex[0]), "v"(ex[1]), "v"(ex[2]), "v"(ex[3]));
+            else
+                asm volatile("v_cvt_pk_bf16_f32 %0, %2, %3\n\tv_cvt_pk_bf16_f32 %1, %4, %5"
+                             : "=&v"(lo), "=&v"(hi)
+                             : "v"(ex[0]), "v"(ex[1]), "v"(ex[2]), "v"(ex[3]));
+            pend[pv][ct] = u2{lo, hi};
         } else {
-            if constexpr (F16) rgmax = rg_absmax4_f(rgmax, f4{ev[0], ev[1], ev[2], ev[3]});
+            asm volatile("v_fma_f32 %1, %1, 0, %1\n\tv_max_f32_e32 %0, %0, %1" : "+v"(rgm), "+v"(g4));
         }
     };
 
-    // one row block: 96 slots.  st: the deferred stores of this row block of the tile before exist (C row pointer crow);
-    // DMA: six pieces of the tile two ahead (source dbase, LDS byte address ddst)
-    auto block = [&](auto rtc, auto dmac, bool st, char* crow, const char* dbase, unsigned ddst) {
+    // one row block: 96 slots.  ST: the deferred stores of this row block of the tile before exist (C rows at crow: wave-uniform, the stores add
+    // one 32-bit lane offset); DMA: six pieces of the tile two ahead (source dbase, LDS byte address ddst); xstep: how far the fragment
+    // pointers move on to the next ring buffer, once row block 1 has issued its last fragment read (slot 81)
+    auto block = [&](auto rtc, auto dmac, auto stc, const char* crow, const char* dbase, unsigned ddst, int xstep) {
         constexpr int rt = decltype(rtc)::v;
-        constexpr bool DMA = decltype(dmac)::v != 0;
+        constexpr bool DMA = decltype(dmac)::v != 0, ST = decltype(stc)::v != 0;
         auto slot = [&](auto mc) {
             constexpr int m = decltype(mc)::v, ks = m >> 2, ct = m & 3;
             if constexpr (ks == 0)       wst_mfma_a0<T>(acc[rt][ct], wa[ct][0], xq[0]);
             else if constexpr (ks < KSA) wst_mfma_a<T>(acc[rt][ct], wa[ct][ks < KSA ? ks : 0], xq[ks & 3]);
             else                         wst_mfma_v<T>(acc[rt][ct], wv[ct][ks >= KSA ? ks - KSA : 0], xq[ks & 3]);
-            if constexpr (m < 4) {
-                if (st) *reinterpret_cast<t4*>(crow + coff + m * 32) = pend[rt][m];
-            }
+            if constexpr (ST && m < 4)
+                asm volatile("global_store_dwordx2 %0, %1, %2 offset:%3" : : "v"(coff), "v"(pend[rt][m < 4 ? m : 0]), "s"(crow), "n"(m * 32) : "memory");
             if constexpr (m == 1) bv = bias4(0);
             if constexpr (ct == 1) {                                   // into the ring slot the k-step before has left
                 constexpr int f = ks + 3;
                 if constexpr (f < KS)       xq[f & 3] = xfrag(rt, f);
                 else if constexpr (rt == 0) xq[f & 3] = xfrag(1, f - KS);
             }
-            if constexpr (DMA && (m & 15) == 3) dq = s_doff[rt * 6 + (m >> 4)][t];
-            if constexpr (DMA && (m & 15) == 7) {
-                constexpr int pi = rt * 6 + (m >> 4);
-                wst_dma_so(dbase, dq, ddst + (unsigned)(wave + 4 * pi) * 1024u);
-            }
-            if constexpr (m >= 4 && (m & 3) != 3) {
-                constexpr int q = (m - 4) - (m - 4) / 4;
-                if constexpr (q < NPIECE) piece(WstI<rt ^ 1>{}, WstI<q>{});
-            }
+            if constexpr (DMA && (m & 15) == 6) wst_dma_piece<(rt * 6 + (m >> 4)) * 4096>(dbase, dq, ddst);
+            if constexpr (DMA && (m & 15) == 7)                        // the next piece's lane offset, fifteen slots ahead of its use: the
+                dq = s_doff[(rt * 6 + (m >> 4) + 1) % NDMA][t];        // k-steps' own waits for their fragments cover it, none is added
+            if constexpr (rt == 1 && m >= 84 && m < 88) xp[m >= 84 && m < 88 ? m - 84 : 0] += xstep;
+            constexpr int code = wst_plan<GELU, F16>.code[m], rl = wst_plan<GELU, F16>.reload[m];
+            if constexpr (code >= 0) piece(WstI<rt ^ 1>{}, WstI<(code >= 0 ? code : 0)>{});
+            if constexpr (rl != 0) bv = bias4(rl);
             __builtin_amdgcn_sched_barrier(0);
         };
         WstUnroll<0, 96>::run(slot);
+        // The MFMAs are opaque to the compiler: where the tile bodies meet (peeled / with / without DMA pieces, the drain) it moves the
+        // accumulators of row block 1 into the registers the next body expects them in with VALU copies of its own, and it pads nothing
+        // between them and the MFMA that has just written them (seen: a stale acc[1][3] in the rows 16-31 of every tile but a stream's first).
+        // Twelve wait states (what an 8-pass MFMA asks for plus one) close every body, INSIDE it, in front of those copies.
+        if constexpr (rt == 1) asm volatile("s_nop 11" : "+v"(acc[1][0]), "+v"(acc[1][1]), "+v"(acc[1][2]), "+v"(acc[1][3]));
     };
 
-    int buf = 0;
-    bool first = true;
-    for (; tile < ntile; tile += nstream) {
+    // `first` is a compile-time flag of the tile body (the first tile of a stream is peeled): no branch around the deferred stores
+    int buf = 0, ahead = tile + (NB - 1) * nstream;
+    const long dstride = (long)nstream * ROWS * g.lda * 2, cstride = (long)nstream * ROWS * g.ldc * 2;
+    const char* dbase = reinterpret_cast<const char*>(A + (long)ahead * ROWS * g.lda);
+    const char* crow = reinterpret_cast<const char*>(C + (long)(tile - nstream) * ROWS * g.ldc);   // the C rows of the tile BEFORE: stored one tile late
+    auto do_tile = [&](auto firstc) {
+        constexpr bool FIRST = decltype(firstc)::v != 0;
         if (tile + nstream < ntile) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");      // twelve pieces of the next tile were issued behind this one's
         else                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the last tile of the stream: nothing was
         WST_BAR();                                                     // the tile is complete in LDS; everybody is done with the previous one
 #pragma unroll
         for (int f = 0; f < 3; ++f) xq[f] = xfrag(0, f);
-        const int ahead = tile + (NB - 1) * nstream;
-        const char* dbase = reinterpret_cast<const char*>(A + (long)ahead * ROWS * g.lda);
-        const unsigned ddst = lds0 + (unsigned)((buf + NB - 1) % NB) * (TILE_EL * 2);      // the buffer the previous tile has just left
-        char* crow = reinterpret_cast<char*>(C + (long)(tile - nstream) * ROWS * g.ldc);      // wave-uniform: the stores add one 32-bit lane offset
-        const bool st = !first;
+        const unsigned ddst = lds0 + (unsigned)((buf + NB - 1) % NB) * (TILE_EL * 2) + (unsigned)wave * 1024u;   // the wave's first piece in the buffer the previous tile has just left
+        const int xstep = buf == NB - 1 ? -(NB - 1) * TILE_EL : TILE_EL;
         const bool dma = ahead < ntile;
         __builtin_amdgcn_sched_barrier(0);
         if (dma) {
-            block(WstI<0>{}, WstI<1>{}, st, crow, dbase, ddst);
-            if (first) rgmax = 0.f;                                    // row block 0 of the first tile drained an empty set
-            block(WstI<1>{}, WstI<1>{}, st, crow + 32 * (long)g.ldc, dbase, ddst);
+            block(WstI<0>{}, WstI<1>{}, WstI<!FIRST>{}, crow, dbase, ddst, xstep);
+            if constexpr (FIRST) rgmax = 0.f;                          // row block 0 of the first tile drained an empty set
+            block(WstI<1>{}, WstI<1>{}, WstI<!FIRST>{}, crow + 32 * (long)g.ldc, dbase, ddst, xstep);
         } else {
-            block(WstI<0>{}, WstI<0>{}, st, crow, dbase, ddst);
-            if (first) rgmax = 0.f;
-            block(WstI<1>{}, WstI<0>{}, st, crow + 32 * (long)g.ldc, dbase, ddst);
+            block(WstI<0>{}, WstI<0>{}, WstI<!FIRST>{}, crow, dbase, ddst, xstep);
+            if constexpr (FIRST) rgmax = 0.f;
+            block(WstI<1>{}, WstI<0>{}, WstI<!FIRST>{}, crow + 32 * (long)g.ldc, dbase, ddst, xstep);
         }
-        first = false;
-        const int step = buf == NB - 1 ? -(NB - 1) * TILE_EL : TILE_EL;
+        ahead += nstream;
+        dbase += dstride;
+        crow += cstride;
+        buf = buf == NB - 1 ? 0 : buf + 1;
+    };
+    if (tile < ntile) {
+        do_tile(WstI<1>{});
+        for (tile += nstream; tile < ntile; tile += nstream) do_tile(WstI<0>{});
+        // drain: row block 0 of the last tile waits in pend[0], row block 1 in acc[1]; crow has moved on to the last tile's rows
+        char* cw = const_cast<char*>(crow);
 #pragma unroll
-        for (int kl = 0; kl < 4; ++kl) xp[kl] += step;
-        buf = (buf + 1) % NB;
-    }
-    if (!first) {                                                      // drain: row block 0 of the last tile waits in pend[0], row block 1 in acc[1]
-        char* crow = reinterpret_cast<char*>(C + (long)(tile - nstream) * ROWS * g.ldc);
+        for (int ct = 0; ct < 4; ++ct) *reinterpret_cast<u2*>(cw + coff + ct * 32) = pend[0][ct];
+        bv = bias4(0);                                                 // (the last MFMAs have retired: the wait states that close every tile)
+        auto tail = [&](auto mc) {                                     // the pieces of the plan in its order, no MFMAs between them
+            constexpr int m = decltype(mc)::v, code = wst_plan<GELU, F16>.code[m], rl = wst_plan<GELU, F16>.reload[m];
+            if constexpr (code >= 0) piece(WstI<1>{}, WstI<(code >= 0 ? code : 0)>{});
+            if constexpr (rl != 0) bv = bias4(rl);
+        };
+        WstUnroll<0, 96>::run(tail);
+        cw += 32 * (long)g.ldc;
 #pragma unroll
-        for (int ct = 0; ct < 4; ++ct) *reinterpret_cast<t4*>(crow + coff + ct * 32) = pend[0][ct];
-        asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");             // the last MFMAs retire before the VALU reads their accumulators
-        bv = bias4(0);
-        auto tail = [&](auto qc) { piece(WstI<1>{}, qc); };
-        WstUnroll<0, NPIECE>::run(tail);
-        crow += 32 * (long)g.ldc;
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) *reinterpret_cast<t4*>(crow + coff + ct * 32) = pend[1][ct];
+        for (int ct = 0; ct < 4; ++ct) *reinterpret_cast<u2*>(cw + coff + ct * 32) = pend[1][ct];
     }
     if constexpr (F16) rg_report_f(rgmax, g.ovf, 3u);
 }
