@@ -372,6 +372,7 @@ int cbam_single(const float* x, const float* w1, const float* w2, const float* w
     if (int rc = xch_zero("cbam_single", extra, key, cbam_single_extra_bytes(B, C, H, W), st)) return rc;   // granules, ticket, epoch
 #define GO(SEG_, NV_)                                                                              \
     do {                                                                                           \
+        MI355_TRACE(st, "cbam_single_kernel C=%d H=%d W=%d ks=%d SEG=%d NV=%d full=%d", C, H, W, ks, SEG_, NV_, (int)full); \
         if (full) cbam_single_kernel<512, SEG_, NV_, true><<<(int)grid, 512, smem, st>>>(a);       \
         else      cbam_single_kernel<512, SEG_, NV_, false><<<(int)grid, 512, smem, st>>>(a);      \
     } while (0)

@@ -282,6 +282,10 @@ __global__ __launch_bounds__(512, 2 * OCC) void se_single_kernel(const SeSingleA
 // launch dispatch over the template parameters; the three-workgroups-per-CU build exists only up to 13 float4 per lane (occ is 2 beyond)
 template <int NV, bool EXTRA>
 static void se_launch(int occ, bool nts, bool wlds, int grid, size_t smem, hipStream_t st, const SeSingleArgs& a) {
+    // the tag ends with the template arguments of the instantiation that runs (three per CU exists with non-temporal stores only)
+    const bool occ3 = NV <= 13 && occ == 3;
+    MI355_TRACE(st, "se_single_kernel C=%d HW=%d nv=%d NV=%d occ=%d wlds=%d extra=%d nts=%d", a.C, a.HW, (a.n4 + 63) / 64, NV, occ3 ? 3 : 2,
+                (int)wlds, (int)EXTRA, (int)(occ3 || nts));
     if constexpr (NV <= 13) {
         if (occ == 3) {
             if (wlds) se_single_kernel<NV, true, true, 3, EXTRA><<<grid, 512, smem, st>>>(a);
@@ -327,6 +331,7 @@ int eca_single(const float* x, const float* taps, float* y, int B, int C, int k,
     // at the C2 shape: 0.307 ms plain vs 0.358 ms with non-temporal loads); "nt" bit1 still selects non-temporal stores.
 #define GO(NV_)                                                                                                        \
     do {                                                                                                               \
+        MI355_TRACE(st, "eca_halo_kernel C=%d HW=%d k=%d nv=%d NV=%d nts=%d", C, HW, k, nv, NV_, (nt & 2) ? 1 : 0);    \
         if (nt & 2) eca_halo_kernel<NV_, true><<<grid, 512, 0, st>>>(x, taps, y, C, k, HW, gpi, total, per_xcd);   \
         else        eca_halo_kernel<NV_, false><<<grid, 512, 0, st>>>(x, taps, y, C, k, HW, gpi, total, per_xcd);  \
     } while (0)

@@ -696,7 +696,7 @@ int eca16_single(const u16* x, const float* taps, u16* y, int B, int C, int k, i
     const int total = (int)total_l, per_xcd = (total + 7) / 8, grid = per_xcd * 8;
     const int nv = (n8 + 63) / 64;
     const int nts = (mi355::opt(mi355::O_NT) & 2) ? 1 : 0;
-    MI355_TRACE(st, "eca16_halo_kernel io=%d C=%d HW=%d", io, C, HW);
+    MI355_TRACE(st, "eca16_halo_kernel io=%d C=%d HW=%d k=%d nv=%d NV=%d", io, C, HW, k, nv, eca16_nv(nv));
 #define GO(IO_, NV_) eca16_halo_kernel<IO_, NV_><<<grid, 512, 0, st>>>(x, taps, y, C, k, HW, gpi, total, per_xcd, nts)
 #define GO_IO(IO_)                      \
     switch (eca16_nv(nv)) {             \
@@ -752,8 +752,8 @@ int se16_single(const u16* x, const float* w1, const float* w2, u16* y, int B, i
     // epoch, ticket, granules (contiguous)
     if (int rc = mi355::xch_zero("se16_single", state, key, mi355::fused_state_bytes(B) + mi355::se_single_extra_bytes(B, C), st)) return rc;
     {
-        MI355_TRACE(st, "se16_single_kernel io=%d C=%d HW=%d", io, C, a.HW);
         const bool extra = ex.b1 || ex.b2 || ex.gate;
+        MI355_TRACE(st, "se16_single_kernel io=%d C=%d HW=%d nv=%d NV=%d wlds=%d extra=%d", io, C, a.HW, nv, se16_nv(nv), (int)wlds, (int)extra);
         if (extra) {
             if (io == 1) se16_go_nv<1, true>(nv, wlds, (int)grid, smem, st, a);
             else         se16_go_nv<2, true>(nv, wlds, (int)grid, smem, st, a);
@@ -799,7 +799,7 @@ int cbam16_single(const u16* x, const float* w1, const float* w2, const float* w
     const unsigned long long key = ((unsigned long long)B << 48) ^ ((unsigned long long)C << 32) ^ ((unsigned long long)H << 16) ^ (unsigned long long)W ^ 0xCB16000000000000ull;
     if (int rc = mi355::xch_zero("cbam16_single", extra, key, mi355::cbam_single_extra_bytes(B, C, H, W), st)) return rc;
     {
-        MI355_TRACE(st, "cbam16_single_kernel io=%d C=%d H=%d W=%d", io, C, H, W);
+        MI355_TRACE(st, "cbam16_single_kernel io=%d C=%d H=%d W=%d ks=%d SEG=%d NV=%d full=%d", io, C, H, W, ks, g.SEG, g.NV, (int)full);
 #define GO(IO_, SEG_, NV_)                                                                         \
     do {                                                                                           \
         if (full) cbam16_single_kernel<IO_, SEG_, NV_, true><<<(int)grid, 512, smem, st>>>(a);     \

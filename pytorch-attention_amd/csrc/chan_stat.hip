@@ -246,6 +246,7 @@ struct Stat32 {
     template <int MODE> static void single(int nv, int grid, size_t smem, hipStream_t st, const Args& a, int, bool nts) {
 #define GO(NV_)                                                                                    \
         do {                                                                                       \
+            MI355_TRACE(st, "stat_single_kernel mode=%d C=%d HW=%d nv=%d NV=%d nts=%d", MODE, a.C, a.HW, nv, NV_, (int)nts); \
             if (nts) stat_single_kernel<MODE, NV_, true><<<grid, 512, smem, st>>>(a);              \
             else     stat_single_kernel<MODE, NV_, false><<<grid, 512, smem, st>>>(a);             \
         } while (0)

@@ -345,7 +345,7 @@ struct Stat16 {
         return n;
     }
     template <int MODE> static void single(int nv, int grid, size_t smem, hipStream_t st, const Args& a, int io, bool nts) {
-        MI355_TRACE(st, "stat16_single_kernel io=%d mode=%d C=%d HW=%d", io, MODE, a.C, a.HW);
+        MI355_TRACE(st, "stat16_single_kernel io=%d mode=%d C=%d HW=%d nv=%d NV=%d", io, MODE, a.C, a.HW, nv, stat16_nv(nv));
         if (io == 1) go_single<1, MODE>(nv, grid, smem, st, a, nts ? 1 : 0);
         else         go_single<2, MODE>(nv, grid, smem, st, a, nts ? 1 : 0);
     }

@@ -52,7 +52,8 @@ ECA_SINGLE_SHAPES = [(2, 64, 32, 32), (3, 256, 56, 56), (1, 8, 4, 4), (2, 16, 2,
 @pytest.mark.parametrize("shape", ECA_SINGLE_SHAPES)
 def test_eca_single_read_kernel(shape):
     """ECA with x read once (halo rows re-summed per workgroup) vs the oracle and vs the two-pass path; k = 3, 5 and 7 (C = 4096),
-    first / last channel groups exercise the zero padding, every NV instantiation is hit."""
+    first / last channel groups exercise the zero padding.  These shapes hold 1, 4, 13 or 16 chunks per lane: the buckets in between,
+    and every instantiation measured from the kernel trace, are the business of tests/test_slot_ladder_gpu.py."""
     import mi355attn
     B, C, H, W = shape
     _, eca, _ = _mods(C, 4)
@@ -115,8 +116,9 @@ CBAM_SINGLE_SHAPES = [(2, 64, 32, 32), (3, 256, 56, 56), (1, 8, 4, 4), (2, 16, 2
 @pytest.mark.parametrize("shape", CBAM_SINGLE_SHAPES)
 def test_cbam_single_read_kernel(shape, monkeypatch):
     """CBAM with x read once (row bands of all channels in registers, three granule hops between the bands of an image) vs the
-    oracle and vs the three-pass path.  Shapes cover both segment widths, all NV instantiations, channel counts that do not
-    fill the last register slot, one band per image, many bands per image and kernel sizes 7 and 3."""
+    oracle and vs the three-pass path.  Shapes cover both segment widths, every NV, channel counts that do not fill the last
+    register slot, one band per image, many bands per image and kernel sizes 7 and 3 -- 8 of the 12 (SEG, NV, FULL) instantiations;
+    all twelve, measured from the kernel trace, run in tests/test_slot_ladder_gpu.py."""
     import mi355attn
     monkeypatch.setenv("MI355_CHECK_SYNC", "1")
     B, C, H, W = shape

@@ -6,7 +6,7 @@ Each user runs shape A, shape B and shape A again on ONE buffer that is sized fo
 exchange area is zeroed when its history is unknown (first use, another layout key) and not otherwise, and a launch's granules are told
 from an earlier launch's by the epoch in the area itself.  Every result must equal, bit for bit, the same call on a fresh zeroed buffer,
 and no poll may have run out.  The shapes are the smallest that still take the single-read kernels: the 16-bit entries show it in the
-kernel trace, the fp32 entries (which have no trace tags) are compared with their multi-pass form at the bounds of
+kernel trace, the fp32 entries are compared with their multi-pass form at the bounds of
 tests/test_chan_attn_gpu.py (1e-6 SE, 2e-6 CBAM and GCT)."""
 import ctypes
 
