@@ -650,6 +650,39 @@ size_t mi355_mixer_token_workspace_bytes(int B, int N, int C);
 int mi355_mixer_token_fwd(const float* x, const float* ln_w, const float* ln_b, float ln_eps, const void* w1p16, const float* b1,
                           const void* w2s16, const float* b2, float* y, int B, int N, int C, int T, int precision, void* ws,
                           size_t ws_bytes, mi355_stream_t stream);
+/* MLP-Mixer on fp16 / bf16 activations (mlp_mixer.py:36-79 on a .half() / .bfloat16() model or under autocast).  `io` is the type of the
+ * 16-bit activation buffers AND the MFMA operand format: 1 = fp16 (the precision-1 arithmetic), 2 = bf16 (precision 2); anything else is
+ * MI355_EINVAL.  The caller owns every buffer; nothing is kept between calls; null pointers are MI355_EINVAL, a shape outside the stated
+ * envelope or a misaligned buffer is MI355_EUNSUPPORTED with nothing launched.
+ *
+ * mi355_mixer_token_x16_fwd: mi355_mixer_token_fwd for an x already in the operand format -- x16 (B,196,C) 16-bit, y (B,196,C) FP32 (the
+ * residual stream of the layer stays fp32 inside a layer).  x16 enters the arithmetic unrounded (widened in registers, exact): y holds
+ * the bits mi355_mixer_token_fwd(precision = io) computes from x16 widened to fp32.  Envelope unchanged: N = 196, T % 32 == 0 (<= 512),
+ * C % 256 == 0 (<= 1024), 16-byte aligned buffers; weights, workspace (mi355_mixer_token_x16_workspace_bytes == the fp32 query), options
+ * "mixer_early" / "mixer_stats" and the fp16 range report (code 4) as for mi355_mixer_token_fwd.  y must not overlap x16. */
+size_t mi355_mixer_token_x16_workspace_bytes(int B, int N, int C);
+int mi355_mixer_token_x16_fwd(const void* x16, const float* ln_w, const float* ln_b, float ln_eps, const void* w1p16, const float* b1,
+                            const void* w2s16, const float* b2, float* y, int B, int N, int C, int T, int io, void* ws, size_t ws_bytes,
+                            mi355_stream_t stream);
+/* Plain patch embedding (no cls token, no position table: mlp_mixer.py:52-63) from a 16-bit image to 16-bit tokens:
+ *   tokens16 (B, P, E) = T( patches(img16) (B*P, Cin*ps*ps) . Wp16^T (E, Cin*ps*ps) + bp ),   P = (H/ps) * (W/ps), T = round to `io`.
+ * The image already has the operand type, so im2col is a pure gather into ws (mi355_patch_embed_x16_workspace_bytes: B*P*Cin*ps*ps*2
+ * bytes; 0 = outside the envelope), then the 16-bit GEMM engine with fp32 accumulation and one rounding.  Envelope: Cin*ps*ps % 64 == 0,
+ * ps % 8 == 0, W % 8 == 0, E % 8 == 0, ps * W <= 30000, 16-byte aligned buffers.  fp16 tokens beyond 65504 are reported like any
+ * 16-bit GEMM epilogue (range code 3). */
+size_t mi355_patch_embed_x16_workspace_bytes(int B, int Cin, int H, int W, int ps, int E);
+int mi355_patch_embed_x16_fwd(const void* img16, const void* Wp16, const float* bp, void* tokens16, int B, int Cin, int H, int W, int ps, int E,
+                            int io, void* ws, size_t ws_bytes, mi355_stream_t stream);
+/* y (B, C) fp32 = mean over n of x16[b * batch_stride + n * C + c] for a 16-bit token stream, fp32 accumulation (mi355_token_mean_fwd
+ * for 16-bit tokens; batch_stride in elements).  Envelope: C % 4 == 0, batch_stride % 4 == 0, x16 8-byte and y 16-byte aligned. */
+int mi355_token_mean_x16_fwd(const void* x16, float* y, int B, int N, int C, long batch_stride, int io, mi355_stream_t stream);
+/* dst[i] = (float)src16[i], exact -- the way into the fp32 routes for a 16-bit activation that has no 16-bit-x kernel (a MixerLayer
+ * outside the token kernel's envelope, precision 0).  Any n > 0; envelope: 16-byte aligned buffers. */
+int mi355_widen16_fwd(const void* src16, float* dst, size_t n, int io, mi355_stream_t stream);
+/* dst16[i] = T(src[i]), round to nearest even -- the way out of those routes where the last kernel writes fp32.  Unlike mi355_cast16_fwd
+ * it produces a RESULT, not an operand: nothing is reported, an fp16 value beyond 65504 is inf as m(x.float()).half() has it.  Any
+ * n > 0; envelope: 16-byte aligned buffers. */
+int mi355_round16_fwd(const float* src, void* dst16, size_t n, int io, mi355_stream_t stream);
 /* LayerNorm + Linear in one pass for narrow rows (K = 64 or 128 = the normalised width; CSWin stage 1 / 2 and XCiT-nano qkv):
  *   Y = act( ((x - mean) / sqrt(var + eps)) . W16^T + bias ),  x (M,K) fp32 with row stride ldx floats, Y fp32 or 16-bit (out16).
  * The LayerNorm affine part must be folded into W16 / bias by the caller (W' = W diag(ln_weight), b' = b + W ln_bias).  The rows are

@@ -319,6 +319,27 @@ __global__ __launch_bounds__(256) void im2col16_kernel(const float* __restrict__
     }
 }
 
+// im2col16_kernel for an image that already HAS the operand type (mi355_patch_embed_x16_fwd, plain patches: no cls row): a pure gather of
+// 16-bit words, no conversion and nothing to report.  Same blocks, same band in LDS (ps x W 16-bit values); W % 8 == 0 and ps % 8 == 0:
+// every access is 16 bytes.
+typedef unsigned short pe_u16;
+typedef pe_u16 pe_u16x8 __attribute__((ext_vector_type(8)));
+__global__ __launch_bounds__(256) void im2col_gather16_kernel(const pe_u16* __restrict__ img, pe_u16* __restrict__ a16, int Cin, int H, int W, int ps,
+                                                              int K) {
+    extern __shared__ __attribute__((aligned(16))) pe_u16 s_band16[];        // ps x W
+    const int gw = W / ps, gh = H / ps;
+    const int c = blockIdx.x % Cin, py = (blockIdx.x / Cin) % gh, b = blockIdx.x / (Cin * gh);
+    const pe_u16* src = img + (((long)b * Cin + c) * H + (long)py * ps) * W;
+    for (int i = threadIdx.x; i < ps * W / 8; i += 256) reinterpret_cast<pe_u16x8*>(s_band16)[i] = reinterpret_cast<const pe_u16x8*>(src)[i];
+    __syncthreads();
+    const int cpr = ps / 8, cpp = ps * cpr;                                  // 16-byte chunks per patch row / per patch
+    for (int q = threadIdx.x; q < gw * cpp; q += 256) {
+        const int px = q / cpp, r = q - px * cpp, ky = r / cpr, kx0 = (r - ky * cpr) * 8;
+        *reinterpret_cast<pe_u16x8*>(a16 + ((long)b * gw * gh + py * gw + px) * K + (long)c * ps * ps + ky * ps + kx0) =
+            *reinterpret_cast<const pe_u16x8*>(s_band16 + ky * W + px * ps + kx0);
+    }
+}
+
 // residual table of the product: rows p < P = pos[p], row P = cls + pos[P] - bias (the GEMM adds the bias to every row)
 __global__ void patch_table_kernel(const float* __restrict__ cls, const float* __restrict__ pos, const float* __restrict__ bias,
                                    float* __restrict__ table, int P, int E) {
@@ -490,6 +511,45 @@ int mi355_patch_embed_ws_fwd(const float* img, const float* Wp, const float* bp,
     rc = mi355::linear16_dispatch(g, 0, precision, nullptr, 0, st);
     if (rc == MI355_EUNSUPPORTED) return mi355_patch_embed_fwd(img, Wp, bp, cls, pos, tokens, B, Cin, H, W, ps, E, precision, stream);
     return rc;
+}
+
+// Plain patch embedding from a 16-bit image to 16-bit tokens (the MLP-Mixer family on fp16 / bf16 activations; io = the type of both and
+// the operand format): the gather above into ws, then the 16-bit GEMM engine with a 16-bit epilogue (fp32 accumulation, one rounding).
+static bool patch_embed_x16_ok(int Cin, int W, int ps, int E) {
+    const long K = (long)Cin * ps * ps;
+    return !((K % 64) || (ps & 7) || (W & 7) || (E & 7) || (size_t)ps * W * 2 > 60000);
+}
+
+size_t mi355_patch_embed_x16_workspace_bytes(int B, int Cin, int H, int W, int ps, int E) {
+    if (B <= 0 || Cin <= 0 || ps <= 0 || E <= 0 || H < ps || W < ps || !patch_embed_x16_ok(Cin, W, ps, E)) return 0;
+    return (size_t)B * (H / ps) * (W / ps) * Cin * ps * ps * 2;
+}
+
+int mi355_patch_embed_x16_fwd(const void* img16, const void* Wp16, const float* bp, void* tokens16, int B, int Cin, int H, int W, int ps, int E,
+                              int io, void* ws, size_t ws_bytes, mi355_stream_t stream) {
+    MI355_CHECK_ARG(img16 && Wp16 && bp && tokens16 && ws);
+    MI355_CHECK_ARG(B > 0 && Cin > 0 && ps > 0 && E > 0 && H >= ps && W >= ps && H % ps == 0 && W % ps == 0);
+    MI355_CHECK_ARG(io == MI355_PREC_FP16 || io == MI355_PREC_BF16);
+    const long rows = (long)B * (H / ps) * (W / ps);
+    if (!patch_embed_x16_ok(Cin, W, ps, E) || rows >= (1L << 31) || (long)B * (H / ps) * Cin >= (1L << 31))
+        return mi355::fail(MI355_EUNSUPPORTED, "mi355_patch_embed_x16_fwd: needs Cin * ps * ps %% 64 == 0, ps %% 8 == 0, W %% 8 == 0, E %% 8 == 0 and "
+                                               "ps * W <= 30000 (Cin=%d W=%d ps=%d E=%d)", Cin, W, ps, E);
+    if (!aligned16(img16) || !aligned16(Wp16) || !aligned16(bp) || !aligned16(tokens16) || !aligned16(ws))
+        return mi355::fail(MI355_EUNSUPPORTED, "mi355_patch_embed_x16_fwd: 16-byte aligned buffers required");
+    MI355_CHECK_ARG(ws_bytes >= mi355_patch_embed_x16_workspace_bytes(B, Cin, H, W, ps, E));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int K = Cin * ps * ps;
+    {
+        MI355_TRACE(st, "im2col_gather16_kernel B=%d %dx%d ps=%d", B, H, W, ps);
+        im2col_gather16_kernel<<<B * (H / ps) * Cin, 256, (size_t)ps * W * 2, st>>>(static_cast<const pe_u16*>(img16), static_cast<pe_u16*>(ws), Cin, H,
+                                                                                  W, ps, K);
+        MI355_LAUNCH_CHECK();
+    }
+    g16::G16Args g{};
+    g.A = ws; g.B = Wp16; g.C = tokens16; g.bias = bp;
+    g.M = (int)rows; g.N = E; g.K = K; g.lda = K; g.ldb = K; g.ldc = E; g.act = MI355_ACT_NONE;
+    if (io == MI355_PREC_FP16) g.ovf = mi355::range_word(st);            // the tokens are fp16 operands of the first layer: a producer (code 3)
+    return mi355::linear16_dispatch(g, 1, io, nullptr, 0, st);
 }
 
 // Conv2d as implicit GEMM (no im2col buffer): rows = output pixels, K = Cin*KH*KW gathered in the A-operand load with zero padding.

@@ -423,6 +423,36 @@ __global__ __launch_bounds__(256) void cast16_kernel(const float* __restrict__ s
     if constexpr (std::is_same<T, _Float16>::value) rg_report(rgmax, ovf, 1u);
 }
 
+// 16-bit -> fp32, exact, 8 elements per thread (one 16-byte load, two 16-byte stores): how a 16-bit activation enters a route that has
+// no 16-bit-x kernel (mi355_widen16_fwd)
+template <typename T>
+__global__ __launch_bounds__(256) void widen16_kernel(const T* __restrict__ src, float* __restrict__ dst, long n8, long n) {
+    using v8 = typename Vec8<T>::t;
+    long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const long stride = (long)gridDim.x * 256;
+    for (; i < n8; i += stride) {
+        const v8 v = reinterpret_cast<const v8*>(src)[i];
+        reinterpret_cast<f4*>(dst)[2 * i] = f4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
+        reinterpret_cast<f4*>(dst)[2 * i + 1] = f4{(float)v[4], (float)v[5], (float)v[6], (float)v[7]};
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 7)) dst[n8 * 8 + threadIdx.x] = (float)src[n8 * 8 + threadIdx.x];
+}
+
+// fp32 -> 16-bit, round to nearest even: cast16_kernel for a RESULT (the 16-bit y of a module whose last kernel writes fp32), not for an
+// operand -- it reports nothing into the range word: an fp16 value beyond 65504 becomes inf, as m(x.float()).half() has it
+// (mi355_round16_fwd; the contract of DoubleAttention's 16-bit store)
+template <typename T>
+__global__ __launch_bounds__(256) void round16_kernel(const float* __restrict__ src, T* __restrict__ dst, long n8, long n) {
+    using v8 = typename Vec8<T>::t;
+    long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const long stride = (long)gridDim.x * 256;
+    for (; i < n8; i += stride) {
+        const f4 a = reinterpret_cast<const f4*>(src)[2 * i], b = reinterpret_cast<const f4*>(src)[2 * i + 1];
+        reinterpret_cast<v8*>(dst)[i] = v8{(T)a.x, (T)a.y, (T)a.z, (T)a.w, (T)b.x, (T)b.y, (T)b.z, (T)b.w};
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 7)) dst[n8 * 8 + threadIdx.x] = (T)src[n8 * 8 + threadIdx.x];
+}
+
 template <typename T, bool OUT16, bool LNA>
 void launch_ws_bn(const G16Args& g, int bn, int grid, int workers, hipStream_t st) {
     if (g.K == 64) {
@@ -494,6 +524,34 @@ int mi355_cast16_fwd(const float* src, void* dst16, size_t n, int precision, mi3
     MI355_TRACE(st, "cast16_kernel n=%zu", n);
     if (precision == MI355_PREC_FP16) cast16_kernel<_Float16><<<grid, 256, 0, st>>>(src, static_cast<_Float16*>(dst16), n8, (long)n, ovf);
     else                              cast16_kernel<__bf16><<<grid, 256, 0, st>>>(src, static_cast<__bf16*>(dst16), n8, (long)n, ovf);
+    MI355_LAUNCH_CHECK();
+    return MI355_OK;
+}
+
+int mi355_widen16_fwd(const void* src16, float* dst, size_t n, int io, mi355_stream_t stream) {
+    MI355_CHECK_ARG(src16 && dst && n > 0);
+    MI355_CHECK_ARG(io == MI355_PREC_FP16 || io == MI355_PREC_BF16);
+    if (!aligned16(src16) || !aligned16(dst)) return mi355::fail(MI355_EUNSUPPORTED, "mi355_widen16_fwd: 16-byte aligned buffers required");
+    const long n8 = (long)(n / 8);
+    const int grid = (int)((n8 + 255) / 256 < 4096 ? (n8 + 255) / 256 + 1 : 4096);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    MI355_TRACE(st, "widen16_kernel<%s> n=%zu", io == MI355_PREC_FP16 ? "f16" : "bf16", n);
+    if (io == MI355_PREC_FP16) widen16_kernel<_Float16><<<grid, 256, 0, st>>>(static_cast<const _Float16*>(src16), dst, n8, (long)n);
+    else                       widen16_kernel<__bf16><<<grid, 256, 0, st>>>(static_cast<const __bf16*>(src16), dst, n8, (long)n);
+    MI355_LAUNCH_CHECK();
+    return MI355_OK;
+}
+
+int mi355_round16_fwd(const float* src, void* dst16, size_t n, int io, mi355_stream_t stream) {
+    MI355_CHECK_ARG(src && dst16 && n > 0);
+    MI355_CHECK_ARG(io == MI355_PREC_FP16 || io == MI355_PREC_BF16);
+    if (!aligned16(src) || !aligned16(dst16)) return mi355::fail(MI355_EUNSUPPORTED, "mi355_round16_fwd: 16-byte aligned buffers required");
+    const long n8 = (long)(n / 8);
+    const int grid = (int)((n8 + 255) / 256 < 4096 ? (n8 + 255) / 256 + 1 : 4096);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    MI355_TRACE(st, "round16_kernel<%s> n=%zu", io == MI355_PREC_FP16 ? "f16" : "bf16", n);
+    if (io == MI355_PREC_FP16) round16_kernel<_Float16><<<grid, 256, 0, st>>>(src, static_cast<_Float16*>(dst16), n8, (long)n);
+    else                       round16_kernel<__bf16><<<grid, 256, 0, st>>>(src, static_cast<__bf16*>(dst16), n8, (long)n);
     MI355_LAUNCH_CHECK();
     return MI355_OK;
 }

@@ -347,3 +347,45 @@ extern "C" int mi355_token_mean_fwd(const float* x, float* y, int B, int N, int 
     MI355_LAUNCH_CHECK();
     return MI355_OK;
 }
+
+// The same mean over a 16-bit token stream (the MLP-Mixer family on fp16 / bf16 activations), fp32 accumulation, fp32 result (the head's
+// input): workgroup = (image, 256-channel slab), thread = (token quarter tq, 4 channels): 8-byte loads, 512 contiguous bytes per wave
+// and token; the four quarters meet in LDS and are added in a fixed order.  Nothing is converted TO 16 bit here: nothing to report.
+namespace {
+template <typename T>
+__global__ __launch_bounds__(256) void token_mean16_kernel(const T* __restrict__ x, float* __restrict__ y, int N, int C, long batch_stride, int slabs) {
+    typedef T x4 __attribute__((ext_vector_type(4)));
+    __shared__ f4 s_part[4][64];
+    const int b = blockIdx.x / slabs, tq = threadIdx.x >> 6, c = (blockIdx.x % slabs) * 256 + (threadIdx.x & 63) * 4;
+    f4 s = f4{0.f, 0.f, 0.f, 0.f};
+    if (c < C) {                                                             // C % 4 == 0: a quad is in or out
+        const T* p = x + (long)b * batch_stride + c;
+        for (int n = tq; n < N; n += 4) {
+            const x4 v = *reinterpret_cast<const x4*>(p + (long)n * C);
+            s = s + f4{(float)v.x, (float)v.y, (float)v.z, (float)v.w};
+        }
+    }
+    s_part[tq][threadIdx.x & 63] = s;
+    __syncthreads();
+    if (tq == 0 && c < C) {
+        const int l = threadIdx.x & 63;
+        const f4 t = (s_part[0][l] + s_part[1][l]) + (s_part[2][l] + s_part[3][l]);
+        const float inv = 1.0f / (float)N;
+        *reinterpret_cast<f4*>(y + (long)b * C + c) = f4{t.x * inv, t.y * inv, t.z * inv, t.w * inv};
+    }
+}
+}  // namespace
+
+extern "C" int mi355_token_mean_x16_fwd(const void* x16, float* y, int B, int N, int C, long batch_stride, int io, mi355_stream_t stream) {
+    MI355_CHECK_ARG(x16 && y && B > 0 && N > 0 && C > 0 && batch_stride >= (long)N * C);
+    MI355_CHECK_ARG(io == MI355_PREC_FP16 || io == MI355_PREC_BF16);
+    const int slabs = cdiv(C, 256);
+    if ((C & 3) || (batch_stride & 3) || (reinterpret_cast<uintptr_t>(x16) & 7) || !aligned16(y) || (long)B * slabs >= (1L << 31))
+        return mi355::fail(MI355_EUNSUPPORTED, "mi355_token_mean_x16_fwd: needs C %% 4 == 0, batch_stride %% 4 == 0, x16 8-byte and y 16-byte aligned (C=%d)", C);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    MI355_TRACE(st, "token_mean16_kernel<%s> B=%d N=%d C=%d", io == MI355_PREC_FP16 ? "f16" : "bf16", B, N, C);
+    if (io == MI355_PREC_FP16) token_mean16_kernel<_Float16><<<B * slabs, 256, 0, st>>>(static_cast<const _Float16*>(x16), y, N, C, batch_stride, slabs);
+    else                       token_mean16_kernel<__bf16><<<B * slabs, 256, 0, st>>>(static_cast<const __bf16*>(x16), y, N, C, batch_stride, slabs);
+    MI355_LAUNCH_CHECK();
+    return MI355_OK;
+}

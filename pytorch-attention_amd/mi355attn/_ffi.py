@@ -139,7 +139,15 @@ SIGNATURES = {
     "mi355_cam_x16_fwd": (c_int, [c_vp] * 3 + [c_int] * 5 + [c_vp, c_size, c_vp]),
     "mi355_conv1x1_tokens16_fwd": (c_int, [c_vp] * 4 + [c_int] * 6 + [c_vp]),
     "mi355_tokens_to_nchw_axpy_x16_fwd": (c_int, [c_vp] * 4 + [c_int] * 3 + [ctypes.c_long, c_int, c_vp]),
-    "mi355_dwconv_nchw_tokens_fwd": (c_int, [c_vp] * 4 + [c_int] * 5 + [c_vp]),
+    # the MLP-Mixer family on fp16 / bf16 activations (csrc/mixer_fused.hip; gemm.hip, layernorm.hip, gemm16.hip): `int io` coded like IO_CODES
+    "mi355_mixer_token_x16_workspace_bytes": (c_size, [c_int] * 3),
+    "mi355_mixer_token_x16_fwd": (c_int, [c_vp] * 3 + [c_float] + [c_vp] * 5 + [c_int] * 5 + [c_vp, c_size, c_vp]),
+    "mi355_patch_embed_x16_workspace_bytes": (c_size, [c_int] * 6),
+    "mi355_patch_embed_x16_fwd": (c_int, [c_vp] * 4 + [c_int] * 7 + [c_vp, c_size, c_vp]),
+    "mi355_token_mean_x16_fwd": (c_int, [c_vp, c_vp, c_int, c_int, c_int, ctypes.c_long, c_int, c_vp]),
+    "mi355_widen16_fwd": (c_int, [c_vp, c_vp, c_size, c_int, c_vp]),
+    "mi355_round16_fwd": (c_int, [c_vp, c_vp, c_size, c_int, c_vp]),
+    "mi355_dwconv_nchw_tokens_fwd":(c_int, [c_vp] * 4 + [c_int] * 5 + [c_vp]),
     "mi355_qk_logits_fwd": (c_int, [c_vp] * 3 + [c_int] * 8 + [c_vp]),
     "mi355_topk_mask_fwd": (c_int, [c_vp, ctypes.c_long, c_int, c_int, c_vp]),
     "mi355_adaptive_pool_tokens_fwd": (c_int, [c_vp] * 2 + [c_int] * 6 + [c_vp]),
@@ -270,7 +278,8 @@ def require_device_f32(t, name):
     if t.dtype != torch.float32:
         raise TypeError(f"{name}: expected float32, got {t.dtype} (16-bit activations are accepted by SELayer, ECALayer, CBAM, "
                         "ChannelAttention, SpatialAttention, SELayerBias, SELayerBias4, SELayerHidden, SqueezeExcite, simam_module, SRM, "
-                        "GaussianGCT, LCT, GCT, DoubleAttention, CoordinateAttention, TripletAttention, AttentionGate, BAM, PAM and CAM only)")
+                        "GaussianGCT, LCT, GCT, DoubleAttention, CoordinateAttention, TripletAttention, AttentionGate, MixerLayer, MLP_Mixer "
+                        "(with its PatchEmbedding), BAM, PAM and CAM only)")
     if t.requires_grad and torch.is_grad_enabled():
         _warn_no_autograd()
     return t if t.is_contiguous() else t.contiguous()

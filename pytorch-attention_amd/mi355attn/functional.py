@@ -834,6 +834,11 @@ def weight16(param, precision=None):
     """16-bit copy of a weight, converted once and reused until the parameter is modified (in-place version bump),
     moved, re-precisioned or collected."""
     p = _prec(precision)
+    if param.dtype in _ffi.IO_CODES:                      # module.half() / .bfloat16(): already in the operand format -> used as it is;
+        if _ffi.IO_CODES[param.dtype] == p and param.is_cuda:       # the other 16-bit type -> through its cached fp32 copy (param32)
+            return param.detach() if param.is_contiguous() else param.detach().contiguous()
+        tag = (param._version, param.data_ptr(), tuple(param.shape))
+        return _derived_get((param,), ("w16", p), tag, lambda: cast16(param32(param, "weight"), p))
     tag = (param._version, param.data_ptr(), tuple(param.shape))
     return _derived_get((param,), ("w16", p), tag, lambda: cast16(param.detach(), p))
 
@@ -1131,6 +1136,75 @@ def mixer_token_mlp(x, norm, fc1, fc2, precision=None):
                                       float(norm.eps), dptr(w1p), dptr(require_device_f32(fc1.bias, "fc1.bias")), dptr(w2s),
                                       dptr(require_device_f32(fc2.bias, "fc2.bias")), dptr(y), B, N, C, T, p, dptr(ws), ws.numel(),
                                       stream_ptr(x.device)), "mi355_mixer_token_fwd")
+    return y
+
+
+# ---- the MLP-Mixer family on fp16 / bf16 activations (csrc/mixer_fused.hip: the 16-bit-x token kernel) ----------------------
+def _require_io16(x, name):
+    """A dense fp16 / bf16 device tensor and its `io` code (_ffi.IO_CODES); a CPU tensor raises the package's device error."""
+    x, io = _ffi.require_device_io(x, name)
+    if not io:
+        raise TypeError(f"{name}: expected a float16 or bfloat16 device tensor, got {x.dtype}")
+    return x, io
+
+
+def widen16(x):
+    """16-bit -> fp32, exact (mi355_widen16_fwd): how a 16-bit activation enters a route that has no 16-bit-x kernel."""
+    x, io = _require_io16(x, "x")
+    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    check(lib().mi355_widen16_fwd(dptr(x), dptr(y), x.numel(), io, stream_ptr(x.device)), "mi355_widen16_fwd")
+    return y
+
+
+def round16(x, dtype):
+    """fp32 -> fp16 / bf16, round to nearest even (mi355_round16_fwd).  A result, not an operand: nothing is reported to the range guard."""
+    x = require_device_f32(x, "x")
+    y = torch.empty(x.shape, dtype=dtype, device=x.device)
+    check(lib().mi355_round16_fwd(dptr(x), dptr(y), x.numel(), _ffi.IO_CODES[dtype], stream_ptr(x.device)), "mi355_round16_fwd")
+    return y
+
+
+def mixer_token_mlp16(x, norm, fc1, fc2):
+    """mixer_token_mlp for a 16-bit x (B, 196, C): the result is the FP32 residual stream x1 of the layer.  The operand format is the type
+    of x; parameters may be fp32 or 16-bit (param32 / weight16_padk / weight16_slices: converted once, cached per parameter version)."""
+    x, io = _require_io16(x, "x")
+    B, N, C = x.shape
+    T = fc1.weight.shape[0]
+    w1p = weight16_padk(fc1.weight, 224, io)
+    w2s = weight16_slices(fc2.weight, 208, io)
+    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    ws = workspace(lib().mi355_mixer_token_x16_workspace_bytes(B, N, C), x.device)
+    check(lib().mi355_mixer_token_x16_fwd(dptr(x), dptr(param32(norm.weight, "norm.weight")), dptr(param32(norm.bias, "norm.bias")),
+                                        float(norm.eps), dptr(w1p), dptr(param32(fc1.bias, "fc1.bias")), dptr(w2s),
+                                        dptr(param32(fc2.bias, "fc2.bias")), dptr(y), B, N, C, T, io, dptr(ws), ws.numel(),
+                                        stream_ptr(x.device)), "mi355_mixer_token_x16_fwd")
+    return y
+
+
+def patch_embed16(img, wp, bp, patch):
+    """Plain patch embedding of a 16-bit image (B, Cin, H, W) -> 16-bit tokens (B, P, E) in the type of img (mi355_patch_embed_x16_fwd).
+    Returns None where the entry is not built for the geometry (its workspace query answers 0: the caller widens and runs
+    patch_embed)."""
+    img, io = _require_io16(img, "img")
+    B, Cin, H, W = img.shape
+    E = wp.shape[0]
+    if lib().mi355_patch_embed_x16_workspace_bytes(B, Cin, H, W, patch, E) == 0:
+        return None
+    w16 = weight16(wp, io).reshape(E, -1)
+    tokens = torch.empty(B, (H // patch) * (W // patch), E, dtype=img.dtype, device=img.device)
+    _range_check()
+    ws = workspace(lib().mi355_patch_embed_x16_workspace_bytes(B, Cin, H, W, patch, E), img.device)
+    check(lib().mi355_patch_embed_x16_fwd(dptr(img), dptr(w16), dptr(param32(bp, "proj.bias")), dptr(tokens), B, Cin, H, W, patch, E, io,
+                                        dptr(ws), ws.numel(), stream_ptr(img.device)), "mi355_patch_embed_x16_fwd")
+    return tokens
+
+
+def token_mean16(x):
+    """fp32 mean over the token axis of a 16-bit x (B, N, C), fp32 accumulation (mi355_token_mean_x16_fwd)."""
+    x, io = _require_io16(x, "x")
+    B, N, C = x.shape
+    y = torch.empty(B, C, dtype=torch.float32, device=x.device)
+    check(lib().mi355_token_mean_x16_fwd(dptr(x), dptr(y), B, N, C, N * C, io, stream_ptr(x.device)), "mi355_token_mean_x16_fwd")
     return y
 
 

@@ -3,10 +3,26 @@
 Token mixing is a LEFT multiplication of each image's (N x C) matrix, so the reference's two transposes
 (mlp_mixer.py:47) never materialise: the batched GEMM reads the activation as its K-major operand.
 """
+import torch
 from torch import nn
 
+from .. import _ffi
 from .. import functional as F
 from .vit import _fast, _mlp16
+
+
+def _is16(x):
+    return isinstance(x, torch.Tensor) and x.dtype in _ffi.IO_CODES
+
+
+def _same(t, name):
+    return t
+
+
+def _p32(t, name):
+    """A parameter of a module that runs on 16-bit activations, as fp32: fp32 (autocast) as it is, 16-bit (module.half() / .bfloat16())
+    through its cached fp32 copy (F.param32); None stays None."""
+    return None if t is None else F.param32(t, name)
 
 
 class Mlp(nn.Module):
@@ -33,29 +49,67 @@ class MixerLayer(nn.Module):
         self.precision = precision
         self.channel_mlp.precision = precision
 
+    _mi355_fp16_io_saturates = True          # an fp16 x is guarded like an fp32 one: LN(x), gelu(H) and the 16-bit epilogues can saturate
+
     def forward(self, x):
+        """x (B, N, C) fp32, or fp16 / bf16 (the result has the type of x; see _forward16)."""
+        if _is16(x):
+            return self._forward16(x)
         t = self.token_mlp
-        p = F._prec(self.precision)
         T, N = t.fc1.weight.shape
         if x.dim() == 3 and t.fc1.bias is not None and t.fc2.bias is not None and F.mixer_token_ok(N, T, x.shape[-1], self.precision):
             # the whole half in one kernel: neither LN(x)^T nor the hidden tensor exists in HBM (csrc/mixer_fused.hip)
-            x = F.mixer_token_mlp(x.contiguous(), self.norm1, t.fc1, t.fc2, p)
-        elif p in (F.PREC_FP16, F.PREC_BF16) and T % 64 == 0 and x.shape[-1] % 4 == 0 and x.shape[-1] <= 1024:
-            # channel-major on the 16-bit GEMM engine: LN(x)^T (B,C,NP) -> gelu(. W1^T + b1) (B,C,T) -> (. W2^T + b2)^T + x
-            NP = -(-N // 64) * 64
-            ut = F.layernorm16_t(x, self.norm1.weight, self.norm1.bias, self.norm1.eps, NP, p)
-            ht = F.linear16(ut, F.weight16_padk(t.fc1.weight, NP, p), t.fc1.bias, act=F.ACT_GELU, out16=True, precision=p)
-            x = F.linear16_tr(ht, F.weight16(t.fc2.weight, p), t.fc2.bias, x, p)
+            x = F.mixer_token_mlp(x.contiguous(), self.norm1, t.fc1, t.fc2, F._prec(self.precision))
         else:
-            u = F.layernorm(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)
-            hid = F.token_mix(t.fc1.weight, u, t.fc1.bias, act=F.ACT_GELU, precision=self.precision)     # (B,T,C)
-            x = F.token_mix(t.fc2.weight, hid, t.fc2.bias, resid=x, precision=self.precision)            # (B,N,C)
+            x = self._token_mix(x, self.precision, _same)
         c = self.channel_mlp
         if _fast(self.precision, c.fc1, c.fc2):
             u = F.layernorm16(x, self.norm2.weight, self.norm2.bias, self.norm2.eps, F._prec(self.precision))
         else:
             u = F.layernorm(x, self.norm2.weight, self.norm2.bias, self.norm2.eps)
         return c(u, resid=x)
+
+    def _token_mix(self, x, precision, P):
+        """x + token_mlp(norm1(x)^T)^T for an fp32 x outside the fused kernel's envelope.  `precision`: the setting (None = the default);
+        P(param, name): the parameter as the fp32 kernels take it (the identity on the fp32 path, _p32 behind a 16-bit x)."""
+        t = self.token_mlp
+        p = F._prec(precision)
+        T, N = t.fc1.weight.shape
+        if p in (F.PREC_FP16, F.PREC_BF16) and T % 64 == 0 and x.shape[-1] % 4 == 0 and x.shape[-1] <= 1024:
+            # channel-major on the 16-bit GEMM engine: LN(x)^T (B,C,NP) -> gelu(. W1^T + b1) (B,C,T) -> (. W2^T + b2)^T + x
+            NP = -(-N // 64) * 64
+            ut = F.layernorm16_t(x, P(self.norm1.weight, "norm1.weight"), P(self.norm1.bias, "norm1.bias"), self.norm1.eps, NP, p)
+            ht = F.linear16(ut, F.weight16_padk(t.fc1.weight, NP, p), P(t.fc1.bias, "fc1.bias"), act=F.ACT_GELU, out16=True, precision=p)
+            return F.linear16_tr(ht, F.weight16(t.fc2.weight, p), P(t.fc2.bias, "fc2.bias"), x, p)
+        u = F.layernorm(x, P(self.norm1.weight, "norm1.weight"), P(self.norm1.bias, "norm1.bias"), self.norm1.eps)
+        hid = F.token_mix(P(t.fc1.weight, "fc1.weight"), u, P(t.fc1.bias, "fc1.bias"), act=F.ACT_GELU, precision=precision)     # (B,T,C)
+        return F.token_mix(P(t.fc2.weight, "fc2.weight"), hid, P(t.fc2.bias, "fc2.bias"), resid=x, precision=precision)         # (B,N,C)
+
+    def _forward16(self, x):
+        """The layer on an fp16 / bf16 x; the result has the type of x.  The MFMA operand format is that type (fp16: the precision-1
+        arithmetic, bf16: precision 2) and a `precision` of None / 1 / 2 / 3 is ignored; precision 0 (explicit, the package default, or
+        a strict re-run) widens x, runs the strict route and rounds.  x enters the arithmetic unrounded, the residual stream x1 behind the
+        token mixing stays fp32, and y = fc2(..) + x1 is rounded once, in the epilogue of the last GEMM (an fp16 y beyond 65504 is what
+        every 16-bit GEMM epilogue makes of it: reported to the range guard, code 3, so the module re-runs strict and returns inf).
+        Inside the fused token kernel's envelope x is read in 16 bit by that kernel (mi355_mixer_token_x16_fwd); outside it (N != 196,
+        C > 1024, ...) one launch widens x (widen16_kernel) and the fp32 routes run; the final store is 16-bit either way."""
+        x, io = F._require_io16(x, "x")
+        p = F.PREC_STRICT if F._prec(self.precision) == F.PREC_STRICT else io
+        t, c = self.token_mlp, self.channel_mlp
+        T, N = t.fc1.weight.shape
+        if p and x.dim() == 3 and t.fc1.bias is not None and t.fc2.bias is not None and F.mixer_token_ok(N, T, x.shape[-1], p):
+            x1 = F.mixer_token_mlp16(x, self.norm1, t.fc1, t.fc2)
+        else:
+            x1 = self._token_mix(F.widen16(x), p, _p32)
+        nw, nb = _p32(self.norm2.weight, "norm2.weight"), _p32(self.norm2.bias, "norm2.bias")
+        b1, b2 = _p32(c.fc1.bias, "fc1.bias"), _p32(c.fc2.bias, "fc2.bias")
+        if _fast(p, c.fc1, c.fc2):
+            u = F.layernorm16(x1, nw, nb, self.norm2.eps, p)
+            h = F.linear16(u, F.weight16(c.fc1.weight, p), b1, act=F.ACT_GELU, out16=True, precision=p)
+            return F.linear16(h, F.weight16(c.fc2.weight, p), b2, resid=x1, out16=True, precision=p)
+        u = F.layernorm(x1, nw, nb, self.norm2.eps)
+        h = F.linear(u, _p32(c.fc1.weight, "fc1.weight"), b1, act=F.ACT_GELU, precision=p)
+        return F.round16(F.linear(h, _p32(c.fc2.weight, "fc2.weight"), b2, resid=x1, precision=p), x.dtype)
 
 
 class PatchEmbedding(nn.Module):
@@ -69,7 +123,20 @@ class PatchEmbedding(nn.Module):
         self.proj = nn.Conv2d(in_chanels, embedding_dim, kernel_size=patch_size, stride=patch_size)
         self.precision = None
 
+    _mi355_fp16_io_saturates = True          # fp16 tokens beyond 65504 are reported by the GEMM epilogue
+
     def forward(self, x):
+        """x (B, Cin, H, W) fp32 -> fp32 tokens, or fp16 / bf16 -> tokens of that type (operand format = the type; precision 0 widens,
+        runs the strict route and rounds; so does a geometry outside the envelope of mi355_patch_embed_x16_fwd, in the format of x)."""
+        if _is16(x):
+            x, io = F._require_io16(x, "img")
+            p = F.PREC_STRICT if F._prec(self.precision) == F.PREC_STRICT else io
+            w = self.proj.weight
+            t = F.patch_embed16(x, w, self.proj.bias, self.patch_size) if p else None
+            if t is not None:
+                return t
+            t = F.patch_embed(F.widen16(x), _p32(w, "proj.weight"), _p32(self.proj.bias, "proj.bias"), None, None, self.patch_size, p)
+            return F.round16(t, x.dtype)
         return F.patch_embed(x, self.proj.weight, self.proj.bias, None, None, self.patch_size, self.precision)
 
 
@@ -85,8 +152,17 @@ class MLP_Mixer(nn.Module):
         self.head = nn.Linear(dim, num_classes)
         self.precision = precision
 
+    _mi355_fp16_io_saturates = True
+
     def forward(self, x):
+        """fp32 image -> fp32 logits.  An fp16 / bf16 image runs the composition of the parts on 16-bit tensors -- embedding, every layer
+        (16-bit in, 16-bit out), token mean (fp32 accumulation, fp32 pooled row), head -- and returns the logits in that type."""
+        io16 = _is16(x)
         x = self.patch_embedding(x)
         for blk in self.blocks:
             x = blk(x)
+        if io16:
+            p = F.PREC_STRICT if F._prec(self.precision) == F.PREC_STRICT else _ffi.IO_CODES[x.dtype]
+            logits = F.linear(F.token_mean16(x), _p32(self.head.weight, "head.weight"), _p32(self.head.bias, "head.bias"), precision=p)
+            return logits.to(x.dtype)                # (B, classes): the one torch cast, not a pass over activations
         return F.linear(F.token_mean(x), self.head.weight, self.head.bias, precision=self.precision)
