@@ -683,6 +683,28 @@ int mi355_widen16_fwd(const void* src16, float* dst, size_t n, int io, mi355_str
  * it produces a RESULT, not an operand: nothing is reported, an fp16 value beyond 65504 is inf as m(x.float()).half() has it.  Any
  * n > 0; envelope: 16-byte aligned buffers. */
 int mi355_round16_fwd(const float* src, void* dst16, size_t n, int io, mi355_stream_t stream);
+/* ViT encoder on fp16 / bf16 activations (ViT.py:107-119 on a .half() / .bfloat16() model or under autocast): the two kernels the block
+ * needs beside the entries above and the 16-bit GEMM engine.  `io` / `precision` name the 16-bit type of the buffers AND the MFMA
+ * operand format (1 = fp16, 2 = bf16; anything else is MI355_EINVAL).  The caller owns every buffer; nothing is kept between calls; null
+ * pointers are MI355_EINVAL, a shape outside the stated envelope or a misaligned buffer is MI355_EUNSUPPORTED with nothing launched.
+ *
+ * mi355_layernorm16_x16_fwd: mi355_layernorm16_fwd for rows that are already 16-bit -- x16 (rows, cols) and y16 (rows, cols) in the type
+ * `io`, weight / bias (cols) fp32.  x16 is widened in registers (exact) and enters the arithmetic unrounded: y16 holds the bits
+ * mi355_layernorm16_fwd(precision = io) computes from x16 widened to fp32.  Envelope: that entry's -- any cols > 0; cols % 4 == 0,
+ * cols <= 2048 and 16-byte aligned buffers take the packed kernel (8-byte reads), anything else the element-wise one; buffers aligned
+ * to their element size.  An fp16 result beyond 65504 is reported to the range guard (code 2), as there. */
+int mi355_layernorm16_x16_fwd(const void* x16, const float* weight, const float* bias, void* y16, int rows, int cols, float eps, int io,
+                              mi355_stream_t stream);
+/* Y = round_out( widen(resid) + act(X16 . W16^T + bias) ): the 16-bit GEMM with a residual that is 16-bit, a result that is 16-bit, or
+ * both -- X16 (M, K; row stride ldx), W16 (N, K) in the type `precision`, bias (N) fp32 or NULL, resid and Y (M, N; row stride ldy for
+ * both) each fp32 (resid_io / out_io = 0) or in the type `precision` (= precision).  The sum is formed in fp32 and rounded ONCE; K order,
+ * MFMA and epilogue order (bias, act, residual) are the engine's, so the fp32 sum is the bits mi355_linear16_ws_fwd computes for the
+ * widened residual.  act: MI355_ACT_NONE or MI355_ACT_GELU.  An fp16 Y beyond 65504 is reported like every 16-bit GEMM epilogue (range
+ * code 3).  Envelope: K % 64 == 0, N % 8 == 0, ldx % 8 == 0, ldy % 8 == 0, any M >= 1, 16-byte aligned buffers, resid not NULL, at least
+ * one of resid_io / out_io 16-bit (the all-fp32 pair is mi355_linear16_ws_fwd's: MI355_EUNSUPPORTED here).  No workspace, no exchange
+ * between workgroups: safe under hipGraph capture, a row's bits do not depend on the rows around it.  Y must not overlap X16 or W16. */
+int mi355_linear16_res_fwd(const void* X16, const void* W16, const float* bias, const void* resid, int resid_io, void* Y, int out_io, int M,
+                           int N, int K, int ldx, int ldy, int act, int precision, mi355_stream_t stream);
 /* LayerNorm + Linear in one pass for narrow rows (K = 64 or 128 = the normalised width; CSWin stage 1 / 2 and XCiT-nano qkv):
  *   Y = act( ((x - mean) / sqrt(var + eps)) . W16^T + bias ),  x (M,K) fp32 with row stride ldx floats, Y fp32 or 16-bit (out16).
  * The LayerNorm affine part must be folded into W16 / bias by the caller (W' = W diag(ln_weight), b' = b + W ln_bias).  The rows are

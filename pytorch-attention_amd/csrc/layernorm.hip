@@ -240,6 +240,128 @@ int mi355_layernorm16_fwd(const float* x, const float* weight, const float* bias
 
 }  // extern "C"
 
+// layernorm_kernel<out16> for rows that are ALREADY 16-bit (a ViT encoder block on fp16 / bf16 activations): a lane reads its float4
+// groups as 8-byte packs of four 16-bit values and widens them in registers (exact), then runs layernorm_kernel's statistics and
+// normalise expression on the same lane layout -- so a row gets the bits mi355_layernorm16_fwd gives the widened row.
+namespace {
+template <int LPR, int NV, typename T>
+__global__ __launch_bounds__(256) void layernorm_x16_kernel(const T* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
+                                                           T* __restrict__ y, long rows, int cols, float eps, unsigned* ovf) {
+    typedef T x4 __attribute__((ext_vector_type(4)));
+    float rgmax = 0.f;
+    constexpr int RPW = 64 / LPR;
+    const int lane = threadIdx.x & 63, sub = lane % LPR, rsel = lane / LPR;
+    const long wave0 = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (long)gridDim.x * 4;
+    const int n4 = cols >> 2;
+    const float inv = 1.0f / (float)cols;
+    for (long r0 = wave0 * RPW; r0 < rows; r0 += nwaves * RPW) {
+        const long row = r0 + rsel;
+        const bool rok = row < rows;
+        const x4* xr = reinterpret_cast<const x4*>(x + (rok ? row : 0) * cols);
+        v4f v[NV];
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int i = sub + LPR * j;
+            if (rok && i < n4) {
+                const x4 h = xr[i];
+                v[j] = v4f{(float)h.x, (float)h.y, (float)h.z, (float)h.w};
+            } else {
+                v[j] = v4f{0.f, 0.f, 0.f, 0.f};
+            }
+            s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
+        }
+        const float mean = group_sum<LPR>(s) * inv;
+        float q = 0.f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int i = sub + LPR * j;
+            if (i < n4) {
+                const v4f d = v[j] - mean;
+                q += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
+            }
+        }
+        const float rstd = 1.0f / sqrtf(group_sum<LPR>(q) * inv + eps);
+        if (!rok) continue;
+        T* yr = y + row * cols;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int i = sub + LPR * j;
+            if (i < n4) {
+                const v4f ww = reinterpret_cast<const v4f*>(w)[i], bb = reinterpret_cast<const v4f*>(b)[i];
+                const v4f o = (v[j] - mean) * rstd * ww + bb;
+                if constexpr (std::is_same<T, _Float16>::value) rgmax = rg_absmax4(rgmax, o);
+                store4<T>(yr + 4 * i, o);
+            }
+        }
+    }
+    if constexpr (std::is_same<T, _Float16>::value) rg_report(rgmax, ovf, 2u);
+}
+
+// any width / alignment: layernorm_generic_kernel on 16-bit rows
+template <typename T>
+__global__ __launch_bounds__(256) void layernorm_x16_generic_kernel(const T* __restrict__ x, const float* __restrict__ w,
+                                                                   const float* __restrict__ b, T* __restrict__ y, long rows, int cols,
+                                                                   float eps, unsigned* ovf) {
+    float rgmax = 0.f;
+    const int lane = threadIdx.x & 63;
+    const long wave0 = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (long)gridDim.x * 4;
+    for (long row = wave0; row < rows; row += nwaves) {
+        const T* xr = x + row * cols;
+        float s = 0.f;
+        for (int i = lane; i < cols; i += 64) s += (float)xr[i];
+        const float mean = wave_sum(s) / (float)cols;
+        float q = 0.f;
+        for (int i = lane; i < cols; i += 64) { const float d = (float)xr[i] - mean; q += d * d; }
+        const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)cols + eps);
+        for (int i = lane; i < cols; i += 64) {
+            const float o = ((float)xr[i] - mean) * rstd * w[i] + b[i];
+            if constexpr (std::is_same<T, _Float16>::value) rgmax = rg_absmax1(rgmax, o);
+            y[row * cols + i] = (T)o;
+        }
+    }
+    if constexpr (std::is_same<T, _Float16>::value) rg_report(rgmax, ovf, 2u);
+}
+
+template <typename T>
+void launch_ln_x16(const T* x, const float* weight, const float* bias, T* y, int rows, int cols, float eps, hipStream_t st) {
+    unsigned* ovf = std::is_same<T, _Float16>::value ? mi355::range_word(st) : nullptr;
+    MI355_TRACE(st, "layernorm_x16_kernel<%s> rows=%d cols=%d", std::is_same<T, _Float16>::value ? "f16" : "bf16", rows, cols);
+    const bool vec = (cols % 4 == 0) && aligned16(x) && aligned16(y) && aligned16(weight) && aligned16(bias);
+#define LNX(LPR_, NV_)                                                                                               \
+    do {                                                                                                             \
+        const long waves = ((long)rows + (64 / LPR_) - 1) / (64 / LPR_);                                            \
+        const int grid = (int)((waves + 3) / 4 < 8192 ? (waves + 3) / 4 : 8192);                                    \
+        layernorm_x16_kernel<LPR_, NV_, T><<<grid, 256, 0, st>>>(x, weight, bias, y, rows, cols, eps, ovf);         \
+    } while (0)
+    if (vec && cols <= 64)        LNX(16, 1);           // the width classes of launch_ln (the lane layout decides the summation order)
+    else if (vec && cols <= 128)  LNX(32, 1);
+    else if (vec && cols <= 256)  LNX(64, 1);
+    else if (vec && cols <= 512)  LNX(64, 2);
+    else if (vec && cols <= 1024) LNX(64, 4);
+    else if (vec && cols <= 2048) LNX(64, 8);
+    else {
+        const int grid = cdiv(rows, 4) < 8192 ? cdiv(rows, 4) : 8192;
+        layernorm_x16_generic_kernel<T><<<grid, 256, 0, st>>>(x, weight, bias, y, rows, cols, eps, ovf);
+    }
+#undef LNX
+}
+}  // namespace
+
+extern "C" int mi355_layernorm16_x16_fwd(const void* x16, const float* weight, const float* bias, void* y16, int rows, int cols, float eps,
+                                         int io, mi355_stream_t stream) {
+    MI355_CHECK_ARG(x16 && weight && bias && y16 && rows > 0 && cols > 0);
+    MI355_CHECK_ARG(io == MI355_PREC_FP16 || io == MI355_PREC_BF16);
+    if ((reinterpret_cast<uintptr_t>(x16) & 1) || (reinterpret_cast<uintptr_t>(y16) & 1) || (reinterpret_cast<uintptr_t>(weight) & 3) ||
+        (reinterpret_cast<uintptr_t>(bias) & 3))
+        return mi355::fail(MI355_EUNSUPPORTED, "mi355_layernorm16_x16_fwd: buffers must be aligned to their element size");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (io == MI355_PREC_FP16) launch_ln_x16<_Float16>(static_cast<const _Float16*>(x16), weight, bias, static_cast<_Float16*>(y16), rows, cols, eps, st);
+    else                       launch_ln_x16<__bf16>(static_cast<const __bf16*>(x16), weight, bias, static_cast<__bf16*>(y16), rows, cols, eps, st);
+    MI355_LAUNCH_CHECK();
+    return MI355_OK;
+}
+
 // LayerNorm over channels, written TRANSPOSED per image in the 16-bit operand format: x (B, N, C) fp32 -> ut (B, C, NP), ut[b,c,n] =
 // LN(x[b,n,:])[c] for n < N and 0 for N <= n < NP.  This is the K-major activation the Mixer token-mixing product wants as a
 // plain row-major GEMM operand (mlp_mixer.py:45-47: norm1 -> transpose(1,2) -> token_mlp).  One workgroup = 32 tokens of one image;

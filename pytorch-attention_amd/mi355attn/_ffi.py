@@ -147,6 +147,9 @@ SIGNATURES = {
     "mi355_token_mean_x16_fwd": (c_int, [c_vp, c_vp, c_int, c_int, c_int, ctypes.c_long, c_int, c_vp]),
     "mi355_widen16_fwd": (c_int, [c_vp, c_vp, c_size, c_int, c_vp]),
     "mi355_round16_fwd": (c_int, [c_vp, c_vp, c_size, c_int, c_vp]),
+    # the ViT encoder on fp16 / bf16 activations (csrc/layernorm.hip, csrc/gemm16_res.hip)
+    "mi355_layernorm16_x16_fwd": (c_int, [c_vp] * 4 + [c_int, c_int, c_float, c_int, c_vp]),
+    "mi355_linear16_res_fwd": (c_int, [c_vp] * 4 + [c_int, c_vp] + [c_int] * 8 + [c_vp]),
     "mi355_dwconv_nchw_tokens_fwd":(c_int, [c_vp] * 4 + [c_int] * 5 + [c_vp]),
     "mi355_qk_logits_fwd": (c_int, [c_vp] * 3 + [c_int] * 8 + [c_vp]),
     "mi355_topk_mask_fwd": (c_int, [c_vp, ctypes.c_long, c_int, c_int, c_vp]),
@@ -279,7 +282,7 @@ def require_device_f32(t, name):
         raise TypeError(f"{name}: expected float32, got {t.dtype} (16-bit activations are accepted by SELayer, ECALayer, CBAM, "
                         "ChannelAttention, SpatialAttention, SELayerBias, SELayerBias4, SELayerHidden, SqueezeExcite, simam_module, SRM, "
                         "GaussianGCT, LCT, GCT, DoubleAttention, CoordinateAttention, TripletAttention, AttentionGate, MixerLayer, MLP_Mixer "
-                        "(with its PatchEmbedding), BAM, PAM and CAM only)")
+                        "(with its PatchEmbedding), TransformerEncoder, VisionTransformer (with its PatchEmbedding), BAM, PAM and CAM only)")
     if t.requires_grad and torch.is_grad_enabled():
         _warn_no_autograd()
     return t if t.is_contiguous() else t.contiguous()

@@ -1199,12 +1199,52 @@ def patch_embed16(img, wp, bp, patch):
     return tokens
 
 
-def token_mean16(x):
-    """fp32 mean over the token axis of a 16-bit x (B, N, C), fp32 accumulation (mi355_token_mean_x16_fwd)."""
+def token_mean16(x, skip_first=0):
+    """fp32 mean over the token axis of a 16-bit x (B, N, C), fp32 accumulation (mi355_token_mean_x16_fwd), optionally skipping the first
+    `skip_first` tokens (ViT global_pool="avg": an offset base pointer, as token_mean does it)."""
     x, io = _require_io16(x, "x")
     B, N, C = x.shape
     y = torch.empty(B, C, dtype=torch.float32, device=x.device)
-    check(lib().mi355_token_mean_x16_fwd(dptr(x), dptr(y), B, N, C, N * C, io, stream_ptr(x.device)), "mi355_token_mean_x16_fwd")
+    base = ctypes.c_void_p(x.data_ptr() + skip_first * C * 2)
+    check(lib().mi355_token_mean_x16_fwd(base, dptr(y), B, N - skip_first, C, N * C, io, stream_ptr(x.device)), "mi355_token_mean_x16_fwd")
+    return y
+
+
+# ---- the ViT encoder on fp16 / bf16 activations (csrc/layernorm.hip layernorm_x16_kernel, csrc/gemm16_res.hip) ----------------
+def layernorm16_x16(x, weight, bias, eps=1e-5):
+    """LayerNorm over the last axis of a 16-bit x, written in the type of x = the MFMA operand format (mi355_layernorm16_x16_fwd): the
+    bits layernorm16(x.float(), precision = the type) gives.  weight / bias: fp32, or 16-bit through their cached fp32 copies."""
+    x, io = _require_io16(x, "x")
+    _range_check()
+    weight, bias = param32(weight, "weight"), param32(bias, "bias")
+    cols = x.shape[-1]
+    y = torch.empty_like(x)
+    check(lib().mi355_layernorm16_x16_fwd(dptr(x), dptr(weight), dptr(bias), dptr(y), x.numel() // cols, cols, float(eps), io,
+                                          stream_ptr(x.device)), "mi355_layernorm16_x16_fwd")
+    return y
+
+
+def linear16_res(x16, w16, bias, resid, act=ACT_NONE, out_dtype=torch.float32, precision=None):
+    """Y = round( resid + act(x16 @ w16^T + bias) ) with a 16-bit residual, a 16-bit result, or both (mi355_linear16_res_fwd): the sum
+    is formed in fp32 and rounded once.  resid: fp32 or the operand type of `precision`; out_dtype: torch.float32 or that type.  The
+    all-fp32 pair is linear16's."""
+    _range_check()
+    p = _prec(precision)
+    x16 = _require16(x16, "x16", p)
+    w16 = _require16(w16, "w16", p)
+    bias = None if bias is None else param32(bias, "bias")
+    N, K = w16.shape
+    if x16.shape[-1] != K:
+        raise ValueError(f"linear16_res: x last dim {x16.shape[-1]} != weight in_features {K}")
+    M = x16.numel() // K
+    if not isinstance(resid, torch.Tensor) or resid.numel() != M * N:
+        raise ValueError("linear16_res: residual shape mismatch")
+    resid, rio = _ffi.require_device_io(resid, "resid")
+    if rio not in (0, p) or out_dtype not in (torch.float32, dtype16(p)):
+        raise TypeError(f"linear16_res: residual and result are float32 or {dtype16(p)} (got {resid.dtype}, {out_dtype})")
+    y = torch.empty(*x16.shape[:-1], N, dtype=out_dtype, device=x16.device)
+    check(lib().mi355_linear16_res_fwd(dptr(x16), dptr(w16), dptr(bias), dptr(resid), rio, dptr(y), 0 if out_dtype == torch.float32 else p,
+                                       M, N, K, K, N, act, p, stream_ptr(x16.device)), "mi355_linear16_res_fwd")
     return y
 
 

@@ -3,26 +3,11 @@
 Token mixing is a LEFT multiplication of each image's (N x C) matrix, so the reference's two transposes
 (mlp_mixer.py:47) never materialise: the batched GEMM reads the activation as its K-major operand.
 """
-import torch
 from torch import nn
 
 from .. import _ffi
 from .. import functional as F
-from .vit import _fast, _mlp16
-
-
-def _is16(x):
-    return isinstance(x, torch.Tensor) and x.dtype in _ffi.IO_CODES
-
-
-def _same(t, name):
-    return t
-
-
-def _p32(t, name):
-    """A parameter of a module that runs on 16-bit activations, as fp32: fp32 (autocast) as it is, 16-bit (module.half() / .bfloat16())
-    through its cached fp32 copy (F.param32); None stays None."""
-    return None if t is None else F.param32(t, name)
+from .vit import _fast, _is16, _mlp16, _p32, _same
 
 
 class Mlp(nn.Module):

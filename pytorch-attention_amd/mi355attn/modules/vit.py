@@ -13,15 +13,52 @@ Precision 3 ("logit-compensated", F.PREC_LOGIT) is precision 1 with the logit pa
 projection, the stored q and k, Q K^T -- in the strict operand format (bf16 hi + lo, three MFMAs): the 16-bit error of the block that
 grows with the logit size is made there, the value path is scale-free (profiles/logit_mode.md).  Pick it for weights whose pre-softmax
 logits have a standard deviation above ~1, i.e. anything trained.  Everything outside `Attention` runs exactly as in precision 1.
+
+`TransformerEncoder`, `PatchEmbedding` and `VisionTransformer` also take an fp16 / bf16 tensor and return that type (the operand format
+is then the tensor's type; see TransformerEncoder._forward16).  `Attention` and `Mlp` on their own keep their internal convention on a
+16-bit x: an operand in, an fp32 result out.
 """
 import torch
 from torch import nn
 
+from .. import _ffi
 from .. import functional as F
 
 
 def _bias(lin):
     return lin.bias if lin.bias is not None else None
+
+
+def _is16(x):
+    return isinstance(x, torch.Tensor) and x.dtype in _ffi.IO_CODES
+
+
+def _p32(t, name):
+    """A parameter of a module that runs on 16-bit activations, as fp32: fp32 (autocast) as it is, 16-bit (module.half() / .bfloat16())
+    through its cached fp32 copy (F.param32); None stays None."""
+    return None if t is None else F.param32(t, name)
+
+
+def _io_precision(precision, io):
+    """The arithmetic of a module on a 16-bit tensor of type code `io`: the tensor's type, unless the setting (or a strict re-run) asks
+    for precision 0."""
+    return F.PREC_STRICT if F._prec(precision) == F.PREC_STRICT else io
+
+
+def _same(t, name):
+    return t
+
+
+class _Lin32:
+    """A Linear as the fp32 routes behind a widened 16-bit x take it: its parameters as fp32 tensors (_p32), its feature counts."""
+
+    def __init__(self, lin, name):
+        self.weight, self.bias = _p32(lin.weight, name + ".weight"), _p32(lin.bias, name + ".bias")
+        self.in_features, self.out_features = lin.in_features, lin.out_features
+
+
+def _lin(lin, P, name):
+    return lin if P is _same else _Lin32(lin, name)
 
 
 def _fast(precision, *linears):
@@ -50,10 +87,16 @@ class Mlp(nn.Module):
         self.drop = drop                     # inference engine: dropout is the identity (eval semantics)
 
     def forward(self, x, resid=None):
-        if _fast(self.precision, self.fc1, self.fc2):
-            return _mlp16(x, self.fc1, self.fc2, self.precision, second_gelu=True, resid=resid)
-        h = F.linear(x, self.fc1.weight, self.fc1.bias, act=F.ACT_GELU, precision=self.precision)
-        return F.linear(h, self.fc2.weight, self.fc2.bias, act=F.ACT_GELU, resid=resid, precision=self.precision)
+        return self._run(x, resid, self.precision, _same)
+
+    def _run(self, x, resid, precision, P):
+        """The forward at `precision` (the setting; None = the default) with the parameters as P hands them over: _same from forward(),
+        _p32 behind a widened 16-bit x (TransformerEncoder._forward16)."""
+        fc1, fc2 = _lin(self.fc1, P, "fc1"), _lin(self.fc2, P, "fc2")
+        if _fast(precision, fc1, fc2):
+            return _mlp16(x, fc1, fc2, precision, second_gelu=True, resid=resid)
+        h = F.linear(x, fc1.weight, fc1.bias, act=F.ACT_GELU, precision=precision)
+        return F.linear(h, fc2.weight, fc2.bias, act=F.ACT_GELU, resid=resid, precision=precision)
 
 
 class Attention(nn.Module):
@@ -73,17 +116,19 @@ class Attention(nn.Module):
         d = self.qkv.in_features // self.num_heads
         return _fast(self.precision, self.qkv, self.proj) and d in F.SDPA_WIDTHS
 
-    def _core(self, qkv, fast):
+    def _core(self, qkv, fast, precision=None):
         """softmax(q k^T scale) v on the (B,N,3C) projection.  Short sequences of 32 / 64 wide heads stay in LDS (attn.hip); longer
         sequences (384 px input: N = 577) and wider heads (ViT.py:68 defaults to 4 heads: d = 192 at dim 768) stream K / V
-        (sdpa_general.hip); any other width runs zero padded to the next built one."""
+        (sdpa_general.hip); any other width runs zero padded to the next built one.  `precision`: the operand format where it is not
+        the module's setting (a block on 16-bit activations: the type of its x)."""
+        p = self.precision if precision is None else precision
         B, N, C3 = qkv.shape
         C = C3 // 3
         d = C // self.num_heads
         if d in (32, 64) and N <= 224:
-            return F.sdpa16(qkv, self.num_heads, self.scale, precision=self.precision) if fast else \
-                F.sdpa(qkv, self.num_heads, self.scale, precision=self.precision)
-        return F.sdpa_general(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], self.num_heads, self.scale, precision=self.precision)
+            return F.sdpa16(qkv, self.num_heads, self.scale, precision=p) if fast else \
+                F.sdpa(qkv, self.num_heads, self.scale, precision=p)
+        return F.sdpa_general(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], self.num_heads, self.scale, precision=p)
 
     def _forward_logit(self, x, resid):
         """Precision 3: one projection launch that computes the q / k columns on bf16 hi / lo pairs and the v columns in fp16
@@ -102,22 +147,28 @@ class Attention(nn.Module):
     def forward(self, x, resid=None):
         if F.logit_mode(self.precision):
             return self._forward_logit(x, resid)
+        return self._run(x, resid, self.precision, _same)
+
+    def _run(self, x, resid, precision, P):
+        """The forward outside precision 3 at `precision` (the setting; None = the default) with the parameters as P hands them over:
+        _same from forward(), _p32 behind a widened 16-bit x (TransformerEncoder._forward16)."""
+        qkv_, proj = _lin(self.qkv, P, "qkv"), _lin(self.proj, P, "proj")
         d = self.qkv.in_features // self.num_heads
         if d not in F.SDPA_WIDTHS:                                                           # odd head width: padded projections
             from .mhsa import _fused_qkv_attention
-            out, _, _ = _fused_qkv_attention(x if x.dtype == torch.float32 else x.float(), self.qkv, self.proj, self.num_heads, d,
-                                             self.scale, self.precision)
+            out, _, _ = _fused_qkv_attention(x if x.dtype == torch.float32 else x.float(), qkv_, proj, self.num_heads, d,
+                                             self.scale, precision)
             return out if resid is None else F.axpby(out, torch.empty_like(out), out.numel() // out.shape[-1], out.shape[-1],
                                                      out.shape[-1], out.shape[-1], u=resid, ldu=out.shape[-1])
-        if self.fast_ok():
+        if _fast(precision, self.qkv, self.proj):
             # q / k / v / ctx stay 16-bit in HBM; the whole block is ONE C call (mi355_mhsa_fwd: cast -> qkv GEMM -> core -> proj GEMM,
             # the same kernels the three-call composition of rounds 1-2 launched)
-            p = F._prec(self.precision)
-            return F.mhsa16(x, F.weight16(self.qkv.weight, p), _bias(self.qkv), F.weight16(self.proj.weight, p), self.proj.bias,
+            p = F._prec(precision)
+            return F.mhsa16(x, F.weight16(qkv_.weight, p), _bias(qkv_), F.weight16(proj.weight, p), proj.bias,
                             self.num_heads, self.scale, resid=resid, precision=p)
-        qkv = F.linear(x, self.qkv.weight, _bias(self.qkv), precision=self.precision)      # (B,N,3C)
-        ctx = self._core(qkv, False)                                                        # (B,N,C)
-        return F.linear(ctx, self.proj.weight, self.proj.bias, resid=resid, precision=self.precision)
+        qkv = F.linear(x, qkv_.weight, _bias(qkv_), precision=precision)                   # (B,N,3C)
+        ctx = self._core(qkv, False, precision)                                             # (B,N,C)
+        return F.linear(ctx, proj.weight, proj.bias, resid=resid, precision=precision)
 
 
 class PatchEmbedding(nn.Module):
@@ -129,7 +180,21 @@ class PatchEmbedding(nn.Module):
         self.proj = nn.Conv2d(in_channels, embedding_dim, kernel_size=patch_size, stride=patch_size)
         self.precision = None
 
+    _mi355_fp16_io_saturates = True          # fp16 tokens beyond 65504 are reported by the GEMM epilogue
+
     def forward(self, x):
+        """x (B, Cin, H, W) fp32 -> fp32 tokens, or fp16 / bf16 -> tokens of that type, as mixer.PatchEmbedding has it (operand format =
+        the type; precision 0 widens, runs the strict route and rounds; so does a geometry outside the envelope of
+        mi355_patch_embed_x16_fwd, in the format of x)."""
+        if _is16(x):
+            x, io = F._require_io16(x, "img")
+            p = _io_precision(self.precision, io)
+            t = F.patch_embed16(x, self.proj.weight, self.proj.bias, self.patch_size) if p else None
+            if t is not None:
+                return t
+            t = F.patch_embed(F.widen16(x), _p32(self.proj.weight, "proj.weight"), _p32(self.proj.bias, "proj.bias"), None, None,
+                              self.patch_size, p)
+            return F.round16(t, x.dtype)
         return F.patch_embed(x, self.proj.weight, self.proj.bias, None, None, self.patch_size, self.precision)
 
 
@@ -147,10 +212,50 @@ class TransformerEncoder(nn.Module):
             return F.layernorm16(x, ln.weight, ln.bias, ln.eps, F._prec(self.attn.precision))
         return F.layernorm(x, ln.weight, ln.bias, ln.eps)
 
+    _mi355_fp16_io_saturates = True          # an fp16 x is guarded like an fp32 one: the fp16 LN operand and the 16-bit epilogues can saturate
+
     def forward(self, x):
+        """x (B, N, C) fp32, or fp16 / bf16 (the result has the type of x; see _forward16)."""
+        if _is16(x):
+            return self._forward16(x)
         if self.fold_ok(x):
             return self.forward_folded(x)[0]
         return self.forward_plain(x)
+
+    def _forward16(self, x):
+        """The block on an fp16 / bf16 x; the result has the type of x.  The MFMA operand format is that type (fp16: the precision-1
+        arithmetic, bf16: precision 2) and a `precision` of None / 1 / 2 / 3 is ignored; precision 0 (explicit, the package default, or
+        a strict re-run) widens x, runs the strict route and rounds.  On the fast route x enters the arithmetic unrounded -- LayerNorm 1
+        reads it in 16 bit (layernorm_x16_kernel), proj adds it as a 16-bit residual -- the residual stream x1 behind the attention
+        half stays fp32, and y = x1 + gelu(fc2(..)) is rounded once, in the epilogue of the last GEMM (gemm16_res_kernel; an fp16 y
+        beyond 65504 is reported to the range guard, code 3, so the block re-runs strict and returns inf).  No widen, round or cast
+        launch.  Outside that envelope (head widths off F.SDPA_WIDTHS, in_features % 64 != 0, precision 0) one launch widens x, the
+        fp32 body runs at the precision of the type, and one launch rounds.  Neither the LayerNorm fold nor the pooled-token tail
+        applies to a 16-bit tensor."""
+        x, io = F._require_io16(x, "x")
+        p = _io_precision(self.attn.precision, io)
+        at, mlp, ln1, ln2 = self.attn, self.mlp, self.layernorm1, self.layernorm2
+        if p and x.dim() == 3 and at.fast_ok(x.shape[1]) and _fast(p, at.qkv, at.proj, mlp.fc1, mlp.fc2):
+            u = F.layernorm16_x16(x, ln1.weight, ln1.bias, ln1.eps)
+            qkv = F.linear16(u, F.weight16(at.qkv.weight, p), _p32(at.qkv.bias, "qkv.bias"), out16=True, precision=p)
+            ctx = at._core(qkv, True, p)
+            x1 = F.linear16_res(ctx, F.weight16(at.proj.weight, p), at.proj.bias, x, precision=p)         # 16-bit residual, fp32 stream
+            u = F.layernorm16(x1, _p32(ln2.weight, "layernorm2.weight"), _p32(ln2.bias, "layernorm2.bias"), ln2.eps, p)
+            h = F.linear16(u, F.weight16(mlp.fc1.weight, p), _p32(mlp.fc1.bias, "fc1.bias"), act=F.ACT_GELU, out16=True, precision=p)
+            return F.linear16_res(h, F.weight16(mlp.fc2.weight, p), mlp.fc2.bias, x1, act=F.ACT_GELU, out_dtype=x.dtype, precision=p)
+        return F.round16(self._plain(F.widen16(x), p, _p32), x.dtype)
+
+    def _plain(self, x, p, P):
+        """forward_plain for the widened x of _forward16: the same body at precision p (0 or the type of the 16-bit x, whatever the
+        setting) with every parameter through P (_p32: 16-bit parameters as their cached fp32 copies)."""
+        at, mlp, ln1, ln2 = self.attn, self.mlp, self.layernorm1, self.layernorm2
+        fast = _fast(p, at.qkv, at.proj, mlp.fc1, mlp.fc2) and at.qkv.in_features // at.num_heads in F.SDPA_WIDTHS
+
+        def norm(ln, t, name):
+            w, b = P(ln.weight, name + ".weight"), P(ln.bias, name + ".bias")
+            return F.layernorm16(t, w, b, ln.eps, p) if fast else F.layernorm(t, w, b, ln.eps)
+        x = at._run(norm(ln1, x, "layernorm1"), x, p, P)
+        return mlp._run(norm(ln2, x, "layernorm2"), x, p, P)
 
     def forward_plain(self, x):
         """The default body: one LayerNorm launch in front of each half (the fold is opt-in: measured slower)."""
@@ -253,7 +358,35 @@ class VisionTransformer(nn.Module):
             return False
         return not any(m._forward_hooks or m._forward_pre_hooks for m in blk.modules())
 
+    _mi355_fp16_io_saturates = True
+
+    def _forward16(self, img):
+        """The model on an fp16 / bf16 image: the composition of its parts on 16-bit tensors, logits in the type of the image.  The
+        tokens are the fp32 tokens of the embedding (patches, cls token, position rows; operand format = the type) computed from the
+        widened image and rounded once -- one widen and one round launch per forward, no torch cast over activations; every block is
+        16-bit in, 16-bit out and runs in full (neither the LayerNorm fold nor the pooled-token tail takes a 16-bit tensor); the
+        pooled row and the head are fp32, and the (B, classes) logits are the one torch cast."""
+        img, io = F._require_io16(img, "img")
+        p = _io_precision(self.precision, io)
+        pe = self.patch_embedding
+        pos = F.vit_pos_table(_p32(self.position_embedding, "position_embedding"), pe.patch_size, img.shape[2], img.shape[3])
+        tok = F.patch_embed(F.widen16(img), _p32(pe.proj.weight, "proj.weight"), _p32(pe.proj.bias, "proj.bias"),
+                            _p32(self.cls_token, "cls_token").reshape(-1), pos, pe.patch_size, p)
+        tok = F.round16(tok, img.dtype)
+        for blk in self.blocks:
+            tok = blk(tok)
+        if self.global_pool == "token":
+            pooled = tok[:, 0].float()                           # (B, C): not a pass over the activations
+        elif self.global_pool == "avg":
+            pooled = F.token_mean16(tok, skip_first=1)
+        else:
+            pooled = F.widen16(tok)
+        logits = F.linear(pooled, _p32(self.head.weight, "head.weight"), _p32(self.head.bias, "head.bias"), precision=p)
+        return logits.to(img.dtype)
+
     def forward(self, x):
+        if _is16(x):
+            return self._forward16(x)
         B, _, H, W = x.shape
         ps = self.patch_embedding.patch_size
         pos = F.vit_pos_table(self.position_embedding, ps, H, W)     # ViT.py:160-178: bicubic resize off the native grid (cached)
