@@ -806,11 +806,18 @@ int mi355_cswin_lepe_attn_fwd(const float* qkv, const float* getv_w, const float
                               float scale, int precision, mi355_stream_t stream);
 
 /* XCA core (xcit.py:249-262): qkv (B,N,3,h,d); temperature (h); out (B,N,h*d).
- *   per head: L2-normalise q,k over N; A = softmax((q^ k^T) * temp_h) (d x d); out = (A v)^T. */
+ *   per head: L2-normalise q,k over N; A = softmax((q^ k^T) * temp_h) (d x d); out = (A v)^T.
+ *   Envelope: head width 1 <= d <= 256, any N >= 1, 16-byte aligned qkv and out; d > 256 is MI355_EUNSUPPORTED before any launch.
+ *   d = 32 / 48 / 64 run template kernels, every other width xca_any_kernel (run-time width, softmax masked to the d live columns,
+ *   16-byte accesses where d % 4 == 0, element-wise otherwise).  Exact-fp32 MFMA arithmetic at every width: `precision` does not change
+ *   the result.  Run-to-run bit-identical; an image's bits do not depend on its batch.  No workspace. */
 int mi355_xca_fwd(const float* qkv, const float* temperature, float* out, int B, int N, int heads, int d,
                   int precision, mi355_stream_t stream);
 /* The same core with out in the 16-bit operand format of `precision` (1 / 2), ready for the proj GEMM (no cast pass over ctx);
- * qkv_is16 != 0: qkv is in that format too (16-bit output of the qkv GEMM).  Arithmetic is fp32 in every case. */
+ * qkv_is16 != 0: qkv is in that format too (16-bit output of the qkv GEMM).  Arithmetic is fp32 in every case.
+ *   Envelope: head width 1 <= d <= 256 as above.  d = 32 / 48 / 64: the template kernels (A V^T on the 16-bit matrix pipe when qkv is
+ *   16-bit).  Every other width: xca_any_kernel -- widened at the load (exact), fp32 throughout, ONE rounding at the store; 16-byte
+ *   accesses where d % 8 == 0 (16-bit tensors) / d % 4 == 0 (fp32 qkv).  An fp32 qkv stored as fp16 is not reported to the range guard. */
 int mi355_xca16_fwd(const void* qkv, int qkv_is16, const float* temperature, void* out16, int B, int N, int heads, int d,
                     int precision, mi355_stream_t stream);
 
@@ -953,7 +960,11 @@ int mi355_token_mean_fwd(const float* x, float* y, int B, int N, int C, long bat
 /* Class attention core (CaiT / XCiT ClassAttention.forward xcit.py:174-188): one query per image and head attends over N keys,
  *   out[b, i*d + j] = sum_n softmax_n(scale * sum_j' q[b, i*d + j'] k[b,n,i*d + j']) v[b,n,i*d + j],   exact fp32.
  * q row b starts at q + b*ldq; key / value token (b,n) starts at k|v + (b*N + n)*ldkv (so the fused (B,N,3C) qkv tensor can be
- * passed in place with k = qkv + C, v = qkv + 2C, ldkv = 3C).  out (B, h*d) dense.  d <= 64, N <= 4096. */
+ * passed in place with k = qkv + C, v = qkv + 2C, ldkv = 3C).  out (B, h*d) dense.
+ *   Envelope: head width 1 <= head_dim <= 256, N <= 4096, any ldq / ldkv >= h*d; anything else is MI355_EUNSUPPORTED before any launch.
+ *   head_dim = 16 / 32 / 48 / 64 with 16-byte aligned k and ldkv % 4 == 0 run template kernels; every other width, leading dimension or
+ *   key alignment class_attn_any_kernel (run-time width; 16-byte key reads where head_dim % 4 == 0, ldkv % 4 == 0 and k is aligned,
+ *   element-wise otherwise). */
 int mi355_class_attn_fwd(const float* q, const float* k, const float* v, float* out, int B, int N, int num_heads, int head_dim,
                          long ldq, long ldkv, float scale, mi355_stream_t stream);
 

@@ -58,6 +58,70 @@ __global__ __launch_bounds__(64) void class_attn_kernel(const float* __restrict_
     }
 }
 
+// The same kernel at a run-time head width, 1 <= d <= 256 (every width and alignment the templates above are not built for): one wave per
+// (image, head), the structure and the summation order of class_attn_kernel -- a key's products go to two partial sums by the parity
+// of their group of four channels, an output channel's terms to four by n % 4.  VEC: 16-byte key reads (head_dim % 4 == 0,
+// ldkv % 4 == 0, 16-byte aligned k); element-wise otherwise.  A lane owns the output channels lane, lane + 64, ...
+constexpr int CLS_ANY_MAX = 256;
+
+template <bool VEC>
+__global__ __launch_bounds__(64) void class_attn_any_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                            const float* __restrict__ v, float* __restrict__ out, int N, int h, int D,
+                                                            long ldq, long ldkv, float scale) {
+    extern __shared__ __attribute__((aligned(16))) float s_p[];      // N probabilities
+    __shared__ __attribute__((aligned(16))) float s_q[CLS_ANY_MAX];
+    const int b = blockIdx.x / h, i = blockIdx.x - b * h, lane = threadIdx.x;
+    for (int j = lane; j < D; j += 64) s_q[j] = q[(long)b * ldq + (long)i * D + j];
+    __syncthreads();
+    float mx = -INFINITY;
+    for (int n = lane; n < N; n += 64) {
+        const float* kp = k + ((long)b * N + n) * ldkv + (long)i * D;
+        float s0 = 0.f, s1 = 0.f;
+        if constexpr (VEC) {
+            const v4f* kr = reinterpret_cast<const v4f*>(kp);
+            const int d4 = D >> 2;
+            for (int j = 0; j < d4; j += 2) {
+                const v4f a = kr[j], qa = reinterpret_cast<const v4f*>(s_q)[j];
+                s0 += qa.x * a.x; s0 += qa.y * a.y; s0 += qa.z * a.z; s0 += qa.w * a.w;
+                if (j + 1 < d4) {
+                    const v4f c = kr[j + 1], qc = reinterpret_cast<const v4f*>(s_q)[j + 1];
+                    s1 += qc.x * c.x; s1 += qc.y * c.y; s1 += qc.z * c.z; s1 += qc.w * c.w;
+                }
+            }
+        } else {
+            for (int j = 0; j < D; ++j) {
+                const float p = s_q[j] * kp[j];
+                if (j & 4) s1 += p; else s0 += p;
+            }
+        }
+        const float s = (s0 + s1) * scale;
+        s_p[n] = s;
+        mx = fmaxf(mx, s);
+    }
+    mx = wave_max(mx);
+    float sum = 0.f;
+    for (int n = lane; n < N; n += 64) {
+        const float e = expf(s_p[n] - mx);
+        s_p[n] = e;
+        sum += e;
+    }
+    sum = wave_sum(sum);
+    __syncthreads();
+    for (int c = lane; c < D; c += 64) {
+        const float* vc = v + (long)b * N * ldkv + (long)i * D + c;
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+        int n = 0;
+        for (; n + 3 < N; n += 4) {
+            a0 += s_p[n] * vc[(long)n * ldkv];
+            a1 += s_p[n + 1] * vc[(long)(n + 1) * ldkv];
+            a2 += s_p[n + 2] * vc[(long)(n + 2) * ldkv];
+            a3 += s_p[n + 3] * vc[(long)(n + 3) * ldkv];
+        }
+        for (; n < N; ++n) a0 += s_p[n] * vc[(long)n * ldkv];
+        out[((long)b * h + i) * D + c] = ((a0 + a1) + (a2 + a3)) / sum;
+    }
+}
+
 template <bool VEC>
 __global__ __launch_bounds__(256) void axpby_kernel(const float* __restrict__ x, const float* __restrict__ u,
                                                     const float* __restrict__ gamma, float* __restrict__ y, long rows, int cols,
@@ -132,17 +196,25 @@ int mi355_class_attn_fwd(const float* q, const float* k, const float* v, float* 
     MI355_CHECK_ARG(q && k && v && out && B > 0 && N > 0 && num_heads > 0);
     MI355_CHECK_ARG(ldq >= (long)num_heads * head_dim && ldkv >= (long)num_heads * head_dim);
     if (N > 4096) return mi355::fail(MI355_EUNSUPPORTED, "mi355_class_attn_fwd: N = %d > 4096", N);
-    if (!aligned16(k) || (ldkv & 3) || (head_dim & 7))
-        return mi355::fail(MI355_EUNSUPPORTED, "mi355_class_attn_fwd: keys must be 16-byte aligned, ldkv %% 4 == 0, head_dim %% 8 == 0");
+    if (head_dim < 1 || head_dim > CLS_ANY_MAX)
+        return mi355::fail(MI355_EUNSUPPORTED, "mi355_class_attn_fwd: head_dim %d (supported: 1 .. %d)", head_dim, CLS_ANY_MAX);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t smem = (size_t)((N + 3) & ~3) * sizeof(float);
     const int grid = B * num_heads;
+    const bool vec = aligned16(k) && !(ldkv & 3) && !(head_dim & 3);
+    const bool built = head_dim == 16 || head_dim == 32 || head_dim == 48 || head_dim == 64;
+    if (!(vec && built)) {                                  // every other width, leading dimension or key alignment
+        MI355_TRACE(st, "class_attn_any_kernel<d=%d%s> B=%d N=%d heads=%d", head_dim, vec ? ",vec" : "", B, N, num_heads);
+        if (vec) class_attn_any_kernel<true><<<grid, 64, smem, st>>>(q, k, v, out, N, num_heads, head_dim, ldq, ldkv, scale);
+        else     class_attn_any_kernel<false><<<grid, 64, smem, st>>>(q, k, v, out, N, num_heads, head_dim, ldq, ldkv, scale);
+        MI355_LAUNCH_CHECK();
+        return MI355_OK;
+    }
     switch (head_dim) {
         case 16: class_attn_kernel<16><<<grid, 64, smem, st>>>(q, k, v, out, N, num_heads, ldq, ldkv, scale); break;
         case 32: class_attn_kernel<32><<<grid, 64, smem, st>>>(q, k, v, out, N, num_heads, ldq, ldkv, scale); break;
         case 48: class_attn_kernel<48><<<grid, 64, smem, st>>>(q, k, v, out, N, num_heads, ldq, ldkv, scale); break;
-        case 64: class_attn_kernel<64><<<grid, 64, smem, st>>>(q, k, v, out, N, num_heads, ldq, ldkv, scale); break;
-        default: return mi355::fail(MI355_EUNSUPPORTED, "mi355_class_attn_fwd: head_dim %d not in {16,32,48,64}", head_dim);
+        default: class_attn_kernel<64><<<grid, 64, smem, st>>>(q, k, v, out, N, num_heads, ldq, ldkv, scale); break;
     }
     MI355_LAUNCH_CHECK();
     return MI355_OK;

@@ -440,6 +440,230 @@ __global__ __launch_bounds__(256, D <= 48 ? 3 : 2) void xca_tr_kernel(const T* _
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// XCA core at a RUN-TIME head width, 1 <= d <= 256: every width the templates above are not built for (they keep 32 / 48 / 64).
+// Zero-padding d onto a built width is wrong here -- the softmax runs over the d channels of a head, a padded column has logit 0 and
+// would take exp(0 - max) of every row -- so this kernel masks.
+//   * Rows of the d x d matrix are independent: workgroup = (image, head, block of RB rows of G).  It streams the tokens through LDS in
+//     chunks of TC: its RB channels of q and all d channels of k; forms its RB x d slab of G, its q norms and ALL k norms (recomputed per
+//     row block: TC reads per column and chunk); masked row softmax; then streams v and writes its RB channels of every token.
+//   * d is padded to dp = the next multiple of 16 in LDS only: channels >= d and tokens >= N are staged as zeros, softmax columns >= d
+//     never enter the maximum or the sum and end up as A = 0, rows >= d are never stored; nothing outside [h d, h d + d) of a token's
+//     row is written.
+//   * One arithmetic for the three type modes (fp32 -> fp32, fp32 -> 16 bit, 16 bit -> same): widened at the load (exact), ONE rounding
+//     at the store, everything between in fp32 -- G and A V^T on the exact-fp32 MFMA, as in xca_kernel, so `precision` changes nothing.
+//   * (16 x 16) tiles of the slab are dealt to the waves whole (full token range each, wave w owns tiles w, w + waves, ...: at most 8),
+//     the column norms are summed in token order by one thread per column: no partial sums, no atomics, nothing between workgroups --
+//     run-to-run bit-identical and safe under graph capture.  RB, TC and the workgroup size are functions of d alone
+//     (xca_any_geom), so an image's bits do not depend on its batch.
+//   * 16-byte global accesses where d allows them (d % 4 == 0 for fp32, d % 8 == 0 for 16-bit elements: every head then starts on a
+//     16-byte boundary of the 16-byte aligned tensors), element-wise otherwise.
+//   * LDS is dynamic and sized by d (odd pitches): 10 KB at d = 16, 50 KB at 64, 59 KB at 128, 70 KB at 256 (two workgroups per CU).
+// The fp32-in / 16-bit-out mode does not report its fp16 conversion to the range guard: the known gap of xca_kernel's same mode.
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int XCA_ANY_MAX = 256;      // widest head
+constexpr int XCA_ANY_UNITS = 8;      // (16 x 16) tiles of G per wave: (RB / 16) * (dp / 16) <= 4 * this
+
+struct XcaAnyGeom { int RB, TC, threads, nrb; size_t lds; };
+static XcaAnyGeom xca_any_geom(int d) {
+    XcaAnyGeom g;
+    const int dp = (d + 15) & ~15;
+    g.RB = dp <= 64 ? dp : 32;                 // whole heads up to 64 (k is streamed once), 32-row blocks above
+    g.TC = dp <= 128 ? 64 : 32;
+    const int units = (g.RB / 16) * (dp / 16);
+    g.threads = 64 * (units < 4 ? units : 4);
+    g.nrb = (dp + g.RB - 1) / g.RB;
+    g.lds = ((size_t)g.RB * (dp + 1) + (size_t)g.TC * (dp + 1) + (size_t)g.TC * (g.RB + 1) + dp + g.RB) * sizeof(float);
+    return g;
+}
+
+// `width` channels from channel c0 on (a multiple of 16) of the tokens n0 .. n0 + tc - 1 -> dst[token][channel] (pitch floats), zeros for
+// channels >= d and tokens >= N.  VW elements per load; (token, channel group) advances by the workgroup size without a division.
+template <int VW, typename IT>
+__device__ __forceinline__ void xca_any_stage(const IT* __restrict__ src, long row3, float* __restrict__ dst, int pitch, int c0, int width,
+                                              int d, int n0, int tc, int N, int t, int nthr) {
+    const int wv = width / VW, total = tc * wv;
+    const int qs = nthr / wv, rs = nthr - qs * wv;
+    int nl = t / wv, cv = t - nl * wv;
+#pragma unroll 4
+    for (int idx = t; idx < total; idx += nthr) {
+        const int c = c0 + cv * VW, n = n0 + nl;
+        float v[VW];
+#pragma unroll
+        for (int e = 0; e < VW; ++e) v[e] = 0.f;
+        if (n < N && c < d) {
+            const IT* p = src + (long)n * row3 + c;
+            if constexpr (VW == 1) v[0] = (float)p[0];
+            else {
+                typedef IT iv __attribute__((ext_vector_type(VW)));
+                const iv r = *reinterpret_cast<const iv*>(p);
+#pragma unroll
+                for (int e = 0; e < VW; ++e) v[e] = (float)r[e];
+            }
+        }
+        float* q = dst + nl * pitch + cv * VW;
+#pragma unroll
+        for (int e = 0; e < VW; ++e) q[e] = v[e];
+        nl += qs;
+        cv += rs;
+        if (cv >= wv) { cv -= wv; ++nl; }
+    }
+}
+
+template <typename OT, typename IT>
+__global__ __launch_bounds__(256) void xca_any_kernel(const IT* __restrict__ qkv, const float* __restrict__ temperature, OT* __restrict__ out,
+                                                      int N, int heads, int d, int RB, int TC, int vec_in, int vec_out) {
+    extern __shared__ __attribute__((aligned(16))) float xa_smem[];
+    constexpr int VWI = 16 / (int)sizeof(IT);
+    const int dp = (d + 15) & ~15, DT = dp >> 4, PG = dp + 1, PQ = RB + 1;
+    const int nrb = (dp + RB - 1) / RB;
+    float* s_g = xa_smem;               // [RB][PG]: the slab of G, then of A = softmax(G)
+    float* s_k = s_g + RB * PG;         // [TC][PG]: k chunk, later the v chunk
+    float* s_q = s_k + TC * PG;         // [TC][PQ]: the block's channels of the q chunk
+    float* s_n = s_q + TC * PQ;         // [dp] k norms | [RB] q norms
+    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), l15 = lane & 15, g = lane >> 4;
+    const int nthr = blockDim.x, nw = nthr >> 6;
+    const int lid = xcd_contiguous_block();                 // the row blocks of a head, then the heads of an image, read the same rows
+    const int rb = lid % nrb, hb = lid / nrb, h = hb % heads, b = hb / heads;
+    const int r0 = rb * RB, rt = min(RB, dp - r0) >> 4;     // first row, row tiles of this block
+    const int nunits = rt * DT;
+    const int C = heads * d;
+    const long row3 = 3L * C;
+    const IT* base = qkv + (long)b * N * row3 + h * d;
+    const int nchunks = (N + TC - 1) / TC;
+    auto stage = [&](const IT* src, float* dst, int pitch, int c0, int width, int n0) {
+        if (vec_in) xca_any_stage<VWI>(src, row3, dst, pitch, c0, width, d, n0, TC, N, t, nthr);
+        else        xca_any_stage<1>(src, row3, dst, pitch, c0, width, d, n0, TC, N, t, nthr);
+    };
+
+    // ---- phase 1: the slab of G = Q^T K and the squared column norms ---------------------------------------------------------------
+    f4 gacc[XCA_ANY_UNITS];
+    int offa[XCA_ANY_UNITS], offb[XCA_ANY_UNITS];
+#pragma unroll
+    for (int s = 0; s < XCA_ANY_UNITS; ++s) {
+        const int u = wave + nw * s, ui = u / DT, uj = u - ui * DT;
+        gacc[s] = f4{0.f, 0.f, 0.f, 0.f};
+        offa[s] = ui * 16 + l15;
+        offb[s] = uj * 16 + l15;
+    }
+    float nrm0 = 0.f, nrm1 = 0.f;       // columns t and t + nthr of (k | q): dp + RB <= 2 nthr
+    const int ncol = dp + RB;
+    const float* col0 = t < dp ? s_k + t : s_q + (t - dp);
+    const int cp0 = t < dp ? PG : PQ;
+    const int t1 = t + nthr;
+    const float* col1 = t1 < dp ? s_k + t1 : s_q + (t1 - dp);
+    const int cp1 = t1 < dp ? PG : PQ;
+    for (int ch = 0; ch < nchunks; ++ch) {
+        const int n0 = ch * TC, nv = min(TC, N - n0);
+        stage(base, s_q, PQ, r0, RB, n0);
+        stage(base + C, s_k, PG, 0, dp, n0);
+        __syncthreads();
+        if (t < ncol) {
+#pragma unroll 8
+            for (int n = 0; n < nv; ++n) { const float x = col0[n * cp0]; nrm0 = __builtin_fmaf(x, x, nrm0); }
+        }
+        if (t1 < ncol) {
+#pragma unroll 8
+            for (int n = 0; n < nv; ++n) { const float x = col1[n * cp1]; nrm1 = __builtin_fmaf(x, x, nrm1); }
+        }
+        const int ksteps = (nv + 3) >> 2;                   // token quads beyond N hold only zero rows
+        for (int ks = 0; ks < ksteps; ++ks) {
+            const int row = ks * 4 + g;
+#pragma unroll
+            for (int s = 0; s < XCA_ANY_UNITS; ++s) {
+                if (wave + nw * s < nunits) {               // wave-uniform
+                    const float av = s_q[row * PQ + offa[s]];
+                    const float bv = s_k[row * PG + offb[s]];
+                    gacc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, gacc[s], 0, 0, 0);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (t < ncol) s_n[t] = fmaxf(sqrtf(nrm0), 1e-12f);      // F.normalize: x / max(||x||, 1e-12)
+    if (t1 < ncol) s_n[t1] = fmaxf(sqrtf(nrm1), 1e-12f);
+#pragma unroll
+    for (int s = 0; s < XCA_ANY_UNITS; ++s) {
+        if (wave + nw * s < nunits) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) s_g[(offa[s] - l15 + g * 4 + r) * PG + offb[s]] = gacc[s][r];
+        }
+    }
+    __syncthreads();
+    // ---- phase 2: A = softmax_rows(G / (|q_i| |k_j|) * temperature) over the columns j < d, 16 lanes per row, in place ---------------
+    {
+        const float temp = temperature[h];
+        const int tj = t & 15;
+        for (int il = t >> 4; il < rt * 16; il += nthr >> 4) {
+            float* grow = s_g + il * PG;
+            const bool live = r0 + il < d;                  // the same for the 16 lanes of a row
+            const float nqi = s_n[dp + il];
+            float m = -INFINITY;
+            for (int j = tj; j < dp; j += 16) {
+                if (live && j < d) {
+                    const float v = grow[j] / (nqi * s_n[j]) * temp;
+                    grow[j] = v;
+                    m = fmaxf(m, v);
+                }
+            }
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, WAVE));
+            float sum = 0.f;
+            for (int j = tj; j < dp; j += 16) {
+                if (live && j < d) {
+                    const float e = expf(grow[j] - m);
+                    grow[j] = e;
+                    sum += e;
+                }
+            }
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) sum += __shfl_xor(sum, o, WAVE);
+            for (int j = tj; j < dp; j += 16) grow[j] = (live && j < d) ? grow[j] / sum : 0.f;
+        }
+    }
+    __syncthreads();
+    // ---- phase 3: O[i][n] = sum_j A[i][j] v[n][j]; a lane holds 4 consecutive i of one token ------------------------------------------
+    const int ntl = TC >> 4, kq = (d + 3) >> 2;             // A is zero from column d on
+    for (int ch = 0; ch < nchunks; ++ch) {
+        const int n0 = ch * TC;
+        stage(base + 2 * C, s_k, PG, 0, dp, n0);
+        __syncthreads();
+        for (int tl = wave; tl < rt * ntl; tl += nw) {
+            const int nt = tl / rt, it = tl - nt * rt;
+            if (n0 + nt * 16 >= N) continue;                // wave-uniform: token tiles beyond N
+            const float* ap = s_g + (it * 16 + l15) * PG + g;
+            const float* bp = s_k + (nt * 16 + l15) * PG + g;
+            f4 acc = {0.f, 0.f, 0.f, 0.f};
+            for (int ks = 0; ks < kq; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[ks * 4], bp[ks * 4], acc, 0, 0, 0);
+            const int n = n0 + nt * 16 + l15, i0 = r0 + it * 16 + g * 4;
+            if (n < N && i0 < d) {
+                OT* o = out + ((long)b * N + n) * C + h * d + i0;
+                if (vec_out) {                              // d % 4 == 0: the four rows are in range together
+                    typedef OT o4 __attribute__((ext_vector_type(4)));
+                    *reinterpret_cast<o4*>(o) = o4{(OT)acc.x, (OT)acc.y, (OT)acc.z, (OT)acc.w};
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (i0 + r < d) o[r] = (OT)acc[r];
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+template <typename OT, typename IT>
+static int xca_any_launch(const char* who, const IT* qkv, const float* temperature, OT* out, int B, int N, int heads, int d, hipStream_t st) {
+    const XcaAnyGeom gm = xca_any_geom(d);
+    const long grid = (long)B * heads * gm.nrb;
+    if (grid > 0x7fffffffL) return mi355::fail(MI355_EUNSUPPORTED, "%s: B * heads * row blocks = %ld workgroups", who, grid);
+    if (gm.lds > 65536)
+        if (int rc = mi355::func_dynamic_lds(reinterpret_cast<const void*>(xca_any_kernel<OT, IT>), (int)gm.lds)) return rc;
+    const int vec_in = d % (16 / (int)sizeof(IT)) == 0, vec_out = d % (16 / (int)sizeof(OT)) == 0;
+    xca_any_kernel<OT, IT><<<(int)grid, gm.threads, gm.lds, st>>>(qkv, temperature, out, N, heads, d, gm.RB, gm.TC, vec_in, vec_out);
+    return MI355_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // LPI: workgroup = (image, 32 channels); 256 threads = 32 token lanes x 8 channel quads (16-byte LDS / HBM accesses).
 // Round 3: ONE LDS tile with a zero halo.  The first conv's results of a thread's (at most 8) tokens wait in registers until every
 // thread has read its 3x3 neighbourhoods, then overwrite the tile's interior in place -- 32 KB instead of 50 KB per workgroup at 14x14
@@ -918,15 +1142,18 @@ int mi355_xca_fwd(const float* qkv, const float* temperature, float* out, int B,
     MI355_CHECK_ARG(aligned16(qkv) && aligned16(out));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int grid = B * heads;
-    if (d != 32 && d != 48 && d != 64) return mi355::fail(MI355_EUNSUPPORTED, "mi355_xca_fwd: head dim %d (built: 32, 48, 64)", d);
+    if (d < 1 || d > XCA_ANY_MAX) return mi355::fail(MI355_EUNSUPPORTED, "mi355_xca_fwd: head dim %d (supported: 1 .. %d)", d, XCA_ANY_MAX);
+    if (d != 32 && d != 48 && d != 64) {                    // every width without a template: the run-time-width kernel
+        MI355_TRACE(st, "xca_any_kernel<d=%d> B=%d N=%d heads=%d", d, B, N, heads);
+        if (int rc = xca_any_launch<float, float>("mi355_xca_fwd", qkv, temperature, out, B, N, heads, d, st)) return rc;
+        MI355_LAUNCH_CHECK();
+        return MI355_OK;
+    }
     MI355_TRACE(st, "xca_kernel<d=%d> B=%d N=%d heads=%d", d, B, N, heads);
     switch (d) {
         case 32: xca_kernel<32><<<grid, 256, 0, st>>>(qkv, temperature, out, N, heads); break;
         case 48: xca_kernel<48><<<grid, 256, 0, st>>>(qkv, temperature, out, N, heads); break;
-        case 64:
-            
-            xca_kernel<64><<<grid, 256, 0, st>>>(qkv, temperature, out, N, heads); break;
-        default: return mi355::fail(MI355_EUNSUPPORTED, "mi355_xca_fwd: head dim %d (built: 32, 48, 64)", d);
+        default: xca_kernel<64><<<grid, 256, 0, st>>>(qkv, temperature, out, N, heads); break;
     }
     MI355_LAUNCH_CHECK();
     return MI355_OK;
@@ -941,6 +1168,19 @@ int mi355_xca16_fwd(const void* qkv, int qkv_is16, const float* temperature, voi
     MI355_CHECK_ARG(aligned16(qkv) && aligned16(out16));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int grid = B * heads;
+    if (d < 1 || d > XCA_ANY_MAX) return mi355::fail(MI355_EUNSUPPORTED, "mi355_xca16_fwd: head dim %d (supported: 1 .. %d)", d, XCA_ANY_MAX);
+    if (d != 32 && d != 48 && d != 64) {                    // every width without a template: the run-time-width kernel, same three type modes
+        MI355_TRACE(st, "xca_any_kernel<d=%d%s,out16> B=%d N=%d heads=%d", d, qkv_is16 ? ",in16" : "", B, N, heads);
+        int rc;
+        if (qkv_is16) {
+            if (precision == MI355_PREC_FP16) rc = xca_any_launch<_Float16, _Float16>("mi355_xca16_fwd", static_cast<const _Float16*>(qkv), temperature, static_cast<_Float16*>(out16), B, N, heads, d, st);
+            else                              rc = xca_any_launch<__bf16, __bf16>("mi355_xca16_fwd", static_cast<const __bf16*>(qkv), temperature, static_cast<__bf16*>(out16), B, N, heads, d, st);
+        } else if (precision == MI355_PREC_FP16) rc = xca_any_launch<_Float16, float>("mi355_xca16_fwd", static_cast<const float*>(qkv), temperature, static_cast<_Float16*>(out16), B, N, heads, d, st);
+        else                              rc = xca_any_launch<__bf16, float>("mi355_xca16_fwd", static_cast<const float*>(qkv), temperature, static_cast<__bf16*>(out16), B, N, heads, d, st);
+        if (rc) return rc;
+        MI355_LAUNCH_CHECK();
+        return MI355_OK;
+    }
     if (qkv_is16 && N <= 224 && mi355::opt(mi355::O_XCA_TR) && (d == 32 || d == 48 || d == 64)) {
         // 16-bit q / k / v, at most 224 tokens: covariance on the 16-bit matrix pipe from ONE transposed LDS image (xca_tr_kernel)
         MI355_TRACE(st, "xca_tr_kernel<d=%d> B=%d N=%d heads=%d", d, B, N, heads);
@@ -966,8 +1206,7 @@ int mi355_xca16_fwd(const void* qkv, int qkv_is16, const float* temperature, voi
     switch (d) {
         case 32: XCA16(32); break;
         case 48: XCA16(48); break;
-        case 64: XCA16(64); break;
-        default: return mi355::fail(MI355_EUNSUPPORTED, "mi355_xca16_fwd: head dim %d (built: 32, 48, 64)", d);
+        default: XCA16(64); break;
     }
 #undef XCA16
     MI355_LAUNCH_CHECK();

@@ -1546,7 +1546,8 @@ def cswin_lepe_attention(qkv, getv_w, getv_b, out, reso, c0, Cb, heads, Hsp, Wsp
 
 
 def xca_core(qkv, temperature, num_heads, precision=None, out16=False):
-    """`out16`: the context in the 16-bit operand format of `precision` (what linear16 reads) instead of fp32; qkv may then be in that
+    """XCA core on qkv (B, N, 3 * C) with C = num_heads * d, any head width 1 <= d <= 256 (a wider head raises Mi355Error).
+    `out16`: the context in the 16-bit operand format of `precision` (what linear16 reads) instead of fp32; qkv may then be in that
     format as well (the 16-bit output of the qkv GEMM)."""
     temperature = require_device_f32(temperature, "temperature").reshape(-1)
     B, N, C3 = qkv.shape
@@ -1919,7 +1920,8 @@ def dwconv_patch_tokens(x, conv_w, conv_b, bn, H, W, sr):
 
 
 def class_attention(q, k, v, num_heads, scale, N, ldq, ldkv):
-    """One query per (image, head) over N keys; q/k/v are (possibly strided) views into fp32 device tensors."""
+    """One query per (image, head) over N <= 4096 keys; q/k/v are (possibly strided) views into fp32 device tensors.  Any head width
+    from 1 to 256, any ldq / ldkv."""
     B = q.shape[0]
     C = q.shape[-1]
     out = torch.empty(B, C, dtype=torch.float32, device=q.device)

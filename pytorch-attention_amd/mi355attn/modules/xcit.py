@@ -10,6 +10,11 @@
   XCiT, xcit_nano_12_p16     xcit.py:296-414
 
 BatchNorm runs with its running statistics (inference engine); compare against the reference in .eval().
+
+Envelope of XCA, XCABlock, ClassAttention(Block) and XCiT: every `num_heads` that divides `dim`, head width dim // num_heads up to 256,
+dim % 4 == 0 (the condition of functional.linear).  Head widths 32 / 48 / 64 (class attention: 16 / 32 / 48 / 64) run template kernels,
+every other width the run-time-width kernels of the same entries (xca_any_kernel, class_attn_any_kernel): same arithmetic, the softmax
+over a head's channels masked to the d live columns.  A wider head raises Mi355Error in forward().
 """
 import math
 
