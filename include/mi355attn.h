@@ -573,7 +573,8 @@ int mi355_topk_mask_fwd(float* logits, long rows, int N, int k, mi355_stream_t s
 
 /* nn.Linear (+ optional GELU, LayerScale, residual):  Y = resid + gamma * act(X W^T + bias)
  *   X (M,K) row-major with row stride ldx, W (N,K) row-major (nn.Linear layout), Y (M,N) row stride ldy.
- *   bias (N) / gamma (N) / resid (M,N; row stride ldy) may be NULL.  Covers ViT.py:58-65,81,87;
+ *   bias (N) / gamma (N) / resid (M,N; row stride ldy) may be NULL.  K % 4 == 0, ldx >= K with ldx % 4 == 0, X and W 16-byte
+ *   aligned (else MI355_EUNSUPPORTED); any ldy >= N (ldy % 4 != 0 or a Y off 16 bytes: element-wise stores).  Covers ViT.py:58-65,81,87;
  *   cswin.py:185,192,40-48; xcit.py:32-38,248,263; mlp_mixer.py:26-33. */
 int mi355_linear_fwd(const float* X, const float* W, const float* bias, const float* gamma, const float* resid,
                      float* Y, int M, int N, int K, int ldx, int ldy, int act, int precision,
@@ -597,7 +598,12 @@ int mi355_cast16_fwd(const float* src, void* dst16, size_t n, int precision, mi3
 int mi355_layernorm16_fwd(const float* x, const float* weight, const float* bias, void* y16, int rows, int cols, float eps,
                           int precision, mi355_stream_t stream);
 /* Y = resid + gamma * act(X16 W16^T + bias); Y is fp32 (out16 = 0) or 16-bit (out16 = 1); bias/gamma/resid fp32 or NULL.
- * Needs K % 64 == 0, N % 4 == 0, ldx % 8 == 0 (other shapes: cast back and use mi355_linear_fwd). */
+ * Needs K % 64 == 0, N % 4 == 0, ldx % 8 == 0, ldy % 4 == 0 (other shapes: cast back and use mi355_linear_fwd).
+ * Row strides: X16 rows are ldx >= K elements apart, Y and resid rows ldy >= N elements of their own type apart (resid shares ldy with
+ * Y also where Y is 16-bit and resid fp32); columns [K, ldx) of X16 are never read, columns [N, ldy) of Y never written -- a column
+ * block of a wider matrix is a valid operand or result.  A 16-bit Y with ldy % 8 == 4 (rows 8 bytes off a 16-byte boundary) is computed
+ * by the plain tile kernels, which store 8 bytes per lane; the other kernels of the engine (16-byte stores) are chosen only for
+ * ldy % 8 == 0, and option "gemm_variant" >= 15, which forces one of them, then answers MI355_EUNSUPPORTED.  Same bits either way. */
 int mi355_linear16_fwd(const void* X16, const void* W16, const float* bias, const float* gamma, const float* resid, void* Y,
                        int M, int N, int K, int ldx, int ldy, int act, int out16, int precision, mi355_stream_t stream);
 /* The same with a scratch buffer of mi355_linear16_workspace_bytes(M, N, K) bytes (0 = this shape needs none): the persistent
@@ -616,13 +622,17 @@ int mi355_linear16_x32_fwd(const float* X32, const void* W16, const float* bias,
 /* Y = resid + X16 W16^T + bias (fp32) AND the LayerNorm statistics of every row of Y: row_stats[2 m] = mean, row_stats[2 m + 1] =
  * 1 / sqrt(var + eps) (two-pass, biased variance -- what mi355_ln_lpi_fwd computes with a pass of its own).  Built where a workgroup owns
  * whole output rows: N = K = 256 / 384, M >= 32 (the weight-stationary kernel, option "gemm_wreg"); other shapes MI355_EUNSUPPORTED.
- * XCABlock (xcit.py:290-293): the proj GEMM writes x1 = x + gamma1 * XCA(..) and the statistics norm3 needs in front of LPI. */
+ * XCABlock (xcit.py:290-293): the proj GEMM writes x1 = x + gamma1 * XCA(..) and the statistics norm3 needs in front of LPI.
+ * Row strides: ldx >= K with ldx % 8 == 0 (X16), ldy >= N with ldy % 4 == 0 (Y and resid, both fp32); row_stats is dense (M, 2), 8-byte
+ * aligned; the other buffers 16-byte aligned.  A stride off these rules is MI355_EUNSUPPORTED like a shape outside the envelope. */
 int mi355_linear16_stats_fwd(const void* X16, const void* W16, const float* bias, const float* resid, float* Y, int M, int N, int K, int ldx,
                              int ldy, int precision, float* row_stats, float eps, mi355_stream_t stream);
 /* Y = resid + X16 W16^T + bias (fp32) AND the next LayerNorm of every row of Y in the 16-bit operand format:
  * U16[m][n] = T((Y[m][n] - mean_m) / sqrt(var_m + eps) * ln_w[n] + ln_b[n]) (row stride ldu elements) -- what mi355_layernorm16_fwd would
  * compute from Y with a launch and a pass of its own.  Built at N = K = 256, M >= 32 (other shapes MI355_EUNSUPPORTED).  CSWinBlock at stage 3 (cswin.py:192-194):
- * x = x + proj(att) and norm2(x) in one launch.  The fp16 conversions report into the range word (code 2). */
+ * x = x + proj(att) and norm2(x) in one launch.  The fp16 conversions report into the range word (code 2).
+ * Row strides: ldx >= K with ldx % 8 == 0 (X16), ldy >= N with ldy % 4 == 0 (Y and resid, fp32), ldu >= N with ldu % 4 == 0 (U16, 16-bit
+ * elements; independent of ldy); 16-byte aligned buffers.  A stride off these rules is MI355_EUNSUPPORTED. */
 int mi355_linear16_ln16_fwd(const void* X16, const void* W16, const float* bias, const float* resid, float* Y, const float* ln_w,
                             const float* ln_b, float eps, void* U16, int M, int N, int K, int ldx, int ldy, int ldu, int precision,
                             mi355_stream_t stream);
@@ -634,7 +644,8 @@ int mi355_linear16_ws_fwd(const void* X16, const void* W16, const float* bias, c
  * N <= n < NP (NP % 32 == 0; pick NP % 64 == 0 so that it is a valid K for mi355_linear16_fwd against a weight zero-padded to
  * (T, NP)).  mi355_linear16_tr_fwd is mi355_linear16_fwd with the result written transposed per image and no gamma/act:
  *   Y[(img * N + n) * rows_per_image + c] = resid[same] + (X16[img * rows_per_image + c, :] . W16[n, :]) + bias[n]
- * for M = B * rows_per_image rows of X16; Y / resid fp32 (B, N, rows_per_image).  Needs K % 64 == 0, rows_per_image % 4 == 0. */
+ * for M = B * rows_per_image rows of X16 (row stride ldx >= K, ldx % 8 == 0); Y / resid fp32 (B, N, rows_per_image), dense.  Needs
+ * K % 64 == 0, rows_per_image % 4 == 0. */
 int mi355_layernorm16_t_fwd(const float* x, const float* weight, const float* bias, void* ut16, int B, int N, int C, int NP, float eps,
                             int precision, mi355_stream_t stream);
 int mi355_linear16_tr_fwd(const void* X16, const void* W16, const float* bias, const float* resid, float* Y, int M, int N, int K,
@@ -708,7 +719,8 @@ int mi355_linear16_res_fwd(const void* X16, const void* W16, const float* bias, 
 /* LayerNorm + Linear in one pass for narrow rows (K = 64 or 128 = the normalised width; CSWin stage 1 / 2 and XCiT-nano qkv):
  *   Y = act( ((x - mean) / sqrt(var + eps)) . W16^T + bias ),  x (M,K) fp32 with row stride ldx floats, Y fp32 or 16-bit (out16).
  * The LayerNorm affine part must be folded into W16 / bias by the caller (W' = W diag(ln_weight), b' = b + W ln_bias).  The rows are
- * normalised on their way into LDS, so the 16-bit LayerNorm output never exists in HBM.  N % 8 == 0. */
+ * normalised on their way into LDS, so the 16-bit LayerNorm output never exists in HBM.  N % 8 == 0, ldx >= K with ldx % 4 == 0
+ * (floats), ldy >= N with ldy % 8 == 0 (elements of Y's type, fp32 Y included), 16-byte aligned buffers; else MI355_EUNSUPPORTED. */
 int mi355_ln_linear16_fwd(const float* X, const void* W16, const float* bias, void* Y, int M, int N, int K, int ldx, int ldy, float eps,
                           int act, int out16, int precision, mi355_stream_t stream);
 /* mi355_sdpa_fwd / mi355_cswin_lepe_attn_fwd with 16-bit qkv and out buffers (same layouts).  The LePE entry takes stripe windows
@@ -730,7 +742,7 @@ int mi355_cswin_lepe_attn16_fwd(const void* qkv16, const float* getv_w, const fl
  * lo = bf16(W - hi)), w_v16 (C, K) IEEE half = rows [2C, 3C); bias (3C) fp32 or NULL, added before the result is split.  Output qkv5
  * (M, 5C) 16-bit, FIVE C-wide planes per token row:
  *     [ q_hi | q_lo | k_hi | k_lo | v ]      q_hi, q_lo, k_hi, k_lo bfloat16 (q = q_hi + q_lo, k = k_hi + k_lo), v IEEE half.
- * Envelope: C % 64 == 0, K % 64 == 0 (else MI355_EUNSUPPORTED), any M.  The fp16 conversions of the v columns (x operands: range code
+ * Envelope: C % 64 == 0, K % 64 == 0 (else MI355_EUNSUPPORTED), any M; ldx >= K with ldx % 4 == 0, qkv5 dense (row stride 5C).  The fp16 conversions of the v columns (x operands: range code
  * 1, results: code 3) report into the range word like mi355_cast16_fwd / mi355_linear16_fwd; bf16 is never flagged.  No workspace.
  *
  * mi355_sdpa16_split_fwd: softmax(q k^T scale) v per head on those rows, qkv5 (B, N, 5C) with C = heads * d -> out16 (B, N, C) IEEE half,
@@ -881,6 +893,9 @@ int mi355_patch_embed_ws_fwd(const float* img, const float* Wp, const float* bp,
  *                              bias = b + W beta: = act(LayerNorm(Y) W^T + b) of the reference.  Persistent 256 x 256 kernel.
  *   mi355_ln_center16_fwd      first LayerNorm of a chain (no producer): a16 = T((x - mu) r), rowtau = {1, 0}, cvec = mu for every row;
  *                              cols % 4 == 0, cols <= 2048.
+ * Row strides: mi355_linear16_emit_fwd reads X16 with row stride ldx >= K, ldx % 8 == 0; Y, resid and a16_out are dense (row stride N).
+ * mi355_linear16_lnfold_fwd reads A16 with row stride lda >= K and writes Y16 with row stride ldy >= N, lda % 8 == 0 and ldy % 8 == 0;
+ * rowtau (M, 2) and colsum (N) are dense.  16-byte aligned buffers (stats, rowtau: 8-byte); anything else is MI355_EUNSUPPORTED.
  * precision 1 (fp16) or 2 (bf16).  Results: within operand rounding of LayerNorm -> 16-bit -> GEMM (the rounding point moves from
  * LayerNorm(x) to x - c; tests/test_ln_fold_gpu.py bounds the difference). */
 size_t mi355_ln_fold_stats_bytes(int rows, int cols);

@@ -594,8 +594,8 @@ int mi355_linear16_ws_fwd(const void* X16, const void* W16, const float* bias, c
     MI355_CHECK_ARG(precision == MI355_PREC_FP16 || precision == MI355_PREC_BF16);
     if ((K % BK) || (N & 3) || (ldx & 7) || (ldy & 3) || !aligned16(X16) || !aligned16(W16) || !aligned16(Y) ||
         (bias && !aligned16(bias)) || (gamma && !aligned16(gamma)) || (resid && !aligned16(resid)))
-        return mi355::fail(MI355_EUNSUPPORTED, "mi355_linear16_fwd: needs K %% 64 == 0, N %% 4 == 0, 16-byte aligned rows (K=%d N=%d ldx=%d)",
-                           K, N, ldx);
+        return mi355::fail(MI355_EUNSUPPORTED, "mi355_linear16_fwd / mi355_linear16_ws_fwd: needs K %% 64 == 0, N %% 4 == 0, ldx %% 8 == 0, "
+                                               "ldy %% 4 == 0, 16-byte aligned buffers (K=%d N=%d ldx=%d ldy=%d)", K, N, ldx, ldy);
     G16Args g{};
     g.A = X16; g.B = W16; g.C = Y; g.bias = bias; g.gamma = gamma; g.resid = resid;
     g.M = M; g.N = N; g.K = K; g.lda = ldx; g.ldb = K; g.ldc = ldy; g.act = act;
@@ -649,6 +649,11 @@ int mi355::linear16_dispatch(const G16Args& g, int out16, int precision, void* w
     const int ncu = mi355::resident_slots(1);
     const bool gelu = g.act == MI355_ACT_GELU;
     long variant = opt.variant;
+    // A 16-bit Y whose row stride is a multiple of 4 but not of 8 elements: rows start 8 bytes off a 16-byte boundary.  Only the plain
+    // tile kernels (8-byte stores per lane) are built for that; every other kernel of the engine writes 16-byte units to C + m * ldc + n.
+    const bool y16_rows_8b = out16 && (g.ldc & 7);
+    if (variant >= 15 && y16_rows_8b)
+        return mi355::fail(MI355_EUNSUPPORTED, "mi355_linear16_fwd: the forced kernel needs ldy %% 8 == 0 for a 16-bit Y (ldy=%d)", g.ldc);
     if (variant >= 15) {                   // one persistent kernel forced; a shape it does not take is an error
         static const char* const what[] = {"persistent kernel",                   // 15: 256 x 256 (gemm16_p8.hip)
                                            "the two-accumulator kernel",          // 16: two-accumulator 128 x 256 (gemm16_pa.hip)
@@ -661,16 +666,17 @@ int mi355::linear16_dispatch(const G16Args& g, int out16, int precision, void* w
     if (variant == 0) {
         int rc;
         // ViT qkv / fc1, forced (gemm_wst = 1 .. 4): a 192-column slab of W stays in the registers of a workgroup, X streams through LDS once per slab (gemm16_wst.hip)
-        if ((opt.wst == 2 || opt.wst == 4 || ((opt.wst == 1 || opt.wst == 3) && g.act == MI355_ACT_NONE)) &&
+        if (!y16_rows_8b && (opt.wst == 2 || opt.wst == 4 || ((opt.wst == 1 || opt.wst == 3) && g.act == MI355_ACT_NONE)) &&
             (rc = checked(mi355::gemm16_wst(g, out16, precision, st))) != MI355_EUNSUPPORTED)
             return rc;
         // ViT qkv / fc1 / the k, v product of the pooled-token tail, by default (gemm_wst = 5: GELU products, 6: all): the software-pipelined one-wave-per-SIMD form of the same
         // kernel (bit-identical to the tile kernels; it checks K = 768, N % 256, M % 32 itself).  The row floor is policy and lives here: the
         // weight prologue and the ramp of a stream make it lose on few rows (profiles/gemm_wst_pipe.md).
-        if (out16 && K == 768 && M >= WST_AUTO_MIN_ROWS && (opt.wst == 6 || (opt.wst == 5 && gelu)) &&
+        if (out16 && !y16_rows_8b && K == 768 && M >= WST_AUTO_MIN_ROWS && (opt.wst == 6 || (opt.wst == 5 && gelu)) &&
             (rc = checked(mi355::gemm16_wst(g, out16, precision, st, true))) != MI355_EUNSUPPORTED)
             return rc;
-        if ((K == 64 || K == 128) && M >= 2048 && (!out16 || (N & 7) == 0)) {       // short-K, HBM-bound: weight-stationary streaming kernel
+        // short-K, HBM-bound: weight-stationary streaming kernel (its 16-bit epilogue stores 16-byte units: N % 8 == 0 and ldy % 8 == 0)
+        if ((K == 64 || K == 128) && M >= 2048 && (!out16 || ((N & 7) == 0 && !y16_rows_8b))) {
             MI355_TRACE(st, "gemm16_ws_kernel<%s> M=%d N=%d K=%d", out16 ? "out16" : "out32", M, N, K);
             launch_ws<false>(g, out16, precision, K == 64 ? 2 : 1, ncu, st);
             MI355_LAUNCH_CHECK();
@@ -679,7 +685,7 @@ int mi355::linear16_dispatch(const G16Args& g, int out16, int precision, void* w
         // short reductions, 16-bit output (XCiT / CSWin stage 3-4 / Mixer qkv and fc1): a column slab of W stationary in registers, X through LDS
         // once per slab, 32-row tiles (gemm16_wslab.hip; bit-identical to the tile kernels).  Default policy: where it measured faster -- GELU
         // epilogues (5-12 %) and row counts off the 256-row grid (which otherwise fall to gemm16_p8: 88-96 -> 65-69 us); plain epilogues are a tie.
-        if ((opt.wslab == 2 || (opt.wslab == 1 && (gelu || (M & 255)))) &&
+        if (!y16_rows_8b && (opt.wslab == 2 || (opt.wslab == 1 && (gelu || (M & 255)))) &&
             (rc = checked(mi355::gemm16_wslab(g, out16, precision, st))) != MI355_EUNSUPPORTED)
             return rc;
         // The two-accumulator persistent kernel (gemm16_pa.hip) runs 128 x 256 tiles, or 256 x 128 (operand roles swapped) where N is a
@@ -694,7 +700,7 @@ int mi355::linear16_dispatch(const G16Args& g, int out16, int precision, void* w
         // loop stages 1.5 x fewer bytes per flop, but its GELU epilogue is fully exposed (55 us of ViT-Base's fc1) where the pieces of
         // this kernel hide most of it (29 us): option "gemm_pa16" = 1 (default) sends GELU epilogues here (fc1 313 -> 291 us in a
         // same-process A/B), 2 every 16-bit output (qkv: 221 -> 207 on one kind of box, 197 -> 208 on the other: not the default), 0 neither.
-        if (out16 && opt.pa && pa_fills && (K <= 512 || (opt.pa16 >= 1 && gelu) || opt.pa16 >= 2) &&
+        if (out16 && !y16_rows_8b && opt.pa && pa_fills && (K <= 512 || (opt.pa16 >= 1 && gelu) || opt.pa16 >= 2) &&
             (rc = checked(mi355::gemm16_pa(g, out16, precision, st))) != MI355_EUNSUPPORTED)
             return rc;
         // square short products with an fp32 (+ residual) output (XCiT proj 384 x 384, CSWin stage-3 proj 256 x 256): bound by the residual /
@@ -742,7 +748,7 @@ int mi355::linear16_dispatch(const G16Args& g, int out16, int precision, void* w
         // and K >= 256: it is >= the best 3-workgroups-per-CU variant on all 17 shapes of profiles/r02_gemm_p8.md except CSWin s3 fc1
         // (inside the run-to-run band), shapes just above a round boundary included (the last partial round costs a whole tile time
         // either way; long reductions cut it along K).
-        if ((long)cdiv(M, 256) * cdiv(N, 256) >= ncu && K >= 256) {
+        if (!y16_rows_8b && (long)cdiv(M, 256) * cdiv(N, 256) >= ncu && K >= 256) {
             // 16-bit outputs of a mid-length reduction (ViT qkv: K = 768): one wave per SIMD with 128 x 128 outputs each needs a third fewer LDS
             // bytes per flop and, with its two-slab pipelined epilogue, 5.8 k instead of ~11 k exposed cycles per tile (round 5, same process:
             // qkv 0.193-0.195 -> 0.179-0.182 ms).  Long reductions keep the split last round of the eight-wave kernel.

@@ -9,6 +9,9 @@ buffer a call sees.  Every byte of it belongs to exactly one class:
   input      a registered input or parameter; the arena keeps a copy and `verify()` compares bit for bit
   output     handed out by `torch_proxy()` in place of torch.empty / empty_like / zeros / zeros_like
   workspace  handed out by `workspace()`: exactly the declared size rounded up to 16 bytes, pre-filled (0xFF by default)
+An input or output may also be ROW-STRIDED (`place_rows` / `place_empty_rows`): rows of `width` elements `ld` elements apart in a region of
+exactly (rows - 1) * ld + width elements.  The padding behind each row but the last stays 0xFF and is checked: an input's with the rest
+of its copy, an output's against 0xFF.
 
 Every region starts at an address that is 16 mod 256: aligned to 16 bytes, the alignment the header asks for, and to nothing more.
 The margins are wider than a full 256-row tile of any tensor the suite uses, so an over-read or an overrun stays inside mapped
@@ -38,10 +41,11 @@ class ArenaViolation(AssertionError):
 
 
 class Region:
-    __slots__ = ("name", "kind", "off", "nbytes", "copy")
+    __slots__ = ("name", "kind", "off", "nbytes", "copy", "rows")
 
-    def __init__(self, name, kind, off, nbytes, copy=None):
-        self.name, self.kind, self.off, self.nbytes, self.copy = name, kind, off, nbytes, copy
+    def __init__(self, name, kind, off, nbytes, copy=None, rows=None):
+        """`rows`: (row bytes, stride bytes) of a row-strided region (place_rows / place_empty_rows), else None."""
+        self.name, self.kind, self.off, self.nbytes, self.copy, self.rows = name, kind, off, nbytes, copy, rows
 
     @property
     def end(self):
@@ -103,6 +107,34 @@ class Arena:
             self.buf[r.off:r.end].zero_()
         return v
 
+    def _carve_rows(self, rows, width, ld, dtype, kind, name):
+        rows, width, ld = int(rows), int(width), int(ld)
+        if rows < 1 or width < 1 or ld < width:
+            raise ValueError(f"row-strided region needs rows >= 1 and ld >= width >= 1 (rows={rows} width={width} ld={ld})")
+        esize = torch.empty((), dtype=dtype).element_size()
+        r = self._carve(((rows - 1) * ld + width) * esize, kind, self._name(name, kind))
+        r.rows = (rows, width, ld, esize)
+        flat = self.buf[r.off:r.end].view(dtype)
+        return r, flat.as_strided((rows, width), (ld, 1))
+
+    def place_rows(self, t2d, ld, name=None):
+        """Copy a 2-D tensor into an input region of exactly (rows - 1) * ld + width elements and return the as_strided view (row stride
+        `ld` elements).  The ld - width elements behind every row but the last stay POISON -- a NaN in fp32, fp16 and bf16, so an operand
+        read past the row's width poisons the sum it enters -- and belong to the region: verify() compares them byte for byte, too.
+        Nothing behind the last row's width belongs to the caller: the guard starts there."""
+        src = t2d.detach()
+        if src.dim() != 2:
+            raise ValueError("place_rows takes a 2-D tensor")
+        r, v = self._carve_rows(src.shape[0], src.shape[1], ld, src.dtype, "input", name)
+        v.copy_(src)
+        r.copy = self.buf[r.off:r.end].clone()
+        return v
+
+    def place_empty_rows(self, rows, width, ld, dtype, name=None):
+        """An output region of the same minimal extent, left poisoned; returns the strided view.  verify() additionally requires every
+        padding byte (the ld - width elements behind each row but the last) to still be POISON."""
+        return self._carve_rows(rows, width, ld, dtype, "output", name)[1]
+
     def workspace(self, nbytes, name=None):
         """A scratch region of exactly `nbytes` rounded up to 16, filled with `ws_fill`, a guard right behind it."""
         r = self._carve(_up(nbytes, 16), "workspace", self._name(name, "workspace"))
@@ -126,7 +158,12 @@ class Arena:
             return f"arena offset {off} (nothing placed)"
         for r in self.regions:
             if r.off <= off < r.end:
-                return f"byte {off - r.off:,} of {r.kind} `{r.name}`".replace(",", " ")
+                text = f"byte {off - r.off:,} of {r.kind} `{r.name}`".replace(",", " ")
+                if r.rows is not None:                                 # row-strided: name the row and the column (in elements) as well
+                    _, width, ld, esize = r.rows
+                    row, col = divmod((off - r.off) // esize, ld)
+                    text += f" (row {row}, column {col}: " + ("live)" if col < width else f"padding behind width {width})")
+                return text
         best = min(self.regions, key=lambda r: min(abs(off - r.off), abs(off - (r.end - 1))))
         if off >= best.end:
             return f"{off - best.end + 1:,} bytes past the end of {best.kind} `{best.name}`".replace(",", " ")
@@ -143,7 +180,8 @@ class Arena:
 
     def violations(self):
         """Every broken promise, as text: guard bytes that are no longer 0xFF (the guard behind a workspace included) and inputs that
-        differ from their copy."""
+        differ from their copy (the padding of a row-strided input included), padding bytes of a row-strided output that are no
+        longer 0xFF."""
         out = []
         gaps = list(self._gaps())
         dirty = torch.stack([(self.buf[a:b] != POISON).any() for a, b in gaps]).cpu().tolist()
@@ -159,6 +197,15 @@ class Arena:
                 if not ok:
                     idx = torch.nonzero(self.buf[r.off:r.end] != r.copy).reshape(-1)
                     out.append(f"input modified: {int(idx.numel())} byte(s), first {self._where(r.off + int(idx[0]))}")
+        for r in self.regions:
+            if r.kind != "output" or r.rows is None or r.rows[0] < 2 or r.rows[2] == r.rows[1]:
+                continue
+            rows, width, ld, esize = r.rows
+            pad = self.buf[r.off:r.off + (rows - 1) * ld * esize].view(rows - 1, ld * esize)[:, width * esize:]
+            if bool((pad != POISON).any()):
+                idx = torch.nonzero(pad != POISON)
+                first = r.off + int(idx[0, 0]) * ld * esize + width * esize + int(idx[0, 1])
+                out.append(f"output padding written: {int(idx.shape[0])} byte(s), first {self._where(first)}")
         return out
 
     def verify(self):

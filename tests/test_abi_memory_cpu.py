@@ -104,6 +104,79 @@ def test_recorder_counts_calls_that_returned_ok_not_lookups():
     assert rec.reached == {"mi355_a_fwd"} and rec.calls == [("mi355_a_fwd", 0), ("mi355_b_fwd", -2)]
 
 
+# ---- row-strided regions ------------------------------------------------------------------------------------------------------
+def _strided():
+    a = Arena(SIZE, "cpu")
+    src = torch.arange(6 * 10, dtype=torch.float16).reshape(6, 10)
+    x = a.place_rows(src, 24, "X")
+    y = a.place_empty_rows(5, 7, 12, torch.float32, "Y")
+    return a, src, x, y
+
+
+def test_row_strided_regions_have_the_minimal_extent_and_poisoned_padding():
+    a, src, x, y = _strided()
+    rx, ry = a.regions
+    assert (rx.kind, rx.nbytes) == ("input", (5 * 24 + 10) * 2) and (ry.kind, ry.nbytes) == ("output", (4 * 12 + 7) * 4)
+    assert x.shape == (6, 10) and x.stride() == (24, 1) and y.shape == (5, 7) and y.stride() == (12, 1)
+    assert x.data_ptr() == a.base + rx.off and y.data_ptr() == a.base + ry.off
+    assert x.data_ptr() % ALIGN == PHASE and y.data_ptr() % ALIGN == PHASE
+    assert torch.equal(x, src) and torch.isnan(y).all()
+    # the padding behind every row but the last is POISON (a NaN in the region's type); behind the last row the guard begins
+    flat = a.buf[rx.off:rx.end].view(torch.float16)
+    assert flat.numel() == 5 * 24 + 10
+    pad = flat[:5 * 24].view(5, 24)[:, 10:]
+    assert torch.isnan(pad).all() and bool((pad.contiguous().view(torch.uint8) == POISON).all())
+    assert bool((a.buf[ry.off:ry.end] == POISON).all()) and bool((a.buf[ry.end:ry.end + 256] == POISON).all())
+    a.verify()
+    y.fill_(2.0)                                                         # the live columns are the kernel's to write
+    a.verify()
+    assert bool((a.buf[ry.off:ry.off + 4 * 48].view(4, 48)[:, 28:] == POISON).all())
+    with pytest.raises(ValueError):
+        a.place_rows(src, 9)                                             # ld < width
+    with pytest.raises(ValueError):
+        a.place_empty_rows(3, 8, 7, torch.float32)
+    one = a.place_empty_rows(1, 5, 100, torch.bfloat16, "one_row")      # one row: no padding at all
+    assert a.regions[-1].nbytes == 10 and one.shape == (1, 5)
+    a.verify()
+
+
+def test_a_write_into_output_padding_is_reported_with_its_row_and_column():
+    a, src, x, y = _strided()
+    y.fill_(1.0)
+    ry = a.regions[1]
+    a.buf[ry.off + (2 * 12 + 9) * 4 + 1] = 0                            # row 2, column 9 (width 7), second byte of the element
+    with pytest.raises(ArenaViolation) as e:
+        a.verify()
+    text = str(e.value)
+    assert "output padding written: 1 byte(s)" in text and "output `Y`" in text and "row 2, column 9" in text and "padding behind width 7" in text
+    assert len(a.violations()) == 1
+    a.buf[ry.off + (0 * 12 + 7) * 4] = 3                                 # an earlier one: the FIRST is named
+    assert "2 byte(s)" in a.violations()[0] and "row 0, column 7" in a.violations()[0]
+
+
+def test_a_write_behind_the_last_row_of_a_strided_output_hits_the_guard():
+    a, src, x, y = _strided()
+    ry = a.regions[1]
+    a.buf[ry.end] = 0                                                    # column `width` of the last row: not the caller's
+    with pytest.raises(ArenaViolation, match="guard written: 1 byte.*1 bytes past the end of output `Y`"):
+        a.verify()
+
+
+def test_a_change_of_input_padding_or_of_a_live_input_element_is_reported():
+    a, src, x, y = _strided()
+    rx = a.regions[0]
+    a.buf[rx.off + (3 * 24 + 17) * 2] = 0                                # row 3, column 17: padding of X
+    with pytest.raises(ArenaViolation) as e:
+        a.verify()
+    assert "input modified: 1 byte(s)" in str(e.value) and "row 3, column 17: padding behind width 10" in str(e.value)
+    a.buf[rx.off + (3 * 24 + 17) * 2] = POISON
+    a.verify()
+    x[4, 2] = 5.0
+    with pytest.raises(ArenaViolation) as e:
+        a.verify()
+    assert "input modified" in str(e.value) and "row 4, column 2: live" in str(e.value)
+
+
 # ---- coverage of the header and of the option table ---------------------------------------------------------------------------
 def _device_entries():
     """Every header symbol that takes a device buffer: the forwards, the two stream helpers and the all-gather."""
