@@ -767,6 +767,19 @@ int mi355_cswin_lepe_attn16_pair_fwd(const void* qkv16, const float* getv_w0, co
 int mi355_proj_mlp_fused_fwd(const float* x, const void* ctx16, const void* wp16, const float* bp, const void* w1_16, const float* b1,
                              const void* w2_16, const float* b2, const float* gamma, float* y, long M, int C, int hidden, int layernorm,
                              float eps, int precision, mi355_stream_t stream);
+/* mi355_proj_mlp_fused_fwd for a block on fp16 / bf16 activations: x16 and y16 (M, C) are 16-bit in the operand type of `precision`
+ * (1 fp16, 2 bf16); every other argument, the envelope (C = 64 / hidden 256, C = 128 / hidden 512; "mlp_tt4" at C = 64), the grids and
+ * the LDS are that entry's.  x16 is read once, 16 bytes per lane and k-step, widened in registers (exact) and enters the arithmetic
+ * unrounded; the residual stream x1 stays fp32 in registers and y16 = x1 + gamma * (...) is rounded ONCE, to nearest even, 16 bytes per
+ * store: y16 holds the bits of mi355_proj_mlp_fused_fwd's y, computed from x16 widened to fp32, rounded to the type.  An fp16 y of
+ * magnitude >= 65520 is reported to the range word with code 3, as mi355_linear16_res_fwd reports its 16-bit stores -- whether or not
+ * bit 1 of `layernorm` is set (that bit only silences code 4); bf16 is never reported.  Checked before any launch: NULL pointers,
+ * M <= 0, a precision other than 1 / 2 and a flag word outside 0..3 are MI355_EINVAL; a shape outside the envelope or a buffer that is
+ * not 16-byte aligned (x16, ctx16, y16, the weights, bp) is MI355_EUNSUPPORTED.  No workspace, no scratch; y16 must not overlap x16
+ * or ctx16. */
+int mi355_proj_mlp_fused_x16_fwd(const void* x16, const void* ctx16, const void* wp16, const float* bp, const void* w1_16, const float* b1,
+                                 const void* w2_16, const float* b2, const float* gamma, void* y16, long M, int C, int hidden,
+                                 int layernorm, float eps, int precision, mi355_stream_t stream);
 
 /* First half of a CSWinBlock for the narrow stages in one kernel (cswin.py:180-190, LePEAttention.forward :101-127):
  * ctx16 = concat over branches / heads of  softmax((q * scale) k^T) v + LePE(v)  with  [q | k | v] = LayerNorm(x) Wqkv^T + bqkv
@@ -778,6 +791,15 @@ int mi355_proj_mlp_fused_fwd(const float* x, const void* ctx16, const void* wp16
 int mi355_cswin_stripe_attn_fwd(const float* x, const void* wqkv16, const float* bqkv, const float* getv_w0, const float* getv_b0,
                                 const float* getv_w1, const float* getv_b1, void* ctx16, int B, int reso, int C, int heads_per_branch,
                                 int split, float scale, float eps, int precision, mi355_stream_t stream);
+/* mi355_cswin_stripe_attn_fwd for a block on fp16 / bf16 activations: x16 (B, L, C) is 16-bit in the operand type of `precision`
+ * (1 fp16, 2 bf16); every other argument and the envelope (C = 64 / 128, head width 32, reso * split <= 64 tokens per stripe) are that
+ * entry's.  A thread reads its 16 channels of a token as two 16-byte loads and widens them in registers (exact); LayerNorm, projection,
+ * attention and LePE are the same code, so ctx16 holds the bits mi355_cswin_stripe_attn_fwd computes from x16 widened to fp32.
+ * Checked before any launch: NULL pointers, a precision other than 1 / 2 and non-positive sizes are MI355_EINVAL; a shape outside the
+ * envelope or a buffer that is not 16-byte aligned (x16, wqkv16, bqkv, ctx16) is MI355_EUNSUPPORTED.  No workspace, no scratch. */
+int mi355_cswin_stripe_attn_x16_fwd(const void* x16, const void* wqkv16, const float* bqkv, const float* getv_w0, const float* getv_b0,
+                                    const float* getv_w1, const float* getv_b1, void* ctx16, int B, int reso, int C, int heads_per_branch,
+                                    int split, float scale, float eps, int precision, mi355_stream_t stream);
 
 /* Fused LayerNorm + MLP + residual for narrow token streams (C = 64 / hidden 256: CSWin stage 1; C = 128 / hidden 512: CSWin stage 2,
  * XCiT-nano; cswin.py:194-196 with Mlp :29-44, xcit.py:293 with Mlp :21-38):

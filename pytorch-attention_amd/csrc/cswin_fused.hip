@@ -23,7 +23,7 @@
 namespace {
 
 struct StripeArgs {
-    const float* x;            // (B, L, C) fp32
+    const void* x;             // (B, L, C) fp32, or 16-bit in the operand type (the X16 instantiations)
     const void* w;             // (3C, C) 16-bit, LayerNorm affine folded in (W' = W diag(ln_w))
     const float* b;            // (3C) fp32, folded (b' = b + W ln_b)
     const float* lw[2];        // get_v.weight of the two branches: (C/2, 1, 3, 3)
@@ -58,7 +58,9 @@ __device__ __forceinline__ void lepe_tap(f4& r0, f4& r1, const V8 nb, const f4 w
     }
 }
 
-template <int PREC, int C, int TFULL = 0, bool L1D = false, int ABL = 0>
+// X16: x is 16-bit in the operand type of PREC (mi355_cswin_stripe_attn_x16_fwd).  Only load_x differs: the rows are widened (exact) into
+// the fp32 registers the fp32 kernel fills, so everything from commit_x on computes what that kernel computes from the widened x.
+template <int PREC, int C, int TFULL = 0, bool L1D = false, int ABL = 0, bool X16 = false>
 __global__ __launch_bounds__(C * 4, (C == 64 ? 3 : 2)) void cswin_stripe_kernel(const StripeArgs a) {
     using M_ = Mma<PREC>;
     using v8 = typename M_::v8;
@@ -169,9 +171,20 @@ __global__ __launch_bounds__(C * 4, (C == 64 ? 3 : 2)) void cswin_stripe_kernel(
     const int xoff = slot_off(xs < T ? xs : 0), soff = slot_off(myslot < T ? myslot : 0);
     const int step_b = per_unit / a.win_per_img, step_w = per_unit % a.win_per_img;
     auto load_x = [&](int b, int win) {
-        const float* p = a.x + ((long)b * L + win * org_step + xoff) * C + xq * PT;
+        const long e0 = ((long)b * L + win * org_step + xoff) * C + xq * PT;
+        if constexpr (X16) {                                       // the thread's 16 channels: two 16-byte loads, widened
+            const el* p = static_cast<const el*>(a.x) + e0;
 #pragma unroll
-        for (int i = 0; i < PT / 4; ++i) xr[i] = *reinterpret_cast<const f4*>(p + i * 4);
+            for (int i = 0; i < PT / 8; ++i) {
+                const v8 h = *reinterpret_cast<const v8*>(p + i * 8);
+                xr[2 * i] = f4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+                xr[2 * i + 1] = f4{(float)h[4], (float)h[5], (float)h[6], (float)h[7]};
+            }
+        } else {
+            const float* p = static_cast<const float*>(a.x) + e0;
+#pragma unroll
+            for (int i = 0; i < PT / 4; ++i) xr[i] = *reinterpret_cast<const f4*>(p + i * 4);
+        }
     };
     auto commit_x = [&]() {                                        // LayerNorm (affine folded into the projection) -> s_xn, 16 bit
         float s = 0.f;
@@ -347,6 +360,40 @@ __global__ __launch_bounds__(C * 4, (C == 64 ? 3 : 2)) void cswin_stripe_kernel(
     if constexpr (PREC == 1) rg_report_f(rgmax, a.ovf, 4u);
 }
 
+// what the fp32-x and the 16-bit-x entry share behind their argument checks: `what` names the entry in refusals, X16 picks the instantiations
+// and the tag
+template <bool X16>
+static int stripe_launch(const char* what, const void* x, const void* wqkv16, const float* bqkv, const float* getv_w0, const float* getv_b0,
+                         const float* getv_w1, const float* getv_b1, void* ctx16, int B, int reso, int C, int heads_per_branch, int split,
+                         float scale, float eps, int precision, mi355_stream_t stream) {
+    StripeArgs a{};
+    a.x = x; a.w = wqkv16; a.b = bqkv; a.lw[0] = getv_w0; a.lb[0] = getv_b0; a.lw[1] = getv_w1; a.lb[1] = getv_b1; a.ctx = ctx16;
+    a.B = B; a.reso = reso; a.split = split; a.hb = heads_per_branch; a.scale = scale; a.eps = eps; a.win_per_img = reso / split;
+    const long nwin = (long)B * a.win_per_img;                    // windows per branch
+    if (nwin >= (1L << 30)) return mi355::fail(MI355_EUNSUPPORTED, "%s: too many windows", what);
+    // C = 64: 4-wave workgroups, three per CU; C = 128: 8-wave workgroups (two heads share the LayerNorm'd window), one per CU
+    long per_unit = (long)mi355::resident_slots(C == 64 ? 3 : 1) / 2;
+    if (per_unit > nwin) per_unit = nwin;
+    if (per_unit < 1) per_unit = 1;
+    const int grid = (int)(per_unit * 2);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    a.ovf = precision == MI355_PREC_FP16 ? mi355::range_word(st) : nullptr;
+    const bool t3 = reso * split >= 48;                           // the model shapes (56 tokens): three key tiles need no validity mask
+    MI355_TRACE(st, X16 ? "cswin_stripe_kernel<C=%d,x16> B=%d reso=%d split=%d" : "cswin_stripe_kernel<C=%d> B=%d reso=%d split=%d", C, B, reso, split);
+#define GO(P_, C_)                                                                       \
+    do {                                                                                 \
+        if (split == 1 && t3) cswin_stripe_kernel<P_, C_, 3, true, 0, X16><<<grid, C_ * 4, 0, st>>>(a);    \
+        else if (split == 1)  cswin_stripe_kernel<P_, C_, 0, true, 0, X16><<<grid, C_ * 4, 0, st>>>(a);    \
+        else if (t3)          cswin_stripe_kernel<P_, C_, 3, false, 0, X16><<<grid, C_ * 4, 0, st>>>(a);   \
+        else                  cswin_stripe_kernel<P_, C_, 0, false, 0, X16><<<grid, C_ * 4, 0, st>>>(a);   \
+    } while (0)
+    if (C == 64) { if (precision == MI355_PREC_FP16) GO(1, 64); else GO(2, 64); }
+    else         { if (precision == MI355_PREC_FP16) GO(1, 128); else GO(2, 128); }
+#undef GO
+    MI355_LAUNCH_CHECK();
+    return MI355_OK;
+}
+
 }  // namespace
 
 extern "C" int mi355_cswin_stripe_attn_fwd(const float* x, const void* wqkv16, const float* bqkv, const float* getv_w0, const float* getv_b0,
@@ -359,30 +406,22 @@ extern "C" int mi355_cswin_stripe_attn_fwd(const float* x, const void* wqkv16, c
         return mi355::fail(MI355_EUNSUPPORTED, "mi355_cswin_stripe_attn_fwd: built for C = 64 / 128, head width 32, <= 64 tokens per stripe "
                            "(C = %d, heads per branch = %d, tokens = %d)", C, heads_per_branch, reso * split);
     MI355_CHECK_ARG(aligned16(x) && aligned16(wqkv16) && aligned16(ctx16) && aligned16(bqkv));
-    StripeArgs a{};
-    a.x = x; a.w = wqkv16; a.b = bqkv; a.lw[0] = getv_w0; a.lb[0] = getv_b0; a.lw[1] = getv_w1; a.lb[1] = getv_b1; a.ctx = ctx16;
-    a.B = B; a.reso = reso; a.split = split; a.hb = heads_per_branch; a.scale = scale; a.eps = eps; a.win_per_img = reso / split;
-    const long nwin = (long)B * a.win_per_img;                    // windows per branch
-    if (nwin >= (1L << 30)) return mi355::fail(MI355_EUNSUPPORTED, "mi355_cswin_stripe_attn_fwd: too many windows");
-    // C = 64: 4-wave workgroups, three per CU; C = 128: 8-wave workgroups (two heads share the LayerNorm'd window), one per CU
-    long per_unit = (long)mi355::resident_slots(C == 64 ? 3 : 1) / 2;
-    if (per_unit > nwin) per_unit = nwin;
-    if (per_unit < 1) per_unit = 1;
-    const int grid = (int)(per_unit * 2);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    a.ovf = precision == MI355_PREC_FP16 ? mi355::range_word(st) : nullptr;
-    const bool t3 = reso * split >= 48;                           // the model shapes (56 tokens): three key tiles need no validity mask
-    MI355_TRACE(st, "cswin_stripe_kernel<C=%d> B=%d reso=%d split=%d", C, B, reso, split);
-#define GO(P_, C_)                                                                       \
-    do {                                                                                 \
-        if (split == 1 && t3) cswin_stripe_kernel<P_, C_, 3, true><<<grid, C_ * 4, 0, st>>>(a);    \
-        else if (split == 1)  cswin_stripe_kernel<P_, C_, 0, true><<<grid, C_ * 4, 0, st>>>(a);    \
-        else if (t3)          cswin_stripe_kernel<P_, C_, 3, false><<<grid, C_ * 4, 0, st>>>(a);   \
-        else                  cswin_stripe_kernel<P_, C_, 0, false><<<grid, C_ * 4, 0, st>>>(a);   \
-    } while (0)
-    if (C == 64) { if (precision == MI355_PREC_FP16) GO(1, 64); else GO(2, 64); }
-    else         { if (precision == MI355_PREC_FP16) GO(1, 128); else GO(2, 128); }
-#undef GO
-    MI355_LAUNCH_CHECK();
-    return MI355_OK;
+    return stripe_launch<false>("mi355_cswin_stripe_attn_fwd", x, wqkv16, bqkv, getv_w0, getv_b0, getv_w1, getv_b1, ctx16, B, reso, C,
+                                heads_per_branch, split, scale, eps, precision, stream);
+}
+
+// x16 (B, L, C) in the operand type of `precision`: read as it is and widened in registers (the X16 instantiations)
+extern "C" int mi355_cswin_stripe_attn_x16_fwd(const void* x16, const void* wqkv16, const float* bqkv, const float* getv_w0, const float* getv_b0,
+                                               const float* getv_w1, const float* getv_b1, void* ctx16, int B, int reso, int C,
+                                               int heads_per_branch, int split, float scale, float eps, int precision, mi355_stream_t stream) {
+    MI355_CHECK_ARG(x16 && wqkv16 && bqkv && getv_w0 && getv_b0 && getv_w1 && getv_b1 && ctx16);
+    MI355_CHECK_ARG(B > 0 && reso > 0 && split > 0 && reso % split == 0 && heads_per_branch > 0);
+    MI355_CHECK_ARG(precision == MI355_PREC_FP16 || precision == MI355_PREC_BF16);
+    if (!(C == 64 || C == 128) || heads_per_branch * 64 != C || reso * split > 64)
+        return mi355::fail(MI355_EUNSUPPORTED, "mi355_cswin_stripe_attn_x16_fwd: built for C = 64 / 128, head width 32, <= 64 tokens per stripe "
+                           "(C = %d, heads per branch = %d, tokens = %d)", C, heads_per_branch, reso * split);
+    if (!aligned16(x16) || !aligned16(wqkv16) || !aligned16(ctx16) || !aligned16(bqkv))
+        return mi355::fail(MI355_EUNSUPPORTED, "mi355_cswin_stripe_attn_x16_fwd: 16-byte aligned buffers required");
+    return stripe_launch<true>("mi355_cswin_stripe_attn_x16_fwd", x16, wqkv16, bqkv, getv_w0, getv_b0, getv_w1, getv_b1, ctx16, B, reso, C,
+                               heads_per_branch, split, scale, eps, precision, stream);
 }

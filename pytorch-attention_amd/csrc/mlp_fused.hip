@@ -19,7 +19,7 @@
 namespace {
 
 struct MlpArgs {
-    const float* x; float* y;
+    const void* x; void* y;                    // (M, C) fp32; the IO16 instantiations: 16-bit in the operand type
     const void* w1; const void* w2;            // 16-bit: (HD, C) and (C, HD), row-major
     const float* b1; const float* b2; const float* gamma;
     long M;
@@ -31,13 +31,23 @@ struct MlpArgs {
     // fp16 range word (common.h rg_report_f, code 4; null for bf16 / under capture without a word): gelu(H) is the one 16-bit intermediate
     // whose magnitude the weights do not bound a priori -- LN(x) is at most sqrt(C - 1) -- and it never reaches HBM, so nobody else sees it
     unsigned* ovf;
+    // IO16 kernels in fp16: the range word again for the y store (code 3, as gemm16_res_kernel reports its 16-bit stores) -- set whether
+    // or not the hidden activation is proven, since y = x1 + ... is bounded by nothing
+    unsigned* ovf_y;
 };
 
 // NWV waves per workgroup (one workgroup per CU), TT 16-token tiles per wave and step.  <16, 2>: 128 registers per lane, four waves per
 // SIMD (the default).  <8, 4> (option "mlp_tt4"): 256 registers, two waves per SIMD, every weight fragment read from LDS feeds FOUR
 // MFMAs instead of two -- the lever VERDICT rounds 2-4 name for CSWin stages 1-2; measured in round 5.
-template <int PREC, int C, int HD, bool PROJ = false, int NWV = 16, int TT = 2>
+// IO16 (PROJ only: mi355_proj_mlp_fused_x16_fwd): x and y are 16-bit in the operand type.  x is read once, at the top of the chunk, as one
+// 16-byte load of 8 elements per lane and k-step and widened (exact); the epilogue rounds the fp32 sums x1 + mlp once and stores 16 bytes.
+template <int PREC, int C, int HD, bool PROJ = false, int NWV = 16, int TT = 2, bool IO16 = false>
 __global__ __launch_bounds__(NWV * 64, NWV / 4) void mlp_fused_kernel(const MlpArgs a) {
+    static_assert(!IO16 || PROJ, "the 16-bit I/O form exists for the proj + MLP kernels");
+    // PARK (the 16-bit I/O form at 128 registers per lane): x1 of the second token tile waits in the wave's slab -- unused until the epilogue --
+    // while the hidden blocks run, and comes back into registers in front of the epilogue.  Sixteen registers fewer across the main loop:
+    // no scratch.  A lane reads back what it wrote itself; the values and the order of the arithmetic are the same.
+    constexpr bool PARK = IO16 && TT == 2;
     using M_ = Mma<PREC>;
     using v8 = typename M_::v8;
     using v4 = typename M_::v4;
@@ -79,23 +89,30 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void mlp_fused_kernel(const MlpA
     __syncthreads();
     float* slab = s_slab + wave * 16 * SP;
     const float invC = 1.0f / (float)C;
-    float rgmax = 0.f;
+    float rgmax = 0.f, rgy = 0.f;
 
     const long nchunk = (a.M + 16 * TT - 1) / (16 * TT);
     for (long ch = (long)blockIdx.x * NWV + wave; ch < nchunk; ch += (long)gridDim.x * NWV) {
         const long tok0 = ch * (16 * TT);
         // ---- tokens in B-operand layout: lane (l15, g) holds channels ks*32 + g*8 + [0,8) of token tok0 + tt*16 + l15 -------------
         v8 xb[TT][KS];
-        f4 x1lo[PROJ ? TT : 1][KS], x1hi[PROJ ? TT : 1][KS];       // PROJ: the residual stream after the projection, kept for the epilogue
+        f4 x1lo[PROJ && !PARK ? TT : 1][KS], x1hi[PROJ && !PARK ? TT : 1][KS];       // PROJ: the residual stream after the projection, kept for the epilogue
 #pragma unroll
         for (int tt = 0; tt < TT; ++tt) {
             const long tok = tok0 + tt * 16 + l15;
             f4 lo[KS], hi[KS];
-            const float* xr = a.x + (tok < a.M ? tok : 0) * C + g * 8;
+            const long xo = (tok < a.M ? tok : 0) * C + g * 8;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                lo[ks] = *reinterpret_cast<const f4*>(xr + ks * 32);
-                hi[ks] = *reinterpret_cast<const f4*>(xr + ks * 32 + 4);
+                if constexpr (IO16) {
+                    const v8 h = *reinterpret_cast<const v8*>(static_cast<const el*>(a.x) + xo + ks * 32);
+                    lo[ks] = f4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+                    hi[ks] = f4{(float)h[4], (float)h[5], (float)h[6], (float)h[7]};
+                } else {
+                    const float* xr = static_cast<const float*>(a.x) + xo;
+                    lo[ks] = *reinterpret_cast<const f4*>(xr + ks * 32);
+                    hi[ks] = *reinterpret_cast<const f4*>(xr + ks * 32 + 4);
+                }
             }
             if constexpr (PROJ) {
                 // x1 = x + ctx Wp^T + bp.  P^T = Wp . ctx^T with the rows of each 16-row MFMA tile PERMUTED so that the accumulator
@@ -116,8 +133,17 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void mlp_fused_kernel(const MlpA
                             acc = M_::mma(*reinterpret_cast<const v8*>(s_wp + nrow * P1 + ks * 32 + g * 8), cb[ks], acc);
                         if (h == 0) lo[kp] = lo[kp] + acc; else hi[kp] = hi[kp] + acc;
                     }
+                if (PARK && tt == 1) {
 #pragma unroll
-                for (int ks = 0; ks < KS; ++ks) { x1lo[tt][ks] = lo[ks]; x1hi[tt][ks] = hi[ks]; }
+                    for (int ks = 0; ks < KS; ++ks) {
+                        *reinterpret_cast<f4*>(slab + l15 * SP + ks * 32 + g * 8) = lo[ks];
+                        *reinterpret_cast<f4*>(slab + l15 * SP + ks * 32 + g * 8 + 4) = hi[ks];
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                } else {
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks) { x1lo[PARK ? 0 : tt][ks] = lo[ks]; x1hi[PARK ? 0 : tt][ks] = hi[ks]; }
+                }
             }
             float mean = 0.f, rstd = 1.f;
             if (a.do_ln) {
@@ -184,6 +210,17 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void mlp_fused_kernel(const MlpA
             }
         }
         // ---- epilogue per token tile: (+ b2) * gamma -> slab -> + x -> row stores ------------------------------------------------------
+        f4 pklo[PARK ? KS : 1], pkhi[PARK ? KS : 1];
+        if constexpr (PARK) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                pklo[ks] = *reinterpret_cast<const f4*>(slab + l15 * SP + ks * 32 + g * 8);
+                pkhi[ks] = *reinterpret_cast<const f4*>(slab + l15 * SP + ks * 32 + g * 8 + 4);
+            }
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        }
 #pragma unroll
         for (int tt = 0; tt < TT; ++tt) {
 #pragma unroll
@@ -197,17 +234,25 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void mlp_fused_kernel(const MlpA
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             const long tok = tok0 + tt * 16 + l15;
             if (tok < a.M) {
-                const float* xr = a.x + tok * C + g * 8;
-                float* yr = a.y + tok * C + g * 8;
+                const float* xr = static_cast<const float*>(a.x) + tok * C + g * 8;       // !PROJ (fp32 only): x re-read
+                float* yr = static_cast<float*>(a.y) + tok * C + g * 8;
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) {
                     const f4 r0 = *reinterpret_cast<const f4*>(slab + l15 * SP + ks * 32 + g * 8);
                     const f4 r1 = *reinterpret_cast<const f4*>(slab + l15 * SP + ks * 32 + g * 8 + 4);
                     f4 x0, x1;
-                    if constexpr (PROJ) { x0 = x1lo[tt][ks]; x1 = x1hi[tt][ks]; }
+                    if constexpr (PARK) { x0 = tt ? pklo[ks] : x1lo[0][ks]; x1 = tt ? pkhi[ks] : x1hi[0][ks]; }
+                    else if constexpr (PROJ) { x0 = x1lo[tt][ks]; x1 = x1hi[tt][ks]; }
                     else { x0 = *reinterpret_cast<const f4*>(xr + ks * 32); x1 = *reinterpret_cast<const f4*>(xr + ks * 32 + 4); }
-                    *reinterpret_cast<f4*>(yr + ks * 32) = x0 + r0;
-                    *reinterpret_cast<f4*>(yr + ks * 32 + 4) = x1 + r1;
+                    if constexpr (IO16) {                           // 8 fp32 sums -> one conversion -> one 16-byte store
+                        const f4 s0 = x0 + r0, s1 = x1 + r1;
+                        if constexpr (PREC == 1) rgy = rg_absmax4(rg_absmax4(rgy, s0), s1);
+                        const v4 h0 = M_::cvt(s0), h1 = M_::cvt(s1);
+                        *reinterpret_cast<v8*>(static_cast<el*>(a.y) + tok * C + g * 8 + ks * 32) = v8{h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+                    } else {
+                        *reinterpret_cast<f4*>(yr + ks * 32) = x0 + r0;
+                        *reinterpret_cast<f4*>(yr + ks * 32 + 4) = x1 + r1;
+                    }
                 }
             }
             __builtin_amdgcn_wave_barrier();
@@ -215,6 +260,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void mlp_fused_kernel(const MlpA
         }
     }
     if constexpr (PREC == 1) rg_report_f(rgmax, a.ovf, 4u);
+    if constexpr (PREC == 1 && IO16) rg_report(rgy, a.ovf_y, 3u);
 }
 
 // ---- C = 128 (hidden 512: CSWin stage 2, XCiT-nano): the weights (256 KB) do not fit in LDS, so the waves of a workgroup walk the
@@ -225,8 +271,10 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void mlp_fused_kernel(const MlpA
 // the two tiles give a wave independent MFMA chains to run the GELU of one under.
 // PROJ: x1 = x + ctx Wp^T + bp first (Wp resident in LDS).  x1 is parked in the y rows the lane will overwrite at the end and read
 // back there (same lane, same addresses: program order; the lines are L2-resident).
-template <int PREC, int C, int HD, bool PROJ = false>
+// IO16: as in mlp_fused_kernel.
+template <int PREC, int C, int HD, bool PROJ = false, bool IO16 = false>
 __global__ __launch_bounds__(512, 2) void mlp_fused_stream_kernel(const MlpArgs a) {
+    static_assert(!IO16 || PROJ, "the 16-bit I/O form exists for the proj + MLP kernels");
     using M_ = Mma<PREC>;
     using v8 = typename M_::v8;
     using v4 = typename M_::v4;
@@ -272,7 +320,7 @@ __global__ __launch_bounds__(512, 2) void mlp_fused_stream_kernel(const MlpArgs 
         *reinterpret_cast<v4*>(d + d2 + 4) = v4{n2[4], n2[5], n2[6], n2[7]};
     };
 
-    float rgmax = 0.f;
+    float rgmax = 0.f, rgy = 0.f;
     const long ntile = (a.M + 15) / 16;
     const long niter = (ntile + NWV * TT - 1) / (NWV * TT);       // workgroup steps: 256 tokens each, uniform trip count for the barriers
     for (long it = blockIdx.x; it < niter; it += gridDim.x) {
@@ -283,11 +331,18 @@ __global__ __launch_bounds__(512, 2) void mlp_fused_stream_kernel(const MlpArgs 
         for (int tt = 0; tt < TT; ++tt) {
             const long tok = tok0 + tt * 16 + l15;
             f4 lo[KS], hi[KS];
-            const float* xr = a.x + (tok < a.M ? tok : 0) * C + g * 8;
+            const long xo = (tok < a.M ? tok : 0) * C + g * 8;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                lo[ks] = *reinterpret_cast<const f4*>(xr + ks * 32);
-                hi[ks] = *reinterpret_cast<const f4*>(xr + ks * 32 + 4);
+                if constexpr (IO16) {
+                    const v8 h = *reinterpret_cast<const v8*>(static_cast<const el*>(a.x) + xo + ks * 32);
+                    lo[ks] = f4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+                    hi[ks] = f4{(float)h[4], (float)h[5], (float)h[6], (float)h[7]};
+                } else {
+                    const float* xr = static_cast<const float*>(a.x) + xo;
+                    lo[ks] = *reinterpret_cast<const f4*>(xr + ks * 32);
+                    hi[ks] = *reinterpret_cast<const f4*>(xr + ks * 32 + 4);
+                }
             }
             if constexpr (PROJ) {                                   // see mlp_fused_kernel: permuted tile rows = the layout of lo / hi
                 const el* cr = static_cast<const el*>(a.ctx) + (tok < a.M ? tok : 0) * C + g * 8;
@@ -398,8 +453,8 @@ __global__ __launch_bounds__(512, 2) void mlp_fused_stream_kernel(const MlpArgs 
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 if (tok < a.M) {
-                    const float* xr = a.x + tok * C + hh * 64 + g * 8;
-                    float* yr = a.y + tok * C + hh * 64 + g * 8;
+                    const float* xr = static_cast<const float*>(a.x) + tok * C + hh * 64 + g * 8;     // !PROJ (fp32 only): x re-read
+                    float* yr = static_cast<float*>(a.y) + tok * C + hh * 64 + g * 8;
 #pragma unroll
                     for (int k2 = 0; k2 < 2; ++k2) {
                         const f4 r0 = *reinterpret_cast<const f4*>(slab + l15 * SPH + k2 * 32 + g * 8);
@@ -407,8 +462,16 @@ __global__ __launch_bounds__(512, 2) void mlp_fused_stream_kernel(const MlpArgs 
                         f4 x0, x1;
                         if constexpr (PROJ) { x0 = x1lo[tt][hh * 2 + k2]; x1 = x1hi[tt][hh * 2 + k2]; }
                         else { x0 = *reinterpret_cast<const f4*>(xr + k2 * 32); x1 = *reinterpret_cast<const f4*>(xr + k2 * 32 + 4); }
-                        *reinterpret_cast<f4*>(yr + k2 * 32) = x0 + r0;
-                        *reinterpret_cast<f4*>(yr + k2 * 32 + 4) = x1 + r1;
+                        if constexpr (IO16) {                       // 8 fp32 sums -> one conversion -> one 16-byte store
+                            const f4 s0 = x0 + r0, s1 = x1 + r1;
+                            if constexpr (PREC == 1) rgy = rg_absmax4(rg_absmax4(rgy, s0), s1);
+                            const v4 h0 = M_::cvt(s0), h1 = M_::cvt(s1);
+                            *reinterpret_cast<v8*>(static_cast<el*>(a.y) + tok * C + hh * 64 + g * 8 + k2 * 32) =
+                                v8{h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+                        } else {
+                            *reinterpret_cast<f4*>(yr + k2 * 32) = x0 + r0;
+                            *reinterpret_cast<f4*>(yr + k2 * 32 + 4) = x1 + r1;
+                        }
                     }
                 }
                 __builtin_amdgcn_wave_barrier();
@@ -417,6 +480,7 @@ __global__ __launch_bounds__(512, 2) void mlp_fused_stream_kernel(const MlpArgs 
         }
     }
     if constexpr (PREC == 1) rg_report_f(rgmax, a.ovf, 4u);
+    if constexpr (PREC == 1 && IO16) rg_report(rgy, a.ovf_y, 3u);
 }
 
 template <int C, int HD>
@@ -471,18 +535,18 @@ extern "C" int mi355_mlp_fused_fwd(const float* x, const void* w1_16, const floa
     const long nchunk = (M + (tt4 ? 63 : 31)) / (tt4 ? 64 : 32);
     long grid = (nchunk + (tt4 ? 7 : 15)) / (tt4 ? 8 : 16);
     if (grid > ncu) grid = ncu;
-#define MLP64(P_, PR_)                                                                                                                     \
+#define MLP64(P_, PR_, IO_)                                                                                                                   \
     do {                                                                                                                                  \
         if (tt4) {                                                                                                                        \
-            if (int rc = mi355::func_dynamic_lds(reinterpret_cast<const void*>(mlp_fused_kernel<P_, 64, 256, PR_, 8, 4>), (int)smem)) return rc;   \
-            mlp_fused_kernel<P_, 64, 256, PR_, 8, 4><<<(int)grid, 512, smem, st>>>(a);                                                    \
+            if (int rc = mi355::func_dynamic_lds(reinterpret_cast<const void*>(mlp_fused_kernel<P_, 64, 256, PR_, 8, 4, IO_>), (int)smem)) return rc;   \
+            mlp_fused_kernel<P_, 64, 256, PR_, 8, 4, IO_><<<(int)grid, 512, smem, st>>>(a);                                                    \
         } else {                                                                                                                          \
-            if (int rc = mi355::func_dynamic_lds(reinterpret_cast<const void*>(mlp_fused_kernel<P_, 64, 256, PR_>), (int)smem)) return rc; \
-            mlp_fused_kernel<P_, 64, 256, PR_><<<(int)grid, 1024, smem, st>>>(a);                                                         \
+            if (int rc = mi355::func_dynamic_lds(reinterpret_cast<const void*>(mlp_fused_kernel<P_, 64, 256, PR_, 16, 2, IO_>), (int)smem)) return rc; \
+            mlp_fused_kernel<P_, 64, 256, PR_, 16, 2, IO_><<<(int)grid, 1024, smem, st>>>(a);                                                         \
         }                                                                                                                                 \
     } while (0)
-    if (precision == MI355_PREC_FP16) MLP64(1, false);
-    else MLP64(2, false);
+    if (precision == MI355_PREC_FP16) MLP64(1, false, false);
+    else MLP64(2, false, false);
     MI355_LAUNCH_CHECK();
     return MI355_OK;
 }
@@ -527,8 +591,56 @@ extern "C" int mi355_proj_mlp_fused_fwd(const float* x, const void* ctx16, const
     const long nchunk = (M + (tt4 ? 63 : 31)) / (tt4 ? 64 : 32);
     long grid = (nchunk + (tt4 ? 7 : 15)) / (tt4 ? 8 : 16);
     if (grid > ncu) grid = ncu;
-    if (precision == MI355_PREC_FP16) MLP64(1, true);
-    else MLP64(2, true);
+    if (precision == MI355_PREC_FP16) MLP64(1, true, false);
+    else MLP64(2, true, false);
+    MI355_LAUNCH_CHECK();
+    return MI355_OK;
+}
+
+// mi355_proj_mlp_fused_fwd with x16 and y16 (M, C) in the operand type of `precision` (the IO16 instantiations): same grids, same LDS
+extern "C" int mi355_proj_mlp_fused_x16_fwd(const void* x16, const void* ctx16, const void* wp16, const float* bp, const void* w1_16, const float* b1,
+                                            const void* w2_16, const float* b2, const float* gamma, void* y16, long M, int C, int hidden,
+                                            int layernorm, float eps, int precision, mi355_stream_t stream) {
+    MI355_CHECK_ARG(x16 && ctx16 && wp16 && bp && w1_16 && b1 && w2_16 && y16 && M > 0);
+    MI355_CHECK_ARG(precision == MI355_PREC_FP16 || precision == MI355_PREC_BF16);
+    MI355_CHECK_ARG(layernorm >= 0 && layernorm <= 3);                          // flag word: bit 0 LayerNorm, bit 1 range proven
+    if (!((C == 64 && hidden == 256) || (C == 128 && hidden == 512)))
+        return mi355::fail(MI355_EUNSUPPORTED, "mi355_proj_mlp_fused_x16_fwd: built for C = 64, hidden = 256 and C = 128, hidden = 512 (got C = %d, hidden = %d)", C, hidden);
+    if (!aligned16(x16) || !aligned16(y16) || !aligned16(w1_16) || !aligned16(w2_16) || !aligned16(ctx16) || !aligned16(wp16) || !aligned16(bp))
+        return mi355::fail(MI355_EUNSUPPORTED, "mi355_proj_mlp_fused_x16_fwd: 16-byte aligned buffers required");
+    MlpArgs a{};
+    a.x = x16; a.y = y16; a.w1 = w1_16; a.w2 = w2_16; a.b1 = b1; a.b2 = b2; a.gamma = gamma; a.M = M; a.eps = eps; a.do_ln = (layernorm & 1) ? 1 : 0;
+    a.ctx = ctx16; a.wp = wp16; a.bp = bp;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // the fp16 y store can always saturate (code 3), so an fp16 launch is a producer whether or not the hidden activation is proven (bit 1:
+    // code 4 is then not reported)
+    a.ovf_y = precision == MI355_PREC_FP16 ? mi355::range_word(st) : nullptr;
+    a.ovf = (layernorm & 2) ? nullptr : a.ovf_y;
+    const int ncu = mi355::resident_slots(1);
+    MI355_TRACE(st, "mlp_fused_kernel<C=%d,proj,x16> M=%ld", C, M);
+    if (C == 128) {
+        constexpr size_t sm = (size_t)2 * (32 * (128 + 8) + 128 * 36) * 2 + (size_t)8 * 16 * 68 * 4 + (size_t)128 * (128 + 8) * 2 + (size_t)512 * 4;
+        static_assert(sm <= 160 * 1024, "LDS budget");
+        const long niter = ((M + 15) / 16 + 15) / 16;
+        const int grid2 = (int)(niter < ncu ? niter : ncu);
+        if (precision == MI355_PREC_FP16) {
+            if (int rc = mi355::func_dynamic_lds(reinterpret_cast<const void*>(mlp_fused_stream_kernel<1, 128, 512, true, true>), (int)sm)) return rc;
+            mlp_fused_stream_kernel<1, 128, 512, true, true><<<grid2, 512, sm, st>>>(a);
+        } else {
+            if (int rc = mi355::func_dynamic_lds(reinterpret_cast<const void*>(mlp_fused_stream_kernel<2, 128, 512, true, true>), (int)sm)) return rc;
+            mlp_fused_stream_kernel<2, 128, 512, true, true><<<grid2, 512, sm, st>>>(a);
+        }
+        MI355_LAUNCH_CHECK();
+        return MI355_OK;
+    }
+    constexpr size_t smem = mlp_smem<64, 256>(true);
+    static_assert(smem <= 160 * 1024, "LDS budget");
+    const bool tt4 = mi355::opt(mi355::O_MLP_TT4) != 0;
+    const long nchunk = (M + (tt4 ? 63 : 31)) / (tt4 ? 64 : 32);
+    long grid = (nchunk + (tt4 ? 7 : 15)) / (tt4 ? 8 : 16);
+    if (grid > ncu) grid = ncu;
+    if (precision == MI355_PREC_FP16) MLP64(1, true, true);
+    else MLP64(2, true, true);
 #undef MLP64
     MI355_LAUNCH_CHECK();
     return MI355_OK;

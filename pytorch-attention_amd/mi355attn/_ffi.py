@@ -157,10 +157,12 @@ SIGNATURES = {
     "mi355_dwconv3x3_tokens_residual_fwd": (c_int, [c_vp] * 4 + [c_int] * 4 + [ctypes.c_long, c_vp]),
     "mi355_mlp_fused_fwd": (c_int, [c_vp] * 7 + [ctypes.c_long, c_int, c_int, c_int, ctypes.c_float, c_int, c_vp]),
     "mi355_proj_mlp_fused_fwd": (c_int, [c_vp] * 10 + [ctypes.c_long, c_int, c_int, c_int, ctypes.c_float, c_int, c_vp]),
+    "mi355_proj_mlp_fused_x16_fwd": (c_int, [c_vp] * 10 + [ctypes.c_long, c_int, c_int, c_int, ctypes.c_float, c_int, c_vp]),
     "mi355_sdpa_general_fwd": (c_int, [c_vp] * 5 + [c_int] * 5 + [ctypes.c_long] * 5 + [ctypes.c_float, c_int, c_int, c_vp]),
     "mi355_dwconv_patch_tokens_fwd": (c_int, [c_vp] * 4 + [c_int] * 5 + [c_vp]),
     "mi355_cswin_lepe_attn16_pair_fwd": (c_int, [c_vp] * 6 + [c_int] * 5 + [ctypes.c_float, c_int, c_vp]),
     "mi355_cswin_stripe_attn_fwd": (c_int, [c_vp] * 8 + [c_int] * 5 + [c_float, c_float, c_int, c_vp]),
+    "mi355_cswin_stripe_attn_x16_fwd": (c_int, [c_vp] * 8 + [c_int] * 5 + [c_float, c_float, c_int, c_vp]),
     "mi355_class_attn_fwd": (c_int, [c_vp] * 4 + [c_int] * 4 + [ctypes.c_long, ctypes.c_long, ctypes.c_float, c_vp]),
     "mi355_axpby_fwd": (c_int, [c_vp] * 4 + [ctypes.c_long, c_int, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_float, c_vp]),
     "mi355_comm_unique_id": (c_int, [c_vp, c_size]),
@@ -282,7 +284,8 @@ def require_device_f32(t, name):
         raise TypeError(f"{name}: expected float32, got {t.dtype} (16-bit activations are accepted by SELayer, ECALayer, CBAM, "
                         "ChannelAttention, SpatialAttention, SELayerBias, SELayerBias4, SELayerHidden, SqueezeExcite, simam_module, SRM, "
                         "GaussianGCT, LCT, GCT, DoubleAttention, CoordinateAttention, TripletAttention, AttentionGate, MixerLayer, MLP_Mixer "
-                        "(with its PatchEmbedding), TransformerEncoder, VisionTransformer (with its PatchEmbedding), BAM, PAM and CAM only)")
+                        "(with its PatchEmbedding), TransformerEncoder, VisionTransformer (with its PatchEmbedding), CSWinBlock, LePEAttention, "
+                        "Merge_Block, CSWinTransformer, BAM, PAM and CAM only)")
     if t.requires_grad and torch.is_grad_enabled():
         _warn_no_autograd()
     return t if t.is_contiguous() else t.contiguous()

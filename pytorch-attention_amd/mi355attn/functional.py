@@ -747,15 +747,21 @@ def cswin_stripe_ok(C, reso, split, heads, precision=None):
     return _prec(precision) in (PREC_FP16, PREC_BF16) and C in (64, 128) and heads * 32 == C and reso * split <= 64 and reso % split == 0
 
 
+def _w32(t, name):
+    """A parameter inside a fold: fp32 as it is, 16-bit (module.half() / .bfloat16()) through its cached fp32 copy (param32)."""
+    return param32(t, name) if t.dtype in _ffi.IO_CODES else t.detach()
+
+
 def _ln_folded16(ln, lin, p):
-    """(W diag(ln.weight) in 16 bit, b + W ln.bias in fp32) of a Linear behind a LayerNorm, cached per parameter version."""
+    """(W diag(ln.weight) in 16 bit, b + W ln.bias in fp32) of a Linear behind a LayerNorm, cached per parameter version.  Parameters:
+    fp32, or 16-bit through their fp32 copies (a block on 16-bit activations)."""
     N = lin.weight.shape[0]
 
     def build():
-        w = lin.weight.detach()
-        b = lin.bias.detach() if lin.bias is not None else torch.zeros(N, dtype=torch.float32, device=w.device)
-        b = linear(ln.bias.detach().reshape(1, -1).contiguous(), w.contiguous(), b, precision=PREC_STRICT).reshape(-1)   # b + W ln.bias on the library's own engine (no vendor BLAS launch)
-        return cast16((w * ln.weight.detach()[None, :]).contiguous(), p), b.contiguous()
+        w = _w32(lin.weight, "weight")
+        b = _w32(lin.bias, "bias") if lin.bias is not None else torch.zeros(N, dtype=torch.float32, device=w.device)
+        b = linear(_w32(ln.bias, "ln.bias").reshape(1, -1).contiguous(), w.contiguous(), b, precision=PREC_STRICT).reshape(-1)   # b + W ln.bias on the library's own engine (no vendor BLAS launch)
+        return cast16((w * _w32(ln.weight, "ln.weight")[None, :]).contiguous(), p), b.contiguous()
 
     parts = [lin.weight] + ([] if lin.bias is None else [lin.bias]) + [ln.weight, ln.bias]
     tag = tuple((t._version, t.data_ptr()) for t in parts)
@@ -775,6 +781,22 @@ def cswin_stripe_attention(x, ln, qkv, getv0, getv1, reso, heads, split, scale, 
     check(lib().mi355_cswin_stripe_attn_fwd(dptr(x), dptr(w16), dptr(b), dptr(ws[0]), dptr(ws[1]), dptr(ws[2]), dptr(ws[3]), dptr(ctx), B, reso,
                                             C, heads // 2, split, float(scale), float(ln.eps), p, stream_ptr(x.device)),
           "mi355_cswin_stripe_attn_fwd")
+    return ctx
+
+
+def cswin_stripe_attention16(x16, ln, qkv, getv0, getv1, reso, heads, split, scale):
+    """cswin_stripe_attention for a 16-bit x (B, L, C): the operand format is the type of x, which is read as it is (mi355_cswin_stripe_attn_x16_fwd:
+    no widen, no cast); ctx (B, L, C) in that type holds the bits cswin_stripe_attention(x16.float(), precision = the type) gives.
+    Parameters: fp32, or 16-bit through their cached fp32 copies."""
+    x16, p = _require_io16(x16, "x")
+    B, L, C = x16.shape
+    w16, b = _ln_folded16(ln, qkv, p)
+    ws = [param32(t, n) for t, n in ((getv0.weight, "attns.0.get_v.weight"), (getv0.bias, "attns.0.get_v.bias"),
+                                     (getv1.weight, "attns.1.get_v.weight"), (getv1.bias, "attns.1.get_v.bias"))]
+    ctx = torch.empty_like(x16)
+    check(lib().mi355_cswin_stripe_attn_x16_fwd(dptr(x16), dptr(w16), dptr(b), dptr(ws[0]), dptr(ws[1]), dptr(ws[2]), dptr(ws[3]), dptr(ctx), B,
+                                                reso, C, heads // 2, split, float(scale), float(ln.eps), p, stream_ptr(x16.device)),
+          "mi355_cswin_stripe_attn_x16_fwd")
     return ctx
 
 
@@ -923,13 +945,42 @@ def mlp_fused(x, ln, fc1, fc2, gamma=None, precision=None, ctx16=None, proj=None
     x = require_device_f32(x, "x")
     C = x.shape[-1]
     Hd = fc1.weight.shape[0]
+    w1_16, b1, ln_flags, w2_16 = _mlp_fused_weights(ln, fc1, fc2, C, p)
+    y = torch.empty_like(x)
+    M = x.numel() // C
+    if ctx16 is not None:
+        ctx16 = _require16(ctx16, "ctx16", p)
+        wp16, bp = _proj_operands(proj, C, p)
+        check(lib().mi355_proj_mlp_fused_fwd(dptr(x), dptr(ctx16), dptr(wp16), dptr(require_device_f32(bp, "proj.bias")), dptr(w1_16), dptr(b1),
+                                             dptr(w2_16), dptr(_opt(fc2.bias, "fc2.bias")), dptr(_opt(gamma, "gamma")), dptr(y), M, C, Hd,
+                                             ln_flags, float(ln.eps) if ln is not None else 0.0, p, stream_ptr(x.device)),
+              "mi355_proj_mlp_fused_fwd")
+        return y
+    check(lib().mi355_mlp_fused_fwd(dptr(x), dptr(w1_16), dptr(b1), dptr(w2_16), dptr(_opt(fc2.bias, "fc2.bias")), dptr(_opt(gamma, "gamma")),
+                                    dptr(y), M, C, Hd, ln_flags, float(ln.eps) if ln is not None else 0.0, p,
+                                    stream_ptr(x.device)), "mi355_mlp_fused_fwd")
+    return y
+
+
+def _proj_operands(proj, C, p):
+    """(wp16, bp) of the proj Linear in front of a fused MLP: the cached 16-bit weight and the bias (a cached zero row where there is none)."""
+    bp = proj.bias if proj.bias is not None else _derived_get((proj,), ("zero_bias",), (proj.weight.data_ptr(),),
+                                                              lambda: torch.zeros(C, dtype=torch.float32, device=proj.weight.device))
+    return weight16(proj.weight, p), bp
+
+
+def _mlp_fused_weights(ln, fc1, fc2, C, p):
+    """(w1_16, b1, flag word, w2_16) of mi355_mlp_fused_fwd and its proj / x16 forms: the LayerNorm affine part folded into fc1, the range
+    proof of the hidden activation, fc2 row-major or slice-major; cached per parameter version.  Parameters: fp32, or 16-bit through
+    their fp32 copies."""
+    Hd = fc1.weight.shape[0]
 
     def build():
-        w1 = fc1.weight.detach()
-        b1 = fc1.bias.detach() if fc1.bias is not None else torch.zeros(Hd, dtype=torch.float32, device=w1.device)
+        w1 = _w32(fc1.weight, "fc1.weight")
+        b1 = _w32(fc1.bias, "fc1.bias") if fc1.bias is not None else torch.zeros(Hd, dtype=torch.float32, device=w1.device)
         if ln is not None:
-            b1 = linear(ln.bias.detach().reshape(1, -1).contiguous(), w1.contiguous(), b1, precision=PREC_STRICT).reshape(-1)    # b1 + W1 ln.bias, no vendor BLAS
-            w1 = w1 * ln.weight.detach()[None, :]
+            b1 = linear(_w32(ln.bias, "ln.bias").reshape(1, -1).contiguous(), w1.contiguous(), b1, precision=PREC_STRICT).reshape(-1)    # b1 + W1 ln.bias, no vendor BLAS
+            w1 = w1 * _w32(ln.weight, "ln.weight")[None, :]
         # range proof (round 6): behind a LayerNorm |xn| <= sqrt(C - 1), so the 16-bit hidden activation is bounded by the folded weights
         # alone; proven once per parameter version (one flag read), the kernel then has nothing to report and the host nothing to wait for.
         # 60000 leaves room for the fp16 rounding of W1' (2^-11 relative).  Under stream capture no read is possible: unproven.
@@ -948,22 +999,26 @@ def mlp_fused(x, ln, fc1, fc2, gamma=None, precision=None, ctx16=None, proj=None
         w2_16 = weight16(fc2.weight, p)
     else:                                               # slice-major (hidden/32, C, 32): the kernel streams 32-unit slices through LDS
         w2_16 = _derived_get((fc2,), ("mlp_fused_w2", p), (fc2.weight._version, fc2.weight.data_ptr()),
-                             lambda: cast16(fc2.weight.detach().reshape(C, Hd // 32, 32).permute(1, 0, 2).contiguous(), p))
-    y = torch.empty_like(x)
-    M = x.numel() // C
-    if ctx16 is not None:
-        ctx16 = _require16(ctx16, "ctx16", p)
-        wp16 = weight16(proj.weight, p)
-        bp = proj.bias if proj.bias is not None else _derived_get((proj,), ("zero_bias",), (proj.weight.data_ptr(),),
-                                                                  lambda: torch.zeros(C, dtype=torch.float32, device=x.device))
-        check(lib().mi355_proj_mlp_fused_fwd(dptr(x), dptr(ctx16), dptr(wp16), dptr(require_device_f32(bp, "proj.bias")), dptr(w1_16), dptr(b1),
-                                             dptr(w2_16), dptr(_opt(fc2.bias, "fc2.bias")), dptr(_opt(gamma, "gamma")), dptr(y), M, C, Hd,
-                                             ln_flags, float(ln.eps) if ln is not None else 0.0, p, stream_ptr(x.device)),
-              "mi355_proj_mlp_fused_fwd")
-        return y
-    check(lib().mi355_mlp_fused_fwd(dptr(x), dptr(w1_16), dptr(b1), dptr(w2_16), dptr(_opt(fc2.bias, "fc2.bias")), dptr(_opt(gamma, "gamma")),
-                                    dptr(y), M, C, Hd, ln_flags, float(ln.eps) if ln is not None else 0.0, p,
-                                    stream_ptr(x.device)), "mi355_mlp_fused_fwd")
+                             lambda: cast16(_w32(fc2.weight, "fc2.weight").reshape(C, Hd // 32, 32).permute(1, 0, 2).contiguous(), p))
+    return w1_16, b1, ln_flags, w2_16
+
+
+def proj_mlp_fused16(x16, ctx16, proj, ln, fc1, fc2):
+    """Second half of a CSWinBlock on a 16-bit x (M rows of C): y16 = round(x1 + fc2(gelu(fc1(ln(x1))))) with x1 = x16 + proj(ctx16) kept
+    fp32 inside the kernel (mi355_proj_mlp_fused_x16_fwd).  The operand format is the type of x16, which is read as it is; y16 holds
+    mlp_fused(x16.float(), ..., ctx16, proj) rounded once, written by the kernel (no round launch).  Parameters: fp32 or 16-bit."""
+    x16, p = _require_io16(x16, "x")
+    _range_check()
+    C = x16.shape[-1]
+    Hd = fc1.weight.shape[0]
+    w1_16, b1, ln_flags, w2_16 = _mlp_fused_weights(ln, fc1, fc2, C, p)
+    ctx16 = _require16(ctx16, "ctx16", p)
+    wp16, bp = _proj_operands(proj, C, p)
+    y = torch.empty_like(x16)
+    check(lib().mi355_proj_mlp_fused_x16_fwd(dptr(x16), dptr(ctx16), dptr(wp16), dptr(param32(bp, "proj.bias")), dptr(w1_16), dptr(b1), dptr(w2_16),
+                                             dptr(None if fc2.bias is None else param32(fc2.bias, "fc2.bias")), dptr(None), dptr(y),
+                                             x16.numel() // C, C, Hd, ln_flags, float(ln.eps) if ln is not None else 0.0, p,
+                                             stream_ptr(x16.device)), "mi355_proj_mlp_fused_x16_fwd")
     return y
 
 

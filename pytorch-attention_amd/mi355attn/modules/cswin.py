@@ -6,12 +6,15 @@
 The window partition (img2windows / windows2img, cswin.py:199-216) never materialises: the attention
 kernel gathers q/k/v straight from the (B,L,3,C) qkv buffer with window index math and scatters its
 output back in (B,L,C) order.
+
+`CSWinBlock`, `LePEAttention`, `Merge_Block`, `CSWinTransformer` and the two factories also take an fp16 / bf16 tensor and return that
+type (the operand format is then the tensor's type; see CSWinBlock._forward16).
 """
 import torch
 from torch import nn
 
 from .. import functional as F
-from .vit import _fast, _mlp16
+from .vit import _fast, _io_precision, _is16, _mlp16, _p32, _same
 
 
 def _stripe(resolution, idx, split_size):
@@ -51,17 +54,30 @@ class LePEAttention(nn.Module):
         self.get_v = nn.Conv2d(dim, dim, kernel_size=3, stride=1, padding=1, groups=dim)
         self.precision = precision
 
-    def run(self, qkv_blc, out, c0):
+    def run(self, qkv_blc, out, c0, precision=None, P=_same):
         """Attend over channels [c0, c0+dim) of a (B,L,3,Ctot) buffer, writing the same slice of `out` (B,L,Ctot).
-        fp32 buffers use the converting kernel, 16-bit buffers the 16-bit-I/O kernel."""
+        fp32 buffers use the converting kernel, 16-bit buffers the 16-bit-I/O kernel.  `precision`: the operand format where it is not
+        the module's setting, P: how the parameters are handed over (_p32 for a block on 16-bit activations: the type of its x)."""
         fn = F.cswin_lepe_attention if qkv_blc.dtype == torch.float32 else F.cswin_lepe_attention16
-        return fn(qkv_blc, self.get_v.weight, self.get_v.bias, out, self.resolution, c0, self.dim, self.num_heads, self.H_sp,
-                  self.W_sp, self.scale, self.precision)
+        return fn(qkv_blc, P(self.get_v.weight, "get_v.weight"), P(self.get_v.bias, "get_v.bias"), out, self.resolution, c0, self.dim,
+                  self.num_heads, self.H_sp, self.W_sp, self.scale, self.precision if precision is None else precision)
+
+    _mi355_fp16_io_saturates = True          # an fp16 qkv is guarded like an fp32 one: the core's fp16 context can saturate
 
     def forward(self, qkv):
-        """qkv: (3,B,L,C) as in the reference (cswin.py:101-105); returns (B,L,C)."""
+        """qkv: (3,B,L,C) as in the reference (cswin.py:101-105); returns (B,L,C).  fp32, or fp16 / bf16: the result then has the type
+        of qkv, which is the operand format of the 16-bit core whatever `precision` says; precision 0 (or a strict re-run) widens,
+        runs the strict core and rounds."""
         three, B, L, C = qkv.shape
         assert three == 3 and C == self.dim and L == self.resolution * self.resolution, "flatten img_tokens has wrong size"
+        if _is16(qkv):
+            qkv, io = F._require_io16(qkv, "qkv")
+            p = _io_precision(self.precision, io)
+            buf = qkv.permute(1, 2, 0, 3).contiguous().view(B, L, 3 * C)
+            if p:
+                return self.run(buf, torch.empty(B, L, C, dtype=qkv.dtype, device=qkv.device), 0, p, _p32)
+            out = torch.empty(B, L, C, dtype=torch.float32, device=qkv.device)
+            return F.round16(self.run(F.widen16(buf), out, 0, p, _p32), qkv.dtype)
         buf = qkv.permute(1, 2, 0, 3).contiguous().view(B, L, 3 * C)     # no copy when qkv is the usual permuted view
         out = torch.empty(B, L, C, dtype=torch.float32, device=qkv.device)
         return self.run(buf, out, 0)
@@ -90,7 +106,71 @@ class CSWinBlock(nn.Module):
         self.mlp.precision = precision
         self.norm2 = norm_layer(dim)
 
+    _mi355_fp16_io_saturates = True          # an fp16 x is guarded like an fp32 one: fp16 operands and the 16-bit y store can saturate
+
+    def _forward16(self, x):
+        """The block on an fp16 / bf16 x; the result has the type of x.  The MFMA operand format is that type (fp16: the precision-1
+        arithmetic, bf16: precision 2) and a `precision` of None / 1 / 2 / 3 is ignored; precision 0 (explicit, the package default, or
+        a strict re-run) widens x, runs the strict route and rounds.  Parameters may be fp32 or 16-bit.  The residual stream inside the
+        block stays fp32 and y is rounded once.
+          A  narrow stages (F.cswin_stripe_ok): the stripe kernel reads x16 itself (cswin_stripe_kernel<.., x16>), the proj + MLP kernel
+             reads x16 and writes y16 (mlp_fused_kernel<.., proj, x16>) -- two launches, no widen, round or cast of an activation.  With
+             an MLP the fused kernel is not built for (mlp_ratio != 4): proj adds x16 as a 16-bit residual into the fp32 stream,
+             LayerNorm, fc1, and fc2 rounds y in its epilogue (gemm16_res_kernel).
+          B  head width 32 on the fast GEMMs, stripe kernel not applicable (C = 256 / 512, the one-branch last stage, stripes above 64
+             tokens): LayerNorm 1 reads x16 (layernorm_x16_kernel), qkv GEMM, the 16-bit LePE core, then the second half as in A.
+          C  everything else (precision 0, widths off the fast GEMM; another head width raises as it does in fp32): one widen launch,
+             the fp32 body, one round launch.
+        An fp16 y beyond 65504 is reported to the range guard (code 3) on every route but C, so the block re-runs strict and returns inf."""
+        x, io = F._require_io16(x, "x")
+        B, L, C = x.shape
+        assert L == self.patches_resolution ** 2, "flatten img_tokens has wrong size"
+        p = _io_precision(self.precision, io)
+        n1, n2, fc1, fc2 = self.norm1, self.norm2, self.mlp.fc1, self.mlp.fc2
+        a0 = self.attns[0]
+        if not (p and _fast(p, self.qkv, self.proj, fc1, fc2) and a0.dim // a0.num_heads == 32):
+            return F.round16(self._plain(F.widen16(x), p, _p32), x.dtype)
+        if self.branch_num == 2 and F.cswin_stripe_ok(C, self.patches_resolution, self.split_size, self.num_heads, p):
+            att = F.cswin_stripe_attention16(x, n1, self.qkv, a0.get_v, self.attns[1].get_v, self.patches_resolution, self.num_heads,
+                                             self.split_size, a0.scale)
+        else:
+            u = F.layernorm16_x16(x, n1.weight, n1.bias, n1.eps)
+            qkv = F.linear16(u, F.weight16(self.qkv.weight, p), _p32(self.qkv.bias, "qkv.bias"), out16=True, precision=p)
+            att = torch.empty(B, L, C, dtype=x.dtype, device=x.device)
+            if self.branch_num == 2:
+                a1 = self.attns[1]
+                F.cswin_lepe_attention16_pair(qkv, _p32(a0.get_v.weight, "attns.0.get_v.weight"), _p32(a0.get_v.bias, "attns.0.get_v.bias"),
+                                              _p32(a1.get_v.weight, "attns.1.get_v.weight"), _p32(a1.get_v.bias, "attns.1.get_v.bias"), att,
+                                              self.patches_resolution, a0.num_heads, self.split_size, a0.scale, p)
+            else:
+                a0.run(qkv, att, 0, p, _p32)
+        if F.proj_mlp_fused_ok(C, fc1.weight.shape[0], p) and fc1.bias is not None:
+            return F.proj_mlp_fused16(x, att, self.proj, n2, fc1, fc2)
+        x1 = F.linear16_res(att, F.weight16(self.proj.weight, p), self.proj.bias, x, precision=p)          # 16-bit residual, fp32 stream
+        u = F.layernorm16(x1, _p32(n2.weight, "norm2.weight"), _p32(n2.bias, "norm2.bias"), n2.eps, p)
+        h = F.linear16(u, F.weight16(fc1.weight, p), _p32(fc1.bias, "fc1.bias"), act=F.ACT_GELU, out16=True, precision=p)
+        return F.linear16_res(h, F.weight16(fc2.weight, p), fc2.bias, x1, out_dtype=x.dtype, precision=p)
+
+    def _plain(self, x, p, P):
+        """The body of forward() outside the 16-bit dataflow for the widened x of _forward16: the same calls at precision p (0, or the
+        type of the 16-bit x where a width is off the fast GEMM) with every parameter through P (_p32)."""
+        B, L, C = x.shape
+        n1, n2, fc1, fc2 = self.norm1, self.norm2, self.mlp.fc1, self.mlp.fc2
+        u = F.layernorm(x, P(n1.weight, "norm1.weight"), P(n1.bias, "norm1.bias"), n1.eps)
+        qkv = F.linear(u, P(self.qkv.weight, "qkv.weight"), P(self.qkv.bias, "qkv.bias"), precision=p)
+        att = torch.empty(B, L, C, dtype=torch.float32, device=x.device)
+        self.attns[0].run(qkv, att, 0, p, P)
+        if self.branch_num == 2:
+            self.attns[1].run(qkv, att, C // 2, p, P)
+        x = F.linear(att, P(self.proj.weight, "proj.weight"), P(self.proj.bias, "proj.bias"), resid=x, precision=p)
+        u = F.layernorm(x, P(n2.weight, "norm2.weight"), P(n2.bias, "norm2.bias"), n2.eps)
+        h = F.linear(u, P(fc1.weight, "fc1.weight"), P(fc1.bias, "fc1.bias"), act=F.ACT_GELU, precision=p)
+        return F.linear(h, P(fc2.weight, "fc2.weight"), P(fc2.bias, "fc2.bias"), resid=x, precision=p)
+
     def forward(self, x):
+        """x (B, L, C) fp32, or fp16 / bf16 (the result has the type of x; see _forward16)."""
+        if _is16(x):
+            return self._forward16(x)
         B, L, C = x.shape
         assert L == self.patches_resolution ** 2, "flatten img_tokens has wrong size"
         p = F._prec(self.precision)
@@ -152,9 +232,18 @@ class Merge_Block(nn.Module):
         self.norm = norm_layer(dim_out)
         self.precision = precision
 
+    _mi355_fp16_io_saturates = True          # the conv stages its operands in the format of the type: guarded like an fp32 x
+
     def forward(self, x):
+        """x (B, L, C) fp32, or fp16 / bf16: widened, the fp32 conv (operand format = the type; precision 0 stays strict) and LayerNorm,
+        rounded once -- the result has the type of x.  It runs three times per model: no 16-bit kernel of its own."""
         B, L, C = x.shape
         H = W = int(round(L ** 0.5))
+        if _is16(x):
+            x, io = F._require_io16(x, "x")
+            y, _ = F.conv2d_tokens(F.widen16(x), _p32(self.conv.weight, "conv.weight"), _p32(self.conv.bias, "conv.bias"), 3, 2, 1, in_layout=1,
+                                   hw=(H, W), precision=_io_precision(self.precision, io))
+            return F.round16(F.layernorm(y, _p32(self.norm.weight, "norm.weight"), _p32(self.norm.bias, "norm.bias"), self.norm.eps), x.dtype)
         y, _ = F.conv2d_tokens(x, self.conv.weight, self.conv.bias, 3, 2, 1, in_layout=1, hw=(H, W), precision=self.precision)
         return F.layernorm(y, self.norm.weight, self.norm.bias, self.norm.eps)
 
@@ -216,7 +305,37 @@ class CSWinTransformer(nn.Module):
         x = F.layernorm(x, self.norm.weight, self.norm.bias, self.norm.eps)
         return F.token_mean(x)
 
+    _mi355_fp16_io_saturates = True
+
+    def _forward16(self, img):
+        """The model on an fp16 / bf16 image: the composition of its parts on 16-bit tensors, logits in the type of the image.  The stem
+        (conv + LayerNorm) runs on the widened image and is rounded once; every block and merge is 16-bit in, 16-bit out; the final
+        LayerNorm reads the 16-bit stream (layernorm_x16_kernel), the token mean accumulates it in fp32, the head is fp32 and the
+        (B, classes) logits are the one torch cast.  Precision 0 (or a strict re-run): the final LayerNorm is the fp32 one on the widened
+        stream."""
+        img, io = F._require_io16(img, "img")
+        p = _io_precision(self.precision, io)
+        stem, ln = self.stage1_conv_embed[0], self.stage1_conv_embed[2]
+        x, _ = F.conv2d_tokens(F.widen16(img), _p32(stem.weight, "stem.weight"), _p32(stem.bias, "stem.bias"), 7, 4, 2, in_layout=0, precision=p)
+        x = F.round16(F.layernorm(x, _p32(ln.weight, "stem.norm.weight"), _p32(ln.bias, "stem.norm.bias"), ln.eps), img.dtype)
+        for blk in self.stage1:
+            x = blk(x)
+        for pre, blocks in ((self.merge1, self.stage2), (self.merge2, self.stage3), (self.merge3, self.stage4)):
+            x = pre(x)
+            for blk in blocks:
+                x = blk(x)
+        if p:
+            pooled = F.token_mean16(F.layernorm16_x16(x, self.norm.weight, self.norm.bias, self.norm.eps))
+        else:
+            pooled = F.token_mean(F.layernorm(F.widen16(x), _p32(self.norm.weight, "norm.weight"), _p32(self.norm.bias, "norm.bias"), self.norm.eps))
+        if isinstance(self.head, nn.Identity):
+            return pooled.to(img.dtype)
+        return F.linear(pooled, _p32(self.head.weight, "head.weight"), _p32(self.head.bias, "head.bias"), precision=p).to(img.dtype)
+
     def forward(self, x):
+        """x (B, 3, H, W) fp32, or fp16 / bf16 (logits in the type of x; see _forward16)."""
+        if _is16(x):
+            return self._forward16(x)
         x = self.forward_features(x)
         if isinstance(self.head, nn.Identity):
             return x
