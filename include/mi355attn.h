@@ -627,6 +627,16 @@ int mi355_linear16_x32_fwd(const float* X32, const void* W16, const float* bias,
  * aligned; the other buffers 16-byte aligned.  A stride off these rules is MI355_EUNSUPPORTED like a shape outside the envelope. */
 int mi355_linear16_stats_fwd(const void* X16, const void* W16, const float* bias, const float* resid, float* Y, int M, int N, int K, int ldx,
                              int ldy, int precision, float* row_stats, float eps, mi355_stream_t stream);
+/* mi355_linear16_stats_fwd with a 16-bit residual: resid16 (M, N; row stride ldy ELEMENTS, the stride of Y) is in the operand type of
+ * `precision` (1 fp16, 2 bf16) -- the 16-bit input of an XCABlock on fp16 / bf16 activations, added by its proj GEMM.  A lane reads its
+ * four residual values as one 8-byte load and widens them in registers (exact); the fp32 sum resid + X16 W16^T + bias is stored as it
+ * is -- Y is fp32 and nothing is rounded here: the block rounds ONCE, in the epilogue of its last stage -- so Y and row_stats hold the
+ * bits mi355_linear16_stats_fwd writes for resid16 widened to fp32.  No 16-bit store: no range code.  Envelope and strides are that
+ * entry's: N = K = 256 / 384, M >= 32, option "gemm_wreg" = 1, ldx % 8 == 0, ldy % 4 == 0, row_stats 8-byte aligned, the other buffers
+ * 16-byte aligned; anything else is MI355_EUNSUPPORTED before any launch (NULL pointers, non-positive sizes and a precision other than
+ * 1 / 2: MI355_EINVAL).  No workspace. */
+int mi355_linear16_stats_r16_fwd(const void* X16, const void* W16, const float* bias, const void* resid16, float* Y, int M, int N, int K,
+                                 int ldx, int ldy, int precision, float* row_stats, float eps, mi355_stream_t stream);
 /* Y = resid + X16 W16^T + bias (fp32) AND the next LayerNorm of every row of Y in the 16-bit operand format:
  * U16[m][n] = T((Y[m][n] - mean_m) / sqrt(var_m + eps) * ln_w[n] + ln_b[n]) (row stride ldu elements) -- what mi355_layernorm16_fwd would
  * compute from Y with a launch and a pass of its own.  Built at N = K = 256, M >= 32 (other shapes MI355_EUNSUPPORTED).  CSWinBlock at stage 3 (cswin.py:192-194):
@@ -716,6 +726,15 @@ int mi355_layernorm16_x16_fwd(const void* x16, const float* weight, const float*
  * between workgroups: safe under hipGraph capture, a row's bits do not depend on the rows around it.  Y must not overlap X16 or W16. */
 int mi355_linear16_res_fwd(const void* X16, const void* W16, const float* bias, const void* resid, int resid_io, void* Y, int out_io, int M,
                            int N, int K, int ldx, int ldy, int act, int precision, mi355_stream_t stream);
+/* mi355_linear16_res_fwd with a LayerScale: Y = round_out( widen(resid) + gamma * act(X16 . W16^T + bias) ), gamma (N) fp32, 16-byte
+ * aligned, or NULL (then this IS mi355_linear16_res_fwd: the same kernel, the same bits).  Epilogue order bias, act, * gamma, + residual
+ * -- the order of mi355_linear16_ws_fwd -- and the fp32 sum is rounded ONCE, so Y holds that entry's bits for the widened residual
+ * (rounded to the type where out_io is 16-bit).  For the XCiT blocks whose gamma cannot be folded into fp16 weights (eta = 1e-5:
+ * gamma * W lies in the fp16 subnormals) behind a 16-bit residual or in front of a 16-bit store.  An fp16 Y beyond 65504 is reported
+ * with range code 3.  Envelope, strides and argument checks are mi355_linear16_res_fwd's (K % 64 == 0, N % 8 == 0, 16-byte aligned
+ * buffers, at least one of resid_io / out_io 16-bit; else MI355_EUNSUPPORTED, nothing launched).  No workspace. */
+int mi355_linear16_res_scale_fwd(const void* X16, const void* W16, const float* bias, const float* gamma, const void* resid, int resid_io,
+                                 void* Y, int out_io, int M, int N, int K, int ldx, int ldy, int act, int precision, mi355_stream_t stream);
 /* LayerNorm + Linear in one pass for narrow rows (K = 64 or 128 = the normalised width; CSWin stage 1 / 2 and XCiT-nano qkv):
  *   Y = act( ((x - mean) / sqrt(var + eps)) . W16^T + bias ),  x (M,K) fp32 with row stride ldx floats, Y fp32 or 16-bit (out16).
  * The LayerNorm affine part must be folded into W16 / bias by the caller (W' = W diag(ln_weight), b' = b + W ln_bias).  The rows are
@@ -818,6 +837,17 @@ int mi355_cswin_stripe_attn_x16_fwd(const void* x16, const void* wqkv16, const f
  * mi355_proj_mlp_fused_fwd takes the same flag word. */
 int mi355_mlp_fused_fwd(const float* x, const void* w1_16, const float* b1, const void* w2_16, const float* b2, const float* gamma,
                         float* y, long M, int C, int hidden, int layernorm, float eps, int precision, mi355_stream_t stream);
+/* mi355_mlp_fused_fwd with a 16-bit result: y16 (M, C) is in the operand type of `precision` (1 fp16, 2 bf16), x stays fp32 and is read
+ * as there -- the last third of an XCABlock on fp16 / bf16 activations, whose residual stream behind LPI is fp32 and whose output is
+ * 16-bit.  The epilogue (+ b2) * gamma, + x is that entry's up to the store, which rounds the fp32 sum ONCE, to nearest even, and writes
+ * 16 bytes per lane: y16 holds mi355_mlp_fused_fwd's y rounded to the type.  An fp16 y of magnitude >= 65520 is reported to the range
+ * word with code 3 whether or not bit 1 of `layernorm` is set (that bit only silences code 4); bf16 is never reported.  Built for
+ * C = 64 / hidden 256 (option "mlp_tt4" as there) and C = 128 / hidden 512 (w2_16 slice-major): the grids and the LDS of those kernels;
+ * every other shape -- C = 256 / 384 included -- is MI355_EUNSUPPORTED, as is a buffer that is not 16-byte aligned (x, y16, the
+ * weights), before any launch.  NULL pointers, M <= 0, a precision other than 1 / 2 and a flag word outside 0..3: MI355_EINVAL.
+ * No workspace, no scratch; y16 must not overlap x. */
+int mi355_mlp_fused_o16_fwd(const float* x, const void* w1_16, const float* b1, const void* w2_16, const float* b2, const float* gamma,
+                            void* y16, long M, int C, int hidden, int layernorm, float eps, int precision, mi355_stream_t stream);
 
 /* ---- attention cores ------------------------------------------------------------------------------ */
 

@@ -280,7 +280,7 @@ int range_pending(const char* who) {
     if (!w || !__atomic_load_n(w, __ATOMIC_ACQUIRE)) return MI355_OK;
     const unsigned code = __atomic_exchange_n(w, 0u, __ATOMIC_ACQ_REL);
     if (!code) return MI355_OK;
-    static const char* const names[] = {"?", "mi355_cast16_fwd", "mi355_layernorm16_fwd", "a 16-bit-output GEMM epilogue (mi355_linear16_fwd family) or the 16-bit store of mi355_proj_mlp_fused_x16_fwd",
+    static const char* const names[] = {"?", "mi355_cast16_fwd", "mi355_layernorm16_fwd", "a 16-bit-output GEMM epilogue (mi355_linear16_fwd family) or the 16-bit store of mi355_proj_mlp_fused_x16_fwd / mi355_mlp_fused_o16_fwd",
                                         "a fused block kernel (mi355_mlp_fused_fwd / mi355_proj_mlp_fused_fwd / mi355_cswin_stripe_attn_fwd / "
                                         "mi355_ln_linear16_fwd / mi355_layernorm16_t_fwd / mi355_mixer_token_fwd)",
                                         "the LayerNorm-folding GEMM epilogue (mi355_linear16_lnc_fwd / mi355_ln_center16_fwd)",

@@ -52,7 +52,7 @@ int gemm16_p8(const g16::G16Args& g, int out16, int precision, void* ws, size_t 
 size_t gemm16_p8_workspace_bytes(int M, int N, int K);
 int gemm16_pa(const g16::G16Args& g, int out16, int precision, hipStream_t st, int abl = 0);        // g.lnc_a != null: emitting variant                                 // gemm16_pa.hip
 int gemm16_w4(const g16::G16Args& g, int out16, int precision, hipStream_t st);                        // gemm16_w4.hip
-int gemm16_wreg(const g16::G16Args& g, int out16, int precision, hipStream_t st);                      // gemm16_wreg.hip
+int gemm16_wreg(const g16::G16Args& g, int out16, int precision, hipStream_t st, bool resid16 = false);    // gemm16_wreg.hip; resid16: g.resid points at 16-bit rows
 int gemm16_wst(const g16::G16Args& g, int out16, int precision, hipStream_t st, bool one_wave = false);                       // gemm16_wst.hip
 int gemm16_wslab(const g16::G16Args& g, int out16, int precision, hipStream_t st);                     // gemm16_wslab.hip
 int gemm16_wslab_check(const g16::G16Args& g, int precision);                                            // would gemm16_wslab take it? (nothing launched)

@@ -498,13 +498,13 @@ int checked(int rc) {
 // also writes what the caller asked for in g (row statistics, or the next LayerNorm in the 16-bit operand format).  `entry` names the
 // caller in the error texts, `instead` what to use where the kernel is not built for the shape.  MI355_OK: launched, not yet checked.
 int linear16_wreg_fwd(G16Args& g, const void* X16, const void* W16, const float* bias, const float* resid, float* Y, int M, int N, int K,
-                      int ldx, int ldy, int precision, hipStream_t st, const char* entry, const char* instead) {
+                      int ldx, int ldy, int precision, hipStream_t st, const char* entry, const char* instead, bool resid16 = false) {
     if (!aligned16(X16) || !aligned16(W16) || !aligned16(Y) || !aligned16(resid) || (bias && !aligned16(bias)) || !mi355::opt(mi355::O_GEMM_WREG))
         return mi355::fail(MI355_EUNSUPPORTED, "%s: 16-byte aligned buffers and option gemm_wreg = 1 required", entry);
     g.A = X16; g.B = W16; g.C = Y; g.bias = bias; g.resid = resid;
     g.M = M; g.N = N; g.K = K; g.lda = ldx; g.ldb = K; g.ldc = ldy; g.act = MI355_ACT_NONE;
     if (g.ln16_out && precision == MI355_PREC_FP16) g.ovf = mi355::range_word(st);     // U16 is an fp16 operand tensor: a producer
-    const int rc = mi355::gemm16_wreg(g, 0, precision, st);
+    const int rc = mi355::gemm16_wreg(g, 0, precision, st, resid16);
     if (rc == MI355_EUNSUPPORTED)
         return mi355::fail(rc, "%s: built for N = K = 256 / 384, M >= 32 (got M=%d N=%d K=%d): use mi355_linear16_fwd %s", entry, M, N, K, instead);
     return rc;
@@ -611,6 +611,22 @@ int mi355_linear16_stats_fwd(const void* X16, const void* W16, const float* bias
     g.row_stats = row_stats; g.ln_eps = eps;
     if (const int rc = linear16_wreg_fwd(g, X16, W16, bias, resid, Y, M, N, K, ldx, ldy, precision, static_cast<hipStream_t>(stream),
                                          "mi355_linear16_stats_fwd", "and a statistics pass"))
+        return rc;
+    MI355_LAUNCH_CHECK();
+    return MI355_OK;
+}
+
+// mi355_linear16_stats_fwd with the residual in the operand type (gemm16_wreg_r16_kernel): the argument block carries the pointer in its
+// fp32 slot and the kernel choice knows (resid16)
+int mi355_linear16_stats_r16_fwd(const void* X16, const void* W16, const float* bias, const void* resid16, float* Y, int M, int N, int K, int ldx,
+                                 int ldy, int precision, float* row_stats, float eps, mi355_stream_t stream) {
+    MI355_CHECK_ARG(X16 && W16 && resid16 && Y && row_stats && M > 0 && N > 0 && K > 0 && ldx >= K && ldy >= N);
+    MI355_CHECK_ARG(precision == MI355_PREC_FP16 || precision == MI355_PREC_BF16);
+    G16Args g{};
+    g.row_stats = row_stats; g.ln_eps = eps;
+    if (const int rc = linear16_wreg_fwd(g, X16, W16, bias, static_cast<const float*>(resid16), Y, M, N, K, ldx, ldy, precision,
+                                         static_cast<hipStream_t>(stream), "mi355_linear16_stats_r16_fwd",
+                                         "(mi355_linear16_res_scale_fwd for a 16-bit residual) and a statistics pass", true))
         return rc;
     MI355_LAUNCH_CHECK();
     return MI355_OK;

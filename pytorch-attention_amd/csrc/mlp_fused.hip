@@ -19,7 +19,7 @@
 namespace {
 
 struct MlpArgs {
-    const void* x; void* y;                    // (M, C) fp32; the IO16 instantiations: 16-bit in the operand type
+    const void* x; void* y;                    // (M, C) fp32; the IO16 instantiations: 16-bit in the operand type; the o16 kernels: y alone
     const void* w1; const void* w2;            // 16-bit: (HD, C) and (C, HD), row-major
     const float* b1; const float* b2; const float* gamma;
     long M;
@@ -31,457 +31,19 @@ struct MlpArgs {
     // fp16 range word (common.h rg_report_f, code 4; null for bf16 / under capture without a word): gelu(H) is the one 16-bit intermediate
     // whose magnitude the weights do not bound a priori -- LN(x) is at most sqrt(C - 1) -- and it never reaches HBM, so nobody else sees it
     unsigned* ovf;
-    // IO16 kernels in fp16: the range word again for the y store (code 3, as gemm16_res_kernel reports its 16-bit stores) -- set whether
+    // IO16 and o16 kernels in fp16: the range word again for the y store (code 3, as gemm16_res_kernel reports its 16-bit stores) -- set whether
     // or not the hidden activation is proven, since y = x1 + ... is bounded by nothing
     unsigned* ovf_y;
 };
 
-// NWV waves per workgroup (one workgroup per CU), TT 16-token tiles per wave and step.  <16, 2>: 128 registers per lane, four waves per
-// SIMD (the default).  <8, 4> (option "mlp_tt4"): 256 registers, two waves per SIMD, every weight fragment read from LDS feeds FOUR
-// MFMAs instead of two -- the lever VERDICT rounds 2-4 name for CSWin stages 1-2; measured in round 5.
-// IO16 (PROJ only: mi355_proj_mlp_fused_x16_fwd): x and y are 16-bit in the operand type.  x is read once, at the top of the chunk, as one
-// 16-byte load of 8 elements per lane and k-step and widened (exact); the epilogue rounds the fp32 sums x1 + mlp once and stores 16 bytes.
-template <int PREC, int C, int HD, bool PROJ = false, int NWV = 16, int TT = 2, bool IO16 = false>
-__global__ __launch_bounds__(NWV * 64, NWV / 4) void mlp_fused_kernel(const MlpArgs a) {
-    static_assert(!IO16 || PROJ, "the 16-bit I/O form exists for the proj + MLP kernels");
-    // PARK (the 16-bit I/O form at 128 registers per lane): x1 of the second token tile waits in the wave's slab -- unused until the epilogue --
-    // while the hidden blocks run, and comes back into registers in front of the epilogue.  Sixteen registers fewer across the main loop:
-    // no scratch.  A lane reads back what it wrote itself; the values and the order of the arithmetic are the same.
-    constexpr bool PARK = IO16 && TT == 2;
-    using M_ = Mma<PREC>;
-    using v8 = typename M_::v8;
-    using v4 = typename M_::v4;
-    using el = typename M_::e;
-    constexpr int NTH = NWV * 64;                   // threads per workgroup
-    constexpr int P1 = C + 8;                       // W1 row pitch (elements): rows = hidden units, k = channels
-    constexpr int P2 = HD + 4;                      // W2 row pitch: rows = output channels, k = hidden units
-    constexpr int SP = C + 4;                       // slab pitch (floats)
-    constexpr int KS = C / 32, NT = C / 16, NKB = HD / 32;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    el* s_w1 = reinterpret_cast<el*>(lds);
-    el* s_w2 = s_w1 + HD * P1;
-    float* s_b1 = reinterpret_cast<float*>(s_w2 + C * P2);
-    float* s_slab = s_b1 + HD;
-    el* s_wp = reinterpret_cast<el*>(s_slab + NWV * 16 * SP);          // PROJ: (C, C) rows = output channels, pitch P1
-
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l15 = lane & 15, g = lane >> 4;
-    // ---- weights -> LDS once per workgroup (16-byte chunks) -----------------------------------------------------------------------
-    {
-        const el* w1 = static_cast<const el*>(a.w1);
-        const el* w2 = static_cast<const el*>(a.w2);
-        for (int i = t; i < HD * (C / 8); i += NTH) {
-            const int r = i / (C / 8), c8 = (i % (C / 8)) * 8;
-            *reinterpret_cast<v8*>(s_w1 + r * P1 + c8) = *reinterpret_cast<const v8*>(w1 + (long)r * C + c8);
-        }
-        for (int i = t; i < C * (HD / 4); i += NTH) {
-            const int r = i / (HD / 4), c4 = (i % (HD / 4)) * 4;
-            *reinterpret_cast<v4*>(s_w2 + r * P2 + c4) = *reinterpret_cast<const v4*>(w2 + (long)r * HD + c4);
-        }
-        for (int i = t; i < HD; i += NTH) s_b1[i] = a.b1[i];
-        if constexpr (PROJ) {
-            const el* wp = static_cast<const el*>(a.wp);
-            for (int i = t; i < C * (C / 8); i += NTH) {
-                const int r = i / (C / 8), c8 = (i % (C / 8)) * 8;
-                *reinterpret_cast<v8*>(s_wp + r * P1 + c8) = *reinterpret_cast<const v8*>(wp + (long)r * C + c8);
-            }
-        }
-    }
-    __syncthreads();
-    float* slab = s_slab + wave * 16 * SP;
-    const float invC = 1.0f / (float)C;
-    float rgmax = 0.f, rgy = 0.f;
-
-    const long nchunk = (a.M + 16 * TT - 1) / (16 * TT);
-    for (long ch = (long)blockIdx.x * NWV + wave; ch < nchunk; ch += (long)gridDim.x * NWV) {
-        const long tok0 = ch * (16 * TT);
-        // ---- tokens in B-operand layout: lane (l15, g) holds channels ks*32 + g*8 + [0,8) of token tok0 + tt*16 + l15 -------------
-        v8 xb[TT][KS];
-        f4 x1lo[PROJ && !PARK ? TT : 1][KS], x1hi[PROJ && !PARK ? TT : 1][KS];       // PROJ: the residual stream after the projection, kept for the epilogue
-#pragma unroll
-        for (int tt = 0; tt < TT; ++tt) {
-            const long tok = tok0 + tt * 16 + l15;
-            f4 lo[KS], hi[KS];
-            const long xo = (tok < a.M ? tok : 0) * C + g * 8;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                if constexpr (IO16) {
-                    const v8 h = *reinterpret_cast<const v8*>(static_cast<const el*>(a.x) + xo + ks * 32);
-                    lo[ks] = f4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
-                    hi[ks] = f4{(float)h[4], (float)h[5], (float)h[6], (float)h[7]};
-                } else {
-                    const float* xr = static_cast<const float*>(a.x) + xo;
-                    lo[ks] = *reinterpret_cast<const f4*>(xr + ks * 32);
-                    hi[ks] = *reinterpret_cast<const f4*>(xr + ks * 32 + 4);
-                }
-            }
-            if constexpr (PROJ) {
-                // x1 = x + ctx Wp^T + bp.  P^T = Wp . ctx^T with the rows of each 16-row MFMA tile PERMUTED so that the accumulator
-                // layout (lane (l15, g): rows g*4 + r of token l15) is the layout x is held in (channels ks*32 + g*8 + [0,8)):
-                // tile (ks', h) row i  <->  output channel ks'*32 + (i / 4)*8 + h*4 + i % 4
-                const el* cr = static_cast<const el*>(a.ctx) + (tok < a.M ? tok : 0) * C + g * 8;
-                v8 cb[KS];
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) cb[ks] = *reinterpret_cast<const v8*>(cr + ks * 32);
-#pragma unroll
-                for (int kp = 0; kp < KS; ++kp)
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        const int nrow = kp * 32 + (l15 >> 2) * 8 + h * 4 + (l15 & 3);
-                        f4 acc = *reinterpret_cast<const f4*>(a.bp + kp * 32 + g * 8 + h * 4);
-#pragma unroll
-                        for (int ks = 0; ks < KS; ++ks)
-                            acc = M_::mma(*reinterpret_cast<const v8*>(s_wp + nrow * P1 + ks * 32 + g * 8), cb[ks], acc);
-                        if (h == 0) lo[kp] = lo[kp] + acc; else hi[kp] = hi[kp] + acc;
-                    }
-                if (PARK && tt == 1) {
-#pragma unroll
-                    for (int ks = 0; ks < KS; ++ks) {
-                        *reinterpret_cast<f4*>(slab + l15 * SP + ks * 32 + g * 8) = lo[ks];
-                        *reinterpret_cast<f4*>(slab + l15 * SP + ks * 32 + g * 8 + 4) = hi[ks];
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                } else {
-#pragma unroll
-                    for (int ks = 0; ks < KS; ++ks) { x1lo[PARK ? 0 : tt][ks] = lo[ks]; x1hi[PARK ? 0 : tt][ks] = hi[ks]; }
-                }
-            }
-            float mean = 0.f, rstd = 1.f;
-            if (a.do_ln) {
-                float s = 0.f;
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) s += ((lo[ks].x + lo[ks].y) + (lo[ks].z + lo[ks].w)) + ((hi[ks].x + hi[ks].y) + (hi[ks].z + hi[ks].w));
-                s += __shfl_xor(s, 16, WAVE);
-                s += __shfl_xor(s, 32, WAVE);
-                mean = s * invC;
-                float q = 0.f;
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-                    const f4 d0 = lo[ks] - mean, d1 = hi[ks] - mean;
-                    q += ((d0.x * d0.x + d0.y * d0.y) + (d0.z * d0.z + d0.w * d0.w)) + ((d1.x * d1.x + d1.y * d1.y) + (d1.z * d1.z + d1.w * d1.w));
-                }
-                q += __shfl_xor(q, 16, WAVE);
-                q += __shfl_xor(q, 32, WAVE);
-                rstd = 1.0f / sqrtf(q * invC + a.eps);
-            }
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const v4 h0 = M_::cvt((lo[ks] - mean) * rstd), h1 = M_::cvt((hi[ks] - mean) * rstd);
-                xb[tt][ks] = v8{h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-            }
-        }
-        // ---- hidden units in blocks of 32: H^T = W1 Xn^T -> gelu -> Y += gelu(H) W2^T ------------------------------------------------
-        f4 o[TT][NT];
-#pragma unroll
-        for (int tt = 0; tt < TT; ++tt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) o[tt][nt] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-        for (int kb = 0; kb < NKB; ++kb) {
-            f4 s[TT][2];
-#pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2) {
-                const f4 bias = *reinterpret_cast<const f4*>(s_b1 + kb * 32 + h2 * 16 + g * 4);
-#pragma unroll
-                for (int tt = 0; tt < TT; ++tt) s[tt][h2] = bias;
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-                    const v8 wf = *reinterpret_cast<const v8*>(s_w1 + (kb * 32 + h2 * 16 + l15) * P1 + ks * 32 + g * 8);
-#pragma unroll
-                    for (int tt = 0; tt < TT; ++tt) s[tt][h2] = M_::mma(wf, xb[tt][ks], s[tt][h2]);
-                }
-            }
-            v8 pf[TT];
-#pragma unroll
-            for (int tt = 0; tt < TT; ++tt) {
-                f4 p0 = s[tt][0], p1 = s[tt][1];
-                p0 = gelu16_fast4(p0);
-                p1 = gelu16_fast4(p1);
-                if constexpr (PREC == 1) rgmax = rg_max3abs4(rg_max3abs4(rgmax, p0), p1);
-                const v4 h0 = M_::cvt(p0), h1 = M_::cvt(p1);
-                pf[tt] = v8{h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-            }
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const el* wr = s_w2 + (nt * 16 + l15) * P2 + kb * 32 + g * 4;
-                const v4 a0 = *reinterpret_cast<const v4*>(wr), a1 = *reinterpret_cast<const v4*>(wr + 16);
-                const v8 vf = v8{a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-#pragma unroll
-                for (int tt = 0; tt < TT; ++tt) o[tt][nt] = M_::mma(pf[tt], vf, o[tt][nt]);
-            }
-        }
-        // ---- epilogue per token tile: (+ b2) * gamma -> slab -> + x -> row stores ------------------------------------------------------
-        f4 pklo[PARK ? KS : 1], pkhi[PARK ? KS : 1];
-        if constexpr (PARK) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                pklo[ks] = *reinterpret_cast<const f4*>(slab + l15 * SP + ks * 32 + g * 8);
-                pkhi[ks] = *reinterpret_cast<const f4*>(slab + l15 * SP + ks * 32 + g * 8 + 4);
-            }
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        }
-#pragma unroll
-        for (int tt = 0; tt < TT; ++tt) {
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const int cidx = nt * 16 + l15;
-                const float b2 = a.b2 ? a.b2[cidx] : 0.f, gm = a.gamma ? a.gamma[cidx] : 1.f;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) slab[(g * 4 + r) * SP + cidx] = (o[tt][nt][r] + b2) * gm;
-            }
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            const long tok = tok0 + tt * 16 + l15;
-            if (tok < a.M) {
-                const float* xr = static_cast<const float*>(a.x) + tok * C + g * 8;       // !PROJ (fp32 only): x re-read
-                float* yr = static_cast<float*>(a.y) + tok * C + g * 8;
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-                    const f4 r0 = *reinterpret_cast<const f4*>(slab + l15 * SP + ks * 32 + g * 8);
-                    const f4 r1 = *reinterpret_cast<const f4*>(slab + l15 * SP + ks * 32 + g * 8 + 4);
-                    f4 x0, x1;
-                    if constexpr (PARK) { x0 = tt ? pklo[ks] : x1lo[0][ks]; x1 = tt ? pkhi[ks] : x1hi[0][ks]; }
-                    else if constexpr (PROJ) { x0 = x1lo[tt][ks]; x1 = x1hi[tt][ks]; }
-                    else { x0 = *reinterpret_cast<const f4*>(xr + ks * 32); x1 = *reinterpret_cast<const f4*>(xr + ks * 32 + 4); }
-                    if constexpr (IO16) {                           // 8 fp32 sums -> one conversion -> one 16-byte store
-                        const f4 s0 = x0 + r0, s1 = x1 + r1;
-                        if constexpr (PREC == 1) rgy = rg_absmax4(rg_absmax4(rgy, s0), s1);
-                        const v4 h0 = M_::cvt(s0), h1 = M_::cvt(s1);
-                        *reinterpret_cast<v8*>(static_cast<el*>(a.y) + tok * C + g * 8 + ks * 32) = v8{h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-                    } else {
-                        *reinterpret_cast<f4*>(yr + ks * 32) = x0 + r0;
-                        *reinterpret_cast<f4*>(yr + ks * 32 + 4) = x1 + r1;
-                    }
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        }
-    }
-    if constexpr (PREC == 1) rg_report_f(rgmax, a.ovf, 4u);
-    if constexpr (PREC == 1 && IO16) rg_report(rgy, a.ovf_y, 3u);
-}
-
-// ---- C = 128 (hidden 512: CSWin stage 2, XCiT-nano): the weights (256 KB) do not fit in LDS, so the waves of a workgroup walk the
-// hidden blocks in lockstep and the 32-unit slices of W1 (rows) and W2 (columns, pre-arranged slice-major by the caller) stream
-// through a double-buffered 16 KB LDS stage: loads of slice kb+1 are in flight during the MFMAs of slice kb, one barrier per slice.
-// EIGHT waves (one workgroup per CU, <= 256 VGPRs) with TWO 16-token tiles each: a weight fragment read from LDS feeds two MFMAs
-// (with sixteen one-tile waves the stage was read 256 KB per slice -- 2048 LDS clocks against 256 matrix-pipe clocks per wave), and
-// the two tiles give a wave independent MFMA chains to run the GELU of one under.
-// PROJ: x1 = x + ctx Wp^T + bp first (Wp resident in LDS).  x1 is parked in the y rows the lane will overwrite at the end and read
-// back there (same lane, same addresses: program order; the lines are L2-resident).
-// IO16: as in mlp_fused_kernel.
-template <int PREC, int C, int HD, bool PROJ = false, bool IO16 = false>
-__global__ __launch_bounds__(512, 2) void mlp_fused_stream_kernel(const MlpArgs a) {
-    static_assert(!IO16 || PROJ, "the 16-bit I/O form exists for the proj + MLP kernels");
-    using M_ = Mma<PREC>;
-    using v8 = typename M_::v8;
-    using v4 = typename M_::v4;
-    using el = typename M_::e;
-    constexpr int NWV = 8, TT = 2, NTHR = 64 * NWV;
-    constexpr int P1 = C + 8, P2 = 32 + 4, SPH = 64 + 4;       // W1 slice [32][P1], W2 slice [C][P2], slab [16][SPH] (64 channels at a time)
-    constexpr int KS = C / 32, NT = C / 16, NKB = HD / 32;
-    constexpr int W1S = 32 * P1, W2S = C * P2, STAGE = W1S + W2S;
-    static_assert(32 * C / 8 == NTHR && C * 32 / 8 == NTHR, "one 16-byte load of each matrix per thread and slice");
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    el* s_stage = reinterpret_cast<el*>(lds);                   // two stages
-    float* s_slab = reinterpret_cast<float*>(s_stage + 2 * STAGE);
-    el* s_wp = reinterpret_cast<el*>(s_slab + NWV * 16 * SPH);  // PROJ: (C, C), rows = output channels, pitch P1
-    // b1 lives in LDS: read from global memory inside the slice loop it sat BEHIND the fetch of the next weight slice in the wave's
-    // in-order memory queue, so every slice began by waiting for that fetch (the latency the double buffer is there to hide)
-    float* s_b1 = reinterpret_cast<float*>(s_wp + (PROJ ? C * P1 : 0));
-    for (int i = threadIdx.x; i < HD; i += NTHR) s_b1[i] = a.b1[i];
-    if constexpr (PROJ) {
-        const el* wp = static_cast<const el*>(a.wp);
-        for (int i = threadIdx.x; i < C * (C / 8); i += NTHR) {
-            const int r = i / (C / 8), c8 = (i % (C / 8)) * 8;
-            *reinterpret_cast<v8*>(s_wp + r * P1 + c8) = *reinterpret_cast<const v8*>(wp + (long)r * C + c8);
-        }
-        __syncthreads();
-    }
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l15 = lane & 15, g = lane >> 4;
-    float* slab = s_slab + wave * 16 * SPH;
-    const float invC = 1.0f / (float)C;
-    const el* w1 = static_cast<const el*>(a.w1);
-    const el* w2c = static_cast<const el*>(a.w2);               // (HD/32, C, 32) slice-major
-    // this thread's 16 bytes of every W1 slice (row r1, columns c1) and of every W2 slice (row r2, columns c2)
-    const int r1 = t / (C / 8), c1 = (t % (C / 8)) * 8, r2 = t / 4, c2 = (t % 4) * 8;
-    const int d1 = r1 * P1 + c1, d2 = W1S + r2 * P2 + c2;
-    v8 n1, n2;
-    auto fetch = [&](int kb) {
-        n1 = *reinterpret_cast<const v8*>(w1 + ((long)kb * 32 + r1) * C + c1);
-        n2 = *reinterpret_cast<const v8*>(w2c + ((long)kb * C + r2) * 32 + c2);
-    };
-    auto commit = [&](int buf) {
-        el* d = s_stage + buf * STAGE;
-        *reinterpret_cast<v8*>(d + d1) = n1;
-        *reinterpret_cast<v4*>(d + d2) = v4{n2[0], n2[1], n2[2], n2[3]};
-        *reinterpret_cast<v4*>(d + d2 + 4) = v4{n2[4], n2[5], n2[6], n2[7]};
-    };
-
-    float rgmax = 0.f, rgy = 0.f;
-    const long ntile = (a.M + 15) / 16;
-    const long niter = (ntile + NWV * TT - 1) / (NWV * TT);       // workgroup steps: 256 tokens each, uniform trip count for the barriers
-    for (long it = blockIdx.x; it < niter; it += gridDim.x) {
-        const long tok0 = (it * NWV + wave) * (16 * TT);
-        v8 xb[TT][KS];
-        f4 x1lo[PROJ ? TT : 1][KS], x1hi[PROJ ? TT : 1][KS];       // PROJ: the residual stream after the projection, kept for the epilogue
-#pragma unroll
-        for (int tt = 0; tt < TT; ++tt) {
-            const long tok = tok0 + tt * 16 + l15;
-            f4 lo[KS], hi[KS];
-            const long xo = (tok < a.M ? tok : 0) * C + g * 8;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                if constexpr (IO16) {
-                    const v8 h = *reinterpret_cast<const v8*>(static_cast<const el*>(a.x) + xo + ks * 32);
-                    lo[ks] = f4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
-                    hi[ks] = f4{(float)h[4], (float)h[5], (float)h[6], (float)h[7]};
-                } else {
-                    const float* xr = static_cast<const float*>(a.x) + xo;
-                    lo[ks] = *reinterpret_cast<const f4*>(xr + ks * 32);
-                    hi[ks] = *reinterpret_cast<const f4*>(xr + ks * 32 + 4);
-                }
-            }
-            if constexpr (PROJ) {                                   // see mlp_fused_kernel: permuted tile rows = the layout of lo / hi
-                const el* cr = static_cast<const el*>(a.ctx) + (tok < a.M ? tok : 0) * C + g * 8;
-                v8 cb[KS];
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) cb[ks] = *reinterpret_cast<const v8*>(cr + ks * 32);
-#pragma unroll
-                for (int kp = 0; kp < KS; ++kp)
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        const int nrow = kp * 32 + (l15 >> 2) * 8 + h * 4 + (l15 & 3);
-                        f4 acc = *reinterpret_cast<const f4*>(a.bp + kp * 32 + g * 8 + h * 4);
-#pragma unroll
-                        for (int ks = 0; ks < KS; ++ks)
-                            acc = M_::mma(*reinterpret_cast<const v8*>(s_wp + nrow * P1 + ks * 32 + g * 8), cb[ks], acc);
-                        if (h == 0) lo[kp] = lo[kp] + acc; else hi[kp] = hi[kp] + acc;
-                    }
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) { x1lo[tt][ks] = lo[ks]; x1hi[tt][ks] = hi[ks]; }
-            }
-            float mean = 0.f, rstd = 1.f;
-            if (a.do_ln) {
-                float s = 0.f;
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) s += ((lo[ks].x + lo[ks].y) + (lo[ks].z + lo[ks].w)) + ((hi[ks].x + hi[ks].y) + (hi[ks].z + hi[ks].w));
-                s += __shfl_xor(s, 16, WAVE);
-                s += __shfl_xor(s, 32, WAVE);
-                mean = s * invC;
-                float q = 0.f;
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-                    const f4 d0 = lo[ks] - mean, d1_ = hi[ks] - mean;
-                    q += ((d0.x * d0.x + d0.y * d0.y) + (d0.z * d0.z + d0.w * d0.w)) + ((d1_.x * d1_.x + d1_.y * d1_.y) + (d1_.z * d1_.z + d1_.w * d1_.w));
-                }
-                q += __shfl_xor(q, 16, WAVE);
-                q += __shfl_xor(q, 32, WAVE);
-                rstd = 1.0f / sqrtf(q * invC + a.eps);
-            }
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const v4 h0 = M_::cvt((lo[ks] - mean) * rstd), h1 = M_::cvt((hi[ks] - mean) * rstd);
-                xb[tt][ks] = v8{h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-            }
-        }
-        f4 o[TT][NT];
-#pragma unroll
-        for (int tt = 0; tt < TT; ++tt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) o[tt][nt] = f4{0.f, 0.f, 0.f, 0.f};
-        fetch(0);
-        __syncthreads();                                           // previous step's readers of stage 0 are done
-        commit(0);
-        __syncthreads();
-#pragma unroll 1
-        for (int kb = 0; kb < NKB; ++kb) {
-            const int buf = kb & 1;
-            if (kb + 1 < NKB) fetch(kb + 1);                       // in flight during the MFMAs below
-            const el* sw1 = s_stage + buf * STAGE;
-            const el* sw2 = sw1 + W1S;
-            f4 s[TT][2];
-#pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2) {
-                const f4 bias = *reinterpret_cast<const f4*>(s_b1 + kb * 32 + h2 * 16 + g * 4);
-#pragma unroll
-                for (int tt = 0; tt < TT; ++tt) s[tt][h2] = bias;
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-                    const v8 wf = *reinterpret_cast<const v8*>(sw1 + (h2 * 16 + l15) * P1 + ks * 32 + g * 8);
-#pragma unroll
-                    for (int tt = 0; tt < TT; ++tt) s[tt][h2] = M_::mma(wf, xb[tt][ks], s[tt][h2]);
-                }
-            }
-            v8 pf[TT];
-#pragma unroll
-            for (int tt = 0; tt < TT; ++tt) {
-                const f4 p0 = gelu16_fast4(s[tt][0]);
-                const f4 p1 = gelu16_fast4(s[tt][1]);
-                if constexpr (PREC == 1) rgmax = rg_max3abs4(rg_max3abs4(rgmax, p0), p1);
-                const v4 h0 = M_::cvt(p0), h1 = M_::cvt(p1);
-                pf[tt] = v8{h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-            }
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const el* wr = sw2 + (nt * 16 + l15) * P2 + g * 4;
-                const v4 a0 = *reinterpret_cast<const v4*>(wr), a1 = *reinterpret_cast<const v4*>(wr + 16);
-                const v8 vf = v8{a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-#pragma unroll
-                for (int tt = 0; tt < TT; ++tt) o[tt][nt] = M_::mma(pf[tt], vf, o[tt][nt]);
-            }
-            if (kb + 1 < NKB) {
-                commit(buf ^ 1);                                   // stage buf^1 was last read at slice kb-1: everybody passed the barrier below
-                __syncthreads();
-            }
-        }
-        // ---- epilogue per token tile, 64 channels at a time: (+ b2) * gamma -> slab -> + x -> row stores ---------------------------------
-#pragma unroll
-        for (int tt = 0; tt < TT; ++tt) {
-            const long tok = tok0 + tt * 16 + l15;
-#pragma unroll
-            for (int hh = 0; hh < C / 64; ++hh) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int cidx = hh * 64 + j * 16 + l15;
-                    const float b2 = a.b2 ? a.b2[cidx] : 0.f, gm = a.gamma ? a.gamma[cidx] : 1.f;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) slab[(g * 4 + r) * SPH + j * 16 + l15] = (o[tt][hh * 4 + j][r] + b2) * gm;
-                }
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                if (tok < a.M) {
-                    const float* xr = static_cast<const float*>(a.x) + tok * C + hh * 64 + g * 8;     // !PROJ (fp32 only): x re-read
-                    float* yr = static_cast<float*>(a.y) + tok * C + hh * 64 + g * 8;
-#pragma unroll
-                    for (int k2 = 0; k2 < 2; ++k2) {
-                        const f4 r0 = *reinterpret_cast<const f4*>(slab + l15 * SPH + k2 * 32 + g * 8);
-                        const f4 r1 = *reinterpret_cast<const f4*>(slab + l15 * SPH + k2 * 32 + g * 8 + 4);
-                        f4 x0, x1;
-                        if constexpr (PROJ) { x0 = x1lo[tt][hh * 2 + k2]; x1 = x1hi[tt][hh * 2 + k2]; }
-                        else { x0 = *reinterpret_cast<const f4*>(xr + k2 * 32); x1 = *reinterpret_cast<const f4*>(xr + k2 * 32 + 4); }
-                        if constexpr (IO16) {                       // 8 fp32 sums -> one conversion -> one 16-byte store
-                            const f4 s0 = x0 + r0, s1 = x1 + r1;
-                            if constexpr (PREC == 1) rgy = rg_absmax4(rg_absmax4(rgy, s0), s1);
-                            const v4 h0 = M_::cvt(s0), h1 = M_::cvt(s1);
-                            *reinterpret_cast<v8*>(static_cast<el*>(a.y) + tok * C + hh * 64 + g * 8 + k2 * 32) =
-                                v8{h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-                        } else {
-                            *reinterpret_cast<f4*>(yr + k2 * 32) = x0 + r0;
-                            *reinterpret_cast<f4*>(yr + k2 * 32 + 4) = x1 + r1;
-                        }
-                    }
-                }
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            }
-        }
-    }
-    if constexpr (PREC == 1) rg_report_f(rgmax, a.ovf, 4u);
-    if constexpr (PREC == 1 && IO16) rg_report(rgy, a.ovf_y, 3u);
-}
+// the kernels: once in the forms of mi355_mlp_fused_fwd / mi355_proj_mlp_fused_fwd / mi355_proj_mlp_fused_x16_fwd, once with an fp32 x and a
+// 16-bit y (mlp_fused_body.h)
+#define MLP_O16 0
+#include "mlp_fused_body.h"
+#undef MLP_O16
+#define MLP_O16 1
+#include "mlp_fused_body.h"
+#undef MLP_O16
 
 template <int C, int HD>
 constexpr size_t mlp_smem(bool proj = false) {
@@ -642,6 +204,64 @@ extern "C" int mi355_proj_mlp_fused_x16_fwd(const void* x16, const void* ctx16, 
     if (precision == MI355_PREC_FP16) MLP64(1, true, true);
     else MLP64(2, true, true);
 #undef MLP64
+    MI355_LAUNCH_CHECK();
+    return MI355_OK;
+}
+
+// mi355_mlp_fused_fwd with y16 (M, C) in the operand type of `precision` (I/O form 2): x stays fp32 -- the residual stream behind the LPI
+// third of an XCABlock on fp16 / bf16 activations -- and the epilogue rounds x + gamma * mlp once.  Same grids, same LDS; C = 64 / 128 only
+// (the weight-split kernel of C = 256 / 384 has no 16-bit store).
+extern "C" int mi355_mlp_fused_o16_fwd(const float* x, const void* w1_16, const float* b1, const void* w2_16, const float* b2, const float* gamma,
+                                       void* y16, long M, int C, int hidden, int layernorm, float eps, int precision, mi355_stream_t stream) {
+    MI355_CHECK_ARG(x && w1_16 && b1 && w2_16 && y16 && M > 0);
+    MI355_CHECK_ARG(precision == MI355_PREC_FP16 || precision == MI355_PREC_BF16);
+    MI355_CHECK_ARG(layernorm >= 0 && layernorm <= 3);                          // flag word: bit 0 LayerNorm, bit 1 range proven
+    if (!((C == 64 && hidden == 256) || (C == 128 && hidden == 512)))
+        return mi355::fail(MI355_EUNSUPPORTED, "mi355_mlp_fused_o16_fwd: built for C = 64, hidden = 256 and C = 128, hidden = 512 (got C = %d, hidden = %d)", C, hidden);
+    if (!aligned16(x) || !aligned16(y16) || !aligned16(w1_16) || !aligned16(w2_16))
+        return mi355::fail(MI355_EUNSUPPORTED, "mi355_mlp_fused_o16_fwd: 16-byte aligned buffers required");
+    MlpArgs a{};
+    a.x = x; a.y = y16; a.w1 = w1_16; a.w2 = w2_16; a.b1 = b1; a.b2 = b2; a.gamma = gamma; a.M = M; a.eps = eps; a.do_ln = (layernorm & 1) ? 1 : 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // the fp16 y store can always saturate (code 3): an fp16 launch is a producer whether or not the hidden activation is proven (bit 1)
+    a.ovf_y = precision == MI355_PREC_FP16 ? mi355::range_word(st) : nullptr;
+    a.ovf = (layernorm & 2) ? nullptr : a.ovf_y;
+    const int ncu = mi355::resident_slots(1);
+    MI355_TRACE(st, "mlp_fused_kernel<C=%d,o16> M=%ld", C, M);
+    if (C == 128) {
+        constexpr size_t sm = (size_t)2 * (32 * (128 + 8) + 128 * 36) * 2 + (size_t)8 * 16 * 68 * 4 + (size_t)512 * 4;
+        static_assert(sm <= 160 * 1024, "LDS budget");
+        const long niter = ((M + 15) / 16 + 15) / 16;
+        const int grid2 = (int)(niter < ncu ? niter : ncu);
+        if (precision == MI355_PREC_FP16) {
+            if (int rc = mi355::func_dynamic_lds(reinterpret_cast<const void*>(mlp_fused_stream_o16_kernel<1, 128, 512>), (int)sm)) return rc;
+            mlp_fused_stream_o16_kernel<1, 128, 512><<<grid2, 512, sm, st>>>(a);
+        } else {
+            if (int rc = mi355::func_dynamic_lds(reinterpret_cast<const void*>(mlp_fused_stream_o16_kernel<2, 128, 512>), (int)sm)) return rc;
+            mlp_fused_stream_o16_kernel<2, 128, 512><<<grid2, 512, sm, st>>>(a);
+        }
+        MI355_LAUNCH_CHECK();
+        return MI355_OK;
+    }
+    constexpr size_t smem = mlp_smem<64, 256>();
+    static_assert(smem <= 160 * 1024, "LDS budget");
+    const bool tt4 = mi355::opt(mi355::O_MLP_TT4) != 0;
+    const long nchunk = (M + (tt4 ? 63 : 31)) / (tt4 ? 64 : 32);
+    long grid = (nchunk + (tt4 ? 7 : 15)) / (tt4 ? 8 : 16);
+    if (grid > ncu) grid = ncu;
+#define MLP64_O16(P_)                                                                                                                     \
+    do {                                                                                                                                  \
+        if (tt4) {                                                                                                                        \
+            if (int rc = mi355::func_dynamic_lds(reinterpret_cast<const void*>(mlp_fused_o16_kernel<P_, 64, 256, 8, 4>), (int)smem)) return rc;  \
+            mlp_fused_o16_kernel<P_, 64, 256, 8, 4><<<(int)grid, 512, smem, st>>>(a);                                                       \
+        } else {                                                                                                                          \
+            if (int rc = mi355::func_dynamic_lds(reinterpret_cast<const void*>(mlp_fused_o16_kernel<P_, 64, 256, 16, 2>), (int)smem)) return rc; \
+            mlp_fused_o16_kernel<P_, 64, 256, 16, 2><<<(int)grid, 1024, smem, st>>>(a);                                                     \
+        }                                                                                                                                 \
+    } while (0)
+    if (precision == MI355_PREC_FP16) MLP64_O16(1);
+    else MLP64_O16(2);
+#undef MLP64_O16
     MI355_LAUNCH_CHECK();
     return MI355_OK;
 }

@@ -150,12 +150,14 @@ SIGNATURES = {
     # the ViT encoder on fp16 / bf16 activations (csrc/layernorm.hip, csrc/gemm16_res.hip)
     "mi355_layernorm16_x16_fwd": (c_int, [c_vp] * 4 + [c_int, c_int, c_float, c_int, c_vp]),
     "mi355_linear16_res_fwd": (c_int, [c_vp] * 4 + [c_int, c_vp] + [c_int] * 8 + [c_vp]),
+    "mi355_linear16_res_scale_fwd": (c_int, [c_vp] * 5 + [c_int, c_vp] + [c_int] * 8 + [c_vp]),
     "mi355_dwconv_nchw_tokens_fwd":(c_int, [c_vp] * 4 + [c_int] * 5 + [c_vp]),
     "mi355_qk_logits_fwd": (c_int, [c_vp] * 3 + [c_int] * 8 + [c_vp]),
     "mi355_topk_mask_fwd": (c_int, [c_vp, ctypes.c_long, c_int, c_int, c_vp]),
     "mi355_adaptive_pool_tokens_fwd": (c_int, [c_vp] * 2 + [c_int] * 6 + [c_vp]),
     "mi355_dwconv3x3_tokens_residual_fwd": (c_int, [c_vp] * 4 + [c_int] * 4 + [ctypes.c_long, c_vp]),
     "mi355_mlp_fused_fwd": (c_int, [c_vp] * 7 + [ctypes.c_long, c_int, c_int, c_int, ctypes.c_float, c_int, c_vp]),
+    "mi355_mlp_fused_o16_fwd": (c_int, [c_vp] * 7 + [ctypes.c_long, c_int, c_int, c_int, ctypes.c_float, c_int, c_vp]),
     "mi355_proj_mlp_fused_fwd": (c_int, [c_vp] * 10 + [ctypes.c_long, c_int, c_int, c_int, ctypes.c_float, c_int, c_vp]),
     "mi355_proj_mlp_fused_x16_fwd": (c_int, [c_vp] * 10 + [ctypes.c_long, c_int, c_int, c_int, ctypes.c_float, c_int, c_vp]),
     "mi355_sdpa_general_fwd": (c_int, [c_vp] * 5 + [c_int] * 5 + [ctypes.c_long] * 5 + [ctypes.c_float, c_int, c_int, c_vp]),
@@ -177,6 +179,7 @@ SIGNATURES = {
     "mi355_event_time_end": (c_int, [c_vp, c_vp, ctypes.POINTER(c_float)]),
     "mi355_linear16_x32_fwd": (c_int, [c_vp] * 4 + [c_int] * 7 + [c_vp]),
     "mi355_linear16_stats_fwd": (c_int, [c_vp] * 5 + [c_int] * 6 + [c_vp, c_float, c_vp]),
+    "mi355_linear16_stats_r16_fwd": (c_int, [c_vp] * 5 + [c_int] * 6 + [c_vp, c_float, c_vp]),
     "mi355_linear16_ln16_fwd": (c_int, [c_vp] * 7 + [c_float, c_vp] + [c_int] * 7 + [c_vp]),
     "mi355_ln_lpi_stats_fwd": (c_int, [c_vp] * 10 + [c_float] + [c_vp] * 5 + [c_int] * 4 + [c_vp]),
     # SURVEY.md 8(b) spellings: aliases of mi355_sdpa_fwd / mi355_linear_fwd / mi355_mixer_token_fwd and the zero-byte workspace queries
@@ -285,7 +288,8 @@ def require_device_f32(t, name):
                         "ChannelAttention, SpatialAttention, SELayerBias, SELayerBias4, SELayerHidden, SqueezeExcite, simam_module, SRM, "
                         "GaussianGCT, LCT, GCT, DoubleAttention, CoordinateAttention, TripletAttention, AttentionGate, MixerLayer, MLP_Mixer "
                         "(with its PatchEmbedding), TransformerEncoder, VisionTransformer (with its PatchEmbedding), CSWinBlock, LePEAttention, "
-                        "Merge_Block, CSWinTransformer, BAM, PAM and CAM only)")
+                        "Merge_Block, CSWinTransformer, XCABlock, XCA, LPI, ClassAttention, ClassAttentionBlock, ConvPatchEmbed, XCiT (with its Mlp), "
+                        "BAM, PAM and CAM only)")
     if t.requires_grad and torch.is_grad_enabled():
         _warn_no_autograd()
     return t if t.is_contiguous() else t.contiguous()

@@ -1283,23 +1283,88 @@ def linear16_res(x16, w16, bias, resid, act=ACT_NONE, out_dtype=torch.float32, p
     """Y = round( resid + act(x16 @ w16^T + bias) ) with a 16-bit residual, a 16-bit result, or both (mi355_linear16_res_fwd): the sum
     is formed in fp32 and rounded once.  resid: fp32 or the operand type of `precision`; out_dtype: torch.float32 or that type.  The
     all-fp32 pair is linear16's."""
+    return _linear16_res("linear16_res", x16, w16, bias, None, resid, act, out_dtype, precision)
+
+
+def linear16_res_scale(x16, w16, bias, gamma, resid, act=ACT_NONE, out_dtype=torch.float32, precision=None):
+    """linear16_res with a LayerScale: Y = round( resid + gamma * act(x16 @ w16^T + bias) ) (mi355_linear16_res_scale_fwd; epilogue order
+    bias, act, gamma, residual -- linear16's -- and one rounding).  gamma (N): fp32, or 16-bit through its cached fp32 copy, or None
+    (then the kernel is linear16_res's).  The XCiT block on 16-bit activations: the LayerScale that cannot be folded into fp16 weights."""
+    return _linear16_res("linear16_res_scale", x16, w16, bias, gamma, resid, act, out_dtype, precision)
+
+
+def _linear16_res(who, x16, w16, bias, gamma, resid, act, out_dtype, precision):
+    scale = who == "linear16_res_scale"
     _range_check()
     p = _prec(precision)
     x16 = _require16(x16, "x16", p)
     w16 = _require16(w16, "w16", p)
     bias = None if bias is None else param32(bias, "bias")
+    gamma = None if gamma is None else param32(gamma, "gamma").reshape(-1)
     N, K = w16.shape
     if x16.shape[-1] != K:
-        raise ValueError(f"linear16_res: x last dim {x16.shape[-1]} != weight in_features {K}")
+        raise ValueError(f"{who}: x last dim {x16.shape[-1]} != weight in_features {K}")
     M = x16.numel() // K
     if not isinstance(resid, torch.Tensor) or resid.numel() != M * N:
-        raise ValueError("linear16_res: residual shape mismatch")
+        raise ValueError(f"{who}: residual shape mismatch")
+    if gamma is not None and gamma.numel() != N:
+        raise ValueError(f"{who}: gamma must hold one value per output column")
     resid, rio = _ffi.require_device_io(resid, "resid")
     if rio not in (0, p) or out_dtype not in (torch.float32, dtype16(p)):
-        raise TypeError(f"linear16_res: residual and result are float32 or {dtype16(p)} (got {resid.dtype}, {out_dtype})")
+        raise TypeError(f"{who}: residual and result are float32 or {dtype16(p)} (got {resid.dtype}, {out_dtype})")
     y = torch.empty(*x16.shape[:-1], N, dtype=out_dtype, device=x16.device)
-    check(lib().mi355_linear16_res_fwd(dptr(x16), dptr(w16), dptr(bias), dptr(resid), rio, dptr(y), 0 if out_dtype == torch.float32 else p,
-                                       M, N, K, K, N, act, p, stream_ptr(x16.device)), "mi355_linear16_res_fwd")
+    oio = 0 if out_dtype == torch.float32 else p
+    if scale:
+        check(lib().mi355_linear16_res_scale_fwd(dptr(x16), dptr(w16), dptr(bias), dptr(gamma), dptr(resid), rio, dptr(y), oio, M, N, K, K, N,
+                                                 act, p, stream_ptr(x16.device)), "mi355_linear16_res_scale_fwd")
+    else:
+        check(lib().mi355_linear16_res_fwd(dptr(x16), dptr(w16), dptr(bias), dptr(resid), rio, dptr(y), oio, M, N, K, K, N, act, p,
+                                           stream_ptr(x16.device)), "mi355_linear16_res_fwd")
+    return y
+
+
+def linear16_stats_r16(x16, w16, bias, resid16, eps, precision=None):
+    """linear16_stats with the residual in the operand type of `precision` (mi355_linear16_stats_r16_fwd): (Y, stats) with Y = resid16 +
+    x16 @ w16^T + bias in fp32 -- nothing is rounded -- and stats (rows, 2) = (mean, 1 / sqrt(var + eps)) of every row of Y: the bits
+    linear16_stats gives for resid16.float().  Returns None where the entry is not built for the shape (N = K = 256 / 384, M >= 32,
+    option "gemm_wreg" = 1)."""
+    _range_check()
+    p = _prec(precision)
+    x16 = _require16(x16, "x16", p)
+    w16 = _require16(w16, "w16", p)
+    N, K = w16.shape
+    M = x16.numel() // K
+    if not (N == K and K in (256, 384) and M >= 32 and resid16 is not None and _ffi.get_option("gemm_wreg") == 1):
+        return None
+    bias = None if bias is None else param32(bias, "bias")
+    resid16 = _require16(resid16, "resid16", p)
+    if resid16.numel() != M * N:
+        raise ValueError("linear16_stats_r16: residual shape mismatch")
+    y = torch.empty(x16.shape[:-1] + (N,), dtype=torch.float32, device=x16.device)
+    stats = torch.empty(M, 2, dtype=torch.float32, device=x16.device)
+    check(lib().mi355_linear16_stats_r16_fwd(dptr(x16), dptr(w16), dptr(bias), dptr(resid16), dptr(y), M, N, K, K, N, p, dptr(stats),
+                                             float(eps), stream_ptr(x16.device)), "mi355_linear16_stats_r16_fwd")
+    return y, stats
+
+
+def mlp_fused_o16(x, ln, fc1, fc2, gamma=None, precision=None):
+    """mlp_fused with a 16-bit result: y16 = round(x + gamma * fc2(gelu(fc1(ln(x))))) for an fp32 x, in the operand type of `precision`,
+    rounded once by the kernel (mi355_mlp_fused_o16_fwd): the bits of mlp_fused(x, ...).to(that type), without the round launch.  The last
+    third of an XCABlock on 16-bit activations.  Parameters: fp32, or 16-bit through their cached copies.  Returns None where the entry
+    is not built for the shape (C = 64 / hidden 256 and C = 128 / hidden 512 only: the weight-split kernel of C = 256 / 384 has no 16-bit
+    store) or fc1 has no bias: the caller runs LayerNorm, fc1 and linear16_res_scale."""
+    p = _prec(precision)
+    x = require_device_f32(x, "x")
+    C = x.shape[-1]
+    Hd = fc1.weight.shape[0]
+    if p not in (PREC_FP16, PREC_BF16) or (C, Hd) not in ((64, 256), (128, 512)) or fc1.bias is None:
+        return None
+    _range_check()
+    w1_16, b1, ln_flags, w2_16 = _mlp_fused_weights(ln, fc1, fc2, C, p)
+    y = torch.empty(x.shape, dtype=dtype16(p), device=x.device)
+    check(lib().mi355_mlp_fused_o16_fwd(dptr(x), dptr(w1_16), dptr(b1), dptr(w2_16), dptr(None if fc2.bias is None else param32(fc2.bias, "fc2.bias")),
+                                        dptr(None if gamma is None else param32(gamma, "gamma")), dptr(y), x.numel() // C, C, Hd, ln_flags,
+                                        float(ln.eps) if ln is not None else 0.0, p, stream_ptr(x.device)), "mi355_mlp_fused_o16_fwd")
     return y
 
 
@@ -1711,10 +1776,10 @@ def conv_bn_rows(conv_w, bn, in_layout):
     """Conv weight with the eval-mode BatchNorm that follows it folded in (xcit.py:79-86 conv3x3 = Conv2d(bias=False) + BatchNorm2d):
     w' = w * s, b' = beta - mean * s with s = gamma / sqrt(var + eps), as GEMM rows like conv_weight_rows.  Cached per version
     of the five tensors involved."""
-    def build():
-        s = bn.weight.detach() / torch.sqrt(bn.running_var.detach() + bn.eps)
-        bias = (bn.bias.detach() - bn.running_mean.detach() * s).contiguous()
-        return _gemm_rows(conv_w.detach() * s[:, None, None, None], in_layout), bias
+    def build():                                              # 16-bit parameters (module.half()): through their fp32 copies
+        s = _w32(bn.weight, "bn.weight") / torch.sqrt(_w32(bn.running_var, "bn.running_var") + bn.eps)
+        bias = (_w32(bn.bias, "bn.bias") - _w32(bn.running_mean, "bn.running_mean") * s).contiguous()
+        return _gemm_rows(_w32(conv_w, "conv.weight") * s[:, None, None, None], in_layout), bias
 
     tag = ((conv_w._version, conv_w.data_ptr(), tuple(conv_w.shape)),) + _bn_tag(bn)
     return _derived_get((conv_w, bn), ("bnrows", in_layout), tag, build)
