@@ -291,6 +291,31 @@ int    mi355_cbam16_fwd(const void* x, const float* w1, const float* w2, const f
                         int B, int C, int Cr, int ks, int H, int W, int stage, int io,
                         void* ws, size_t ws_bytes, mi355_stream_t stream);
 
+/* ---- SELayer / ECALayer / CBAM with the shortcut add (and ReLU) of their residual block in the store epilogue (gate_res.h) ----------------
+ *   y = gate(x) + resid          (relu = 0)
+ *   y = relu(gate(x) + resid)    (relu = 1; NaN stays NaN, as in torch.relu)
+ * where gate(x) is what mi355_se_fwd / mi355_eca_fwd / mi355_cbam_fwd (stage 0) compute: the call site of SE-ResNet, ECA-Net and CBAM-ResNet
+ * (out = se(out); out += identity; out = relu(out)) in two reads and one write of the map instead of seven passes.
+ * `io` selects the type of x, resid and y together: 0 = fp32, 1 = IEEE half, 2 = bfloat16; parameters stay fp32.  resid (B,C,H,W, dense
+ * NCHW like x) is non-NULL; relu is 0 or 1.  The arithmetic is fp32, in this order and never contracted: t = fl(x * g) (CBAM: the product
+ * (x * gc) * gs of the plain kernel), s = fl(t + widen(resid)), ReLU, ONE rounding to the I/O type at the store -- an fp32 result is bit
+ * for bit torch.relu(gate(x) + resid).  |y| can reach |x| + |resid|: an fp16 y is inf exactly where the fp32 sum rounds to inf, and that
+ * is not reported to mi355_range_status (the contract of mi355_bam16_fwd).
+ * The route (single-read or multi-pass form) is chosen by the plain entry's shape conditions and options ("se_single", "eca_single",
+ * "cbam_single"), the workspace is the plain entry's (mi355_se_workspace_bytes, mi355_eca_workspace_bytes, mi355_cbam_workspace_bytes for
+ * io 0 / mi355_cbam16_workspace_bytes otherwise) with the same layout, ticket and epoch words: plain calls, these calls and hipGraph
+ * replays of either can be mixed on one workspace.  (One exception to "the plain entry's route": single-read CBAM with 16 register slots
+ * per lane -- more than 128 / 256 channels at bands wider / narrower than 64 pixels -- runs one workgroup per CU here; an image with more
+ * bands than the device has CUs takes the multi-pass form, and its fp32 result has the bits of the multi-pass composition.)
+ * y must not overlap x or resid (MI355_EINVAL).  MI355_EINVAL with nothing launched: NULL pointers, non-positive sizes, relu outside 0 / 1,
+ * io outside 0 .. 2; MI355_EUNSUPPORTED with nothing launched: a shape the plain entry refuses, with that entry's code. */
+int    mi355_se_res_fwd(const void* x, const float* w1, const float* w2, const void* resid, void* y,
+                        int B, int C, int Cr, int H, int W, int relu, int io, void* ws, size_t ws_bytes, mi355_stream_t stream);
+int    mi355_eca_res_fwd(const void* x, const float* wconv, const void* resid, void* y,
+                         int B, int C, int k, int H, int W, int relu, int io, void* ws, size_t ws_bytes, mi355_stream_t stream);
+int    mi355_cbam_res_fwd(const void* x, const float* w1, const float* w2, const float* wconv, const void* resid, void* y,
+                          int B, int C, int Cr, int ks, int H, int W, int relu, int io, void* ws, size_t ws_bytes, mi355_stream_t stream);
+
 /* DoubleAttention.forward  (attention_mechanisms/double_attention.py:32-48)
  *   wA (cm,C) bA (cm) | wB (cn,C) bB (cn) | wV (cn,C) bV (cn) | wP (C,cm) bP (C);  x,y (B,C,H,W). */
 size_t mi355_double_attn_workspace_bytes(int B, int C, int cm, int cn, int H, int W);

@@ -36,8 +36,8 @@ struct CbamSingleArgs : CbamArgsT<float> {};       // a type of its own, not an 
 #define STAMP(k) do { } while (0)
 #endif
 
-template <int NT, int SEG, int NV, bool FULL>
-__global__ __launch_bounds__(NT, 4) void cbam_single_kernel(const CbamSingleArgs a) {
+template <int NT, int SEG, int NV, bool FULL, int RES>      // RES (gate_res.h): 0 plain, 1 / 2 = y = [relu]((x * gc) * gs + resid)
+__device__ __forceinline__ void cbam_single_body(const CbamSingleArgs a, const float* __restrict__ resid) {
     constexpr int CL = NT / SEG;                                     // channel groups (segments) per workgroup
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ u32 s_tk[2];
@@ -294,26 +294,26 @@ __global__ __launch_bounds__(NT, 4) void cbam_single_kernel(const CbamSingleArgs
             const v4f s4 = reinterpret_cast<const v4f*>(s_gs)[q & (SEG - 1)];       // lanes beyond the band: stores are dropped (OOB)
             u32 ob = off0;
             asm volatile("" : "+v"(ob));
-            if (a.nts) {
-#pragma unroll
-                for (int j = 0; j < NV; ++j) {
-                    const v4f v = (r[j] * s_gc[cl + CL * j]) * s4;
-                    const u32 vo = (FULL || cl + CL * j < C) ? ob + (u32)j * offs : OOB;
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry, vo, 0, AUX_NT);
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < NV; ++j) {
-                    const v4f v = (r[j] * s_gc[cl + CL * j]) * s4;
-                    const u32 vo = (FULL || cl + CL * j < C) ? ob + (u32)j * offs : OOB;
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ry, vo, 0, 0);
-                }
-            }
+            cbam_store<NV, CL, FULL, RES>(r, s_gc, s4, ry, ob, offs, cl, C, a.nts, resid + img, ext);       // bufops.h (+ residual band, ReLU)
         }
         if (t == 0) s_tk[par ^ 1] = next_tk;
         STAMP(8);                                                                    // stores issued
         par ^= 1;
     }
+}
+
+template <int NT, int SEG, int NV, bool FULL>
+__global__ __launch_bounds__(NT, 4) void cbam_single_kernel(const CbamSingleArgs a) {
+    cbam_single_body<NT, SEG, NV, FULL, 0>(a, nullptr);
+}
+// The residual form, a kernel of its own: the plain instantiations keep their names and arguments.  16 slots per lane leave no room for a
+// residual slot in the 128 registers of two workgroups per CU: that instantiation is built for one.  (The body takes its argument block
+// by value: by reference hipcc allocated the plain kernel's registers differently and its full 16-slot instantiation spilled 8 bytes;
+// by value tools/kernel_resources.py shows the plain instantiations within one register of their earlier counts and no new scratch.)
+constexpr int cbam_res_waves(int nv) { return nv >= 16 ? 2 : 4; }
+template <int NT, int SEG, int NV, bool FULL, bool RELU>
+__global__ __launch_bounds__(NT, cbam_res_waves(NV)) void cbam_single_res_kernel(const CbamSingleArgs a, const float* __restrict__ resid) {
+    cbam_single_body<NT, SEG, NV, FULL, RELU ? 2 : 1>(a, resid);
 }
 
 // 512-thread workgroups, two per CU.  (256-thread workgroups with half-size bands -- four exchange chains per CU instead of two -- were
@@ -341,7 +341,7 @@ bool cbam_single_applicable(int C, int Cr, int H, int W, int ks) {
 }
 
 int cbam_single(const float* x, const float* w1, const float* w2, const float* wconv, float* y, int B, int C, int Cr, int H, int W,
-                int ks, void* extra, hipStream_t st) {
+                int ks, void* extra, hipStream_t st, const float* resid, int relu) {
     Geo g;
     if (!pick_geometry(C, Cr, H, W, ks, g)) return fail(MI355_EUNSUPPORTED, "cbam_single: unsupported shape");
     CbamSingleArgs a{};
@@ -360,9 +360,10 @@ int cbam_single(const float* x, const float* w1, const float* w2, const float* w
     a.nts = (opt(O_NT) & 2) ? 1 : 0;
     const bool full = (C == g.CL * g.NV);
     const int per_cu = 2;
+    const int per_cu_run = resid ? cbam_res_waves(g.NV) / 2 : per_cu;           // workgroups per CU of the kernel that runs (the grid)
     a.wlds = (g.smem_base + g.smem_w <= (size_t)(120 * 1024) / per_cu) ? 1 : 0;
     const size_t smem = g.smem_base + (a.wlds ? g.smem_w : 0);
-    long grid = (long)resident_slots(per_cu);                                   // 16 waves per CU at <= 128 VGPRs, <= 120 KB LDS per CU
+    long grid = (long)resident_slots(per_cu_run);                                // 16 waves per CU at <= 128 VGPRs, <= 120 KB LDS per CU
 #ifdef CBAM_TIMING
     a.dbg = g_cbam_dbg;
 #endif
@@ -370,8 +371,19 @@ int cbam_single(const float* x, const float* w1, const float* w2, const float* w
     if (grid > a.total) grid = a.total;
     const unsigned long long key = ((unsigned long long)B << 48) ^ ((unsigned long long)C << 32) ^ ((unsigned long long)H << 16) ^ (unsigned long long)W ^ ((unsigned long long)g.NT << 40) ^ 0xCBA0000000000000ull;
     if (int rc = xch_zero("cbam_single", extra, key, cbam_single_extra_bytes(B, C, H, W), st)) return rc;   // granules, ticket, epoch
+#define GO_RES(SEG_, NV_, RELU_)                                                                                  \
+    do {                                                                                                          \
+        if (full) cbam_single_res_kernel<512, SEG_, NV_, true, RELU_><<<(int)grid, 512, smem, st>>>(a, resid);   \
+        else      cbam_single_res_kernel<512, SEG_, NV_, false, RELU_><<<(int)grid, 512, smem, st>>>(a, resid);  \
+    } while (0)
 #define GO(SEG_, NV_)                                                                              \
     do {                                                                                           \
+        if (resid) {                                                                               \
+            MI355_TRACE(st, "cbam_single_res_kernel C=%d H=%d W=%d ks=%d SEG=%d NV=%d full=%d res=1 relu=%d", C, H, W, ks, SEG_, NV_, (int)full, relu); \
+            if (relu) GO_RES(SEG_, NV_, true);                                                     \
+            else      GO_RES(SEG_, NV_, false);                                                    \
+            break;                                                                                 \
+        }                                                                                          \
         MI355_TRACE(st, "cbam_single_kernel C=%d H=%d W=%d ks=%d SEG=%d NV=%d full=%d", C, H, W, ks, SEG_, NV_, (int)full); \
         if (full) cbam_single_kernel<512, SEG_, NV_, true><<<(int)grid, 512, smem, st>>>(a);       \
         else      cbam_single_kernel<512, SEG_, NV_, false><<<(int)grid, 512, smem, st>>>(a);      \
@@ -386,7 +398,15 @@ int cbam_single(const float* x, const float* w1, const float* w2, const float* w
         else GO(16, 16);
     }
 #undef GO
+#undef GO_RES
     return xch_launched("cbam_single", extra);
+}
+
+// The residual form takes the shapes of the plain one, except where its 16-slot instantiation (one workgroup per CU) cannot hold an image's
+// bands at once: more bands than CUs at more than 128 (SEG 32) or 256 (SEG 16) channels.  Those calls take the multi-pass form.
+bool cbam_single_res_applicable(int C, int Cr, int H, int W, int ks) {
+    Geo g;
+    return cbam_single_applicable(C, Cr, H, W, ks) && pick_geometry(C, Cr, H, W, ks, g) && g.NB <= resident_slots(cbam_res_waves(g.NV) / 2);
 }
 
 }  // namespace mi355

@@ -13,6 +13,7 @@
 // `chunk_images` images so that the re-read of a chunk is served by the 256 MiB Infinity Cache instead of
 // HBM (DESIGN.md section "channel attention").
 #include "common.h"
+#include "gate_res.h"
 
 namespace {
 
@@ -112,11 +113,12 @@ __device__ __forceinline__ void stx(v4f v, v4f* p) {
     else *p = v;
 }
 
-template <int MODE, bool VEC, bool NTL, bool NTS>
-__global__ __launch_bounds__(256) void gate_scale_kernel(const float* __restrict__ x, const float* __restrict__ pooled,
-                                                        const float* __restrict__ wa, const float* __restrict__ wb,
-                                                        float* __restrict__ y, int C, int Cr, int HW, int groups, int reverse,
-                                                        const mi355::SeExtra ex) {
+// RES (gate_res.h): 0 = the plain gate, 1 / 2 = y = [relu](x * g + resid).  The residual has the layout of y and is read beside x with the
+// load hint of x (NTL: option "nt" bit 0).
+template <int MODE, bool VEC, bool NTL, bool NTS, int RES>
+__device__ __forceinline__ void gate_scale_body(const float* __restrict__ x, const float* __restrict__ pooled, const float* __restrict__ wa,
+                                                const float* __restrict__ wb, float* __restrict__ y, const float* __restrict__ resid, int C,
+                                                int Cr, int HW, int groups, int reverse, const mi355::SeExtra ex) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* s_p = smem;            // C
     float* s_h = smem + C;        // Cr (SE)
@@ -165,22 +167,59 @@ __global__ __launch_bounds__(256) void gate_scale_kernel(const float* __restrict
             v4f* yr = reinterpret_cast<v4f*>(y + off);
             const int n4 = HW >> 2;
             int i = lane;
-            for (; i + 192 < n4; i += 256) {
-                v4f a = ldx<NTL>(&xr[i]), bq = ldx<NTL>(&xr[i + 64]);
-                v4f c = ldx<NTL>(&xr[i + 128]), d = ldx<NTL>(&xr[i + 192]);
-                stx<NTS>(a * g, &yr[i]);
-                stx<NTS>(bq * g, &yr[i + 64]);
-                stx<NTS>(c * g, &yr[i + 128]);
-                stx<NTS>(d * g, &yr[i + 192]);
-            }
-            for (; i < n4; i += 64) {
-                v4f a = ldx<NTL>(&xr[i]);
-                stx<NTS>(a * g, &yr[i]);
+            if constexpr (RES != 0) {
+                const v4f* qr = reinterpret_cast<const v4f*>(resid + off);
+                for (; i + 192 < n4; i += 256) {
+                    v4f a = ldx<NTL>(&xr[i]), bq = ldx<NTL>(&xr[i + 64]);
+                    v4f c = ldx<NTL>(&xr[i + 128]), d = ldx<NTL>(&xr[i + 192]);
+                    v4f qa = ldx<NTL>(&qr[i]), qb = ldx<NTL>(&qr[i + 64]);
+                    v4f qc = ldx<NTL>(&qr[i + 128]), qd = ldx<NTL>(&qr[i + 192]);
+                    stx<NTS>(res4<RES>(a * g, qa), &yr[i]);
+                    stx<NTS>(res4<RES>(bq * g, qb), &yr[i + 64]);
+                    stx<NTS>(res4<RES>(c * g, qc), &yr[i + 128]);
+                    stx<NTS>(res4<RES>(d * g, qd), &yr[i + 192]);
+                }
+                for (; i < n4; i += 64) {
+                    v4f a = ldx<NTL>(&xr[i]), qa = ldx<NTL>(&qr[i]);
+                    stx<NTS>(res4<RES>(a * g, qa), &yr[i]);
+                }
+            } else {
+                for (; i + 192 < n4; i += 256) {
+                    v4f a = ldx<NTL>(&xr[i]), bq = ldx<NTL>(&xr[i + 64]);
+                    v4f c = ldx<NTL>(&xr[i + 128]), d = ldx<NTL>(&xr[i + 192]);
+                    stx<NTS>(a * g, &yr[i]);
+                    stx<NTS>(bq * g, &yr[i + 64]);
+                    stx<NTS>(c * g, &yr[i + 128]);
+                    stx<NTS>(d * g, &yr[i + 192]);
+                }
+                for (; i < n4; i += 64) {
+                    v4f a = ldx<NTL>(&xr[i]);
+                    stx<NTS>(a * g, &yr[i]);
+                }
             }
         } else {
-            for (int i = lane; i < HW; i += 64) y[off + i] = x[off + i] * g;
+            if constexpr (RES != 0) {
+                for (int i = lane; i < HW; i += 64) y[off + i] = res1<RES>(x[off + i] * g, resid[off + i]);
+            } else {
+                for (int i = lane; i < HW; i += 64) y[off + i] = x[off + i] * g;
+            }
         }
     }
+}
+
+template <int MODE, bool VEC, bool NTL, bool NTS>
+__global__ __launch_bounds__(256) void gate_scale_kernel(const float* __restrict__ x, const float* __restrict__ pooled,
+                                                        const float* __restrict__ wa, const float* __restrict__ wb,
+                                                        float* __restrict__ y, int C, int Cr, int HW, int groups, int reverse,
+                                                        const mi355::SeExtra ex) {
+    gate_scale_body<MODE, VEC, NTL, NTS, 0>(x, pooled, wa, wb, y, nullptr, C, Cr, HW, groups, reverse, ex);
+}
+template <int MODE, bool VEC, bool NTL, bool NTS, bool RELU>
+__global__ __launch_bounds__(256) void gate_scale_res_kernel(const float* __restrict__ x, const float* __restrict__ pooled,
+                                                            const float* __restrict__ wa, const float* __restrict__ wb,
+                                                            const float* __restrict__ resid, float* __restrict__ y, int C, int Cr, int HW,
+                                                            int groups, int reverse, const mi355::SeExtra ex) {
+    gate_scale_body<MODE, VEC, NTL, NTS, RELU ? 2 : 1>(x, pooled, wa, wb, y, resid, C, Cr, HW, groups, reverse, ex);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -289,12 +328,13 @@ __global__ __launch_bounds__(256) void cbam_spatial_stats_kernel(const float* __
 // of the reference: the channel-stage product is rounded to fp32 before the spatial multiply).
 // smem: gc[C] | scratch[2C+Cr] | w[2*ks*ks (pad 4)] | tile[2][TH][TW] | gs[TR*W (pad 4)]
 // ---------------------------------------------------------------------------------------------------
-template <int KS, bool VEC, bool NTL, bool NTS>
-__global__ __launch_bounds__(256) void cbam_apply_band_kernel(const float* __restrict__ x, const float* __restrict__ avg,
-                                                             const float* __restrict__ mx, const float* __restrict__ w1,
-                                                             const float* __restrict__ w2, const float* __restrict__ smap,
-                                                             const float* __restrict__ wconv, float* __restrict__ y, int C, int Cr,
-                                                             int H, int W, int ks_rt, int TR, int bands) {
+// RES (gate_res.h): 0 = the plain gate, 1 / 2 = y = [relu]((x * gc) * gs + resid); the residual is read beside x with its load hint.
+template <int KS, bool VEC, bool NTL, bool NTS, int RES>
+__device__ __forceinline__ void cbam_apply_band_body(const float* __restrict__ x, const float* __restrict__ avg, const float* __restrict__ mx,
+                                                     const float* __restrict__ w1, const float* __restrict__ w2,
+                                                     const float* __restrict__ smap, const float* __restrict__ wconv,
+                                                     float* __restrict__ y, const float* __restrict__ resid, int C, int Cr, int H, int W,
+                                                     int ks_rt, int TR, int bands) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const bool has_c = avg != nullptr, has_s = smap != nullptr;
     const int ks = KS > 0 ? KS : ks_rt;
@@ -365,6 +405,8 @@ __global__ __launch_bounds__(256) void cbam_apply_band_kernel(const float* __res
     const int npx = rows_here * W;
     const float* xb = x + (long)b * C * HW + band0;
     float* yb = y + (long)b * C * HW + band0;
+    const float* qb = nullptr;
+    if constexpr (RES != 0) qb = resid + (long)b * C * HW + band0;
     if constexpr (VEC) {
         const int n4 = npx >> 2;                                    // W % 4 == 0 on this path
         int c = wave, i = lane;
@@ -375,6 +417,7 @@ __global__ __launch_bounds__(256) void cbam_apply_band_kernel(const float* __res
             if (has_s) s4 = reinterpret_cast<const v4f*>(s_gs)[i];
             v4f v = ldx<NTL>(&reinterpret_cast<const v4f*>(xb + (long)c * HW)[i]);
             v = (v * g) * s4;
+            if constexpr (RES != 0) v = res4<RES>(v, ldx<NTL>(&reinterpret_cast<const v4f*>(qb + (long)c * HW)[i]));
             stx<NTS>(v, &reinterpret_cast<v4f*>(yb + (long)c * HW)[i]);
             i += 64;
             while (i >= n4) { i -= n4; c += 4; }
@@ -384,10 +427,29 @@ __global__ __launch_bounds__(256) void cbam_apply_band_kernel(const float* __res
             const float g = has_c ? s_gc[c] : 1.0f;
             for (int i = lane; i < npx; i += 64) {
                 const float sp = has_s ? s_gs[i] : 1.0f;
-                yb[(long)c * HW + i] = (xb[(long)c * HW + i] * g) * sp;
+                if constexpr (RES != 0) yb[(long)c * HW + i] = res1<RES>((xb[(long)c * HW + i] * g) * sp, qb[(long)c * HW + i]);
+                else yb[(long)c * HW + i] = (xb[(long)c * HW + i] * g) * sp;
             }
         }
     }
+}
+
+template <int KS, bool VEC, bool NTL, bool NTS>
+__global__ __launch_bounds__(256) void cbam_apply_band_kernel(const float* __restrict__ x, const float* __restrict__ avg,
+                                                             const float* __restrict__ mx, const float* __restrict__ w1,
+                                                             const float* __restrict__ w2, const float* __restrict__ smap,
+                                                             const float* __restrict__ wconv, float* __restrict__ y, int C, int Cr,
+                                                             int H, int W, int ks_rt, int TR, int bands) {
+    cbam_apply_band_body<KS, VEC, NTL, NTS, 0>(x, avg, mx, w1, w2, smap, wconv, y, nullptr, C, Cr, H, W, ks_rt, TR, bands);
+}
+template <int KS, bool VEC, bool NTL, bool NTS, bool RELU>
+__global__ __launch_bounds__(256) void cbam_apply_band_res_kernel(const float* __restrict__ x, const float* __restrict__ avg,
+                                                                 const float* __restrict__ mx, const float* __restrict__ w1,
+                                                                 const float* __restrict__ w2, const float* __restrict__ smap,
+                                                                 const float* __restrict__ wconv, const float* __restrict__ resid,
+                                                                 float* __restrict__ y, int C, int Cr, int H, int W, int ks_rt, int TR,
+                                                                 int bands) {
+    cbam_apply_band_body<KS, VEC, NTL, NTS, RELU ? 2 : 1>(x, avg, mx, w1, w2, smap, wconv, y, resid, C, Cr, H, W, ks_rt, TR, bands);
 }
 
 __global__ __launch_bounds__(256) void stream_copy_kernel(const float4* __restrict__ src, float4* __restrict__ dst, long n4) {
@@ -453,19 +515,21 @@ size_t mi355_se_workspace_bytes(int B, int C, int, int) {
 size_t mi355_eca_workspace_bytes(int B, int C, int, int) { return mi355::pooled_bytes(B, C) + mi355::fused_state_bytes(B); }
 
 static int se_eca_common(int mode, const float* x, const float* wa, const float* wb, float* y, int B, int C, int Cr,
-                         int H, int W, void* ws, size_t ws_bytes, hipStream_t st, mi355::SeExtra ex = mi355::SeExtra{nullptr, nullptr, 0}) {
+                         int H, int W, void* ws, size_t ws_bytes, hipStream_t st, mi355::SeExtra ex = mi355::SeExtra{nullptr, nullptr, 0},
+                         const float* resid = nullptr, int relu = 0) {
+    // resid (mi355_se_res_fwd / mi355_eca_res_fwd; null: the plain gate): the same route by the same predicates, the residual kernels
     const int HW = H * W;
-    const bool vec = (HW % 4 == 0) && aligned16(x) && aligned16(y);
+    const bool vec = (HW % 4 == 0) && aligned16(x) && aligned16(y) && aligned16(resid);
     float* pooled = static_cast<float*>(ws);
     const int groups = cdiv(C, RPB);
     const size_t smem = (size_t)(C + (mode == 0 ? Cr : 0) + RPB) * sizeof(float);
     if (smem > 64 * 1024) return mi355::fail(MI355_EUNSUPPORTED, "channel count %d too large for the gate stage", C);
     if (mode == 0 && vec && mi355::se_single_applicable(C, Cr, H, W)) {       // SE: x read once, means exchanged as tagged granules
         char* state = static_cast<char*>(ws) + mi355::pooled_bytes(B, C);
-        return mi355::se_single(x, wa, wb, y, B, C, Cr, H, W, state, state + mi355::fused_state_bytes(B), ex, st);
+        return mi355::se_single(x, wa, wb, y, B, C, Cr, H, W, state, state + mi355::fused_state_bytes(B), ex, st, resid, relu);
     }
     if (mode == 1 && vec && mi355::eca_single_applicable(C, Cr, H, W))         // ECA: x read once, no exchange between workgroups
-        return mi355::eca_single(x, wa, y, B, C, Cr, H, W, st);
+        return resid ? mi355::eca_single_res(x, wa, resid, y, B, C, Cr, H, W, relu, st) : mi355::eca_single(x, wa, y, B, C, Cr, H, W, st);
     const Tune tu = resolve_tune(B, (long)C * HW * 4);
     for (int b0 = 0; b0 < B; b0 += tu.chunk) {
         const int nb = (B - b0 < tu.chunk) ? B - b0 : tu.chunk;
@@ -485,7 +549,24 @@ static int se_eca_common(int mode, const float* x, const float* wa, const float*
                 else     gate_scale_kernel<1, false, NTL, NTS><<<grid, 256, smem, st>>>(xc, pc, wa, nullptr, yc, C, Cr, HW, groups, tu.reverse, ex); \
             }                                                                                                          \
         } while (0)
-        NT_DISPATCH(tu.ntl, tu.nts, SCALE_CALL);
+#define SCALE_RES(MODE_, VEC_, NTL, NTS)                                                                                \
+        do {                                                                                                               \
+            if (relu) gate_scale_res_kernel<MODE_, VEC_, NTL, NTS, true><<<grid, 256, smem, st>>>(xc, pc, wa, mode == 0 ? wb : nullptr, resid + (long)b0 * C * HW, yc, C, Cr, HW, groups, tu.reverse, ex);   \
+            else      gate_scale_res_kernel<MODE_, VEC_, NTL, NTS, false><<<grid, 256, smem, st>>>(xc, pc, wa, mode == 0 ? wb : nullptr, resid + (long)b0 * C * HW, yc, C, Cr, HW, groups, tu.reverse, ex);  \
+        } while (0)
+#define SCALE_RES_CALL(NTL, NTS)                                                                                        \
+        do {                                                                                                               \
+            if (mode == 0) { if (vec) SCALE_RES(0, true, NTL, NTS); else SCALE_RES(0, false, NTL, NTS); }                 \
+            else           { if (vec) SCALE_RES(1, true, NTL, NTS); else SCALE_RES(1, false, NTL, NTS); }                 \
+        } while (0)
+        if (resid) {
+            MI355_TRACE(st, "gate_scale_res_kernel mode=%d C=%d HW=%d vec=%d res=1 relu=%d", mode, C, HW, (int)vec, relu);
+            NT_DISPATCH(tu.ntl, tu.nts, SCALE_RES_CALL);
+        } else {
+            NT_DISPATCH(tu.ntl, tu.nts, SCALE_CALL);
+        }
+#undef SCALE_RES_CALL
+#undef SCALE_RES
 #undef SCALE_CALL
     }
     MI355_LAUNCH_CHECK();
@@ -522,6 +603,9 @@ size_t mi355_cbam_workspace_bytes(int B, int C, int H, int W) {
     return mi355::cbam_multipass_bytes(B, C, H, W) + mi355::cbam_single_extra_bytes(B, C, H, W);
 }
 
+static int cbam_run(const char* who, const float* x, const float* w1, const float* w2, const float* wconv, float* y, int B, int C, int Cr, int ks,
+                    int H, int W, int stage, void* ws, mi355_stream_t stream, const float* resid, int relu);
+
 int mi355_cbam_fwd(const float* x, const float* w1, const float* w2, const float* wconv, float* y, int B, int C, int Cr,
                    int ks, int H, int W, int stage, void* ws, size_t ws_bytes, mi355_stream_t stream) {
     MI355_CHECK_ARG(x && y && ws);
@@ -531,13 +615,22 @@ int mi355_cbam_fwd(const float* x, const float* w1, const float* w2, const float
     if (do_c) MI355_CHECK_ARG(w1 && w2 && Cr > 0);
     if (do_s) MI355_CHECK_ARG(wconv && ks > 0 && (ks & 1));
     MI355_CHECK_ARG(ws_bytes >= mi355_cbam_workspace_bytes(B, C, H, W));
+    return cbam_run("mi355_cbam_fwd", x, w1, w2, wconv, y, B, C, Cr, ks, H, W, stage, ws, stream, nullptr, 0);
+}
+
+// The launches of mi355_cbam_fwd and mi355_cbam_res_fwd behind their argument checks.  resid (stage 0 only; null: the plain gate): the same
+// route by the same predicates, the residual kernels.
+static int cbam_run(const char* who, const float* x, const float* w1, const float* w2, const float* wconv, float* y, int B, int C, int Cr, int ks,
+                    int H, int W, int stage, void* ws, mi355_stream_t stream, const float* resid, int relu) {
+    const bool do_c = stage != 2, do_s = stage != 1;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (stage == 0 && aligned16(x) && aligned16(y) && mi355::cbam_single_applicable(C, Cr, H, W, ks))                                                   // x read once
-        return mi355::cbam_single(x, w1, w2, wconv, y, B, C, Cr, H, W, ks, static_cast<char*>(ws) + mi355::cbam_multipass_bytes(B, C, H, W), st);
+    if (stage == 0 && aligned16(x) && aligned16(y) && aligned16(resid) &&
+        (resid ? mi355::cbam_single_res_applicable(C, Cr, H, W, ks) : mi355::cbam_single_applicable(C, Cr, H, W, ks)))                                // x read once
+        return mi355::cbam_single(x, w1, w2, wconv, y, B, C, Cr, H, W, ks, static_cast<char*>(ws) + mi355::cbam_multipass_bytes(B, C, H, W), st, resid, relu);
     if (!do_c) Cr = 0;
     if (!do_s) ks = 1;
     const int HW = H * W;
-    const bool vec_pix = (HW % 4 == 0) && aligned16(x) && aligned16(y);          // whole-image rows
+    const bool vec_pix = (HW % 4 == 0) && aligned16(x) && aligned16(y) && aligned16(resid);          // whole-image rows
     const bool vec_band = vec_pix && (W % 4 == 0);                               // row bands start 16-byte aligned
     char* wsp = static_cast<char*>(ws);
     const size_t bc = mi355::r16((size_t)B * C * 4);
@@ -557,7 +650,7 @@ int mi355_cbam_fwd(const float* x, const float* w1, const float* w2, const float
     };
     while (TR > 1 && apply_smem(TR) > 60 * 1024) --TR;
     if (apply_smem(TR) > 60 * 1024)
-        return mi355::fail(MI355_EUNSUPPORTED, "mi355_cbam_fwd: C=%d / W=%d exceed the LDS budget of the fused final pass", C, W);
+        return mi355::fail(MI355_EUNSUPPORTED, "%s: C=%d / W=%d exceed the LDS budget of the fused final pass", who, C, W);
     const int bands = cdiv(H, TR);
     const size_t smem_apply = apply_smem(TR);
     const size_t smem_stats = do_c ? gate_floats * 4 : 0;
@@ -592,13 +685,81 @@ int mi355_cbam_fwd(const float* x, const float* w1, const float* w2, const float
             else if (ks == 3) APPLY_KS(3, NTL, NTS);           \
             else APPLY_KS(0, NTL, NTS);                        \
         } while (0)
-        NT_DISPATCH(tu.ntl, tu.nts, APPLY_CALL);
+#define APPLY_RES(KS_, VEC_, NTL, NTS)                                                                                            \
+        do {                                                                                                                       \
+            if (relu) cbam_apply_band_res_kernel<KS_, VEC_, NTL, NTS, true><<<nb * bands, 256, smem_apply, st>>>(xc, avgc, mxc, w1, w2, smc, wconv, resid + (long)b0 * C * HW, yc, C, Cr, H, W, ks, TR, bands);   \
+            else      cbam_apply_band_res_kernel<KS_, VEC_, NTL, NTS, false><<<nb * bands, 256, smem_apply, st>>>(xc, avgc, mxc, w1, w2, smc, wconv, resid + (long)b0 * C * HW, yc, C, Cr, H, W, ks, TR, bands);  \
+        } while (0)
+#define APPLY_RES_KS(KS_, NTL, NTS) do { if (vec_band) APPLY_RES(KS_, true, NTL, NTS); else APPLY_RES(KS_, false, NTL, NTS); } while (0)
+#define APPLY_RES_CALL(NTL, NTS)                                  \
+        do {                                                       \
+            if (ks == 7) APPLY_RES_KS(7, NTL, NTS);                \
+            else if (ks == 3) APPLY_RES_KS(3, NTL, NTS);           \
+            else APPLY_RES_KS(0, NTL, NTS);                        \
+        } while (0)
+        if (resid) {
+            MI355_TRACE(st, "cbam_apply_band_res_kernel C=%d H=%d W=%d ks=%d vec=%d res=1 relu=%d", C, H, W, ks, (int)vec_band, relu);
+            NT_DISPATCH(tu.ntl, tu.nts, APPLY_RES_CALL);
+        } else {
+            NT_DISPATCH(tu.ntl, tu.nts, APPLY_CALL);
+        }
+#undef APPLY_RES_CALL
+#undef APPLY_RES_KS
+#undef APPLY_RES
 #undef APPLY_CALL
 #undef APPLY_KS
     }
     MI355_LAUNCH_CHECK();
     return MI355_OK;
 }
+
+// ---- the gates with the residual add (+ ReLU) in their store epilogue: y = [relu](gate(x) + resid), all I/O types (io) ----------------------
+static bool res_overlap(const void* y, const void* p, size_t bytes) {
+    const char* a = static_cast<const char*>(y);
+    const char* b = static_cast<const char*>(p);
+    return a < b + bytes && b < a + bytes;
+}
+#define MI355_CHECK_RES_ARGS()                                                                                  \
+    MI355_CHECK_ARG(io >= 0 && io <= 2);                                                                        \
+    MI355_CHECK_ARG(relu == 0 || relu == 1);                                                                    \
+    MI355_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0);                                                          \
+    MI355_CHECK_ARG(x && resid && y && ws);                                                                     \
+    MI355_CHECK_ARG(io == 0 || mi355::check_io16(io, B, C, H, W));                                              \
+    MI355_CHECK_ARG(!res_overlap(y, x, (size_t)B * C * H * W * (io ? 2 : 4)) && !res_overlap(y, resid, (size_t)B * C * H * W * (io ? 2 : 4)))
+
+int mi355_se_res_fwd(const void* x, const float* w1, const float* w2, const void* resid, void* y, int B, int C, int Cr, int H, int W, int relu,
+                     int io, void* ws, size_t ws_bytes, mi355_stream_t stream) {
+    MI355_CHECK_RES_ARGS();
+    MI355_CHECK_ARG(w1 && w2 && Cr > 0);
+    MI355_CHECK_ARG(ws_bytes >= mi355_se_workspace_bytes(B, C, H, W));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (io) return mi355::se_eca16_res(0, x, w1, w2, resid, y, B, C, Cr, H, W, relu, io, ws, st);
+    return se_eca_common(0, static_cast<const float*>(x), w1, w2, static_cast<float*>(y), B, C, Cr, H, W, ws, ws_bytes, st,
+                         mi355::SeExtra{nullptr, nullptr, 0}, static_cast<const float*>(resid), relu);
+}
+
+int mi355_eca_res_fwd(const void* x, const float* wconv, const void* resid, void* y, int B, int C, int k, int H, int W, int relu, int io,
+                      void* ws, size_t ws_bytes, mi355_stream_t stream) {
+    MI355_CHECK_RES_ARGS();
+    MI355_CHECK_ARG(wconv && k > 0 && (k & 1));
+    MI355_CHECK_ARG(ws_bytes >= mi355_eca_workspace_bytes(B, C, H, W));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (io) return mi355::se_eca16_res(1, x, wconv, nullptr, resid, y, B, C, k, H, W, relu, io, ws, st);
+    return se_eca_common(1, static_cast<const float*>(x), wconv, nullptr, static_cast<float*>(y), B, C, k, H, W, ws, ws_bytes, st,
+                         mi355::SeExtra{nullptr, nullptr, 0}, static_cast<const float*>(resid), relu);
+}
+
+int mi355_cbam_res_fwd(const void* x, const float* w1, const float* w2, const float* wconv, const void* resid, void* y, int B, int C, int Cr,
+                       int ks, int H, int W, int relu, int io, void* ws, size_t ws_bytes, mi355_stream_t stream) {
+    MI355_CHECK_RES_ARGS();
+    MI355_CHECK_ARG(w1 && w2 && Cr > 0);
+    MI355_CHECK_ARG(wconv && ks > 0 && (ks & 1));
+    MI355_CHECK_ARG(ws_bytes >= (io ? mi355_cbam16_workspace_bytes(B, C, H, W) : mi355_cbam_workspace_bytes(B, C, H, W)));
+    if (io) return mi355::cbam16_res(x, w1, w2, wconv, resid, y, B, C, Cr, ks, H, W, relu, io, ws, static_cast<hipStream_t>(stream));
+    return cbam_run("mi355_cbam_res_fwd", static_cast<const float*>(x), w1, w2, wconv, static_cast<float*>(y), B, C, Cr, ks, H, W, 0, ws, stream,
+                    static_cast<const float*>(resid), relu);
+}
+#undef MI355_CHECK_RES_ARGS
 
 int mi355_stream_copy(const void* src, void* dst, size_t bytes, mi355_stream_t stream) {
     MI355_CHECK_ARG(src && dst && bytes % 16 == 0 && aligned16(src) && aligned16(dst));

@@ -30,10 +30,10 @@ constexpr int ECW = 8;
 
 typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 
-template <int NV, bool NTS>
-__global__ __launch_bounds__(512, NV <= 13 ? 6 : 4) void eca_halo_kernel(const float* __restrict__ x, const float* __restrict__ taps,
-                                                          float* __restrict__ y, int C, int k, int HW, int gpi, int total,
-                                                          int per_xcd) {
+template <int NV, bool NTS, int RES>      // RES (gate_res.h): 0 = the plain gate, 1 / 2 = y = [relu](x * g + resid); the kernels follow the body
+__device__ __forceinline__ void eca_halo_body(const float* __restrict__ x, const float* __restrict__ taps, float* __restrict__ y,
+                                              const float* __restrict__ resid, int C, int k, int HW, int gpi, int total,
+                                              int per_xcd) {
     __shared__ float s_mean[ECW + 8];                        // means of channels c0-pad .. c0+ECW+pad-1
     const int s = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
     if (s >= total) return;
@@ -83,12 +83,12 @@ __global__ __launch_bounds__(512, NV <= 13 ? 6 : 4) void eca_halo_kernel(const f
     const rsrc_t ry = make_rsrc(y + ((long)b * C + cw) * HW, (u32)HW * 4u);
     u32 ob = voff;                                            // the row step rides in the VGPR offset of the stores: cbam_single.hip
     asm volatile("" : "+v"(ob));
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const v4f o = r[j] * g;
-        if (NTS) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), ry, ob + (u32)j * 1024u, 0, AUX_NT);
-        else     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), ry, ob + (u32)j * 1024u, 0, 0);
-    }
+    store_row<NV, NTS, RES>(r, g, ry, ob, resid + ((long)b * C + cw) * HW, (u32)HW * 4u);      // bufops.h: y row = r * g (+ residual row, ReLU)
+}
+template <int NV, bool NTS>
+__global__ __launch_bounds__(512, NV <= 13 ? 6 : 4) void eca_halo_kernel(const float* __restrict__ x, const float* __restrict__ taps,
+                                                          float* __restrict__ y, int C, int k, int HW, int gpi, int total, int per_xcd) {
+    eca_halo_body<NV, NTS, 0>(x, taps, y, nullptr, C, k, HW, gpi, total, per_xcd);
 }
 
 // ---- SE, x read once: register-resident rows + data-tagged granules --------------------------------------------------------------
@@ -117,8 +117,8 @@ struct SeSingleArgs {
 // EXTRA: the SE variants of the reference's CNNs (biases of the two excitation layers, hard-sigmoid gate: SeExtra).  The plain SELayer
 // instantiation carries none of their pointers, null checks and select masks -- scalar registers the 80-VGPR build cannot spare (past
 // 102 SGPRs hipcc parks uniform values in VGPRs and then spills those).
-template <int NV, bool NTS, bool WLDS, int OCC, bool EXTRA>
-__global__ __launch_bounds__(512, 2 * OCC) void se_single_kernel(const SeSingleArgs a) {
+template <int NV, bool NTS, bool WLDS, bool EXTRA, int RES>      // RES (gate_res.h): 0 plain, 1 / 2 = y = [relu](x * g + resid)
+__device__ __forceinline__ void se_single_body(const SeSingleArgs& a, const float* __restrict__ resid) {
     extern __shared__ __attribute__((aligned(16))) float smem[];      // p[C] | h[Cr] | (WLDS: W1[Cr*C] | W2[C*Cr])
     __shared__ u32 s_tk[2];
     __shared__ u32 s_ep;
@@ -269,15 +269,15 @@ __global__ __launch_bounds__(512, 2 * OCC) void se_single_kernel(const SeSingleA
         const float g = EXTRA ? se_gate(wave_sum_sw(z) + (a.b2 ? a.b2[c0 + wave] : 0.f), a.gate) : sigmoidf_(wave_sum_sw(z));
         u32 ob = voff;                                                // row step in the VGPR offset of the stores: cbam_single.hip
         asm volatile("" : "+v"(ob));
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const v4f o = r[j] * g;
-            if (NTS) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), ry, ob + (u32)j * 1024u, 0, AUX_NT);
-            else     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), ry, ob + (u32)j * 1024u, 0, 0);
-        }
+        store_row<NV, NTS, RES>(r, g, ry, ob, resid + row, (u32)a.HW * 4u);      // bufops.h: y row = r * g (+ residual row, ReLU)
         par ^= 1;
     }
 }
+template <int NV, bool NTS, bool WLDS, int OCC, bool EXTRA>
+__global__ __launch_bounds__(512, 2 * OCC) void se_single_kernel(const SeSingleArgs a) {
+    se_single_body<NV, NTS, WLDS, EXTRA, 0>(a, nullptr);
+}
+template <bool RELU> static void se_res_launch_nv(int nv, bool nts, bool wlds, int grid, size_t smem, hipStream_t st, const SeSingleArgs& a, const float* resid);
 
 // launch dispatch over the template parameters; the three-workgroups-per-CU build exists only up to 13 float4 per lane (occ is 2 beyond)
 template <int NV, bool EXTRA>
@@ -360,7 +360,7 @@ bool se_single_applicable(int C, int Cr, int H, int W) {
 
 // `state` = epoch | (B - 1 unused words) | ticket | err (fused_state_bytes), `gran` = B*C granules (se_single_extra_bytes)
 int se_single(const float* x, const float* w1, const float* w2, float* y, int B, int C, int Cr, int H, int W, void* state,
-              void* gran, SeExtra ex, hipStream_t st) {
+              void* gran, SeExtra ex, hipStream_t st, const float* resid, int relu) {
     SeSingleArgs a{};
     a.x = x; a.y = y; a.w1 = w1; a.w2 = w2; a.b1 = ex.b1; a.b2 = ex.b2; a.gate = ex.gate;
     a.gran = static_cast<u64*>(gran);
@@ -381,15 +381,99 @@ int se_single(const float* x, const float* w1, const float* w2, float* y, int B,
     long grid = (long)resident_slots(occ);                // 512-thread workgroups per CU: 2 (<= 128 VGPRs) or 3 (<= 80)
     if (a.gpi > grid) return fail(MI355_EUNSUPPORTED, "se_single: an image needs %d resident workgroups, the device holds %ld", a.gpi, grid);
     if (grid > a.total) grid = a.total;
+    // The residual kernels are built for two workgroups per CU.  The layout key below stays the plain launch's (the ticket counts its draws
+    // from the grid of the launch that runs, nothing in the workspace depends on it), so plain and residual calls share one zeroed workspace.
+    long grid_res = (long)resident_slots(2);
+    if (grid_res > a.total) grid_res = a.total;
     const unsigned long long key = ((unsigned long long)B << 32) ^ (unsigned long long)C ^ ((unsigned long long)grid << 44) ^ 0x5E00000000000000ull;
     // epoch, ticket, granules: state | granules are contiguous (chan_attn.hip)
     if (int rc = xch_zero("se_single", state, key, fused_state_bytes(B) + se_single_extra_bytes(B, C), st)) return rc;
     const size_t smem = (size_t)(C + Cr + (wlds ? 2 * C * Cr : 0)) * sizeof(float);
     const bool nts = (opt(O_NT) & 2) != 0;
     const bool extra = ex.b1 || ex.b2 || ex.gate;
-    if (extra) se_launch_nv<true>(nv, occ, nts, wlds, (int)grid, smem, st, a);
+    if (resid) {                                          // the plain SELayer only: no entry passes a residual with the variants' extras
+        if (relu) se_res_launch_nv<true>(nv, nts, wlds, (int)grid_res, smem, st, a, resid);
+        else      se_res_launch_nv<false>(nv, nts, wlds, (int)grid_res, smem, st, a, resid);
+    } else if (extra) se_launch_nv<true>(nv, occ, nts, wlds, (int)grid, smem, st, a);
     else       se_launch_nv<false>(nv, occ, nts, wlds, (int)grid, smem, st, a);
     return xch_launched("se_single", state);
+}
+
+}  // namespace mi355
+
+// ---- the residual forms: y = [relu](x * g + resid) in the store epilogue (gate_res.h; store_row of bufops.h) --------------------------------
+// Kernels of their own around the shared bodies, so the plain instantiations above keep their names, arguments and code.  The slots of the
+// residual in flight need registers beside the resident row: the 13-slot rows run two workgroups per CU here (SE: every row).
+namespace {
+
+template <int NV, bool NTS, bool RELU>
+__global__ __launch_bounds__(512, NV <= 8 ? 6 : 4) void eca_halo_res_kernel(const float* __restrict__ x, const float* __restrict__ taps,
+                                                              const float* __restrict__ resid, float* __restrict__ y, int C, int k,
+                                                              int HW, int gpi, int total, int per_xcd) {
+    eca_halo_body<NV, NTS, RELU ? 2 : 1>(x, taps, y, resid, C, k, HW, gpi, total, per_xcd);
+}
+// the residual form of the plain SELayer (no EXTRA)
+template <int NV, bool NTS, bool WLDS, bool RELU>
+__global__ __launch_bounds__(512, 4) void se_single_res_kernel(const SeSingleArgs a, const float* __restrict__ resid) {
+    se_single_body<NV, NTS, WLDS, false, RELU ? 2 : 1>(a, resid);
+}
+
+// the plain tag's fields plus res / relu
+template <int NV, bool RELU>
+static void se_res_launch(bool nts, bool wlds, int grid, size_t smem, hipStream_t st, const SeSingleArgs& a, const float* resid) {
+    MI355_TRACE(st, "se_single_res_kernel C=%d HW=%d nv=%d NV=%d occ=2 wlds=%d extra=0 nts=%d res=1 relu=%d", a.C, a.HW, (a.n4 + 63) / 64, NV,
+                (int)wlds, (int)nts, (int)RELU);
+    if (nts && wlds) se_single_res_kernel<NV, true, true, RELU><<<grid, 512, smem, st>>>(a, resid);
+    else if (nts)    se_single_res_kernel<NV, true, false, RELU><<<grid, 512, smem, st>>>(a, resid);
+    else if (wlds)   se_single_res_kernel<NV, false, true, RELU><<<grid, 512, smem, st>>>(a, resid);
+    else             se_single_res_kernel<NV, false, false, RELU><<<grid, 512, smem, st>>>(a, resid);
+}
+template <bool RELU>
+static void se_res_launch_nv(int nv, bool nts, bool wlds, int grid, size_t smem, hipStream_t st, const SeSingleArgs& a, const float* resid) {
+    if (nv <= 1) se_res_launch<1, RELU>(nts, wlds, grid, smem, st, a, resid);
+    else if (nv <= 2) se_res_launch<2, RELU>(nts, wlds, grid, smem, st, a, resid);
+    else if (nv <= 4) se_res_launch<4, RELU>(nts, wlds, grid, smem, st, a, resid);
+    else if (nv <= 8) se_res_launch<8, RELU>(nts, wlds, grid, smem, st, a, resid);
+    else if (nv <= 13) se_res_launch<13, RELU>(nts, wlds, grid, smem, st, a, resid);
+    else se_res_launch<16, RELU>(nts, wlds, grid, smem, st, a, resid);
+}
+template void se_res_launch_nv<true>(int, bool, bool, int, size_t, hipStream_t, const SeSingleArgs&, const float*);
+template void se_res_launch_nv<false>(int, bool, bool, int, size_t, hipStream_t, const SeSingleArgs&, const float*);
+
+}  // namespace
+
+namespace mi355 {
+
+// eca_single with the residual: the same geometry, slices and store hints
+int eca_single_res(const float* x, const float* taps, const float* resid, float* y, int B, int C, int k, int H, int W, int relu, hipStream_t st) {
+    const int HW = H * W, n4 = HW / 4, gpi = C / ECW;
+    const long total_l = (long)B * gpi;
+    if (total_l > (1L << 30)) return fail(MI355_EUNSUPPORTED, "eca_single: too many slices");
+    const int total = (int)total_l, per_xcd = (total + 7) / 8, grid = per_xcd * 8;
+    const int nv = (n4 + 63) / 64;
+    const bool nts = (opt(O_NT) & 2) != 0;
+#define GO_RES(NV_, NTS_)                                                                                                             \
+    do {                                                                                                                              \
+        if (relu) eca_halo_res_kernel<NV_, NTS_, true><<<grid, 512, 0, st>>>(x, taps, resid, y, C, k, HW, gpi, total, per_xcd);      \
+        else      eca_halo_res_kernel<NV_, NTS_, false><<<grid, 512, 0, st>>>(x, taps, resid, y, C, k, HW, gpi, total, per_xcd);     \
+    } while (0)
+#define GO(NV_)                                                                                                                       \
+    do {                                                                                                                              \
+        MI355_TRACE(st, "eca_halo_res_kernel C=%d HW=%d k=%d nv=%d NV=%d nts=%d res=1 relu=%d", C, HW, k, nv, NV_, (int)nts, relu);    \
+        if (nts) GO_RES(NV_, true);                                                                                                   \
+        else     GO_RES(NV_, false);                                                                                                  \
+    } while (0)
+    if (nv <= 1) GO(1);
+    else if (nv <= 2) GO(2);
+    else if (nv <= 4) GO(4);
+    else if (nv <= 8) GO(8);
+    else if (nv <= 13) GO(13);
+    else GO(16);
+#undef GO
+#undef GO_RES
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MI355_EHIP, "eca_single: launch -> %s", hipGetErrorString(e));
+    return MI355_OK;
 }
 
 }  // namespace mi355

@@ -36,9 +36,10 @@ constexpr int eca16_waves(int nv) { return nv <= 4 ? 8 : (nv <= 7 ? 6 : 4); }
 // =====================================================================================================================================
 // single read: ECA (eca_halo_kernel of chan_fused.hip on packed rows; no exchange, halo rows re-summed)
 // =====================================================================================================================================
-template <int IO, int NV>
-__global__ __launch_bounds__(512, eca16_waves(NV)) void eca16_halo_kernel(const u16* __restrict__ x, const float* __restrict__ taps, u16* __restrict__ y,
-                                                           int C, int k, int HW, int gpi, int total, int per_xcd, int nts) {
+template <int IO, int NV, int RES>      // RES (gate_res.h): 0 = the plain gate, 1 / 2 = y = round([relu](x * g + resid)); the kernels follow
+__device__ __forceinline__ void eca16_halo_body(const u16* __restrict__ x, const float* __restrict__ taps, u16* __restrict__ y,
+                                                const u16* __restrict__ resid, int C, int k, int HW, int gpi, int total, int per_xcd,
+                                                int nts) {
     static_assert(eca16_nv(NV) == NV, "NV is a bucket of eca16_nv");
     __shared__ float s_mean[ECW + 8];                        // means of channels c0-pad .. c0+ECW+pad-1
     const int s = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
@@ -81,13 +82,12 @@ __global__ __launch_bounds__(512, eca16_waves(NV)) void eca16_halo_kernel(const 
     for (int j = 0; j < k; ++j) z += taps[j] * s_mean[wave + j];
     const float g = sigmoidf_(z);
     const rsrc_t ry = make_rsrc(y + ((long)b * C + cw) * HW, (u32)HW * 2u);
-    if (nts) {
-#pragma unroll
-        for (int j = 0; j < NV; ++j) __builtin_amdgcn_raw_buffer_store_b128(scale8<IO>(r[j], g), ry, voff, (u32)j * 1024u, AUX_NT);
-    } else {
-#pragma unroll
-        for (int j = 0; j < NV; ++j) __builtin_amdgcn_raw_buffer_store_b128(scale8<IO>(r[j], g), ry, voff, (u32)j * 1024u, 0);
-    }
+    store_row16<IO, NV, RES>(r, g, ry, voff, nts, resid + ((long)b * C + cw) * HW, (u32)HW * 2u);      // io16.h (+ residual row, ReLU)
+}
+template <int IO, int NV>
+__global__ __launch_bounds__(512, eca16_waves(NV)) void eca16_halo_kernel(const u16* __restrict__ x, const float* __restrict__ taps, u16* __restrict__ y,
+                                                           int C, int k, int HW, int gpi, int total, int per_xcd, int nts) {
+    eca16_halo_body<IO, NV, 0>(x, taps, y, nullptr, C, k, HW, gpi, total, per_xcd, nts);
 }
 
 // =====================================================================================================================================
@@ -105,8 +105,8 @@ struct Se16Args {
 // How many workgroups per CU the launch uses is a grid size (option "io16_occ", capped by what se16_waves allows), not a template parameter.
 // EXTRA: the SE variants of the reference's CNNs (excitation biases, hard-sigmoid gate: SeExtra), as in se_single_kernel -- the plain
 // SELayer instantiation carries none of their pointers and selects and keeps its code.
-template <int IO, int NV, bool WLDS, bool EXTRA>
-__global__ __launch_bounds__(512, se16_waves(NV)) void se16_single_kernel(const Se16Args a) {
+template <int IO, int NV, bool WLDS, bool EXTRA, int RES>      // RES (gate_res.h): 0 plain, 1 / 2 = y = round([relu](x * g + resid))
+__device__ __forceinline__ void se16_single_body(const Se16Args a, const u16* __restrict__ resid) {
     static_assert(se16_nv(NV) == NV, "NV is a bucket of se16_nv");
     extern __shared__ __attribute__((aligned(16))) float smem[];      // p[C] | h[Cr] | (WLDS: W1[Cr*C] | W2[C*Cr])
     __shared__ u32 s_tk[2];
@@ -222,16 +222,16 @@ __global__ __launch_bounds__(512, se16_waves(NV)) void se16_single_kernel(const 
         float z = 0.f;
         for (int j = lane; j < Cr_; j += 64) z += w2r[j] * s_h[j];
         const float g = EXTRA ? se_gate(wave_sum_sw(z) + (a.b2 ? a.b2[c0 + wave] : 0.f), a.gate) : sigmoidf_(wave_sum_sw(z));
-        if (a.nts) {
-#pragma unroll
-            for (int j = 0; j < NV; ++j) __builtin_amdgcn_raw_buffer_store_b128(scale8<IO>(r[j], g), ry, voff, (u32)j * 1024u, AUX_NT);
-        } else {
-#pragma unroll
-            for (int j = 0; j < NV; ++j) __builtin_amdgcn_raw_buffer_store_b128(scale8<IO>(r[j], g), ry, voff, (u32)j * 1024u, 0);
-        }
+        store_row16<IO, NV, RES>(r, g, ry, voff, a.nts, resid + row, (u32)a.HW * 2u);      // io16.h (+ residual row, ReLU)
         par ^= 1;
     }
 }
+template <int IO, int NV, bool WLDS, bool EXTRA>
+__global__ __launch_bounds__(512, se16_waves(NV)) void se16_single_kernel(const Se16Args a) {
+    se16_single_body<IO, NV, WLDS, EXTRA, 0>(a, nullptr);
+}
+// the residual kernels and their launch table (behind the single-read launchers): MI355_OK or the launch error
+static int se16_res_launch(int io, int relu, int nv, bool wlds, int grid, size_t smem, hipStream_t st, const Se16Args& a, const u16* resid, void* state);
 
 template <int IO, int NV, bool EXTRA>
 static void se16_go(bool wlds, int grid, size_t smem, hipStream_t st, const Se16Args& a) {
@@ -255,8 +255,8 @@ static void se16_go_nv(int nv, bool wlds, int grid, size_t smem, hipStream_t st,
 // granules, DPP reductions and band geometry: cbam_band.h
 struct Cbam16Args : CbamArgsT<u16> {};            // a type of its own, not an alias: the kernels' symbols keep their names
 
-template <int IO, int SEG, int NV, bool FULL>
-__global__ __launch_bounds__(512, 4) void cbam16_single_kernel(const Cbam16Args a) {
+template <int IO, int SEG, int NV, bool FULL, int RES>      // RES (gate_res.h): 0 plain, 1 / 2 = y = round([relu]((x * gc) * gs + resid))
+__device__ __forceinline__ void cbam16_single_body(const Cbam16Args a, const u16* __restrict__ resid) {
     constexpr int NT = 512, CL = NT / SEG;                            // channel groups (segments) per workgroup
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ u32 s_tk[2];
@@ -487,25 +487,23 @@ __global__ __launch_bounds__(512, 4) void cbam16_single_kernel(const Cbam16Args 
             const v4f s4 = reinterpret_cast<const v4f*>(s_gs)[q & (SEG - 1)];       // lanes beyond the band: stores are dropped (OOB)
             u32 ob = off0;
             asm volatile("" : "+v"(ob));
-            if (a.nts) {
-#pragma unroll
-                for (int j = 0; j < NV; ++j) {
-                    const v4f v = (up4<IO>(r[j]) * s_gc[cl + CL * j]) * s4;
-                    const u32 vo = (FULL || cl + CL * j < C) ? ob + (u32)j * offs : OOB;
-                    __builtin_amdgcn_raw_buffer_store_b64(down4<IO>(v), ry, vo, 0, AUX_NT);
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < NV; ++j) {
-                    const v4f v = (up4<IO>(r[j]) * s_gc[cl + CL * j]) * s4;
-                    const u32 vo = (FULL || cl + CL * j < C) ? ob + (u32)j * offs : OOB;
-                    __builtin_amdgcn_raw_buffer_store_b64(down4<IO>(v), ry, vo, 0, 0);
-                }
-            }
+            cbam_store16<IO, NV, CL, FULL, RES>(r, s_gc, s4, ry, ob, offs, cl, C, a.nts, resid + img, ext);      // io16.h (+ residual band, ReLU)
         }
         if (t == 0) s_tk[par ^ 1] = next_tk;
         par ^= 1;
     }
+}
+template <int IO, int SEG, int NV, bool FULL>
+__global__ __launch_bounds__(512, 4) void cbam16_single_kernel(const Cbam16Args a) {
+    cbam16_single_body<IO, SEG, NV, FULL, 0>(a, nullptr);
+}
+// The residual form, a kernel of its own (the plain instantiations keep their names and arguments); 16 register pairs per lane leave no
+// room for the residual in the 128 registers of two workgroups per CU: that instantiation is built for one.  (The bodies take their
+// argument blocks by value: by reference hipcc allocated a scalar register more or less in the plain SE instantiations.)
+constexpr int cbam16_res_waves(int nv) { return nv >= 16 ? 2 : 4; }
+template <int IO, int SEG, int NV, bool FULL, bool RELU>
+__global__ __launch_bounds__(512, cbam16_res_waves(NV)) void cbam16_single_res_kernel(const Cbam16Args a, const u16* __restrict__ resid) {
+    cbam16_single_body<IO, SEG, NV, FULL, RELU ? 2 : 1>(a, resid);
 }
 
 // =====================================================================================================================================
@@ -646,9 +644,9 @@ __global__ __launch_bounds__(256) void cbam16_sgate_kernel(const float* __restri
 }
 
 // y[row, i] = round((x[row, i] * gc[row]) * gs[b, i]); gc / gs may be null (= 1).  One wave per row, four rows per workgroup.
-template <int IO, bool VEC>
-__global__ __launch_bounds__(256) void scale16_kernel(const u16* __restrict__ x, const float* __restrict__ gc, const float* __restrict__ gs,
-                                                     u16* __restrict__ y, long rows, int C, int HW, int nts) {
+template <int IO, bool VEC, int RES>      // RES (gate_res.h): 0 plain, 1 / 2 = y = round([relu](product + resid)); the kernels are further down
+__device__ __forceinline__ void scale16_body(const u16* __restrict__ x, const float* __restrict__ gc, const float* __restrict__ gs,
+                                             u16* __restrict__ y, const u16* __restrict__ resid, long rows, int C, int HW, int nts) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long row = (long)blockIdx.x * 4 + wave;
     if (row >= rows) return;
@@ -668,6 +666,7 @@ __global__ __launch_bounds__(256) void scale16_kernel(const u16* __restrict__ x,
                 a = a * reinterpret_cast<const v4f*>(gsb)[2 * i];
                 c = c * reinterpret_cast<const v4f*>(gsb)[2 * i + 1];
             }
+            if constexpr (RES != 0) add_res8<IO, RES>(a, c, reinterpret_cast<const u32x4*>(resid + row * HW)[i]);
             const u32x4 o = {pack16<IO>(a.x, a.y), pack16<IO>(a.z, a.w), pack16<IO>(c.x, c.y), pack16<IO>(c.z, c.w)};
             if (nts) __builtin_nontemporal_store(o, &y8[i]);
             else y8[i] = o;
@@ -676,6 +675,7 @@ __global__ __launch_bounds__(256) void scale16_kernel(const u16* __restrict__ x,
         for (int i = lane; i < HW; i += 64) {
             float v = from16<IO>(xr[i]) * g;
             if (gsb) v = v * gsb[i];
+            if constexpr (RES != 0) v = res1<RES>(v, from16<IO>(resid[row * HW + i]));
             yr[i] = to16<IO>(v);
         }
     }
@@ -724,7 +724,7 @@ bool se16_single_ok(int C, int Cr, int H, int W) {
 
 // `state` = epoch | (B - 1 unused words) | ticket | err (fused_state_bytes), `gran` = B*C granules: the layout of the fp32 kernel
 int se16_single(const u16* x, const float* w1, const float* w2, u16* y, int B, int C, int Cr, int H, int W, int io, void* state, void* gran,
-                mi355::SeExtra ex, hipStream_t st) {
+                mi355::SeExtra ex, hipStream_t st, const u16* resid = nullptr, int relu = 0) {
     Se16Args a{};
     a.x = x; a.y = y; a.w1 = w1; a.w2 = w2; a.b1 = ex.b1; a.b2 = ex.b2; a.gate = ex.gate;
     a.gran = static_cast<u64*>(gran);
@@ -749,8 +749,8 @@ int se16_single(const u16* x, const float* w1, const float* w2, u16* y, int B, i
         return mi355::fail(MI355_EUNSUPPORTED, "se16_single: an image needs %d resident workgroups, the device holds %d", a.gpi, mi355::resident_slots(2));
     if (grid > a.total) grid = a.total;
     const unsigned long long key = ((unsigned long long)B << 32) ^ (unsigned long long)C ^ ((unsigned long long)grid << 44) ^ 0x5E16000000000000ull;
-    // epoch, ticket, granules (contiguous)
-    if (int rc = mi355::xch_zero("se16_single", state, key, mi355::fused_state_bytes(B) + mi355::se_single_extra_bytes(B, C), st)) return rc;
+    if (int rc = mi355::xch_zero("se16_single", state, key, mi355::fused_state_bytes(B) + mi355::se_single_extra_bytes(B, C), st)) return rc;   // epoch, ticket, granules (contiguous)
+    if (resid) return se16_res_launch(io, relu, nv, wlds, (int)grid, smem, st, a, resid, state);      // (the plain SELayer only: se_eca16)
     {
         const bool extra = ex.b1 || ex.b2 || ex.gate;
         MI355_TRACE(st, "se16_single_kernel io=%d C=%d HW=%d nv=%d NV=%d wlds=%d extra=%d", io, C, a.HW, nv, se16_nv(nv), (int)wlds, (int)extra);
@@ -773,7 +773,7 @@ bool cbam16_single_ok(int C, int Cr, int H, int W, int ks) {
 }
 
 int cbam16_single(const u16* x, const float* w1, const float* w2, const float* wconv, u16* y, int B, int C, int Cr, int H, int W, int ks, int io,
-                  void* extra, hipStream_t st) {
+                  void* extra, hipStream_t st, const u16* resid = nullptr, int relu = 0) {
     Geo g;
     if (!geometry(512, C, Cr, H, W, ks, true, g)) return mi355::fail(MI355_EUNSUPPORTED, "cbam16_single: unsupported shape");
     Cbam16Args a{};
@@ -793,12 +793,40 @@ int cbam16_single(const u16* x, const float* w1, const float* w2, const float* w
     const bool full = (C == g.CL * g.NV);
     a.wlds = (g.smem_base + g.smem_w <= (size_t)(120 * 1024) / 2) ? 1 : 0;
     const size_t smem = g.smem_base + (a.wlds ? g.smem_w : 0);
-    long grid = (long)mi355::resident_slots(2);
+    long grid = (long)mi355::resident_slots(resid ? cbam16_res_waves(g.NV) / 2 : 2);
     if (g.NB > grid) return mi355::fail(MI355_EUNSUPPORTED, "cbam16_single: an image needs %d resident workgroups, the device holds %ld", g.NB, grid);
     if (grid > a.total) grid = a.total;
     const unsigned long long key = ((unsigned long long)B << 48) ^ ((unsigned long long)C << 32) ^ ((unsigned long long)H << 16) ^ (unsigned long long)W ^ 0xCB16000000000000ull;
     if (int rc = mi355::xch_zero("cbam16_single", extra, key, mi355::cbam_single_extra_bytes(B, C, H, W), st)) return rc;
-    {
+    if (resid) {
+        MI355_TRACE(st, "cbam16_single_res_kernel io=%d C=%d H=%d W=%d ks=%d SEG=%d NV=%d full=%d res=1 relu=%d", io, C, H, W, ks, g.SEG, g.NV, (int)full, relu);
+#define GOR(IO_, SEG_, NV_, FULL_)                                                                                     \
+    do {                                                                                                               \
+        if (relu) cbam16_single_res_kernel<IO_, SEG_, NV_, FULL_, true><<<(int)grid, 512, smem, st>>>(a, resid);       \
+        else      cbam16_single_res_kernel<IO_, SEG_, NV_, FULL_, false><<<(int)grid, 512, smem, st>>>(a, resid);      \
+    } while (0)
+#define GOR_F(IO_, SEG_, NV_)                      \
+    do {                                           \
+        if (full) GOR(IO_, SEG_, NV_, true);       \
+        else      GOR(IO_, SEG_, NV_, false);      \
+    } while (0)
+#define GOR_IO(IO_)                                \
+    do {                                           \
+        if (g.SEG == 32) {                         \
+            if (g.NV == 4) GOR_F(IO_, 32, 4);      \
+            else if (g.NV == 8) GOR_F(IO_, 32, 8); \
+            else GOR(IO_, 32, 16, true);           \
+        } else {                                   \
+            if (g.NV == 4) GOR_F(IO_, 16, 4);      \
+            else if (g.NV == 8) GOR_F(IO_, 16, 8); \
+            else GOR(IO_, 16, 16, true);           \
+        }                                          \
+    } while (0)
+        BY_IO(io, GOR_IO);
+#undef GOR_IO
+#undef GOR_F
+#undef GOR
+    } else {
         MI355_TRACE(st, "cbam16_single_kernel io=%d C=%d H=%d W=%d ks=%d SEG=%d NV=%d full=%d", io, C, H, W, ks, g.SEG, g.NV, (int)full);
 #define GO(IO_, SEG_, NV_)                                                                         \
     do {                                                                                           \
@@ -824,6 +852,81 @@ int cbam16_single(const u16* x, const float* w1, const float* w2, const float* w
     return mi355::xch_launched("cbam16_single", extra);
 }
 
+// ---- the residual forms of the single-read SE / ECA kernels: y = round([relu](x * g + resid)) (gate_res.h; store_row16 of io16.h) -------------
+// Kernels of their own around the shared bodies.  Waves per SIMD as for the plain kernels (SE: se16_waves), except ECA at 7 chunks per
+// lane: with the chunks of the residual in flight it spills at 80 registers and is built for two workgroups per CU.
+constexpr int eca16_res_waves(int nv) { return nv <= 4 ? 8 : 4; }
+
+template <int IO, int NV, bool RELU>
+__global__ __launch_bounds__(512, eca16_res_waves(NV)) void eca16_halo_res_kernel(const u16* __restrict__ x, const float* __restrict__ taps,
+                                                                   const u16* __restrict__ resid, u16* __restrict__ y, int C, int k, int HW,
+                                                                   int gpi, int total, int per_xcd, int nts) {
+    eca16_halo_body<IO, NV, RELU ? 2 : 1>(x, taps, y, resid, C, k, HW, gpi, total, per_xcd, nts);
+}
+// the residual form of the plain SELayer (no EXTRA)
+template <int IO, int NV, bool WLDS, bool RELU>
+__global__ __launch_bounds__(512, se16_waves(NV)) void se16_single_res_kernel(const Se16Args a, const u16* __restrict__ resid) {
+    se16_single_body<IO, NV, WLDS, false, RELU ? 2 : 1>(a, resid);
+}
+template <int IO, int NV, bool RELU>
+static void se16_res_go(bool wlds, int grid, size_t smem, hipStream_t st, const Se16Args& a, const u16* resid) {
+    if (wlds) se16_single_res_kernel<IO, NV, true, RELU><<<grid, 512, smem, st>>>(a, resid);
+    else      se16_single_res_kernel<IO, NV, false, RELU><<<grid, 512, smem, st>>>(a, resid);
+}
+template <int IO, bool RELU>
+static void se16_res_go_nv(int nv, bool wlds, int grid, size_t smem, hipStream_t st, const Se16Args& a, const u16* resid) {
+    switch (se16_nv(nv)) {
+        case 1: se16_res_go<IO, 1, RELU>(wlds, grid, smem, st, a, resid); break;
+        case 2: se16_res_go<IO, 2, RELU>(wlds, grid, smem, st, a, resid); break;
+        case 4: se16_res_go<IO, 4, RELU>(wlds, grid, smem, st, a, resid); break;
+        case 7: se16_res_go<IO, 7, RELU>(wlds, grid, smem, st, a, resid); break;
+        default: se16_res_go<IO, 8, RELU>(wlds, grid, smem, st, a, resid);
+    }
+}
+static int se16_res_launch(int io, int relu, int nv, bool wlds, int grid, size_t smem, hipStream_t st, const Se16Args& a, const u16* resid, void* state) {
+    MI355_TRACE(st, "se16_single_res_kernel io=%d C=%d HW=%d nv=%d NV=%d wlds=%d extra=0 res=1 relu=%d", io, a.C, a.HW, nv, se16_nv(nv), (int)wlds, relu);
+    if (io == 1) { if (relu) se16_res_go_nv<1, true>(nv, wlds, grid, smem, st, a, resid); else se16_res_go_nv<1, false>(nv, wlds, grid, smem, st, a, resid); }
+    else         { if (relu) se16_res_go_nv<2, true>(nv, wlds, grid, smem, st, a, resid); else se16_res_go_nv<2, false>(nv, wlds, grid, smem, st, a, resid); }
+    return mi355::xch_launched("se16_single", state);
+}
+
+// eca16_single with the residual: the same geometry, slices and store hint
+int eca16_single_res(const u16* x, const float* taps, const u16* resid, u16* y, int B, int C, int k, int H, int W, int relu, int io, hipStream_t st) {
+    const int HW = H * W, n8 = HW / 8, gpi = C / ECW;
+    const long total_l = (long)B * gpi;
+    if (total_l > (1L << 30)) return mi355::fail(MI355_EUNSUPPORTED, "eca16_single: too many slices");
+    const int total = (int)total_l, per_xcd = (total + 7) / 8, grid = per_xcd * 8;
+    const int nv = (n8 + 63) / 64;
+    const int nts = (mi355::opt(mi355::O_NT) & 2) ? 1 : 0;
+    MI355_TRACE(st, "eca16_halo_res_kernel io=%d C=%d HW=%d k=%d nv=%d NV=%d res=1 relu=%d", io, C, HW, k, nv, eca16_nv(nv), relu);
+#define GOR(IO_, NV_)                                                                                                                   \
+    do {                                                                                                                                \
+        if (relu) eca16_halo_res_kernel<IO_, NV_, true><<<grid, 512, 0, st>>>(x, taps, resid, y, C, k, HW, gpi, total, per_xcd, nts);   \
+        else      eca16_halo_res_kernel<IO_, NV_, false><<<grid, 512, 0, st>>>(x, taps, resid, y, C, k, HW, gpi, total, per_xcd, nts);  \
+    } while (0)
+#define GOR_IO(IO_)                      \
+    switch (eca16_nv(nv)) {              \
+        case 1: GOR(IO_, 1); break;      \
+        case 2: GOR(IO_, 2); break;      \
+        case 4: GOR(IO_, 4); break;      \
+        case 7: GOR(IO_, 7); break;      \
+        default: GOR(IO_, 8);            \
+    }
+    BY_IO(io, GOR_IO);
+#undef GOR_IO
+#undef GOR
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return mi355::fail(MI355_EHIP, "eca16_single: launch -> %s", hipGetErrorString(e));
+    return MI355_OK;
+}
+
+// The residual form of the single-read CBAM takes the shapes of the plain one, except where its 16-pair instantiation (one workgroup per
+// CU) cannot hold an image's bands at once; those calls take the general form.
+bool cbam16_single_res_ok(int C, int Cr, int H, int W, int ks) {
+    Geo g;
+    return cbam16_single_ok(C, Cr, H, W, ks) && geometry(512, C, Cr, H, W, ks, true, g) && g.NB <= mi355::resident_slots(cbam16_res_waves(g.NV) / 2);
+}
+
 // ---- general-form launchers ------------------------------------------------------------------------------------------------------------
 template <int IO>
 void pool16(bool with_max, bool vec, const u16* x, float* avg, float* mx, long rows, int HW, hipStream_t st) {
@@ -837,10 +940,30 @@ void pool16(bool with_max, bool vec, const u16* x, float* avg, float* mx, long r
         else     pool16_kernel<IO, false, false><<<grid, 256, 0, st>>>(x, avg, mx, rows, HW);
     }
 }
+// the scale pass: the plain kernel and its residual form around scale16_body
+template <int IO, bool VEC>
+__global__ __launch_bounds__(256) void scale16_kernel(const u16* __restrict__ x, const float* __restrict__ gc, const float* __restrict__ gs,
+                                                     u16* __restrict__ y, long rows, int C, int HW, int nts) {
+    scale16_body<IO, VEC, 0>(x, gc, gs, y, nullptr, rows, C, HW, nts);
+}
+template <int IO, bool VEC, bool RELU>
+__global__ __launch_bounds__(256) void scale16_res_kernel(const u16* __restrict__ x, const float* __restrict__ gc, const float* __restrict__ gs,
+                                                         const u16* __restrict__ resid, u16* __restrict__ y, long rows, int C, int HW, int nts) {
+    scale16_body<IO, VEC, RELU ? 2 : 1>(x, gc, gs, y, resid, rows, C, HW, nts);
+}
 template <int IO>
-void scale16(bool vec, const u16* x, const float* gc, const float* gs, u16* y, long rows, int C, int HW, hipStream_t st) {
+void scale16(bool vec, const u16* x, const float* gc, const float* gs, u16* y, long rows, int C, int HW, hipStream_t st, const u16* resid = nullptr,
+             int relu = 0) {
     const int grid = cdiv(rows, 4);
     const int nts = (mi355::opt(mi355::O_NT) & 2) ? 1 : 0;
+    if (resid) {
+        MI355_TRACE(st, "scale16_res_kernel io=%d HW=%d res=1 relu=%d", IO, HW, relu);
+        if (vec) { if (relu) scale16_res_kernel<IO, true, true><<<grid, 256, 0, st>>>(x, gc, gs, resid, y, rows, C, HW, nts);
+                   else      scale16_res_kernel<IO, true, false><<<grid, 256, 0, st>>>(x, gc, gs, resid, y, rows, C, HW, nts); }
+        else     { if (relu) scale16_res_kernel<IO, false, true><<<grid, 256, 0, st>>>(x, gc, gs, resid, y, rows, C, HW, nts);
+                   else      scale16_res_kernel<IO, false, false><<<grid, 256, 0, st>>>(x, gc, gs, resid, y, rows, C, HW, nts); }
+        return;
+    }
     MI355_TRACE(st, "scale16_kernel io=%d HW=%d", IO, HW);
     if (vec) scale16_kernel<IO, true><<<grid, 256, 0, st>>>(x, gc, gs, y, rows, C, HW, nts);
     else     scale16_kernel<IO, false><<<grid, 256, 0, st>>>(x, gc, gs, y, rows, C, HW, nts);
@@ -864,18 +987,21 @@ size_t mi355_cbam16_workspace_bytes(int B, int C, int H, int W) {
 
 // mode 0: SE (wa = w1, wb = w2, Cr), mode 1: ECA (wa = taps, Cr = k)
 static int se_eca16(int mode, const void* xv, const float* wa, const float* wb, void* yv, int B, int C, int Cr, int H, int W, int io, void* ws,
-                    hipStream_t st, mi355::SeExtra ex = mi355::SeExtra{nullptr, nullptr, 0}) {
+                    hipStream_t st, mi355::SeExtra ex = mi355::SeExtra{nullptr, nullptr, 0}, const void* residv = nullptr, int relu = 0) {
+    // residv (mi355_se_res_fwd / mi355_eca_res_fwd; null: the plain gate): the same route by the same predicates, the residual kernels
     const u16* x = static_cast<const u16*>(xv);
+    const u16* resid = static_cast<const u16*>(residv);
     u16* y = static_cast<u16*>(yv);
     const int HW = H * W;
-    const bool vec = (HW % 8 == 0) && aligned16(x) && aligned16(y);
+    const bool vec = (HW % 8 == 0) && aligned16(x) && aligned16(y) && aligned16(resid);
     const size_t smem = (size_t)(2 * (size_t)C + (mode == 0 ? Cr : 0)) * sizeof(float);
     if (smem > 64 * 1024) return mi355::fail(MI355_EUNSUPPORTED, "channel count %d too large for the gate stage", C);
     if (mode == 0 && vec && se16_single_ok(C, Cr, H, W)) {
         char* state = static_cast<char*>(ws) + mi355::pooled_bytes(B, C);
-        return se16_single(x, wa, wb, y, B, C, Cr, H, W, io, state, state + mi355::fused_state_bytes(B), ex, st);
+        return se16_single(x, wa, wb, y, B, C, Cr, H, W, io, state, state + mi355::fused_state_bytes(B), ex, st, resid, relu);
     }
-    if (mode == 1 && vec && eca16_single_ok(C, Cr, H, W)) return eca16_single(x, wa, y, B, C, Cr, H, W, io, st);
+    if (mode == 1 && vec && eca16_single_ok(C, Cr, H, W))
+        return resid ? eca16_single_res(x, wa, resid, y, B, C, Cr, H, W, relu, io, st) : eca16_single(x, wa, y, B, C, Cr, H, W, io, st);
     float* pooled = static_cast<float*>(ws);
     const long rows = (long)B * C;
     if (io == 1) pool16<1>(false, vec, x, pooled, nullptr, rows, HW, st);
@@ -889,8 +1015,8 @@ static int se_eca16(int mode, const void* xv, const float* wa, const float* wb, 
         if (mode == 0) chan_gates16_kernel<0><<<B, 256, smem, st>>>(pooled, nullptr, wa, wb, C, Cr, ex);
         else           chan_gates16_kernel<1><<<B, 256, smem, st>>>(pooled, nullptr, wa, nullptr, C, Cr, ex);
     }
-    if (io == 1) scale16<1>(vec, x, pooled, nullptr, y, rows, C, HW, st);
-    else         scale16<2>(vec, x, pooled, nullptr, y, rows, C, HW, st);
+    if (io == 1) scale16<1>(vec, x, pooled, nullptr, y, rows, C, HW, st, resid, relu);
+    else         scale16<2>(vec, x, pooled, nullptr, y, rows, C, HW, st, resid, relu);
     MI355_LAUNCH_CHECK();
     return MI355_OK;
 }
@@ -925,6 +1051,9 @@ int mi355_eca16_fwd(const void* x, const float* wconv, void* y, int B, int C, in
     return se_eca16(1, x, wconv, nullptr, y, B, C, k, H, W, io, ws, static_cast<hipStream_t>(stream));
 }
 
+static int cbam16_run(const void* xv, const float* w1, const float* w2, const float* wconv, void* yv, int B, int C, int Cr, int ks, int H, int W,
+                      int stage, int io, void* ws, hipStream_t st, const void* residv, int relu);
+
 int mi355_cbam16_fwd(const void* xv, const float* w1, const float* w2, const float* wconv, void* yv, int B, int C, int Cr, int ks, int H, int W,
                      int stage, int io, void* ws, size_t ws_bytes, mi355_stream_t stream) {
     MI355_CHECK_ARG(io == 1 || io == 2);
@@ -936,14 +1065,22 @@ int mi355_cbam16_fwd(const void* xv, const float* w1, const float* w2, const flo
     if (do_s) MI355_CHECK_ARG(wconv && ks > 0 && (ks & 1));
     MI355_CHECK_ARG(check_io16(io, B, C, H, W));
     MI355_CHECK_ARG(ws_bytes >= mi355_cbam16_workspace_bytes(B, C, H, W));
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    return cbam16_run(xv, w1, w2, wconv, yv, B, C, Cr, ks, H, W, stage, io, ws, static_cast<hipStream_t>(stream), nullptr, 0);
+}
+
+// The launches of mi355_cbam16_fwd and of mi355_cbam_res_fwd's 16-bit half behind their argument checks.  residv (stage 0 only; null: the
+// plain gate): the same route by the same predicates, the residual kernels.
+static int cbam16_run(const void* xv, const float* w1, const float* w2, const float* wconv, void* yv, int B, int C, int Cr, int ks, int H, int W,
+                      int stage, int io, void* ws, hipStream_t st, const void* residv, int relu) {
+    const bool do_c = stage != 2, do_s = stage != 1;
     const u16* x = static_cast<const u16*>(xv);
+    const u16* resid = static_cast<const u16*>(residv);
     u16* y = static_cast<u16*>(yv);
     char* wsp = static_cast<char*>(ws);
-    if (stage == 0 && aligned16(x) && aligned16(y) && cbam16_single_ok(C, Cr, H, W, ks))                  // x read once
-        return cbam16_single(x, w1, w2, wconv, y, B, C, Cr, H, W, ks, io, wsp + mi355::cbam_multipass_bytes(B, C, H, W), st);
+    if (stage == 0 && aligned16(x) && aligned16(y) && aligned16(resid) && (resid ? cbam16_single_res_ok(C, Cr, H, W, ks) : cbam16_single_ok(C, Cr, H, W, ks)))                  // x read once
+        return cbam16_single(x, w1, w2, wconv, y, B, C, Cr, H, W, ks, io, wsp + mi355::cbam_multipass_bytes(B, C, H, W), st, resid, relu);
     const int HW = H * W;
-    const bool vec = (HW % 8 == 0) && aligned16(x) && aligned16(y);
+    const bool vec = (HW % 8 == 0) && aligned16(x) && aligned16(y) && aligned16(resid);
     const size_t bc = mi355::r16((size_t)B * C * 4);
     float* avg = reinterpret_cast<float*>(wsp);                           // becomes the channel gates in place
     float* mx = reinterpret_cast<float*>(wsp + bc);
@@ -973,10 +1110,23 @@ int mi355_cbam16_fwd(const void* xv, const float* w1, const float* w2, const flo
             cbam16_sgate_kernel<<<B * tiles, 256, 0, st>>>(smap, wconv, gs, H, W, ks, tiles);
         }
     }
-    if (io == 1) scale16<1>(vec, x, do_c ? avg : nullptr, do_s ? gs : nullptr, y, rows, C, HW, st);
-    else         scale16<2>(vec, x, do_c ? avg : nullptr, do_s ? gs : nullptr, y, rows, C, HW, st);
+    if (io == 1) scale16<1>(vec, x, do_c ? avg : nullptr, do_s ? gs : nullptr, y, rows, C, HW, st, resid, relu);
+    else         scale16<2>(vec, x, do_c ? avg : nullptr, do_s ? gs : nullptr, y, rows, C, HW, st, resid, relu);
     MI355_LAUNCH_CHECK();
     return MI355_OK;
 }
 
 }  // extern "C"
+
+// the 16-bit halves of mi355_se_res_fwd / mi355_eca_res_fwd / mi355_cbam_res_fwd (chan_attn.hip checks the arguments)
+namespace mi355 {
+bool check_io16(int io, long B, long C, long H, long W) { return ::check_io16(io, B, C, H, W); }
+int se_eca16_res(int mode, const void* x, const float* wa, const float* wb, const void* resid, void* y, int B, int C, int Cr, int H, int W, int relu,
+                 int io, void* ws, hipStream_t st) {
+    return se_eca16(mode, x, wa, wb, y, B, C, Cr, H, W, io, ws, st, SeExtra{nullptr, nullptr, 0}, resid, relu);
+}
+int cbam16_res(const void* x, const float* w1, const float* w2, const float* wconv, const void* resid, void* y, int B, int C, int Cr, int ks, int H,
+               int W, int relu, int io, void* ws, hipStream_t st) {
+    return cbam16_run(x, w1, w2, wconv, y, B, C, Cr, ks, H, W, 0, io, ws, st, resid, relu);
+}
+}  // namespace mi355

@@ -95,8 +95,9 @@ int   stem_conv(const float* x, const float* w, const float* bias, const float* 
 size_t zoo_workspace_bytes(int B, int C);
 size_t cbam_single_extra_bytes(int B, int C, int H, int W);
 bool  cbam_single_applicable(int C, int Cr, int H, int W, int ks);
+bool  cbam_single_res_applicable(int C, int Cr, int H, int W, int ks);      // the residual form (resid != null below)
 int   cbam_single(const float* x, const float* w1, const float* w2, const float* wconv, float* y, int B, int C, int Cr, int H, int W,
-                  int ks, void* extra, hipStream_t st);
+                  int ks, void* extra, hipStream_t st, const float* resid = nullptr, int relu = 0);
 size_t se_single_extra_bytes(int B, int C);
 bool  se_single_applicable(int C, int Cr, int H, int W);
 // SE variants embedded in the reference's CNNs: optional biases of the two excitation layers and the gate function
@@ -106,10 +107,17 @@ struct SeExtra {
     int gate;            // 0 sigmoid, 1 hard sigmoid relu6(z + 3) / 6
 };
 int   se_single(const float* x, const float* w1, const float* w2, float* y, int B, int C, int Cr, int H, int W, void* state,
-                void* gran, SeExtra ex, hipStream_t st);
+                void* gran, SeExtra ex, hipStream_t st, const float* resid = nullptr, int relu = 0);
 bool  eca_single_applicable(int C, int k, int H, int W);
 int   eca_single(const float* x, const float* taps, float* y, int B, int C, int k, int H, int W, hipStream_t st);
+int   eca_single_res(const float* x, const float* taps, const float* resid, float* y, int B, int C, int k, int H, int W, int relu, hipStream_t st);
 size_t fused_state_bytes(int B);
+// the 16-bit halves of mi355_se_res_fwd / mi355_eca_res_fwd (mode 0 / 1) / mi355_cbam_res_fwd behind their argument checks (chan_io16.hip)
+bool  check_io16(int io, long B, long C, long H, long W);
+int   se_eca16_res(int mode, const void* x, const float* wa, const float* wb, const void* resid, void* y, int B, int C, int Cr, int H, int W,
+                   int relu, int io, void* ws, hipStream_t st);
+int   cbam16_res(const void* x, const float* w1, const float* w2, const float* wconv, const void* resid, void* y, int B, int C, int Cr, int ks,
+                 int H, int W, int relu, int io, void* ws, hipStream_t st);
 // DoubleAttention in two passes over the image (double_attn_fused.hip): 16-bit operand modes, c_m = c_n = 128, C in {128, 256}
 bool   double_attn_fused_ok(int B, int C, int cm, int cn, int HW, int precision);
 size_t double_attn_fused_workspace(int B, int C, int HW);

@@ -57,6 +57,11 @@ SIGNATURES = {
     "mi355_eca16_fwd": (c_int, [c_vp, c_vp, c_vp] + [c_int] * 6 + [c_vp, c_size, c_vp]),
     "mi355_cbam16_workspace_bytes": (c_size, [c_int] * 4),
     "mi355_cbam16_fwd": (c_int, [c_vp] * 5 + [c_int] * 8 + [c_vp, c_size, c_vp]),
+    # SELayer / ECALayer / CBAM with the residual add (+ ReLU) in the store epilogue: one entry per gate for all I/O types (`relu`, `io` in front
+    # of the workspace), called by functional._call_res beside IO_ENTRIES, not through it
+    "mi355_se_res_fwd": (c_int, [c_vp] * 5 + [c_int] * 7 + [c_vp, c_size, c_vp]),
+    "mi355_eca_res_fwd": (c_int, [c_vp] * 4 + [c_int] * 7 + [c_vp, c_size, c_vp]),
+    "mi355_cbam_res_fwd": (c_int, [c_vp] * 6 + [c_int] * 8 + [c_vp, c_size, c_vp]),
     "mi355_double_attn_workspace_bytes": (c_size, [c_int] * 6),
     "mi355_double_attn_ws_bytes": (c_size, [c_int] * 7),
     "mi355_double_attn_fwd": (c_int, [c_vp] * 10 + [c_int] * 7 + [c_vp, c_size, c_vp]),

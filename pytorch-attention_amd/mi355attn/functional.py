@@ -298,9 +298,36 @@ def _call_io(op, io, head, ws, device, slot32=()):
     check(getattr(lib(), name)(*head, *((io,) if io else slot32), dptr(ws), ws.numel(), stream_ptr(device)), name)
 
 
-def se_forward(x, w1, w2):
-    """SELayer forward: x (B,C,H,W) fp32 / fp16 / bf16 (output in the same type), w1 (C/r,C), w2 (C,C/r)."""
+def _resid_io(x, io, resid, relu, what):
+    """The `resid` / `relu` arguments of se_forward / eca_forward / cbam_forward, checked before any launch: resid (or None) has the shape,
+    dtype and device of x and is made contiguous the way x is; relu needs a resid.  Returns the dense resid or None."""
+    if resid is None:
+        if relu:
+            raise ValueError(f"{what}: relu=True needs a resid (y = relu(gate(x) + resid)); no network applies a ReLU to the gate alone")
+        return None
+    if not isinstance(resid, torch.Tensor):
+        raise TypeError(f"resid: expected a torch.Tensor, got {type(resid).__name__}")
+    if resid.dtype != x.dtype:
+        raise TypeError(f"resid: expected {x.dtype} like x, got {resid.dtype}")
+    resid, rio = _ffi.require_device_io(resid, "resid")
+    if rio != io or resid.device != x.device:
+        raise _ffi.Mi355Error(f"resid lives on {resid.device}, x on {x.device}")
+    if tuple(resid.shape) != tuple(x.shape):
+        raise ValueError(f"resid: expected the shape of x {tuple(x.shape)}, got {tuple(resid.shape)}")
+    return resid
+
+
+def _call_res(name, io, head, relu, ws, device):
+    """Call one of the residual entries (mi355_se_res_fwd, mi355_eca_res_fwd, mi355_cbam_res_fwd): one symbol for all I/O types, `relu`
+    and `io` in front of the workspace."""
+    check(getattr(lib(), name)(*head, int(bool(relu)), io, dptr(ws), ws.numel(), stream_ptr(device)), name)
+
+
+def se_forward(x, w1, w2, resid=None, relu=False):
+    """SELayer forward: x (B,C,H,W) fp32 / fp16 / bf16 (output in the same type), w1 (C/r,C), w2 (C,C/r).
+    resid (the type and shape of x): y = gate(x) + resid, with relu=True y = relu(gate(x) + resid), in the kernel's store epilogue."""
     x, io = _ffi.require_device_io(x, "x")
+    resid = _resid_io(x, io, resid, relu, "se_forward")
     w1 = param32(w1, "fc.0.weight")
     w2 = param32(w2, "fc.2.weight")
     B, C, H, W = x.shape
@@ -309,7 +336,10 @@ def se_forward(x, w1, w2):
         raise ValueError(f"SE weight shapes {tuple(w1.shape)}, {tuple(w2.shape)} do not match C={C}")
     y = torch.empty_like(x)
     ws = _dedicated("se", io, x, lib().mi355_se_workspace_bytes(B, C, H, W))
-    _call_io("se", io, (dptr(x), dptr(w1), dptr(w2), dptr(y), B, C, Cr, H, W), ws, x.device)
+    if resid is not None:
+        _call_res("mi355_se_res_fwd", io, (dptr(x), dptr(w1), dptr(w2), dptr(resid), dptr(y), B, C, Cr, H, W), relu, ws, x.device)
+    else:
+        _call_io("se", io, (dptr(x), dptr(w1), dptr(w2), dptr(y), B, C, Cr, H, W), ws, x.device)
     _sync_check()
     return y
 
@@ -528,21 +558,30 @@ def se_ex_forward(x, w1, b1, w2, b2, gate="sigmoid"):
     return y
 
 
-def eca_forward(x, wconv):
-    """ECALayer forward: x (B,C,H,W) fp32 / fp16 / bf16 (output in the same type), wconv (1,1,k) or (k,)."""
+def eca_forward(x, wconv, resid=None, relu=False):
+    """ECALayer forward: x (B,C,H,W) fp32 / fp16 / bf16 (output in the same type), wconv (1,1,k) or (k,).
+    resid / relu: y = [relu](gate(x) + resid) in the kernel's store epilogue (se_forward)."""
     x, io = _ffi.require_device_io(x, "x")
+    resid = _resid_io(x, io, resid, relu, "eca_forward")
     wconv = param32(wconv, "conv.weight").reshape(-1)
     B, C, H, W = x.shape
     k = wconv.numel()
     y = torch.empty_like(x)
     ws = workspace(lib().mi355_eca_workspace_bytes(B, C, H, W), x.device)
-    _call_io("eca", io, (dptr(x), dptr(wconv), dptr(y), B, C, k, H, W), ws, x.device)
+    if resid is not None:
+        _call_res("mi355_eca_res_fwd", io, (dptr(x), dptr(wconv), dptr(resid), dptr(y), B, C, k, H, W), relu, ws, x.device)
+    else:
+        _call_io("eca", io, (dptr(x), dptr(wconv), dptr(y), B, C, k, H, W), ws, x.device)
     return y
 
 
-def cbam_forward(x, w1=None, w2=None, wconv=None, stage=0):
-    """CBAM forward (stage 0), ChannelAttention alone (1) or SpatialAttention alone (2); x fp32 / fp16 / bf16, output in the same type."""
+def cbam_forward(x, w1=None, w2=None, wconv=None, stage=0, resid=None, relu=False):
+    """CBAM forward (stage 0), ChannelAttention alone (1) or SpatialAttention alone (2); x fp32 / fp16 / bf16, output in the same type.
+    resid / relu (stage 0 only): y = [relu](gate(x) + resid) in the kernel's store epilogue (se_forward)."""
+    if stage != 0 and (resid is not None or relu):
+        raise ValueError(f"cbam_forward: resid / relu belong to the whole block (stage 0), got stage={stage}")
     x, io = _ffi.require_device_io(x, "x")
+    resid = _resid_io(x, io, resid, relu, "cbam_forward")
     B, C, H, W = x.shape
     Cr, ks = 0, 0
     if stage != 2:
@@ -560,7 +599,10 @@ def cbam_forward(x, w1=None, w2=None, wconv=None, stage=0):
     ptrs = (dptr(w1 if stage != 2 else None), dptr(w2 if stage != 2 else None), dptr(wconv if stage != 1 else None))
     n = (lib().mi355_cbam16_workspace_bytes if io else lib().mi355_cbam_workspace_bytes)(B, C, H, W)
     ws = _dedicated("cbam", io, x, n) if stage == 0 else workspace(n, x.device)
-    _call_io("cbam", io, (dptr(x), *ptrs, dptr(y), B, C, Cr, ks, H, W, stage), ws, x.device)
+    if resid is not None:
+        _call_res("mi355_cbam_res_fwd", io, (dptr(x), *ptrs, dptr(resid), dptr(y), B, C, Cr, ks, H, W), relu, ws, x.device)
+    else:
+        _call_io("cbam", io, (dptr(x), *ptrs, dptr(y), B, C, Cr, ks, H, W, stage), ws, x.device)
     if stage == 0:
         _sync_check()
     return y

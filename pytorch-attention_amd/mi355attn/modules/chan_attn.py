@@ -34,8 +34,10 @@ class SELayer(nn.Module):
         self.fc = _excite_stack(nn.Linear(channel, hidden, bias=False), nn.Linear(hidden, channel, bias=False))
         self.fc.append(nn.Sigmoid())
 
-    def forward(self, x):
-        return F.se_forward(x, self.fc[0].weight, self.fc[2].weight)
+    def forward(self, x, resid=None, relu=False):
+        """resid (the shape, dtype and device of x): y = self(x) + resid; with relu=True y = relu(self(x) + resid) -- the shortcut add and
+        ReLU of an SE-ResNet block in the gate's store epilogue (fp32: the bits of torch.relu(self(x) + resid))."""
+        return F.se_forward(x, self.fc[0].weight, self.fc[2].weight, resid=resid, relu=relu)
 
 
 class ECALayer(nn.Module):
@@ -47,8 +49,9 @@ class ECALayer(nn.Module):
         k = t + (1 - t % 2)                      # next odd >= t   (eca.py:21-22)
         self.conv = nn.Conv1d(1, 1, kernel_size=k, padding=(k - 1) // 2, bias=False)
 
-    def forward(self, x):
-        return F.eca_forward(x, self.conv.weight)
+    def forward(self, x, resid=None, relu=False):
+        """resid / relu: y = [relu](self(x) + resid) in the gate's store epilogue (SELayer.forward)."""
+        return F.eca_forward(x, self.conv.weight, resid=resid, relu=relu)
 
 
 class ChannelAttention(nn.Module):
@@ -78,8 +81,9 @@ class CBAM(nn.Module):
         self.ca = ChannelAttention(channel, reduction)
         self.sa = SpatialAttention(kernel_size)
 
-    def forward(self, x):
-        return F.cbam_forward(x, self.ca.fc[0].weight, self.ca.fc[2].weight, self.sa.conv.weight, stage=0)
+    def forward(self, x, resid=None, relu=False):
+        """resid / relu: y = [relu](self(x) + resid) in the gate's store epilogue (SELayer.forward)."""
+        return F.cbam_forward(x, self.ca.fc[0].weight, self.ca.fc[2].weight, self.sa.conv.weight, stage=0, resid=resid, relu=relu)
 
 
 class DoubleAttention(nn.Module):
