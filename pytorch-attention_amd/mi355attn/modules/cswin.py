@@ -14,7 +14,7 @@ import torch
 from torch import nn
 
 from .. import functional as F
-from .vit import _fast, _io_precision, _is16, _mlp16, _p32, _same
+from ._io16 import _fast, _half16, _io_precision, _is16, _layernorm, _mlp_run, _p32, _same
 
 
 def _stripe(resolution, idx, split_size):
@@ -37,10 +37,10 @@ class Mlp(nn.Module):
         self.precision = None
 
     def forward(self, x, resid=None):
-        if _fast(self.precision, self.fc1, self.fc2):
-            return _mlp16(x, self.fc1, self.fc2, self.precision, second_gelu=False, resid=resid)
-        h = F.linear(x, self.fc1.weight, self.fc1.bias, act=F.ACT_GELU, precision=self.precision)
-        return F.linear(h, self.fc2.weight, self.fc2.bias, resid=resid, precision=self.precision)
+        return self._run(x, resid, self.precision, _same)
+
+    def _run(self, x, resid, precision, P):
+        return _mlp_run(self.fc1, self.fc2, x, resid, precision, P)
 
 
 class LePEAttention(nn.Module):
@@ -120,7 +120,7 @@ class CSWinBlock(nn.Module):
           B  head width 32 on the fast GEMMs, stripe kernel not applicable (C = 256 / 512, the one-branch last stage, stripes above 64
              tokens): LayerNorm 1 reads x16 (layernorm_x16_kernel), qkv GEMM, the 16-bit LePE core, then the second half as in A.
           C  everything else (precision 0, widths off the fast GEMM; another head width raises as it does in fp32): one widen launch,
-             the fp32 body, one round launch.
+             the fp32 body (_run), one round launch.
         An fp16 y beyond 65504 is reported to the range guard (code 3) on every route but C, so the block re-runs strict and returns inf."""
         x, io = F._require_io16(x, "x")
         B, L, C = x.shape
@@ -129,7 +129,7 @@ class CSWinBlock(nn.Module):
         n1, n2, fc1, fc2 = self.norm1, self.norm2, self.mlp.fc1, self.mlp.fc2
         a0 = self.attns[0]
         if not (p and _fast(p, self.qkv, self.proj, fc1, fc2) and a0.dim // a0.num_heads == 32):
-            return F.round16(self._plain(F.widen16(x), p, _p32), x.dtype)
+            return F.round16(self._run(F.widen16(x), p, _p32), x.dtype)
         if self.branch_num == 2 and F.cswin_stripe_ok(C, self.patches_resolution, self.split_size, self.num_heads, p):
             att = F.cswin_stripe_attention16(x, n1, self.qkv, a0.get_v, self.attns[1].get_v, self.patches_resolution, self.num_heads,
                                              self.split_size, a0.scale)
@@ -147,80 +147,66 @@ class CSWinBlock(nn.Module):
         if F.proj_mlp_fused_ok(C, fc1.weight.shape[0], p) and fc1.bias is not None:
             return F.proj_mlp_fused16(x, att, self.proj, n2, fc1, fc2)
         x1 = F.linear16_res(att, F.weight16(self.proj.weight, p), self.proj.bias, x, precision=p)          # 16-bit residual, fp32 stream
-        u = F.layernorm16(x1, _p32(n2.weight, "norm2.weight"), _p32(n2.bias, "norm2.bias"), n2.eps, p)
-        h = F.linear16(u, F.weight16(fc1.weight, p), _p32(fc1.bias, "fc1.bias"), act=F.ACT_GELU, out16=True, precision=p)
-        return F.linear16_res(h, F.weight16(fc2.weight, p), fc2.bias, x1, out_dtype=x.dtype, precision=p)
-
-    def _plain(self, x, p, P):
-        """The body of forward() outside the 16-bit dataflow for the widened x of _forward16: the same calls at precision p (0, or the
-        type of the 16-bit x where a width is off the fast GEMM) with every parameter through P (_p32)."""
-        B, L, C = x.shape
-        n1, n2, fc1, fc2 = self.norm1, self.norm2, self.mlp.fc1, self.mlp.fc2
-        u = F.layernorm(x, P(n1.weight, "norm1.weight"), P(n1.bias, "norm1.bias"), n1.eps)
-        qkv = F.linear(u, P(self.qkv.weight, "qkv.weight"), P(self.qkv.bias, "qkv.bias"), precision=p)
-        att = torch.empty(B, L, C, dtype=torch.float32, device=x.device)
-        self.attns[0].run(qkv, att, 0, p, P)
-        if self.branch_num == 2:
-            self.attns[1].run(qkv, att, C // 2, p, P)
-        x = F.linear(att, P(self.proj.weight, "proj.weight"), P(self.proj.bias, "proj.bias"), resid=x, precision=p)
-        u = F.layernorm(x, P(n2.weight, "norm2.weight"), P(n2.bias, "norm2.bias"), n2.eps)
-        h = F.linear(u, P(fc1.weight, "fc1.weight"), P(fc1.bias, "fc1.bias"), act=F.ACT_GELU, precision=p)
-        return F.linear(h, P(fc2.weight, "fc2.weight"), P(fc2.bias, "fc2.bias"), resid=x, precision=p)
+        return _half16(n2, "norm2", fc1, x1, p, lambda h: F.linear16_res(h, F.weight16(fc2.weight, p), fc2.bias, x1, out_dtype=x.dtype,
+                                                                        precision=p))
 
     def forward(self, x):
         """x (B, L, C) fp32, or fp16 / bf16 (the result has the type of x; see _forward16)."""
         if _is16(x):
             return self._forward16(x)
+        return self._run(x, self.precision, _same)
+
+    def _run(self, x, precision, P):
+        """The fp32 block at `precision` (the setting; None = the default).  forward() passes _same; route C of _forward16 the widened x,
+        the precision of its type (or 0) and _p32.  Route C is taken exactly when the test of the 16-bit dataflow below fails, so only
+        the fp32 route, written first, hands its parameters through P and overrides the sub-modules' settings; the stripe route and
+        the 16-bit GEMM route after it see an fp32 x from forward() only."""
         B, L, C = x.shape
         assert L == self.patches_resolution ** 2, "flatten img_tokens has wrong size"
-        p = F._prec(self.precision)
-        fast = _fast(p, self.qkv, self.proj, self.mlp.fc1, self.mlp.fc2) and self.attns[0].dim // self.attns[0].num_heads == 32
-        stripe = fast and self.branch_num == 2 and F.cswin_stripe_ok(C, self.patches_resolution, self.split_size, self.num_heads, p)
-        if stripe:                   # narrow stages: LN -> qkv -> both stripe attentions in one kernel, qkv never reaches HBM
-            a0, a1 = self.attns[0], self.attns[1]
-            att = F.cswin_stripe_attention(x, self.norm1, self.qkv, a0.get_v, a1.get_v, self.patches_resolution, self.num_heads,
-                                           self.split_size, a0.scale, p)
-        elif fast:                   # LN -> qkv -> attention -> proj with every GEMM operand kept 16-bit in HBM
-            if F.ln_linear16_ok(C, 3 * C, p):        # narrow stages: LayerNorm applied on the way into the qkv GEMM
-                qkv = F.ln_linear16(x, self.norm1, self.qkv, out16=True, precision=p)
-            else:
-                u = F.layernorm16(x, self.norm1.weight, self.norm1.bias, self.norm1.eps, p)
-                qkv = F.linear16(u, F.weight16(self.qkv.weight, p), self.qkv.bias, out16=True, precision=p)
-            att = torch.empty(B, L, C, dtype=qkv.dtype, device=x.device)
-        else:
-            u = F.layernorm(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)
-            qkv = F.linear(u, self.qkv.weight, self.qkv.bias, precision=self.precision)    # (B,L,3C) == (B,L,3,C)
+        p = F._prec(precision)
+        n1, n2, mlp, a0 = self.norm1, self.norm2, self.mlp, self.attns[0]
+        reso, split = self.patches_resolution, self.split_size
+        if not (_fast(p, self.qkv, self.proj, mlp.fc1, mlp.fc2) and a0.dim // a0.num_heads == 32):
+            own = None if P is _same else precision                  # the branches' own setting, or the caller's
+            qkv = F.linear(_layernorm(n1, x, P, "norm1"), P(self.qkv.weight, "qkv.weight"), P(self.qkv.bias, "qkv.bias"),
+                           precision=precision)                      # (B,L,3C) == (B,L,3,C)
             att = torch.empty(B, L, C, dtype=torch.float32, device=x.device)
-        if stripe:
-            pass
-        elif self.branch_num == 2 and fast:
-            a0, a1 = self.attns[0], self.attns[1]                  # both stripe branches in one launch
-            F.cswin_lepe_attention16_pair(qkv, a0.get_v.weight, a0.get_v.bias, a1.get_v.weight, a1.get_v.bias, att,
-                                          self.patches_resolution, a0.num_heads, self.split_size, a0.scale, p)
-        elif self.branch_num == 2:
-            self.attns[0].run(qkv, att, 0)
-            self.attns[1].run(qkv, att, C // 2)
-        else:
-            self.attns[0].run(qkv, att, 0)
-        if fast:
-            if F.proj_mlp_fused_ok(C, self.mlp.fc1.weight.shape[0], p) and self.mlp.fc1.bias is not None:
-                # proj + residual + LN2 + fc1 + GELU + fc2 + residual in one launch: x1 never reaches HBM
-                return F.mlp_fused(x, self.norm2, self.mlp.fc1, self.mlp.fc2, precision=p, ctx16=att, proj=self.proj)
-            fused_mlp = F.mlp_fused_ok(C, self.mlp.fc1.weight.shape[0], p) and self.mlp.fc1.bias is not None
-            if not fused_mlp:
-                # stage 3 (C = 256): the proj GEMM owns whole rows, so it also writes norm2(x) in the operand format (round 6: no LayerNorm launch)
-                got = F.linear16_ln16(att, F.weight16(self.proj.weight, p), self.proj.bias, x, self.norm2, p)
-                if got is not None:
-                    x, u = got
-                    return self.mlp(u, resid=x)
-            x = F.linear16(att, F.weight16(self.proj.weight, p), self.proj.bias, resid=x, precision=p)
-            if fused_mlp:
-                return F.mlp_fused(x, self.norm2, self.mlp.fc1, self.mlp.fc2, precision=p)      # LN2 + fc1 + GELU + fc2 + residual
-            u = F.layernorm16(x, self.norm2.weight, self.norm2.bias, self.norm2.eps, p)
-        else:
-            x = F.linear(att, self.proj.weight, self.proj.bias, resid=x, precision=self.precision)
-            u = F.layernorm(x, self.norm2.weight, self.norm2.bias, self.norm2.eps)
-        return self.mlp(u, resid=x)
+            a0.run(qkv, att, 0, own, P)
+            if self.branch_num == 2:
+                self.attns[1].run(qkv, att, C // 2, own, P)
+            x = F.linear(att, P(self.proj.weight, "proj.weight"), P(self.proj.bias, "proj.bias"), resid=x, precision=precision)
+            u = _layernorm(n2, x, P, "norm2")
+            return mlp(u, resid=x) if P is _same else mlp._run(u, x, precision, P)
+        if self.branch_num == 2 and F.cswin_stripe_ok(C, reso, split, self.num_heads, p):
+            # narrow stages: LN -> qkv -> both stripe attentions in one kernel, qkv never reaches HBM
+            att = F.cswin_stripe_attention(x, n1, self.qkv, a0.get_v, self.attns[1].get_v, reso, self.num_heads, split, a0.scale, p)
+        else:                        # LN -> qkv -> attention with every GEMM operand kept 16-bit in HBM
+            if F.ln_linear16_ok(C, 3 * C, p):        # narrow stages: LayerNorm applied on the way into the qkv GEMM
+                qkv = F.ln_linear16(x, n1, self.qkv, out16=True, precision=p)
+            else:
+                qkv = F.linear16(F.layernorm16(x, n1.weight, n1.bias, n1.eps, p), F.weight16(self.qkv.weight, p), self.qkv.bias,
+                                 out16=True, precision=p)
+            att = torch.empty(B, L, C, dtype=qkv.dtype, device=x.device)
+            if self.branch_num == 2:
+                a1 = self.attns[1]                                   # both stripe branches in one launch
+                F.cswin_lepe_attention16_pair(qkv, a0.get_v.weight, a0.get_v.bias, a1.get_v.weight, a1.get_v.bias, att, reso,
+                                              a0.num_heads, split, a0.scale, p)
+            else:
+                a0.run(qkv, att, 0)
+        if F.proj_mlp_fused_ok(C, mlp.fc1.weight.shape[0], p) and mlp.fc1.bias is not None:
+            # proj + residual + LN2 + fc1 + GELU + fc2 + residual in one launch: x1 never reaches HBM
+            return F.mlp_fused(x, n2, mlp.fc1, mlp.fc2, precision=p, ctx16=att, proj=self.proj)
+        fused_mlp = F.mlp_fused_ok(C, mlp.fc1.weight.shape[0], p) and mlp.fc1.bias is not None
+        if not fused_mlp:
+            # stage 3 (C = 256): the proj GEMM owns whole rows, so it also writes norm2(x) in the operand format (no LayerNorm launch)
+            got = F.linear16_ln16(att, F.weight16(self.proj.weight, p), self.proj.bias, x, n2, p)
+            if got is not None:
+                x, u = got
+                return mlp(u, resid=x)
+        x = F.linear16(att, F.weight16(self.proj.weight, p), self.proj.bias, resid=x, precision=p)
+        if fused_mlp:
+            return F.mlp_fused(x, n2, mlp.fc1, mlp.fc2, precision=p)      # LN2 + fc1 + GELU + fc2 + residual
+        return mlp(F.layernorm16(x, n2.weight, n2.bias, n2.eps, p), resid=x)
 
 
 class Merge_Block(nn.Module):

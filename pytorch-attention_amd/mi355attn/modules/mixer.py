@@ -7,7 +7,7 @@ from torch import nn
 
 from .. import _ffi
 from .. import functional as F
-from .vit import _fast, _is16, _mlp16, _p32, _same
+from ._io16 import _fast, _half16, _io_precision, _is16, _layernorm, _mlp_run, _p32, _patch_embed16, _same
 
 
 class Mlp(nn.Module):
@@ -18,10 +18,10 @@ class Mlp(nn.Module):
         self.precision = None
 
     def forward(self, x, resid=None):
-        if _fast(self.precision, self.fc1, self.fc2):
-            return _mlp16(x, self.fc1, self.fc2, self.precision, second_gelu=False, resid=resid)
-        h = F.linear(x, self.fc1.weight, self.fc1.bias, act=F.ACT_GELU, precision=self.precision)
-        return F.linear(h, self.fc2.weight, self.fc2.bias, resid=resid, precision=self.precision)
+        return self._run(x, resid, self.precision, _same)
+
+    def _run(self, x, resid, precision, P):
+        return _mlp_run(self.fc1, self.fc2, x, resid, precision, P)
 
 
 class MixerLayer(nn.Module):
@@ -47,12 +47,7 @@ class MixerLayer(nn.Module):
             x = F.mixer_token_mlp(x.contiguous(), self.norm1, t.fc1, t.fc2, F._prec(self.precision))
         else:
             x = self._token_mix(x, self.precision, _same)
-        c = self.channel_mlp
-        if _fast(self.precision, c.fc1, c.fc2):
-            u = F.layernorm16(x, self.norm2.weight, self.norm2.bias, self.norm2.eps, F._prec(self.precision))
-        else:
-            u = F.layernorm(x, self.norm2.weight, self.norm2.bias, self.norm2.eps)
-        return c(u, resid=x)
+        return self._channel_mix(x, self.precision, _same, x.dtype)
 
     def _token_mix(self, x, precision, P):
         """x + token_mlp(norm1(x)^T)^T for an fp32 x outside the fused kernel's envelope.  `precision`: the setting (None = the default);
@@ -79,22 +74,28 @@ class MixerLayer(nn.Module):
         Inside the fused token kernel's envelope x is read in 16 bit by that kernel (mi355_mixer_token_x16_fwd); outside it (N != 196,
         C > 1024, ...) one launch widens x (widen16_kernel) and the fp32 routes run; the final store is 16-bit either way."""
         x, io = F._require_io16(x, "x")
-        p = F.PREC_STRICT if F._prec(self.precision) == F.PREC_STRICT else io
-        t, c = self.token_mlp, self.channel_mlp
+        p = _io_precision(self.precision, io)
+        t = self.token_mlp
         T, N = t.fc1.weight.shape
         if p and x.dim() == 3 and t.fc1.bias is not None and t.fc2.bias is not None and F.mixer_token_ok(N, T, x.shape[-1], p):
             x1 = F.mixer_token_mlp16(x, self.norm1, t.fc1, t.fc2)
         else:
             x1 = self._token_mix(F.widen16(x), p, _p32)
-        nw, nb = _p32(self.norm2.weight, "norm2.weight"), _p32(self.norm2.bias, "norm2.bias")
-        b1, b2 = _p32(c.fc1.bias, "fc1.bias"), _p32(c.fc2.bias, "fc2.bias")
-        if _fast(p, c.fc1, c.fc2):
-            u = F.layernorm16(x1, nw, nb, self.norm2.eps, p)
-            h = F.linear16(u, F.weight16(c.fc1.weight, p), b1, act=F.ACT_GELU, out16=True, precision=p)
-            return F.linear16(h, F.weight16(c.fc2.weight, p), b2, resid=x1, out16=True, precision=p)
-        u = F.layernorm(x1, nw, nb, self.norm2.eps)
-        h = F.linear(u, _p32(c.fc1.weight, "fc1.weight"), b1, act=F.ACT_GELU, precision=p)
-        return F.round16(F.linear(h, _p32(c.fc2.weight, "fc2.weight"), b2, resid=x1, precision=p), x.dtype)
+        return self._channel_mix(x1, p, _p32, x.dtype)
+
+    def _channel_mix(self, x1, precision, P, out_dtype):
+        """x1 + channel_mlp(norm2(x1)) for the fp32 stream x1, in out_dtype.  forward() passes the layer's setting, _same and fp32: the
+        channel MLP is called as a module, at its own setting.  _forward16 passes the precision of its x (or 0), _p32 and the type of its
+        x: on the fast GEMM widths fc2 stores that type in its own epilogue, else the fp32 MLP runs and one launch rounds."""
+        c, n2 = self.channel_mlp, self.norm2
+        fast, out16 = _fast(precision, c.fc1, c.fc2), out_dtype in _ffi.IO_CODES
+        if fast and out16:
+            p = F._prec(precision)
+            return _half16(n2, "norm2", c.fc1, x1, p, lambda h: F.linear16(h, F.weight16(c.fc2.weight, p), _p32(c.fc2.bias, "fc2.bias"),
+                                                                          resid=x1, out16=True, precision=p))
+        u = _layernorm(n2, x1, P, "norm2", fast, precision)
+        y = c(u, resid=x1) if P is _same else c._run(u, x1, precision, P)
+        return F.round16(y, out_dtype) if out16 else y
 
 
 class PatchEmbedding(nn.Module):
@@ -111,17 +112,9 @@ class PatchEmbedding(nn.Module):
     _mi355_fp16_io_saturates = True          # fp16 tokens beyond 65504 are reported by the GEMM epilogue
 
     def forward(self, x):
-        """x (B, Cin, H, W) fp32 -> fp32 tokens, or fp16 / bf16 -> tokens of that type (operand format = the type; precision 0 widens,
-        runs the strict route and rounds; so does a geometry outside the envelope of mi355_patch_embed_x16_fwd, in the format of x)."""
+        """x (B, Cin, H, W) fp32 -> fp32 tokens, or fp16 / bf16 -> tokens of that type (_patch_embed16)."""
         if _is16(x):
-            x, io = F._require_io16(x, "img")
-            p = F.PREC_STRICT if F._prec(self.precision) == F.PREC_STRICT else io
-            w = self.proj.weight
-            t = F.patch_embed16(x, w, self.proj.bias, self.patch_size) if p else None
-            if t is not None:
-                return t
-            t = F.patch_embed(F.widen16(x), _p32(w, "proj.weight"), _p32(self.proj.bias, "proj.bias"), None, None, self.patch_size, p)
-            return F.round16(t, x.dtype)
+            return _patch_embed16(self, x)
         return F.patch_embed(x, self.proj.weight, self.proj.bias, None, None, self.patch_size, self.precision)
 
 
@@ -147,7 +140,7 @@ class MLP_Mixer(nn.Module):
         for blk in self.blocks:
             x = blk(x)
         if io16:
-            p = F.PREC_STRICT if F._prec(self.precision) == F.PREC_STRICT else _ffi.IO_CODES[x.dtype]
+            p = _io_precision(self.precision, _ffi.IO_CODES[x.dtype])
             logits = F.linear(F.token_mean16(x), _p32(self.head.weight, "head.weight"), _p32(self.head.bias, "head.bias"), precision=p)
             return logits.to(x.dtype)                # (B, classes): the one torch cast, not a pass over activations
         return F.linear(F.token_mean(x), self.head.weight, self.head.bias, precision=self.precision)

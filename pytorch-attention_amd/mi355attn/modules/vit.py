@@ -21,61 +21,8 @@ is then the tensor's type; see TransformerEncoder._forward16).  `Attention` and 
 import torch
 from torch import nn
 
-from .. import _ffi
 from .. import functional as F
-
-
-def _bias(lin):
-    return lin.bias if lin.bias is not None else None
-
-
-def _is16(x):
-    return isinstance(x, torch.Tensor) and x.dtype in _ffi.IO_CODES
-
-
-def _p32(t, name):
-    """A parameter of a module that runs on 16-bit activations, as fp32: fp32 (autocast) as it is, 16-bit (module.half() / .bfloat16())
-    through its cached fp32 copy (F.param32); None stays None."""
-    return None if t is None else F.param32(t, name)
-
-
-def _io_precision(precision, io):
-    """The arithmetic of a module on a 16-bit tensor of type code `io`: the tensor's type, unless the setting (or a strict re-run) asks
-    for precision 0."""
-    return F.PREC_STRICT if F._prec(precision) == F.PREC_STRICT else io
-
-
-def _same(t, name):
-    return t
-
-
-class _Lin32:
-    """A Linear as the fp32 routes behind a widened 16-bit x take it: its parameters as fp32 tensors (_p32), its feature counts."""
-
-    def __init__(self, lin, name):
-        self.weight, self.bias = _p32(lin.weight, name + ".weight"), _p32(lin.bias, name + ".bias")
-        self.in_features, self.out_features = lin.in_features, lin.out_features
-
-
-def _lin(lin, P, name):
-    return lin if P is _same else _Lin32(lin, name)
-
-
-def _fast(precision, *linears):
-    """True when the 16-bit dataflow applies: a 16-bit operand mode and every GEMM inside the fast kernel's envelope."""
-    return F._prec(precision) != F.PREC_STRICT and all(F.fast_gemm_ok(l.in_features, l.out_features) for l in linears)
-
-
-def _mlp16(x, fc1, fc2, precision, second_gelu, gamma=None, resid=None):
-    """fc1 -> GELU -> fc2 (-> GELU) with the hidden activation kept in the MFMA operand format; x is fp32 or 16-bit."""
-    p = F._prec(precision)
-    h16 = F.cast_linear16(x, F.weight16(fc1.weight, p), fc1.bias, act=F.ACT_GELU, precision=p)    # fp32 x: the cast rides in the GEMM where it can
-    folded = F.weight16_scaled(fc2.weight, fc2.bias, gamma, p) if gamma is not None and not second_gelu else None
-    if folded is not None:                                    # LayerScale folded into fc2 (XCiT: no activation behind fc2); None =
-        w16, b = folded                                       # gamma * W would leave the fp16 normal range: gamma stays in the epilogue
-        return F.linear16(h16, w16, b, resid=resid, precision=p)
-    return F.linear16(h16, F.weight16(fc2.weight, p), fc2.bias, act=F.ACT_GELU if second_gelu else F.ACT_NONE, gamma=gamma,
-                      resid=resid, precision=p)
+from ._io16 import _fast, _half16, _io_precision, _is16, _layernorm, _lin, _mlp_run, _p32, _patch_embed16, _same
 
 
 class Mlp(nn.Module):
@@ -92,11 +39,7 @@ class Mlp(nn.Module):
     def _run(self, x, resid, precision, P):
         """The forward at `precision` (the setting; None = the default) with the parameters as P hands them over: _same from forward(),
         _p32 behind a widened 16-bit x (TransformerEncoder._forward16)."""
-        fc1, fc2 = _lin(self.fc1, P, "fc1"), _lin(self.fc2, P, "fc2")
-        if _fast(precision, fc1, fc2):
-            return _mlp16(x, fc1, fc2, precision, second_gelu=True, resid=resid)
-        h = F.linear(x, fc1.weight, fc1.bias, act=F.ACT_GELU, precision=precision)
-        return F.linear(h, fc2.weight, fc2.bias, act=F.ACT_GELU, resid=resid, precision=precision)
+        return _mlp_run(self.fc1, self.fc2, x, resid, precision, P, second_gelu=True)
 
 
 class Attention(nn.Module):
@@ -140,7 +83,7 @@ class Attention(nn.Module):
             with F._forced_strict(self):
                 return self.forward(x, resid)
         x = x if x.dtype == torch.float32 else x.float()
-        qkv5 = F.qkv_split16(x, *F.weight_split16(self.qkv.weight), _bias(self.qkv))                    # (B,N,5C)
+        qkv5 = F.qkv_split16(x, *F.weight_split16(self.qkv.weight), self.qkv.bias)                    # (B,N,5C)
         ctx = F.sdpa16_split(qkv5, self.num_heads, self.scale)                                           # (B,N,C) fp16
         return F.linear16(ctx, F.weight16(self.proj.weight, F.PREC_FP16), self.proj.bias, resid=resid, precision=F.PREC_FP16)
 
@@ -164,9 +107,9 @@ class Attention(nn.Module):
             # q / k / v / ctx stay 16-bit in HBM; the whole block is ONE C call (mi355_mhsa_fwd: cast -> qkv GEMM -> core -> proj GEMM,
             # the same kernels the three-call composition of rounds 1-2 launched)
             p = F._prec(precision)
-            return F.mhsa16(x, F.weight16(qkv_.weight, p), _bias(qkv_), F.weight16(proj.weight, p), proj.bias,
+            return F.mhsa16(x, F.weight16(qkv_.weight, p), qkv_.bias, F.weight16(proj.weight, p), proj.bias,
                             self.num_heads, self.scale, resid=resid, precision=p)
-        qkv = F.linear(x, qkv_.weight, _bias(qkv_), precision=precision)                   # (B,N,3C)
+        qkv = F.linear(x, qkv_.weight, qkv_.bias, precision=precision)                   # (B,N,3C)
         ctx = self._core(qkv, False, precision)                                             # (B,N,C)
         return F.linear(ctx, proj.weight, proj.bias, resid=resid, precision=precision)
 
@@ -183,18 +126,9 @@ class PatchEmbedding(nn.Module):
     _mi355_fp16_io_saturates = True          # fp16 tokens beyond 65504 are reported by the GEMM epilogue
 
     def forward(self, x):
-        """x (B, Cin, H, W) fp32 -> fp32 tokens, or fp16 / bf16 -> tokens of that type, as mixer.PatchEmbedding has it (operand format =
-        the type; precision 0 widens, runs the strict route and rounds; so does a geometry outside the envelope of
-        mi355_patch_embed_x16_fwd, in the format of x)."""
+        """x (B, Cin, H, W) fp32 -> fp32 tokens, or fp16 / bf16 -> tokens of that type, as mixer.PatchEmbedding has it (_patch_embed16)."""
         if _is16(x):
-            x, io = F._require_io16(x, "img")
-            p = _io_precision(self.precision, io)
-            t = F.patch_embed16(x, self.proj.weight, self.proj.bias, self.patch_size) if p else None
-            if t is not None:
-                return t
-            t = F.patch_embed(F.widen16(x), _p32(self.proj.weight, "proj.weight"), _p32(self.proj.bias, "proj.bias"), None, None,
-                              self.patch_size, p)
-            return F.round16(t, x.dtype)
+            return _patch_embed16(self, x)
         return F.patch_embed(x, self.proj.weight, self.proj.bias, None, None, self.patch_size, self.precision)
 
 
@@ -207,11 +141,6 @@ class TransformerEncoder(nn.Module):
         self.mlp.precision = precision
         self.layernorm2 = nn.LayerNorm(dim)
 
-    def _norm(self, ln, x, fast):
-        if fast:                     # LayerNorm writes the GEMM's operand format directly
-            return F.layernorm16(x, ln.weight, ln.bias, ln.eps, F._prec(self.attn.precision))
-        return F.layernorm(x, ln.weight, ln.bias, ln.eps)
-
     _mi355_fp16_io_saturates = True          # an fp16 x is guarded like an fp32 one: the fp16 LN operand and the 16-bit epilogues can saturate
 
     def forward(self, x):
@@ -220,7 +149,7 @@ class TransformerEncoder(nn.Module):
             return self._forward16(x)
         if self.fold_ok(x):
             return self.forward_folded(x)[0]
-        return self.forward_plain(x)
+        return self._run(x, self.attn.precision, _same)
 
     def _forward16(self, x):
         """The block on an fp16 / bf16 x; the result has the type of x.  The MFMA operand format is that type (fp16: the precision-1
@@ -230,43 +159,35 @@ class TransformerEncoder(nn.Module):
         half stays fp32, and y = x1 + gelu(fc2(..)) is rounded once, in the epilogue of the last GEMM (gemm16_res_kernel; an fp16 y
         beyond 65504 is reported to the range guard, code 3, so the block re-runs strict and returns inf).  No widen, round or cast
         launch.  Outside that envelope (head widths off F.SDPA_WIDTHS, in_features % 64 != 0, precision 0) one launch widens x, the
-        fp32 body runs at the precision of the type, and one launch rounds.  Neither the LayerNorm fold nor the pooled-token tail
+        fp32 body (_run) runs at the precision of the type, and one launch rounds.  Neither the LayerNorm fold nor the pooled-token tail
         applies to a 16-bit tensor."""
         x, io = F._require_io16(x, "x")
         p = _io_precision(self.attn.precision, io)
-        at, mlp, ln1, ln2 = self.attn, self.mlp, self.layernorm1, self.layernorm2
+        at, mlp, ln1 = self.attn, self.mlp, self.layernorm1
         if p and x.dim() == 3 and at.fast_ok(x.shape[1]) and _fast(p, at.qkv, at.proj, mlp.fc1, mlp.fc2):
             u = F.layernorm16_x16(x, ln1.weight, ln1.bias, ln1.eps)
             qkv = F.linear16(u, F.weight16(at.qkv.weight, p), _p32(at.qkv.bias, "qkv.bias"), out16=True, precision=p)
             ctx = at._core(qkv, True, p)
             x1 = F.linear16_res(ctx, F.weight16(at.proj.weight, p), at.proj.bias, x, precision=p)         # 16-bit residual, fp32 stream
-            u = F.layernorm16(x1, _p32(ln2.weight, "layernorm2.weight"), _p32(ln2.bias, "layernorm2.bias"), ln2.eps, p)
-            h = F.linear16(u, F.weight16(mlp.fc1.weight, p), _p32(mlp.fc1.bias, "fc1.bias"), act=F.ACT_GELU, out16=True, precision=p)
-            return F.linear16_res(h, F.weight16(mlp.fc2.weight, p), mlp.fc2.bias, x1, act=F.ACT_GELU, out_dtype=x.dtype, precision=p)
-        return F.round16(self._plain(F.widen16(x), p, _p32), x.dtype)
+            return _half16(self.layernorm2, "layernorm2", mlp.fc1, x1, p, lambda h: F.linear16_res(
+                h, F.weight16(mlp.fc2.weight, p), mlp.fc2.bias, x1, act=F.ACT_GELU, out_dtype=x.dtype, precision=p))
+        return F.round16(self._run(F.widen16(x), p, _p32), x.dtype)
 
-    def _plain(self, x, p, P):
-        """forward_plain for the widened x of _forward16: the same body at precision p (0 or the type of the 16-bit x, whatever the
-        setting) with every parameter through P (_p32: 16-bit parameters as their cached fp32 copies)."""
-        at, mlp, ln1, ln2 = self.attn, self.mlp, self.layernorm1, self.layernorm2
-        fast = _fast(p, at.qkv, at.proj, mlp.fc1, mlp.fc2) and at.qkv.in_features // at.num_heads in F.SDPA_WIDTHS
-
-        def norm(ln, t, name):
-            w, b = P(ln.weight, name + ".weight"), P(ln.bias, name + ".bias")
-            return F.layernorm16(t, w, b, ln.eps, p) if fast else F.layernorm(t, w, b, ln.eps)
-        x = at._run(norm(ln1, x, "layernorm1"), x, p, P)
-        return mlp._run(norm(ln2, x, "layernorm2"), x, p, P)
-
-    def forward_plain(self, x):
-        """The default body: one LayerNorm launch in front of each half (the fold is opt-in: measured slower)."""
-        if F.logit_mode(self.attn.precision):
-            # precision 3: the projection kernel splits fp32 rows itself, so LayerNorm 1 stays fp32 (a 16-bit LayerNorm output would put
-            # the rounding the mode removes back in front of the q / k columns); the MLP half is precision 1's
-            x = self.attn(F.layernorm(x, self.layernorm1.weight, self.layernorm1.bias, self.layernorm1.eps), resid=x)
-            return self.mlp(self._norm(self.layernorm2, x, _fast(self.attn.precision, self.mlp.fc1, self.mlp.fc2)), resid=x)
-        fast = self.attn.fast_ok(x.shape[1]) and _fast(self.attn.precision, self.mlp.fc1, self.mlp.fc2)
-        x = self.attn(self._norm(self.layernorm1, x, fast), resid=x)
-        return self.mlp(self._norm(self.layernorm2, x, fast), resid=x)
+    def _run(self, x, precision, P):
+        """The fp32 block outside the LayerNorm fold: one LayerNorm launch in front of each half (the fold is opt-in: measured slower,
+        DESIGN.md 6.2c).  forward() passes attn.precision and _same: attn and mlp are called as modules, each at its own setting.
+        _forward16 passes the widened x, the precision of its type (or 0) and _p32: both run at that precision, whatever their setting."""
+        at, mlp = self.attn, self.mlp
+        own = P is _same
+        fast1 = fast2 = _fast(precision, at.qkv, at.proj, mlp.fc1, mlp.fc2) and at.qkv.in_features // at.num_heads in F.SDPA_WIDTHS
+        if own and F.logit_mode(precision):
+            # precision 3 (an fp32 x only): the projection kernel splits fp32 rows itself, so LayerNorm 1 stays fp32 (a 16-bit LayerNorm
+            # output would put the rounding the mode removes back in front of the q / k columns); the MLP half is precision 1's
+            fast1, fast2 = False, _fast(precision, mlp.fc1, mlp.fc2)
+        u = _layernorm(self.layernorm1, x, P, "layernorm1", fast1, precision)     # fast: LayerNorm writes the GEMM's operand format directly
+        x = at(u, resid=x) if own else at._run(u, x, precision, P)
+        u = _layernorm(self.layernorm2, x, P, "layernorm2", fast2, precision)
+        return mlp(u, resid=x) if own else mlp._run(u, x, precision, P)
 
     # ---- LayerNorm folded into the GEMMs around it (csrc/ln_fold.hip): no LayerNorm launch between proj and fc1, nor between fc2 and
     #      the next block's qkv; the first LayerNorm of a chain is one mi355_ln_center16_fwd ---------------------------------------
@@ -408,7 +329,7 @@ class VisionTransformer(nn.Module):
             # row per image, in one C call; the same kernels' arithmetic, bit-identical logits (option "vit_tail" = 0: the full block)
             at, mlp = tail.attn, tail.mlp
             p = F._prec(at.precision)
-            pooled = F.vit_tail16(tok, tail.layernorm1, F.weight16(at.qkv.weight, p), _bias(at.qkv), F.weight16(at.proj.weight, p),
+            pooled = F.vit_tail16(tok, tail.layernorm1, F.weight16(at.qkv.weight, p), at.qkv.bias, F.weight16(at.proj.weight, p),
                                   at.proj.bias, tail.layernorm2, F.weight16(mlp.fc1.weight, p), mlp.fc1.bias,
                                   F.weight16(mlp.fc2.weight, p), mlp.fc2.bias, at.num_heads, at.scale, precision=p)
         elif self.global_pool == "token":

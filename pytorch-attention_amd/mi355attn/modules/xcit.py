@@ -31,28 +31,8 @@ from torch import nn
 
 from .. import _ffi
 from .. import functional as F
-from .vit import _fast, _io_precision, _is16, _lin, _mlp16, _p32, _same
+from ._io16 import _fast, _half16, _io_precision, _is16, _layernorm, _lin, _ln, _mlp_run, _p32, _round, _same, _wide
 from .mhsa import _dropout_is_identity, _no_dropout
-
-
-class _LN32:
-    """A LayerNorm as the fp32 routes behind a widened 16-bit x take it: its parameters as fp32 tensors (_p32), its eps."""
-
-    def __init__(self, ln, name):
-        self.weight, self.bias, self.eps = _p32(ln.weight, name + ".weight"), _p32(ln.bias, name + ".bias"), ln.eps
-
-
-def _ln(ln, P, name):
-    return ln if P is _same or ln is None else _LN32(ln, name)
-
-
-def _layernorm(ln, x, P, name):
-    return F.layernorm(x, P(ln.weight, name + ".weight"), P(ln.bias, name + ".bias"), ln.eps)
-
-
-def _round(y, dtype):
-    """round16 of an fp32 result, or of the tensor part of a (tensor, other) pair."""
-    return (F.round16(y[0], dtype),) + tuple(y[1:]) if isinstance(y, tuple) else F.round16(y, dtype)
 
 
 class Mlp(nn.Module):
@@ -80,18 +60,12 @@ class Mlp(nn.Module):
             if p and gamma is None and resid is None and fc1.bias is not None and _fast(p, fc1, fc2):
                 h = F.linear16(x, F.weight16(fc1.weight, p), _p32(fc1.bias, "fc1.bias"), act=F.ACT_GELU, out16=True, precision=p)
                 return F.linear16(h, F.weight16(fc2.weight, p), _p32(fc2.bias, "fc2.bias"), out16=True, precision=p)
-            wide = None if resid is None else (F.widen16(resid) if _is16(resid) else resid)
-            return F.round16(self._run(F.widen16(x), gamma, wide, p, _p32), x.dtype)
+            return F.round16(self._run(F.widen16(x), gamma, _wide(resid), p, _p32), x.dtype)
         return self._run(x, gamma, resid, self.precision, _same)
 
     def _run(self, x, gamma, resid, precision, P):
         """The fp32 forward at `precision` (the setting; None = the default) with the parameters as P hands them over."""
-        fc1, fc2 = _lin(self.fc1, P, "fc1"), _lin(self.fc2, P, "fc2")
-        gamma = None if gamma is None else P(gamma, "gamma")
-        if fc1.bias is not None and _fast(precision, fc1, fc2):
-            return _mlp16(x, fc1, fc2, precision, second_gelu=False, gamma=gamma, resid=resid)
-        h = F.linear(x, fc1.weight, fc1.bias, act=F.ACT_GELU, precision=precision)
-        return F.linear(h, fc2.weight, fc2.bias, gamma=gamma, resid=resid, precision=precision)
+        return _mlp_run(self.fc1, self.fc2, x, resid, precision, P, gamma=gamma)
 
 
 class LPI(nn.Module):
@@ -110,8 +84,7 @@ class LPI(nn.Module):
         x fp32, or fp16 / bf16: widened once, the fp32 kernels (there is no 16-bit operand in LPI: nothing to report), rounded once."""
         if _is16(x):
             x, _ = F._require_io16(x, "x")
-            wide = None if resid is None else (F.widen16(resid) if _is16(resid) else resid)
-            return F.round16(self._run(F.widen16(x), H, W, gamma, wide, ln, stats, _p32), x.dtype)
+            return F.round16(self._run(F.widen16(x), H, W, gamma, _wide(resid), ln, stats, _p32), x.dtype)
         return self._run(x, H, W, gamma, resid, ln, stats, _same)
 
     def _run(self, x, H, W, gamma, resid, ln, stats, P):
@@ -156,8 +129,7 @@ class XCA(nn.Module):
             qkv = F.linear16(x, F.weight16(self.qkv.weight, p), _p32(self.qkv.bias, "qkv.bias"), out16=True, precision=p)
             ctx16 = F.xca_core(qkv, _p32(self.temperature, "temperature"), self.num_heads, precision=p, out16=True)
             return F.linear16(ctx16, F.weight16(self.proj.weight, p), _p32(self.proj.bias, "proj.bias"), out16=True, precision=p)
-        wide = None if resid is None else (F.widen16(resid) if _is16(resid) else resid)
-        return _round(self._run(F.widen16(x), gamma, wide, ln, stats_eps, p, _p32), x.dtype)
+        return _round(self._run(F.widen16(x), gamma, _wide(resid), ln, stats_eps, p, _p32), x.dtype)
 
     def _run(self, x, gamma, resid, ln, stats_eps, precision, P):
         """The fp32 forward at `precision` (the setting; None = the default) with the parameters as P hands them over: _same from forward(),
@@ -226,20 +198,15 @@ class XCABlock(nn.Module):
         attn, mlp = self.attn, self.mlp
         fast = _fast(p, attn.qkv, attn.proj, mlp.fc1, mlp.fc2)
 
-        def norm(ln, t, to16, name):
-            if to16:
-                return F.layernorm16(t, P(ln.weight, name + ".weight"), P(ln.bias, name + ".bias"), ln.eps, p)
-            return _layernorm(ln, t, P, name)
-
         # the proj GEMM of the attention branch writes norm3's statistics of x beside x where it owns whole rows (gemm16_wreg, round 6)
         if fast and F.ln_linear16_ok(x.shape[-1], 3 * x.shape[-1], p):
             x, st = attn._run(x, self.gamma1, x, self.norm1, self.norm3.eps, precision, P)        # LayerNorm fused into the qkv GEMM
         else:
-            x, st = attn._run(norm(self.norm1, x, fast, "norm1"), self.gamma1, x, None, self.norm3.eps, precision, P)
+            x, st = attn._run(_layernorm(self.norm1, x, P, "norm1", fast, p), self.gamma1, x, None, self.norm3.eps, precision, P)
         x = self.local_mp._run(x, H, W, self.gamma3, x, self.norm3, st, P)                        # norm3 fused into the LPI kernel
         if fast and F.mlp_fused_ok(x.shape[-1], mlp.fc1.weight.shape[0], p) and mlp.fc1.bias is not None:
             return F.mlp_fused(x, self.norm2, mlp.fc1, mlp.fc2, gamma=P(self.gamma2, "gamma2"), precision=p)   # LN2 + MLP + LayerScale + residual
-        return mlp._run(norm(self.norm2, x, fast, "norm2"), self.gamma2, x, mlp.precision if P is _same else precision, P)
+        return mlp._run(_layernorm(self.norm2, x, P, "norm2", fast, p), self.gamma2, x, mlp.precision if P is _same else precision, P)
 
     def _forward16(self, x, H, W):
         """The block on an fp16 / bf16 x; the result has the type of x.  The MFMA operand format is that type (fp16: the precision-1
@@ -271,9 +238,7 @@ class XCABlock(nn.Module):
         y = F.mlp_fused_o16(x2, n2, fc1, fc2, gamma=self.gamma2, precision=p)         # None: not built for the width
         if y is not None:
             return y
-        u = F.layernorm16(x2, _p32(n2.weight, "norm2.weight"), _p32(n2.bias, "norm2.bias"), n2.eps, p)
-        h = F.linear16(u, F.weight16(fc1.weight, p), _p32(fc1.bias, "fc1.bias"), act=F.ACT_GELU, out16=True, precision=p)
-        return self._scaled_res(h, fc2, self.gamma2, x2, x.dtype, p)[0]
+        return _half16(n2, "norm2", fc1, x2, p, lambda h: self._scaled_res(h, fc2, self.gamma2, x2, x.dtype, p)[0])
 
     @staticmethod
     def _scaled_res(a16, lin, gamma, resid, out_dtype, p, stats_eps=None):

@@ -18,7 +18,7 @@ import torch
 from conftest import PKG, ROOT
 from route_cases import BY_ID, ROWS, build_row, predicate_values
 
-MODULE_FILES = ("vit.py", "cswin.py", "xcit.py", "mixer.py")
+MODULE_FILES = ("vit.py", "cswin.py", "xcit.py", "mixer.py", "_io16.py")
 
 
 class _OptionRead(Exception):
